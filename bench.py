@@ -19,9 +19,15 @@ while batch i is finished on a light stream — the way the reference's service
 overlaps up to 64 concurrent retrieve() calls (service.py:137,149); every step's
 results are complete when the region ends.  The dense-scan kernel is
 bracketed with HIP events on its own stream inside the timed region
-(hr_set_profiling(1)) to get roofline.achieved.  The CPU baseline (N=1 only) is
-the oracle's numpy/scipy restatement of the reference path timed on a 1M-row
-subsample and extrapolated per row — labelled as such.
+(hr_set_profiling(1)) to get roofline.achieved.
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything
+else runs only with --full: the parity gate and the CPU baseline (N=1 only: the
+oracle's numpy/scipy restatement of the reference path timed on a 1M-row
+subsample and extrapolated per row — labelled as such), the sparse roofline, the
+finishing kernels alone, config4_full and the retrieve() latency / concurrency
+blocks.  --dump-outputs DIR writes the last timed step's results as DIR/<name>.npy
+(float32 / float64; ids as float64) after the timed region.
 """
 from __future__ import annotations
 
@@ -189,6 +195,38 @@ def make_queries(n_batches: int, B: int, dim: int, seed: int = 4321, dist: str =
     return Q, sq
 
 
+# what a caller of the engine receives for one batch, and the axis that runs over its queries
+DUMP_OUTPUTS = (("fused_ids", 0), ("fused_scores", 0), ("fused_methods", 0), ("fused_n", 0),
+                ("rr_ids", 0), ("rr_scores", 0), ("rr_orig", 0), ("ce_ids", 0), ("ce_scores", 0),
+                ("list_ids", 1), ("list_scores", 1), ("agg_flags", 1))
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, b: dict, max_bytes: int = DUMP_MAX_BYTES, seed: int = 0) -> dict:
+    """Write the results of one batch (an engine buffer dict) as <directory>/<name>.npy: floating arrays as float32 /
+    float64 (float16 widened), integer arrays (ids, methods, counts, flags) as float64, which holds them exactly.
+    Above max_bytes a fixed, seeded sample of the queries is written, and its rows as query_rows.npy."""
+    arrays = {}
+    for name, axis in DUMP_OUTPUTS:
+        if name not in b:
+            continue
+        a = b[name]
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+        arrays[name] = (a, axis)
+    total = sum(a.nbytes for a, _ in arrays.values())
+    if total > max_bytes:
+        n_q = next(a.shape[axis] for a, axis in arrays.values())
+        keep = max(1, int(max_bytes / (total / n_q + 8)) - 1)   # (+ 8 bytes per query of query_rows)
+        rows = np.sort(np.random.default_rng(seed).choice(n_q, keep, replace=False))
+        arrays = {k: (np.take(a, rows, axis=axis), axis) for k, (a, axis) in arrays.items()}
+        arrays["query_rows"] = (rows.astype(np.float64), 0)
+    os.makedirs(directory, exist_ok=True)
+    for name, (a, _) in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
+    return {k: a.shape for k, (a, _) in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -245,8 +283,19 @@ def main():
                     help="hr_debug_option(HR_DEBUG_DENSE_KERNELS) bit mask for A/B runs")
     ap.add_argument("--finish-mode", choices=("auto", "chain", "fused"), default="auto",
                     help="finishing path: auto = fused kernel for batches that fill the chip, chain = five launches")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the parity gate and the CPU baseline "
+                         "(N=1), the sparse roofline, the finishing kernels alone, config4_full and the retrieve() latency / "
+                         "concurrency blocks (the --no-* switches above turn single parts off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's results (fused, reranked and per-modality lists) "
+                         "as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.ingest:
+        if args.dump_outputs:
+            ap.error("--dump-outputs applies to the search step, not to --ingest")
         return bench_ingest(args)
 
     import torch
@@ -299,7 +348,8 @@ def main():
     h.reserve(max(n_local, 64))
 
     # ---- build this rank's shard (generated in blocks by a thread pool, ingested in order) ----------
-    do_cpu = (world == 1 and not args.no_cpu_baseline)
+    do_cpu = (world == 1 and args.full and not args.no_cpu_baseline)
+    sparse_roofline = use_sparse and args.full
     cpu_rows = min(args.cpu_rows, N)
     sample_dense, sample_sparse = [], []
     t0 = time.time()
@@ -328,7 +378,8 @@ def main():
             h.add_dense(Xb)  # fp32 -> fp16 (RNE) on the device
             if use_sparse:
                 h.add_sparse(*Sb)
-                df += np.bincount(Sb[1], minlength=SPARSE_DIM)
+                if sparse_roofline:
+                    df += np.bincount(Sb[1], minlength=SPARSE_DIM)
             if do_cpu and b * blk < cpu_rows:
                 take = min(Xb.shape[0], cpu_rows - b * blk)
                 sample_dense.append(Xb[:take].astype(np.float16))
@@ -516,11 +567,22 @@ def main():
         ft = torch.tensor([1 if flags_exact else 0], dtype=torch.int32, device="cpu" if rehearsal else dev)
         dist.all_reduce(ft, op=dist.ReduceOp.MIN)
         flags_exact = bool(ft.item())
+    if args.rerank == "cross-encoder":
+        ce_events = list(ce_events)  # the forwards of the timed region (the flush below may add the last batch's)
+
+    # ---- the last timed step's results, as a caller of the engine receives them ---------------------------------
+    if args.dump_outputs:
+        if n_fly > 1:
+            eng.synchronize()  # enqueues a deferred cross-encoder hook of the last batch (a collective under torchrun)
+        torch.cuda.synchronize()
+        if rank == 0:
+            shapes = dump_outputs(args.dump_outputs, out)
+            log(f"outputs of step {args.warmup + args.steps - 1} written to {args.dump_outputs}: {shapes}")
 
     # the finishing kernel and the post-exchange kernel of the last batch once more, ALONE on an idle chip (their
     # in-region times are those of kernels starved by the scans they run beside): what the chain costs by itself
     alone = None
-    if n_fly > 1 and use_sparse:
+    if args.full and n_fly > 1 and use_sparse:
         torch.cuda.synchronize()
         st = torch.cuda.current_stream(dev)
         b, slot = out, (eng._n - 1) % eng.depth
@@ -545,7 +607,7 @@ def main():
     # ---- full BASELINE config 4: the same step WITH the cross-encoder rerank 20 -> 5 (reference retrieval.py:518-563,
     # :651-681), a second short timed region on the same shard, at 128 and at 512 tokens per (query, document) pair
     config4_full = None
-    if n_fly > 1 and use_sparse and args.rerank == "learned" and not args.no_config4_full and (N, D) == (10_000_000, 768):
+    if args.full and n_fly > 1 and use_sparse and args.rerank == "learned" and not args.no_config4_full and (N, D) == (10_000_000, 768):
         config4_full = {}
         for T in (128, 512):
             hook, evs, pairs, ce_m = make_cross_encoder(T)
@@ -616,7 +678,7 @@ def main():
     # Sparse scan roofline: algorithmic bytes of one launch = every posting of every kept query term
     # (4 B: fp16 weight | u16 slot) + 2 * 4 B of run bounds per (term, range), averaged over the query batches timed.
     sparse_roof = None
-    if use_sparse:
+    if sparse_roofline:
         sp_ms, sp_launches = phases["sparse_scan"]
         n_ranges = -(-n_local // 16384)
         per_batch = []
@@ -642,7 +704,7 @@ def main():
     # N = 1: the manager holds the one shard.  N > 1: the collection spans the ranks (torchrun form of the sharded
     # manager): rank 0 calls retrieve(), every rank searches its shard, one gather per modality brings the lists back.
     latency = None
-    if not args.no_latency and args.latency_queries > 0:
+    if args.full and not args.no_latency and args.latency_queries > 0:
         latency = measure_latency(h, Q, SQ, args, use_sparse, world, rank, lo, N)
         if world > 1:
             dist.barrier()
@@ -681,6 +743,7 @@ def main():
         res = {
             "metric": "queries_per_sec_hybrid_retrieve", "value": total_q / elapsed, "unit": "queries/s",
             "n_gpus": world, **({"rehearsal_single_gpu_gloo": True} if rehearsal else {}), "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+            "full": args.full,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f16", "data": "synthetic",
             "config": {"workload": f"{N}x{D} fp16 COSINE corpus" + (f" + sparse {SPARSE_NNZ}nnz/{SPARSE_DIM}d" + (" zipf(1.1)" if args.sparse_dist == "zipf" else "") if use_sparse else "")
                        + (f", hybrid dense+sparse k'={kp} -> RRF(k=60, 0.7/0.3)" if use_sparse else f", dense only k'={kp} -> RRF(k=60) of the one list")

@@ -26,13 +26,14 @@ def test_bench_two_ranks_rehearsal_prints_one_valid_line(gpu):
     env = dict(os.environ, BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rows", "200000", "--steps", "3",
-           "--warmup", "1", "--no-cpu-baseline", "--no-api-concurrent", "--no-config4-full", "--latency-queries", "8"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-api-concurrent", "--no-config4-full", "--latency-queries", "8"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["warmup"] == 1
+    assert out["retrieve_shards"] == 2 and out["p50_retrieve_ms"] > 0   # --full: retrieve() through the rank-spanning manager
     assert out["ranks_agree"] is True and out["all_lists_proven_exact"] is True
     assert out["value"] > 0 and out["unit"] and out["higher_is_better"] is True and out["scaling"] in ("strong", "weak")
     assert out["roofline"]["bound"] == "hbm" and 0 < out["roofline"]["frac"] < 1
