@@ -43,7 +43,7 @@ def pack_sparse_queries(queries: Sequence[Tuple[Sequence[int], Sequence[float]]]
     """Host prep of a sparse query batch for the device form: apply
     drop_ratio_search (smallest |value| first; among equals the later entry),
     sort by index, build CSR.  Returns (indptr int64, idx int32, val float32, max_nnz).
-    Indices must be distinct, non-negative and (when sparse_dim is given) below sparse_dim — what
+    Indices must be distinct, non-negative and (when sparse_dim is given) below sparse_dim, values finite — what
     hr_search_sparse checks for the host form."""
     ptr = [0]
     idx_parts, val_parts = [], []
@@ -57,6 +57,8 @@ def pack_sparse_queries(queries: Sequence[Tuple[Sequence[int], Sequence[float]]]
             raise ValueError(f"sparse query index out of range [0, {sparse_dim})")
         if np.unique(qi).size != qi.size:
             raise ValueError("duplicate sparse query index")
+        if not np.isfinite(qv).all():
+            raise ValueError("non-finite sparse query value")
         n_drop = int(np.floor(drop_ratio * len(qi)))
         if n_drop:
             order = np.lexsort((-np.arange(len(qi)), np.abs(qv)))  # |v| asc, later entry first

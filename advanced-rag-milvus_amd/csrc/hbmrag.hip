@@ -91,12 +91,12 @@ struct Workspace {
     hipStream_t side = nullptr;    // side stream + events of hr_search_hybrid_dev
     hipEvent_t ev_scan = nullptr, ev_side = nullptr;
     struct Workspace* sparse_ws = nullptr;  // private buffers of the sparse chain when it runs concurrently
-    DevBuf qfrag, qn2, gmax, bmax, cand, acut, cscore, crow, flags, qscale, qeps, pq_n, pq_idx, pq_w;
+    DevBuf qfrag, qn2, gmax, bmax, cand, acut, cscore, crow, flags, qscale, qeps, qfloor, pq_n, pq_idx, pq_w;
     DevBuf d_q, d_ids, d_scores, d_mask;          // host-form staging
     DevBuf d_qptr, d_qidx, d_qval;                // sparse query staging
     DevBuf f_ids, f_out_ids, f_out_scores, f_out_meth, f_n;  // hr_fuse_rrf staging
     void release() {
-        for (DevBuf* b : {&qfrag, &qn2, &gmax, &bmax, &qscale, &qeps, &pq_n, &pq_idx, &pq_w, &cand, &acut, &cscore, &crow, &flags, &d_q, &d_ids, &d_scores,
+        for (DevBuf* b : {&qfrag, &qn2, &gmax, &bmax, &qscale, &qeps, &qfloor, &pq_n, &pq_idx, &pq_w, &cand, &acut, &cscore, &crow, &flags, &d_q, &d_ids, &d_scores,
                           &d_mask, &d_qptr, &d_qidx, &d_qval, &f_ids, &f_out_ids, &f_out_scores, &f_out_meth, &f_n})
             b->release();
         if (stream) (void)hipStreamDestroy(stream);
@@ -145,6 +145,7 @@ struct hr_index {
     // n_sparse rows added; n_csr / nnz_csr of them in the device CSR; n_sparse_built of them in the postings
     int64_t n_sparse = 0, n_csr = 0, nnz_csr = 0, n_sparse_built = 0;
     float max_sparse_abs = 0.f;  // max |doc weight|: bounds the scan's fixed-point range
+    bool sparse_signed = false;  // some stored weight is negative: the scan's products can cancel (sparse.h)
     DevBuf s_indptr, s_idx, s_val, rt_off, range_base, post;  // post: packed (fp16 weight | u16 accumulator slot)
     DevBuf idle_post;  // 64 x 4 idle postings: what scan lanes with nothing to fetch read (sparse.h)
     int64_t n_ranges = 0;
@@ -471,11 +472,14 @@ hipError_t launch_scan_gemm_g(const hr_index* h, hipStream_t s, const chunk_t* q
                            h->scale.as<float>(), mask, gmax, nq, h->KT, h->n_rows, n_super);
     return hipGetLastError();
 }
+constexpr int kScanTileKiB = 156;   // LDS the LDS-resident pass's query tile may take: G * KT KiB
 int max_groups_for_dim(const hr_index* h) {
-    // query tile must fit LDS: G * KT KiB <= 144 KiB
-    int g = 156 / std::max(h->KT, 1);
+    int g = kScanTileKiB / std::max(h->KT, 1);
     return std::max(1, std::min(4, g));
 }
+// fp32 rows longer than 2496 (KT > 156) do not fit even one group of 16 queries: every batch of such a shard takes the
+// k-chunked pass, whose LDS does not grow with KT
+bool scan_tile_fits(const hr_index* h) { return max_groups_for_dim(h) * h->KT <= kScanTileKiB; }
 
 // Two-level candidate selection: per-bucket maxima, then one block per query — for one modality or for both
 // modalities of a hybrid search in one pair of launches (select.h: GroupSelPair).
@@ -617,6 +621,7 @@ TopkArgs sparse_topk_args(const hr_index* h, Workspace* ws, int C, int GR, int k
     a.row_offset = h->row_offset;
     a.a_cut = ws->acut.as<float>();
     a.cut_floor = 0.0f;
+    a.cut_floor_q = ws->qfloor.as<float>();   // 0, or -q_eps when products can be negative (sparse_query_prep_kernel)
     a.eps_abs = 0.0f;
     a.eps_abs_q = ws->qeps.as<float>();
     a.eps_rel = (float)(std::ldexp(1.0, -11) * 1.01 + std::ldexp(1.0, -22));  // fp16 posting weights
@@ -723,7 +728,10 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
     const int64_t n_groups = n_super * (kSuperRows / GR);  // group maxima per query (tail groups hold -inf)
     const int Gsmall = max_groups_for_dim(h);
     // batches beyond what fits LDS whole go through the k-chunked large-batch pass, 128 or 256 queries at a time
-    const bool big = B > 16 * Gsmall && h->KT % 4 == 0 && !(g_dense_kernels & 4);
+    const bool big = (B > 16 * Gsmall || !scan_tile_fits(h)) && h->KT % 4 == 0 && !(g_dense_kernels & 4);
+    if (!big && !scan_tile_fits(h))
+        return fail(h, HR_ELIMIT, "dim=%lld: the query tile does not fit LDS and the k-chunked pass is switched off",
+                    (long long)h->dim);
     const bool prefer_gemm = (g_dense_kernels & 8) != 0;
     const bool use_qreg = qreg_supported(h) && !(prefer_gemm && gemm_supported(h));
     const bool big256 = big && B > 128 && (use_qreg || gemm_supported(h));   // 256 queries per pass
@@ -824,15 +832,19 @@ int sparse_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const int64
     HIP_TRY(h, ws->crow.ensure((size_t)B * C * GR * sizeof(int32_t)));
     HIP_TRY(h, ws->qscale.ensure((size_t)B * sizeof(float)));
     HIP_TRY(h, ws->qeps.ensure((size_t)B * sizeof(float)));
+    HIP_TRY(h, ws->qfloor.ensure((size_t)B * sizeof(float)));
     const int64_t V1 = h->sparse_dim + 1;
     const int stride = (int)round_up(std::max(max_q_nnz, 1), 64);  // fixed-stride query layout for the scan
     if (phases & PHASE_PREP) {
         HIP_TRY(h, ws->pq_n.ensure((size_t)B * 4));
         HIP_TRY(h, ws->pq_idx.ensure((size_t)B * stride * 4));
         HIP_TRY(h, ws->pq_w.ensure((size_t)B * stride * 4));
-        hipLaunchKernelGGL(sparse_query_prep_kernel, dim3(B), dim3(256), 0, s, d_qptr, d_qidx, d_qval,
-                           h->max_sparse_abs, stride, (int)h->sparse_dim, ws->qscale.as<float>(), ws->qeps.as<float>(),
-                           ws->pq_n.as<int32_t>(), ws->pq_idx.as<int32_t>(), ws->pq_w.as<float>());
+        // the largest posting weight after fp16 rounding: a nonzero weight below 2^-24 is stored as 2^-24 (sparse.h)
+        const float max_post_w = h->max_sparse_abs > 0.f ? std::max(h->max_sparse_abs, 0x1p-24f) : 0.f;
+        hipLaunchKernelGGL(sparse_query_prep_kernel, dim3(B), dim3(256), 0, s, d_qptr, d_qidx, d_qval, max_post_w,
+                           (int)h->sparse_signed, stride, (int)h->sparse_dim, ws->qscale.as<float>(),
+                           ws->qeps.as<float>(), ws->qfloor.as<float>(), ws->pq_n.as<int32_t>(),
+                           ws->pq_idx.as<int32_t>(), ws->pq_w.as<float>());
         HIP_TRY(h, hipGetLastError());
     }
     if (phases & PHASE_SCAN) {
@@ -1035,10 +1047,12 @@ int add_dense_impl(hr_index* h, const SRC* rows, int64_t n, bool src_on_device, 
 }
 
 // One CSR batch as hr_add_sparse and hr_load accept it: indptr monotone, indices in [0, sparse_dim) and strictly
-// ascending inside a row, values finite and within the fp16 posting range.  *batch_max receives max |value|.
+// ascending inside a row, values finite and within the fp16 posting range.  *batch_max receives max |value|, *batch_neg
+// whether some value is negative.
 int validate_csr(const hr_index* h, const int64_t* indptr, const int32_t* indices, const float* values, int64_t n,
-                 float* batch_max) {
+                 float* batch_max, bool* batch_neg) {
     float mx = 0.f;
+    bool neg = false;
     for (int64_t r = 0; r < n; ++r) {
         if (indptr[r + 1] < indptr[r]) return fail(h, HR_EINVAL, "indptr not monotone at row %lld", (long long)r);
         int32_t prev = -1;
@@ -1051,10 +1065,12 @@ int validate_csr(const hr_index* h, const int64_t* indptr, const int32_t* indice
             if (std::fabs(values[e]) > 60000.f)
                 return fail(h, HR_ELIMIT, "sparse weight %g in row %lld exceeds the fp16 posting range", (double)values[e], (long long)r);
             mx = std::max(mx, std::fabs(values[e]));
+            neg |= values[e] < 0.f;
             prev = t;
         }
     }
     *batch_max = mx;
+    *batch_neg = neg;
     return HR_OK;
 }
 
@@ -1312,7 +1328,8 @@ int hr_add_sparse(hr_index* h, const int64_t* indptr, const int32_t* indices, co
     const int64_t nnz = indptr[n] - indptr[0];
     if (nnz < 0 || (nnz > 0 && (!indices || !values))) return fail(h, HR_EINVAL, "bad indices/values");
     float batch_max = 0.f;
-    HR_TRY(validate_csr(h, indptr, indices, values, n, &batch_max));
+    bool batch_neg = false;
+    HR_TRY(validate_csr(h, indptr, indices, values, n, &batch_max, &batch_neg));
     std::unique_lock<std::shared_mutex> lk(h->rw);
     if (h->n_sparse + n > (1ll << 31) - 64) return fail(h, HR_ELIMIT, "too many sparse rows");
     try {  // staged on the host only until the next hr_finalize uploads them
@@ -1326,6 +1343,7 @@ int hr_add_sparse(hr_index* h, const int64_t* indptr, const int32_t* indices, co
     }
     h->n_sparse += n;
     h->max_sparse_abs = std::max(h->max_sparse_abs, batch_max);
+    h->sparse_signed = h->sparse_signed || batch_neg;
     h->finalized = false;
     return HR_OK;
 }
@@ -2129,6 +2147,8 @@ static int search_dense_host(hr_index* h, const float* q, int B, int k, const ui
                              int64_t* out_ids, float* out_scores) {
     HR_TRY(check_search_args(h, B, k, true));
     if (!q || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
+    for (int64_t i = 0; i < (int64_t)B * h->dim; ++i)   // the scan's bound (and the ranking) assume finite queries
+        if (!std::isfinite(q[i])) return fail(h, HR_EINVAL, "non-finite value in query %lld", (long long)(i / h->dim));
     std::shared_lock<std::shared_mutex> lk(h->rw);
     DeviceGuard dg(h->device);
     if (h->n_rows == 0) {
@@ -2196,6 +2216,8 @@ static int search_sparse_host(hr_index* h, const int64_t* q_indptr, const int32_
         if (e1 < e0) return fail(h, HR_EINVAL, "query indptr not monotone");
         const int nnz = (int)(e1 - e0);
         if (nnz > 0 && (!q_idx || !q_val)) return fail(h, HR_EINVAL, "null query arrays");
+        for (int64_t e = e0; e < e1; ++e)   // before drop_ratio: a NaN has no place in the |value| order
+            if (!std::isfinite(q_val[e])) return fail(h, HR_EINVAL, "non-finite value in sparse query %d", b);
         std::vector<int> order(nnz);
         for (int i = 0; i < nnz; ++i) order[i] = i;
         const int n_drop = (int)std::floor((double)drop_ratio * nnz);

@@ -275,7 +275,7 @@ __global__ __launch_bounds__(1024) void select_groups_kernel(GroupSelPair p) {
 // best K by (score desc, row asc), sorted, as global ids.  flags[q] = 1 when
 // the result is provably the exact top-K of the whole shard:
 //   every group was a candidate, or nothing outside can qualify
-//   (a_cut <= floor), or K rows were found and the K-th canonical score beats
+//   (a_cut <= floor, the floor lowered by the error bound where the bound is not a fraction of the score), or K rows were found and the K-th canonical score beats
 //   a_cut by more than the scan's error bound.
 // norm_mode: 0 = scores compare to a_cut as they are; 1 = divide by |q| first
 // (inner-product metric: the scan works on the unit-normalised query).
@@ -286,6 +286,7 @@ struct TopkArgs {
     int64_t row_offset;
     const float* a_cut;
     float cut_floor, eps_abs;
+    const float* cut_floor_q;  // [B] per-query floor instead of cut_floor (sparse: -q_eps when products can be negative)
     const float* eps_abs_q;
     float eps_rel;
     int norm_mode;
@@ -334,8 +335,9 @@ __device__ inline void select_topk_block(const TopkArgs& a, int q, KeyFn key, Se
     }
     if (a.flags && threadIdx.x == 0) {
         const float cut = a.a_cut[q];
+        const float floor_q = a.cut_floor_q ? a.cut_floor_q[q] : a.cut_floor;
         int exact = 0;
-        if (cut == -__builtin_inff() || cut <= a.cut_floor) {
+        if (cut == -__builtin_inff() || cut <= floor_q) {
             exact = 1;
         } else if (found == K) {
             uint64_t kth = sel[0];

@@ -172,23 +172,37 @@ __global__ void sparse_pad_kernel(const unsigned int* __restrict__ rt_off, const
 // It also re-lays the CSR queries out at a fixed stride (pq_idx / pq_w = weight*scale, zero padded,
 // pq_n = term count), so a scan block can fetch its query's terms without first waiting for q_indptr:
 // one dependent round trip less per block.
+// max_doc_w is the largest |posting weight| AFTER fp16 rounding (the host raises a nonzero maximum to the smallest
+// subnormal, 2^-24, which is what a tinier weight is stored as), so that the int32 headroom holds for every posting.
+// Signed products (doc_signed != 0: the shard stores a negative weight; or a negative query weight): the fp16 rounding
+// of a posting errs by up to 2^-11 of |w_q * w_d|, and with cancellation that is no longer a fraction of the score,
+// so 2^-11 * 1.01 * sum|w_q| * max|doc w| joins the absolute part, and q_floor = -q_eps: a list is proven by "nothing
+// outside the candidates scores above 0" only when the largest outside maximum is below 0 by the whole bound.  For
+// unsigned products q_floor = 0 (a positive product always counts at least 1 unit, see above).
+// A scale that is 0 or not finite (sum|w_q| * max|doc w| outside the fp32 range) leaves the scan blind: q_eps = inf and
+// q_floor = -inf, so the list is never proven and the host forms escalate to every group.
 __global__ __launch_bounds__(256) void sparse_query_prep_kernel(const int64_t* __restrict__ q_indptr,
                                                                 const int32_t* __restrict__ q_idx,
                                                                 const float* __restrict__ q_val, float max_doc_w,
-                                                                int stride, int sparse_dim, float* __restrict__ q_scale,
-                                                                float* __restrict__ q_eps, int32_t* __restrict__ pq_n,
+                                                                int doc_signed, int stride, int sparse_dim,
+                                                                float* __restrict__ q_scale, float* __restrict__ q_eps,
+                                                                float* __restrict__ q_floor, int32_t* __restrict__ pq_n,
                                                                 int32_t* __restrict__ pq_idx,
                                                                 float* __restrict__ pq_w) {
     // q_eps = absolute part of the scan's error bound: fixed-point rounding 2*(nnz+1)/scale plus the
-    // fp16 floor of tiny doc weights (6e-8 per unit of query weight); the relative part (fp16
-    // rounding of normal weights, 2^-11) is passed to select_topk as eps_rel.
+    // fp16 floor of tiny doc weights (6e-8 per unit of query weight), plus the signed term above; the relative
+    // part (fp16 rounding of normal weights, 2^-11) is passed to select_topk as eps_rel.
     __shared__ float part[256];
     const int qi = blockIdx.x, tid = threadIdx.x;
     const int64_t t0 = q_indptr[qi], t1 = q_indptr[qi + 1];
     float s = 0.f;
-    for (int64_t i = t0 + tid; i < t1; i += 256) s += fabsf(q_val[i]);
+    int neg = 0;
+    for (int64_t i = t0 + tid; i < t1; i += 256) {
+        s += fabsf(q_val[i]);
+        neg |= q_val[i] < 0.f;
+    }
     part[tid] = s;
-    __syncthreads();
+    const int any_neg = __syncthreads_or(neg);
     for (int off = 128; off > 0; off >>= 1) {  // fixed tree: the same value in every launch
         if (tid < off) part[tid] += part[tid + off];
         __syncthreads();
@@ -197,10 +211,15 @@ __global__ __launch_bounds__(256) void sparse_query_prep_kernel(const int64_t* _
     const float scale = bound > 0.f ? 1073741824.0f / bound : 0.f;
     if (tid == 0) {
         q_scale[qi] = scale;
+        const bool blind = part[0] > 0.f && !(scale > 0.f && scale < __builtin_inff());
         // a query longer than the caller's max_q_nnz would be truncated by the fixed-stride layout: make its
         // list "never proven" so it is redone through the host form
-        q_eps[qi] = (t1 - t0 > stride) ? __builtin_inff()
-                                       : (scale > 0.f ? 2.0f * (float)(t1 - t0 + 1) / scale + part[0] * 6.0e-8f : 0.f);
+        float eps = (t1 - t0 > stride || blind) ? __builtin_inff()
+                    : (scale > 0.f ? 2.0f * (float)(t1 - t0 + 1) / scale + part[0] * 6.0e-8f : 0.f);
+        const bool is_signed = doc_signed || any_neg;
+        if (is_signed) eps += 1.01f * 0x1p-11f * bound;
+        q_eps[qi] = eps;
+        q_floor[qi] = (is_signed || !(eps < __builtin_inff())) ? -eps : 0.f;
         pq_n[qi] = (int32_t)min((int64_t)stride, t1 - t0);
     }
     for (int i = tid; i < stride; i += 256) {

@@ -75,7 +75,9 @@ enum { HR_METRIC_IP = 0, HR_METRIC_COSINE = 1 }; /* dense metric_type           
 enum { HR_METHOD_SEMANTIC = 1, HR_METHOD_SPARSE = 2, HR_METHOD_DOMAIN = 4 };
 
 #define HR_MAX_TOPK 256  /* reference clamps top_k to 100 and over-retrieves 2x (constants.py:47, retrieval.py:351) */
-#define HR_MAX_DIM 4096  /* dense dimension limit of the LDS-resident query tile */
+#define HR_MAX_DIM 4096  /* dense dimension limit; fp32 rows longer than 2496 (and fp16 ones longer than 4992, beyond
+                          this limit) leave no room for the LDS-resident query tile, and every batch of such a shard
+                          takes the k-chunked pass */
 #define HR_MAX_QUERY_NNZ 4096
 
 /* ---- lifecycle -------------------------------------------------------------
@@ -133,6 +135,7 @@ HR_API int64_t hr_device_bytes(const hr_index* h);    /* HBM held by the shard *
 /* ---- search (host buffers, synchronous) --------------------------------------
  * Replace Collection.search on "semantic_index" / "sparse_index"
  * (reference indexing.py:503-525) for a batch of B queries.
+ * Query values must be finite: the host forms (the _dmask forms included) refuse a NaN or an infinity with HR_EINVAL.
  *   q        [B*dim] fp32 query vectors
  *   rowmask  optional bitmask over local rows, 1 bit per row (bit r%8 of byte
  *            r/8), 1 = row passes the filter expression; NULL = all rows
@@ -165,7 +168,12 @@ HR_API int hr_fuse_rrf(hr_index* h, const int64_t* ids_a, int na, const int64_t*
 /* ---- search (device buffers, asynchronous on `stream`) -------------------------
  * Same results as the host forms.  d_flags[B] (optional) receives 1 when the
  * candidate-generation bound proves the list exact, 0 when the caller must
- * re-run that query through the host form (which escalates by itself). */
+ * re-run that query through the host form (which escalates by itself).
+ * The device forms do not look at the query values on the host: finite values are
+ * the caller's to check (pack_sparse_queries does it for the sparse CSR).
+ * Sparse weights may be signed (documents and queries): where products can be negative
+ * the bound widens by 2^-11 * sum|w_q| * max|doc w| and such lists are proven less
+ * often; a query whose sum|w_q| * max|doc w| leaves the fp32 range is never proven. */
 /* The sparse form takes queries already reduced (drop_ratio applied) and
  * sorted by index, as CSR; max_q_nnz = the longest query (sets the scan's
  * rounding bound). */
