@@ -276,6 +276,7 @@ class HybridSearchEngine:
         if weights is not None and (weights.dtype != t.float64 or tuple(weights.shape) != (B, 3) or not weights.is_contiguous()):
             raise ValueError("weights must be a contiguous float64 [B, 3] device tensor")
         b["w_query"] = weights          # kept alive until the next call reuses the buffer set
+        b["rowmask"] = rowmask          # resolve_inexact redoes unproven lists over the same rows
         return self._post_lists(b, B, stream)
 
     def _post_args(self, b: dict, B: int, n_lists: int, gathered) -> "nat.PostArgs":
@@ -352,8 +353,9 @@ class HybridSearchEngine:
                         domain_q_host: Optional[np.ndarray] = None) -> int:
         """The device forms report, per (modality, query), whether the list is PROVEN exact.  For the rare ones
         that are not (ties at the candidate cut), redo those queries through the host forms — which widen the
-        candidate set until the proof holds — patch the lists and redo exchange / fusion / rerank.  `sparse_host`
-        holds the queries as given to pack_sparse_queries (before the drop).  Call after synchronising the batch.
+        candidate set until the proof holds, over the rows of the batch's `rowmask` — patch the lists and redo
+        exchange / fusion / rerank.  `sparse_host` holds the queries as given to pack_sparse_queries (before the
+        drop).  Call after synchronising the batch.
 
         On a sharded corpus EVERY rank calls this with the same arguments: the exchanged flags (minimum over ranks,
         the same on every rank) decide which queries are redone, each rank repairs the lists ITS shard could not
@@ -366,14 +368,16 @@ class HybridSearchEngine:
         own = b["flags"].cpu().numpy()
         redone = 0
         B = own.shape[1]
+        rowmask = b.get("rowmask")
+        d_mask = rowmask.data_ptr() if rowmask is not None else 0
         for m in range(b["n_mod"]):
             bad = np.nonzero((agg[m] == 0) & (own[m] == 0))[0]
             if not len(bad):
                 continue
             if m == 0:
-                ids, sc = self.h.search_dense(np.ascontiguousarray(q_host[bad]), b["kp"])
+                ids, sc = self.h.search_dense(np.ascontiguousarray(q_host[bad]), b["kp"], None, d_mask)
             elif m < b["n_main"]:
-                ids, sc = self.h.search_sparse([sparse_host[i] for i in bad], b["kp"], drop_ratio)
+                ids, sc = self.h.search_sparse([sparse_host[i] for i in bad], b["kp"], drop_ratio, None, d_mask)
             else:
                 ids, sc = self.hd.search_dense(np.ascontiguousarray(domain_q_host[bad]), self.cfg.top_k)
                 sel = t.from_numpy(bad).to(self.device)
