@@ -14,7 +14,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 HR_F32, HR_F16 = 0, 1
-HR_METRIC_IP, HR_METRIC_COSINE = 0, 1
+HR_METRIC_IP, HR_METRIC_COSINE, HR_METRIC_L2 = 0, 1, 2
 HR_METHOD_SEMANTIC, HR_METHOD_SPARSE, HR_METHOD_DOMAIN = 1, 2, 4
 HR_MAX_TOPK = 256
 HR_N_PHASES = 10
@@ -95,6 +95,8 @@ _SIGNATURES = {
                                    _c.c_double, _c.c_double, _c.c_double, _c.c_int, _c.c_int, _c.c_void_p,
                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_merge_topk_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int,
+                                     _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_merge_topk_asc_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_int64, _c.c_int, _c.c_int,
                                      _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_post_lists_dev": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p]),
     "hr_stream_create": (_c.c_int, [_c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_void_p)]),
@@ -424,9 +426,10 @@ def _raise_global(L, rc: int):
 
 
 def merge_topk_dev(d_scores: int, d_ids: int, n_lists: int, B: int, k_in: int, k_out: int, d_out_ids: int,
-                   d_out_scores: int, stream: int = 0, score_stride: int = 0, id_stride: int = 0):
+                   d_out_scores: int, stream: int = 0, score_stride: int = 0, id_stride: int = 0, ascending: bool = False):
+    """hr_merge_topk_dev, or with ascending=True hr_merge_topk_asc_dev (the distance lists of an L2 collection)."""
     L = load_library()
-    rc = L.hr_merge_topk_dev(_vp(d_scores), _vp(d_ids), n_lists, score_stride or B * k_in, id_stride or B * k_in, B,
+    rc = (L.hr_merge_topk_asc_dev if ascending else L.hr_merge_topk_dev)(_vp(d_scores), _vp(d_ids), n_lists, score_stride or B * k_in, id_stride or B * k_in, B,
                              k_in, k_out, _vp(d_out_ids), _vp(d_out_scores), _vp(stream) if stream else None)
     if rc != 0:
         _raise_global(L, rc)
@@ -482,7 +485,7 @@ class PostArgs(ctypes.Structure):
         ("fused_ids", _c.c_void_p), ("fused_scores", _c.c_void_p), ("fused_methods", _c.c_void_p),
         ("fused_n", _c.c_void_p), ("top_k", _c.c_int32), ("rerank", _c.c_int32), ("base_w", _c.c_double),
         ("method_bonus", _c.c_double), ("recency_w", _c.c_double), ("recency", _c.c_void_p), ("k_out", _c.c_int32),
-        ("reserved", _c.c_int32), ("rr_ids", _c.c_void_p), ("rr_scores", _c.c_void_p), ("rr_orig", _c.c_void_p),
+        ("asc_mask", _c.c_int32), ("rr_ids", _c.c_void_p), ("rr_scores", _c.c_void_p), ("rr_orig", _c.c_void_p),
         ("flags", _c.c_void_p), ("flag_stride", _c.c_int64), ("n_flag_rows", _c.c_int32), ("reserved2", _c.c_int32),
         ("agg_flags", _c.c_void_p), ("w_query", _c.c_void_p),
     ]

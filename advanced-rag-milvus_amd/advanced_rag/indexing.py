@@ -73,6 +73,23 @@ class IndexConfig:
             self.index_params = {"M": 16, "efConstruction": 200}
 
 
+METRIC_NAMES = ("L2", "IP", "COSINE")
+
+
+def metric_code(name: str) -> int:
+    """Milvus' dense metric_type ("L2" | "IP" | "COSINE") -> the HR_METRIC_* code of include/hbmrag.h."""
+    from . import _native as nat
+    codes = {"L2": nat.HR_METRIC_L2, "IP": nat.HR_METRIC_IP, "COSINE": nat.HR_METRIC_COSINE}
+    if not isinstance(name, str) or name not in codes:
+        raise ValueError(f"unknown metric_type {name!r}: expected one of {', '.join(METRIC_NAMES)}")
+    return codes[name]
+
+
+def metric_name(code) -> str:
+    """The label of a shard handle's metric code; handles that carry none (stubs) are COSINE collections."""
+    return {0: "IP", 1: "COSINE", 2: "L2"}.get(code, "COSINE")
+
+
 class ShardCollection:
     """What `manager.collections[name]` holds: a named view of one ShardSet (the
     collection's shard handles, one per device) with the handful of Collection methods the reference calls
@@ -111,8 +128,11 @@ class MilvusIndexManager:
     def __init__(self, host: str = "localhost", port: int = 19530, enable_sharding: bool = True, num_shards: int = 4,
                  semantic_dim: int = 1536, sparse_dim: int = 10000, domain_dim: int = 768, connect: bool = True,
                  *, dtype: str = "float16", device: int = 0, devices: Optional[Sequence[int]] = None,
-                 enable_domain: bool = True, device_embedding_cache: int = 0, coalesce: bool = True):
+                 enable_domain: bool = True, device_embedding_cache: int = 0, coalesce: bool = True,
+                 semantic_metric: str = "COSINE", domain_metric: str = "COSINE"):
         self.host, self.port = host, port
+        metric_code(semantic_metric), metric_code(domain_metric)   # ValueError for anything but L2 / IP / COSINE
+        self.semantic_metric, self.domain_metric = semantic_metric, domain_metric
         self.enable_sharding, self.num_shards = enable_sharding, num_shards
         self.semantic_dim, self.sparse_dim, self.domain_dim = semantic_dim, sparse_dim, domain_dim
         # devices = GPU of every shard (a device may be named more than once); default: one shard on `device`
@@ -158,18 +178,18 @@ class MilvusIndexManager:
         nat = self._native
         store = nat.HR_F16 if self.dtype in ("float16", "fp16", "f16") else nat.HR_F32
         sparse_on = os.getenv("ENABLE_SPARSE", "1") == "1"
-        self._main = ShardSet([nat.ShardHandle(self.semantic_dim, store, nat.HR_METRIC_COSINE,
+        self._main = ShardSet([nat.ShardHandle(self.semantic_dim, store, metric_code(self.semantic_metric),
                                                self.sparse_dim if sparse_on else 0, d) for d in self.devices])
         self.collections["semantic_index"] = ShardCollection(self, "semantic_index", "dense", self._main,
-                                                             self.semantic_dim, "COSINE")
+                                                             self.semantic_dim, self.semantic_metric)
         if sparse_on:
             self.collections["sparse_index"] = ShardCollection(self, "sparse_index", "sparse", self._main,
                                                                self.sparse_dim, "IP")
         if self.enable_domain:
-            self._domain = ShardSet([nat.ShardHandle(self.domain_dim, store, nat.HR_METRIC_COSINE, 0, d)
+            self._domain = ShardSet([nat.ShardHandle(self.domain_dim, store, metric_code(self.domain_metric), 0, d)
                                      for d in self.devices])
             self.collections["domain_index"] = ShardCollection(self, "domain_index", "dense", self._domain,
-                                                               self.domain_dim, "COSINE")
+                                                               self.domain_dim, self.domain_metric)
 
     def attach_shards(self, handles, rows_of=None, synthetic_rows: int = 0, process_group=None, first_row: int = 0,
                       local_ids: bool = False):
@@ -203,8 +223,10 @@ class MilvusIndexManager:
         else:
             self._main = local
         self.devices = [h.device for h in handles]
+        # the collection's metric is the handles' own (COSINE for a handle that carries none)
+        self.semantic_metric = metric_name(getattr(handles[0], "metric", None))
         self.collections["semantic_index"] = ShardCollection(self, "semantic_index", "dense", self._main,
-                                                             self.semantic_dim, "COSINE")
+                                                             self.semantic_dim, self.semantic_metric)
         if handles[0].sparse_dim:
             self.collections["sparse_index"] = ShardCollection(self, "sparse_index", "sparse", self._main,
                                                                self.sparse_dim, "IP")
@@ -558,12 +580,12 @@ class MilvusIndexManager:
             if n_shards != len(self.devices):
                 raise ValueError(f"snapshot has {n_shards} shards, this manager was created with {len(self.devices)} devices")
             main = [nat.ShardHandle.load(os.path.join(directory, f"main.{s}.hbmrag"), self.semantic_dim, store,
-                                         nat.HR_METRIC_COSINE, self.sparse_dim if sparse_on else 0, d)
+                                         metric_code(self.semantic_metric), self.sparse_dim if sparse_on else 0, d)
                     for s, d in enumerate(self.devices)]
             self._main.adopt(main, [z[f"rows_main_{s}"] for s in range(n_shards)])
             if self._domain is not None and os.path.exists(os.path.join(directory, "domain.0.hbmrag")):
                 dom = [nat.ShardHandle.load(os.path.join(directory, f"domain.{s}.hbmrag"), self.domain_dim, store,
-                                            nat.HR_METRIC_COSINE, 0, d) for s, d in enumerate(self.devices)]
+                                            metric_code(self.domain_metric), 0, d) for s, d in enumerate(self.devices)]
                 self._domain.adopt(dom, [z[f"rows_domain_{s}"] for s in range(n_shards)])
             self._synthetic_rows = int(z["synthetic_rows"])
             self._deleted = z["deleted"].copy() if z["deleted"].size else None
@@ -591,7 +613,7 @@ class MilvusIndexManager:
             sparse_on = os.getenv("ENABLE_SPARSE", "1") == "1"
             dev = self.devices[0] if device is None else device
             h = nat.ShardHandle.load(os.path.join(directory, f"main.{rank}.hbmrag"), self.semantic_dim, store,
-                                     nat.HR_METRIC_COSINE, self.sparse_dim if sparse_on else 0, dev)
+                                     metric_code(self.semantic_metric), self.sparse_dim if sparse_on else 0, dev)
             synthetic = int(z["synthetic_rows"])
             if rank == 0:
                 self._deleted = z["deleted"].copy() if z["deleted"].size else None
@@ -673,8 +695,9 @@ class MilvusIndexManager:
         return out
 
     def _search_params(self, coll, search_params: Optional[Dict]) -> Dict:
+        # no search_params: the collection's own metric (Milvus refuses a metric_type that differs from the index's)
         params = search_params or ({"metric_type": "IP"} if coll.kind == "sparse"
-                                   else {"metric_type": "COSINE", "params": {"ef": 64}})
+                                   else {"metric_type": coll.metric, "params": {"ef": 64}})
         metric = params.get("metric_type", coll.metric)
         if metric != coll.metric:
             raise ValueError(f"metric_type {metric} does not match collection {coll.name} ({coll.metric})")

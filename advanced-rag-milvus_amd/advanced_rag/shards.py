@@ -24,8 +24,19 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 
-def merge_lists(ids: Sequence[np.ndarray], scores: Sequence[np.ndarray], k: int) -> Tuple[np.ndarray, np.ndarray]:
-    """Merge per-shard top-k lists ([B,k] each, -1 padded) -> [B,k] by (score desc, id asc)."""
+HR_METRIC_L2 = 2   # include/hbmrag.h; a handle of that metric returns squared distances, smallest first
+
+
+def dense_ascending(handle) -> bool:
+    """True when `handle`'s dense lists are distances (ascending): an L2 shard.  Handles without a `metric` (test stubs)
+    are similarity shards."""
+    return getattr(handle, "metric", None) == HR_METRIC_L2
+
+
+def merge_lists(ids: Sequence[np.ndarray], scores: Sequence[np.ndarray], k: int,
+                ascending: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """Merge per-shard top-k lists ([B,k] each, -1 padded) -> [B,k] by (score desc, id asc); with ascending=True (the
+    distance lists of an L2 collection) by (score asc, id asc)."""
     all_ids = np.concatenate(ids, axis=1)
     all_sc = np.concatenate(scores, axis=1)
     B = all_ids.shape[0]
@@ -33,7 +44,8 @@ def merge_lists(ids: Sequence[np.ndarray], scores: Sequence[np.ndarray], k: int)
     out_sc = np.zeros((B, k), dtype=np.float32)
     for b in range(B):
         live = np.nonzero(all_ids[b] >= 0)[0]
-        order = live[np.lexsort((all_ids[b][live], -all_sc[b][live].astype(np.float64)))][:k]
+        key = all_sc[b][live].astype(np.float64)
+        order = live[np.lexsort((all_ids[b][live], key if ascending else -key))][:k]
         out_ids[b, :len(order)] = all_ids[b][order]
         out_sc[b, :len(order)] = all_sc[b][order]
     return out_ids, out_sc
@@ -196,7 +208,11 @@ class ShardSet:
             return [fn(0)]
         return list(self._pool.map(fn, range(self.n_shards)))
 
-    def _gather(self, parts, k: int):
+    @property
+    def dense_ascending(self) -> bool:
+        return dense_ascending(self.handles[0])
+
+    def _gather(self, parts, k: int, ascending: bool = False):
         if self.n_shards == 1:
             return parts[0]
         ids, scores = [], []
@@ -204,7 +220,7 @@ class ShardSet:
             gi = np.where(li >= 0, self.rows_of[s][np.maximum(li, 0)] if len(self.rows_of[s]) else -1, -1)
             ids.append(gi.astype(np.int64))
             scores.append(sc)
-        return merge_lists(ids, scores, k)
+        return merge_lists(ids, scores, k, ascending)
 
     def search_dense(self, q: np.ndarray, k: int, keep: Optional[np.ndarray] = None):
         """q [B, dim] float32; keep = boolean filter over GLOBAL rows (or None) -> (ids [B,k] global rows, scores)."""
@@ -213,7 +229,7 @@ class ShardSet:
                 B = np.atleast_2d(q).shape[0]
                 return np.full((B, k), -1, np.int64), np.zeros((B, k), np.float32)
             return self.handles[s].search_dense(q, k, *self._local_mask(s, keep))
-        return self._gather(self._fan_out(one), k)
+        return self._gather(self._fan_out(one), k, self.dense_ascending)
 
     def search_sparse(self, queries, k: int, drop_ratio: float = 0.0, keep: Optional[np.ndarray] = None):
         def one(s):
@@ -617,13 +633,13 @@ class CollectiveShardSet:
         if bad:
             raise RuntimeError(f"search round failed on rank(s) {bad}")
         out, o = [], 2
-        for B in (Bd, Bs):
+        for B, asc in ((Bd, self.local.dense_ascending), (Bs, False)):
             if not B:
                 out.append(None)
                 continue
             ids = [p[o: o + B * k].reshape(B, k) for p in parts]
             scs = [p[2 + n_vals + (o - 2): 2 + n_vals + (o - 2) + B * k].astype(np.int32).view(np.float32).reshape(B, k) for p in parts]
-            out.append(merge_lists(ids, scs, k))
+            out.append(merge_lists(ids, scs, k, asc))
             o += B * k
         return out
 

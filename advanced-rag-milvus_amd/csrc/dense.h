@@ -32,10 +32,11 @@ __global__ void tile_rows_kernel(const SRC* __restrict__ src, int64_t n, int dim
 }
 
 // One thread per row: sum of squares in fp64, k-ordered (the canonical norm the
-// oracle restates), and the fp32 scan scale (1/||x|| for COSINE, 1 for IP).
+// oracle restates), and the fp32 per-row term of the scan's epilogue: the scale 1/||x|| for COSINE, 1 for IP; for L2 the
+// additive term |x|^2 / 2 (the L2 scans compute acc - term * coef instead of acc * scale, see dense_scan_kernel).
 template <typename STORE>
 __global__ void row_norms_kernel(const chunk_t* __restrict__ tiles, int KT, int64_t row0, int64_t n,
-                                 int cosine, double* __restrict__ norm2, float* __restrict__ scale,
+                                 int metric, double* __restrict__ norm2, float* __restrict__ scale,
                                  unsigned int* __restrict__ max_norm_bits) {
     constexpr int EPC = kChunkBytes / (int)sizeof(STORE);
     int64_t r = row0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -52,7 +53,8 @@ __global__ void row_norms_kernel(const chunk_t* __restrict__ tiles, int KT, int6
     }
     norm2[r] = s;
     float nrm = (float)sqrt(s);
-    scale[r] = cosine ? (s > 0.0 ? (float)(1.0 / sqrt(s)) : 0.0f) : 1.0f;
+    if (metric == HR_METRIC_L2) scale[r] = (float)(0.5 * s);
+    else scale[r] = metric == HR_METRIC_COSINE ? (s > 0.0 ? (float)(1.0 / sqrt(s)) : 0.0f) : 1.0f;
     atomicMax(max_norm_bits, __float_as_uint(nrm));  // non-negative floats order as uints
 }
 
@@ -60,9 +62,13 @@ __global__ void row_norms_kernel(const chunk_t* __restrict__ tiles, int KT, int6
 // query prep: one block per query slot.  Writes the unit-normalised query in
 // the B-operand fragment layout of the scan (fp16 or fp32 to match the shard)
 // and the canonical fp64 |q|^2.  Slots >= B are zero-filled padding.
+// L2 shards (qcoef != nullptr) also get, per slot, the coefficient of the row term, 1 / |q| (1 for a zero query, whose
+// fragments are zero: the scan then ranks by -|x|^2 / 2), and the per-query part of the scan's error bound,
+// rt_eps / |q| (infinite when it leaves the fp32 range: such a list is never proven); padding slots get 0.
 template <typename STORE>
 __global__ void prep_queries_kernel(const float* __restrict__ q, int B, int dim, int KT,
-                                    chunk_t* __restrict__ qfrag, double* __restrict__ qn2) {
+                                    chunk_t* __restrict__ qfrag, double* __restrict__ qn2,
+                                    float* __restrict__ qcoef, float* __restrict__ qeps, float rt_eps) {
     constexpr int EPC = kChunkBytes / (int)sizeof(STORE);
     const int slot = blockIdx.x;
     const int g = slot >> 4, col = slot & 15;
@@ -83,6 +89,13 @@ __global__ void prep_queries_kernel(const float* __restrict__ q, int B, int dim,
             qn2[slot] = s;
         }
         s_inv = (s > 0.0) ? (float)(1.0 / sqrt(s)) : 0.0f;
+        if (qcoef) {
+            const float c = slot < B ? ((s > 0.0) ? (float)(1.0 / sqrt(s)) : 1.0f) : 0.0f;
+            float e = rt_eps * c * 1.000001f;
+            if (!(e < 3.0e38f)) e = __builtin_inff();
+            qcoef[slot] = c;
+            qeps[slot] = e;
+        }
     }
     __syncthreads();
     const float inv = s_inv;
@@ -134,11 +147,14 @@ struct Mfma<float> {
 
 // PF = depth of the per-wave register prefetch ring (k-steps in flight); KT is
 // padded to a multiple of PF at hr_create so ring slots stay compile-time.
-template <typename STORE, int G, int RS, int PF, int NRB>
+// L2 = the squared-Euclidean form (compile time: the COSINE / IP instantiations are what they were): `scale` then holds
+// the row terms |x|^2 / 2, qcoef[16 g + c] the coefficient 1 / |q| of query slot 16 g + c, and the epilogue is
+// acc - term * coef = (2 x.q - |x|^2) / (2 |q|): larger = nearer, so everything downstream of the maxima is unchanged.
+template <typename STORE, int G, int RS, int PF, int NRB, bool L2 = false>
 __global__ __launch_bounds__(512) void dense_scan_kernel(
     const chunk_t* __restrict__ tiles, const chunk_t* __restrict__ qfrag, const float* __restrict__ scale,
     const uint8_t* __restrict__ rowmask, float* __restrict__ gmax, int nq, int KT, int64_t n_rows,
-    int64_t n_super) {
+    int64_t n_super, const float* __restrict__ qcoef) {
     // NRB = row blocks per candidate group: 4 (64-row groups) or 1 (16-row groups).
     // `group` below walks SUPER-groups of 4 row blocks either way; gmax is [nq][n_super*4/NRB].
     static_assert(NRB == 1 || NRB == kRowBlocksPerSuper, "group = one row block or one super-group");
@@ -156,6 +172,9 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
     const int64_t total_waves = (int64_t)gridDim.x * waves_per_block;
     const int quad = lane >> 4;
     const float NEG_INF = -__builtin_inff();
+    float cf[G];  // L2: this lane's query coefficients (the buffer holds every slot of the pass, padding included)
+#pragma unroll
+    for (int g = 0; g < G; ++g) cf[g] = L2 ? qcoef[16 * g + (lane & 15)] : 0.f;
 
     // Prefetch cursor: walks (group, pair, kt) exactly PF steps ahead of the
     // consumer, across pair and group boundaries, so the wave's HBM stream
@@ -229,7 +248,7 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
                     float mr = NEG_INF;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        float v = acc[s][g][r] * sc[r];
+                        float v = L2 ? acc[s][g][r] - sc[r] * cf[g] : acc[s][g][r] * sc[r];
                         v = (ok[r] != 0.f) ? v : NEG_INF;
                         mr = fmaxf(mr, v);
                     }
@@ -267,11 +286,12 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
 // L2: L2 : HBM traffic = 1 : 1.  MFMA work per corpus KiB is GQ x 16 cycles per
 // SIMD (GQ = 16: 64 cycles per KiB per CU against ~100 cycles per KiB of HBM
 // supply), so the pass stays HBM-bound.
-template <typename STORE, int GQ, int NRB>
+// L2: as in dense_scan_kernel.
+template <typename STORE, int GQ, int NRB, bool L2 = false>
 __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
     const chunk_t* __restrict__ tiles, const chunk_t* __restrict__ qfrag, const float* __restrict__ scale,
     const uint8_t* __restrict__ rowmask, float* __restrict__ gmax, int nq, int KT, int64_t n_rows,
-    int64_t n_super) {
+    int64_t n_super, const float* __restrict__ qcoef) {
     constexpr int RS = 2, BKT = 2, PF = 4;  // query chunk = 2 k-steps (16 staging registers), corpus ring = 4 k-steps
     constexpr int kPairs = kRowBlocksPerSuper / RS;
     constexpr int kFrags = GQ * BKT;           // 1 KiB query fragments per k-chunk
@@ -287,6 +307,9 @@ __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
     const int quad = lane >> 4;
     const float NEG_INF = -__builtin_inff();
     const int n_chunks = KT / BKT;
+    float cf[GQ];  // L2: this lane's query coefficients
+#pragma unroll
+    for (int g = 0; g < GQ; ++g) cf[g] = L2 ? qcoef[16 * g + (lane & 15)] : 0.f;
     const int64_t n_rounds = (n_super + total_waves - 1) / total_waves;  // the same for every wave: lockstep
 
     // corpus prefetch cursor (as in dense_scan_kernel); past the end (and for idle waves) re-read a valid group
@@ -391,7 +414,7 @@ __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
                         float mr = NEG_INF;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            float v = acc[s][g][r] * sc[r];
+                            float v = L2 ? acc[s][g][r] - sc[r] * cf[g] : acc[s][g][r] * sc[r];
                             v = (ok[r] != 0.f) ? v : NEG_INF;
                             mr = fmaxf(mr, v);
                         }
@@ -1140,12 +1163,15 @@ __global__ __launch_bounds__(512) void dense_scan_gemm_kernel(
 // Canonical refine: 64 candidate rows per wave (group_rows = 16 or 64 rows per candidate group); lane = row.
 // score = (float) S with S the k-ordered fp64 sum of exact products.  The same
 // arithmetic is restated in oracle/oracle.c:dense_score().
+// L2 (compile time; metric = HR_METRIC_L2): D = the k-ordered fp64 sum of d * d, d = x[k] - q[k], every operation
+// rounded on its own; the slot's score is -(float) D, so that (score desc, row asc) is (distance asc, row asc) and the
+// selection kernels stay as they are (select_topk_block negates back on the way out).
 // One candidate row slot of query qi: returns false (invalid) or the canonical score and the row.
-template <typename STORE>
+template <typename STORE, bool L2 = false>
 __device__ inline bool refine_dense_slot(const chunk_t* __restrict__ tiles, int KT, int dim, const float* __restrict__ qq,
                                          double qn2_q, const double* __restrict__ norm2,
                                          const uint8_t* __restrict__ rowmask, const int32_t* cand_q, int group_rows,
-                                         int64_t n_rows, int cosine, int slot, float* score, int32_t* row_out) {
+                                         int64_t n_rows, int metric, int slot, float* score, int32_t* row_out) {
     constexpr int EPC = kChunkBytes / (int)sizeof(STORE);
     const int32_t group = cand_q[slot / group_rows];
     const int64_t row = (int64_t)group * group_rows + slot % group_rows;
@@ -1168,7 +1194,14 @@ __device__ inline bool refine_dense_slot(const chunk_t* __restrict__ tiles, int 
 #pragma unroll
             for (int j = 0; j < EPC; ++j) {
                 const int k = (kc_first + u) * EPC + j;
-                if (k < dim) s = __dadd_rn(s, __dmul_rn((double)c[u].e[j], (double)qq[k]));
+                if (L2) {
+                    if (k < dim) {
+                        const double d = __dsub_rn((double)c[u].e[j], (double)qq[k]);
+                        s = __dadd_rn(s, __dmul_rn(d, d));
+                    }
+                } else {
+                    if (k < dim) s = __dadd_rn(s, __dmul_rn((double)c[u].e[j], (double)qq[k]));
+                }
             }
         }
     };
@@ -1194,21 +1227,21 @@ __device__ inline bool refine_dense_slot(const chunk_t* __restrict__ tiles, int 
             lo[u].v = nlo[u].v;
         }
     }
-    if (cosine) {
+    if (!L2 && metric == HR_METRIC_COSINE) {
         double d = norm2[row] * qn2_q;
         s = (d > 0.0) ? s / sqrt(d) : 0.0;
     }
-    *score = (float)s;
+    *score = L2 ? -(float)s : (float)s;
     *row_out = (int32_t)row;
     return true;
 }
 
-template <typename STORE>
+template <typename STORE, bool L2 = false>
 __global__ __launch_bounds__(64) void refine_dense_kernel(
     const chunk_t* __restrict__ tiles, int KT, int dim, const float* __restrict__ q,
     const double* __restrict__ qn2, const double* __restrict__ norm2,
     const uint8_t* __restrict__ rowmask, const int32_t* __restrict__ cand, int C, int group_rows,
-    int64_t n_rows, int cosine, float* __restrict__ out_score, int32_t* __restrict__ out_row) {
+    int64_t n_rows, int metric, float* __restrict__ out_score, int32_t* __restrict__ out_row) {
     const int qi = blockIdx.y, lane = threadIdx.x;
     const int slot = blockIdx.x * 64 + lane;          // candidate row slot of this query
     const int n_slots = C * group_rows;
@@ -1216,8 +1249,8 @@ __global__ __launch_bounds__(64) void refine_dense_kernel(
     const int64_t o = (int64_t)qi * n_slots + slot;
     float sc = -__builtin_inff();
     int32_t row = -1;
-    if (!refine_dense_slot<STORE>(tiles, KT, dim, q + (int64_t)qi * dim, qn2[qi], norm2, rowmask, cand + (int64_t)qi * C,
-                                  group_rows, n_rows, cosine, slot, &sc, &row)) {
+    if (!refine_dense_slot<STORE, L2>(tiles, KT, dim, q + (int64_t)qi * dim, qn2[qi], norm2, rowmask, cand + (int64_t)qi * C,
+                                      group_rows, n_rows, metric, slot, &sc, &row)) {
         sc = -__builtin_inff();
         row = -1;
     }

@@ -29,7 +29,7 @@ struct FinishMod {
     const uint8_t* rowmask;
     // dense
     const chunk_t* tiles;
-    int KT, dim, cosine, dtype;
+    int KT, dim, metric, dtype;
     const float* q;
     const double* qn2;
     const double* norm2;
@@ -149,11 +149,19 @@ __global__ __launch_bounds__(kFinishThreads) void finish_kernel(FinishPair p) {
 #endif
             float sc = 0.f;
             int32_t row = -1;
-            const bool ok = a.dtype == HR_F16
-                                ? refine_dense_slot<_Float16>(a.tiles, a.KT, a.dim, qq, qn2, a.norm2, a.rowmask, s_cand,
-                                                              a.group_rows, a.n_rows, a.cosine, slot, &sc, &row)
-                                : refine_dense_slot<float>(a.tiles, a.KT, a.dim, qq, qn2, a.norm2, a.rowmask, s_cand,
-                                                           a.group_rows, a.n_rows, a.cosine, slot, &sc, &row);
+            bool ok;
+            if (a.metric == HR_METRIC_L2)
+                ok = a.dtype == HR_F16
+                         ? refine_dense_slot<_Float16, true>(a.tiles, a.KT, a.dim, qq, qn2, a.norm2, a.rowmask, s_cand,
+                                                             a.group_rows, a.n_rows, a.metric, slot, &sc, &row)
+                         : refine_dense_slot<float, true>(a.tiles, a.KT, a.dim, qq, qn2, a.norm2, a.rowmask, s_cand,
+                                                          a.group_rows, a.n_rows, a.metric, slot, &sc, &row);
+            else
+                ok = a.dtype == HR_F16
+                         ? refine_dense_slot<_Float16>(a.tiles, a.KT, a.dim, qq, qn2, a.norm2, a.rowmask, s_cand,
+                                                       a.group_rows, a.n_rows, a.metric, slot, &sc, &row)
+                         : refine_dense_slot<float>(a.tiles, a.KT, a.dim, qq, qn2, a.norm2, a.rowmask, s_cand,
+                                                    a.group_rows, a.n_rows, a.metric, slot, &sc, &row);
             s_key[slot] = ok ? rank_key(sc, (uint32_t)row) : 0ull;
         }
     } else {

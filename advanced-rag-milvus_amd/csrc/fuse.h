@@ -148,6 +148,8 @@ __global__ __launch_bounds__(256) void rrf_fuse_kernel(
 
 // Cross-shard merge of one query: n_lists per-shard lists of k_in (score, id) pairs, each SORTED by score
 // descending (what the top-k kernels write; ids < 0 pad the tail) -> the best k_out by (score desc, id asc).
+// asc != 0: the lists are sorted ASCENDING (distances of an L2 collection) and merged by (score asc, id asc): every
+// comparison is made on the negated scores (exact), what is written out are the scores as they came.
 // The lists are staged in LDS (s_id / s_sc: n_lists * k_in entries, s_len: n_lists words) and every entry computes its
 // rank in the merged order from two counts per list (entries with a larger score; entries with the same score, which
 // are then compared one by one: id ascending, and — for exact duplicates, which only a caller that feeds the same list
@@ -158,7 +160,8 @@ __global__ __launch_bounds__(256) void rrf_fuse_kernel(
 __device__ inline void merge_runs_block(int q, const float* __restrict__ scores, const int64_t* __restrict__ ids,
                                         int n_lists, int64_t score_stride, int64_t id_stride, int k_in, int k_out,
                                         int64_t* __restrict__ out_ids, float* __restrict__ out_scores,
-                                        int64_t* s_id, float* s_sc, int* s_len) {
+                                        int64_t* s_id, float* s_sc, int* s_len, int asc = 0) {
+    const float sg = asc ? -1.f : 1.f;
     const int tid = threadIdx.x, nt = blockDim.x;
     const int n = n_lists * k_in;
     for (int r = tid; r < n_lists; r += nt) s_len[r] = k_in;
@@ -168,7 +171,7 @@ __device__ inline void merge_runs_block(int q, const float* __restrict__ scores,
         const int64_t o = (int64_t)q * k_in + p;
         const int64_t i = ids[(int64_t)r * id_stride + o];
         s_id[e] = i;
-        s_sc[e] = scores[(int64_t)r * score_stride + o];
+        s_sc[e] = sg * scores[(int64_t)r * score_stride + o];
         if (i < 0) atomicMin(&s_len[r], p);
     }
     __syncthreads();
@@ -206,7 +209,7 @@ __device__ inline void merge_runs_block(int q, const float* __restrict__ scores,
         }
         if (rank < k_out) {
             out_ids[(int64_t)q * k_out + rank] = i;
-            out_scores[(int64_t)q * k_out + rank] = s;
+            out_scores[(int64_t)q * k_out + rank] = sg * s;
         }
     }
     for (int j = (total < k_out ? total : k_out) + tid; j < k_out; j += nt) {
@@ -225,14 +228,14 @@ __global__ __launch_bounds__(256) void merge_topk_kernel(const float* __restrict
                                                          int64_t score_stride, int64_t id_stride,
                                                          int k_in, int k_out,
                                                          int64_t* __restrict__ out_ids,
-                                                         float* __restrict__ out_scores) {
+                                                         float* __restrict__ out_scores, int asc) {
     extern __shared__ int64_t merge_lds[];
     const int n = n_lists * k_in;
     int64_t* s_id = merge_lds;
     float* s_sc = reinterpret_cast<float*>(s_id + n);
     int* s_len = reinterpret_cast<int*>(s_sc + n);
     merge_runs_block(blockIdx.x, scores, ids, n_lists, score_stride, id_stride, k_in, k_out, out_ids, out_scores, s_id,
-                     s_sc, s_len);
+                     s_sc, s_len, asc);
 }
 
 // Fallback for merges too large for LDS (n_lists * k_in beyond ~5000 entries): rank by counting, straight from
@@ -242,12 +245,13 @@ __global__ __launch_bounds__(256) void merge_topk_big_kernel(const float* __rest
                                                              int64_t score_stride, int64_t id_stride,
                                                              int k_in, int k_out,
                                                              int64_t* __restrict__ out_ids,
-                                                             float* __restrict__ out_scores) {
+                                                             float* __restrict__ out_scores, int asc) {
     const int q = blockIdx.x, tid = threadIdx.x;
+    const float sg = asc ? -1.f : 1.f;   // ascending lists: compare the negated scores
     const int n = n_lists * k_in;
     auto at = [&](int e, float& s, int64_t& i) {
         const int64_t o = (int64_t)q * k_in + (e % k_in);
-        s = scores[(int64_t)(e / k_in) * score_stride + o];
+        s = sg * scores[(int64_t)(e / k_in) * score_stride + o];
         i = ids[(int64_t)(e / k_in) * id_stride + o];
     };
     int n_valid = 0;
@@ -264,7 +268,7 @@ __global__ __launch_bounds__(256) void merge_topk_big_kernel(const float* __rest
         }
         if (rank < k_out) {
             out_ids[(int64_t)q * k_out + rank] = i;
-            out_scores[(int64_t)q * k_out + rank] = s;
+            out_scores[(int64_t)q * k_out + rank] = sg * s;
         }
     }
     for (int j = 0; j < n; ++j) {
@@ -355,7 +359,7 @@ __global__ __launch_bounds__(256) void post_lists_kernel(PostArgs pa) {
             float* s_sc = reinterpret_cast<float*>(s_id + n);
             int* s_len = reinterpret_cast<int*>(s_sc + n);
             merge_runs_block(q, a.scores[m], a.ids[m], a.n_lists, a.score_stride, a.id_stride, a.k_in[m], a.k_fuse[m],
-                             a.merged_ids[m], a.merged_scores[m], s_id, s_sc, s_len);
+                             a.merged_ids[m], a.merged_scores[m], s_id, s_sc, s_len, (a.asc_mask >> m) & 1);
             fuse_ids[m] = a.merged_ids[m];
             __syncthreads();  // the merged list is read back below; the LDS staging is reused by the next modality
         }

@@ -92,11 +92,12 @@ struct Workspace {
     hipEvent_t ev_scan = nullptr, ev_side = nullptr;
     struct Workspace* sparse_ws = nullptr;  // private buffers of the sparse chain when it runs concurrently
     DevBuf qfrag, qn2, gmax, bmax, cand, acut, cscore, crow, flags, qscale, qeps, qfloor, pq_n, pq_idx, pq_w;
+    DevBuf qcoef, dqeps;   // L2 shards: per query slot, the row term's coefficient 1 / |q| and the per-query error term
     DevBuf d_q, d_ids, d_scores, d_mask;          // host-form staging
     DevBuf d_qptr, d_qidx, d_qval;                // sparse query staging
     DevBuf f_ids, f_out_ids, f_out_scores, f_out_meth, f_n;  // hr_fuse_rrf staging
     void release() {
-        for (DevBuf* b : {&qfrag, &qn2, &gmax, &bmax, &qscale, &qeps, &qfloor, &pq_n, &pq_idx, &pq_w, &cand, &acut, &cscore, &crow, &flags, &d_q, &d_ids, &d_scores,
+        for (DevBuf* b : {&qcoef, &dqeps, &qfrag, &qn2, &gmax, &bmax, &qscale, &qeps, &qfloor, &pq_n, &pq_idx, &pq_w, &cand, &acut, &cscore, &crow, &flags, &d_q, &d_ids, &d_scores,
                           &d_mask, &d_qptr, &d_qidx, &d_qval, &f_ids, &f_out_ids, &f_out_scores, &f_out_meth, &f_n})
             b->release();
         if (stream) (void)hipStreamDestroy(stream);
@@ -337,11 +338,11 @@ int group_rows_for(const hr_index* h, int64_t n) {
 }
 
 // ---- dense launch helpers ----------------------------------------------------
-template <typename STORE, int G, int NRB>
+template <typename STORE, int G, int NRB, bool L2>
 hipError_t launch_scan(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask, float* gmax,
-                       int nq, int64_t n_groups) {
+                       int nq, int64_t n_groups, const float* qcoef) {
     constexpr int RS = 2, PF = 4;
-    auto kern = dense_scan_kernel<STORE, G, RS, PF, NRB>;
+    auto kern = dense_scan_kernel<STORE, G, RS, PF, NRB, L2>;
     const size_t lds = (size_t)G * h->KT * 1024;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -360,49 +361,50 @@ hipError_t launch_scan(const hr_index* h, hipStream_t s, const chunk_t* qfrag, c
                                        (int64_t)scan_cus(h) * per_cu);
     blocks = std::max<int64_t>(blocks, 1);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), lds, s, h->tiles.as<chunk_t>(), qfrag,
-                       h->scale.as<float>(), mask, gmax, nq, h->KT, h->n_rows, n_groups);
+                       h->scale.as<float>(), mask, gmax, nq, h->KT, h->n_rows, n_groups, qcoef);
     return hipGetLastError();
 }
 
-template <typename STORE>
+template <typename STORE, bool L2>
 hipError_t launch_scan_g(const hr_index* h, hipStream_t s, int G, const chunk_t* qfrag, const uint8_t* mask,
-                         float* gmax, int nq, int64_t n_groups) {
+                         float* gmax, int nq, int64_t n_groups, const float* qcoef) {
     // n_groups here counts SUPER-groups (64 rows) = the scan's loop bound
     if (group_rows_for(h, h->n_rows) == 16) {
         switch (G) {
-            case 1: return launch_scan<STORE, 1, 1>(h, s, qfrag, mask, gmax, nq, n_groups);
-            case 2: return launch_scan<STORE, 2, 1>(h, s, qfrag, mask, gmax, nq, n_groups);
-            case 3: return launch_scan<STORE, 3, 1>(h, s, qfrag, mask, gmax, nq, n_groups);
-            default: return launch_scan<STORE, 4, 1>(h, s, qfrag, mask, gmax, nq, n_groups);
+            case 1: return launch_scan<STORE, 1, 1, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
+            case 2: return launch_scan<STORE, 2, 1, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
+            case 3: return launch_scan<STORE, 3, 1, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
+            default: return launch_scan<STORE, 4, 1, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
         }
     }
     switch (G) {
-        case 1: return launch_scan<STORE, 1, 4>(h, s, qfrag, mask, gmax, nq, n_groups);
-        case 2: return launch_scan<STORE, 2, 4>(h, s, qfrag, mask, gmax, nq, n_groups);
-        case 3: return launch_scan<STORE, 3, 4>(h, s, qfrag, mask, gmax, nq, n_groups);
-        default: return launch_scan<STORE, 4, 4>(h, s, qfrag, mask, gmax, nq, n_groups);
+        case 1: return launch_scan<STORE, 1, 4, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
+        case 2: return launch_scan<STORE, 2, 4, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
+        case 3: return launch_scan<STORE, 3, 4, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
+        default: return launch_scan<STORE, 4, 4, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
     }
 }
 
 // Large-batch pass (dense_scan_bigq_kernel): GQ query groups streamed through LDS in k-chunks.
-template <typename STORE, int GQ, int NRB>
+template <typename STORE, int GQ, int NRB, bool L2>
 hipError_t launch_scan_bigq(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask, float* gmax,
-                            int nq, int64_t n_super) {
-    auto kern = dense_scan_bigq_kernel<STORE, GQ, NRB>;
+                            int nq, int64_t n_super, const float* qcoef) {
+    auto kern = dense_scan_bigq_kernel<STORE, GQ, NRB, L2>;
     const size_t lds = (size_t)2 * GQ * 2 * 1024;  // 2 buffers x GQ groups x BKT(2) fragments of 1 KiB
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     int64_t blocks = std::min<int64_t>((n_super + 7) / 8, (int64_t)scan_cus(h));
     blocks = std::max<int64_t>(blocks, 1);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, s, h->tiles.as<chunk_t>(), qfrag,
-                       h->scale.as<float>(), mask, gmax, nq, h->KT, h->n_rows, n_super);
+                       h->scale.as<float>(), mask, gmax, nq, h->KT, h->n_rows, n_super, qcoef);
     return hipGetLastError();
 }
-template <typename STORE>
+template <typename STORE, bool L2>
 hipError_t launch_scan_bigq_g(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask,
-                              float* gmax, int nq, int64_t n_super) {
-    return group_rows_for(h, h->n_rows) == 16 ? launch_scan_bigq<STORE, 8, 1>(h, s, qfrag, mask, gmax, nq, n_super)
-                                              : launch_scan_bigq<STORE, 8, 4>(h, s, qfrag, mask, gmax, nq, n_super);
+                              float* gmax, int nq, int64_t n_super, const float* qcoef) {
+    return group_rows_for(h, h->n_rows) == 16
+               ? launch_scan_bigq<STORE, 8, 1, L2>(h, s, qfrag, mask, gmax, nq, n_super, qcoef)
+               : launch_scan_bigq<STORE, 8, 4, L2>(h, s, qfrag, mask, gmax, nq, n_super, qcoef);
 }
 
 // 256-query pass with the queries in registers and the corpus streamed through LDS (dense_scan_qreg_kernel):
@@ -539,6 +541,18 @@ int candidate_groups_for_k(int k) {
     return (int)round_up(c, 16);
 }
 
+// L2 (norm_mode 2).  The scan's value of row x for query q is a = fl(acc - fl(fl(R) * fl(c))), R = |x|^2 / 2, c = 1 / |q|,
+// against the exact t = x.q / |q| - R c = (|q|^2 - D) / (2 |q|).  |acc - x.q / |q|| <= unit * |x| as for IP; fl(R), fl(c) and
+// their product carry 2^-24 each (3 * 2^-24 * R c, second-order terms in the margin), the subtraction 2^-24 (|acc| + R c)
+// with |acc| <= |x| (1 + unit).  With M = the largest row norm:
+//   |a - t| <= (unit + 2^-24 * 1.01) M  +  2^-22 * 1.01 * (M^2 / 2) / |q|
+// The first term is eps_abs, the second is per query: dense_l2_rt_eps() / |q|, written by prep_queries_kernel into
+// TopkArgs::eps_abs_q (for a zero query c = 1, acc = 0, and the same expression bounds the error of -fl(R)).
+// select_topk_block carries the K-th returned distance into this domain (select.h, norm_mode 2).
+float dense_l2_rt_eps(const hr_index* h) {
+    const double M = (double)h->max_row_norm * 1.0001;
+    return (float)std::min(std::ldexp(1.0, -22) * 1.01 * 0.5 * M * M, 3.0e38);
+}
 void dense_eps(const hr_index* h, float* eps_abs, int* norm_mode) {
     const double Dp = (double)h->KT * 4 * elems_per_chunk(h->dtype);
     double unit = 2.0 * Dp * std::ldexp(1.0, -24) + 1e-6;        // fp32 accumulation + scale rounding
@@ -547,6 +561,9 @@ void dense_eps(const hr_index* h, float* eps_abs, int* norm_mode) {
     if (h->metric == HR_METRIC_COSINE) {
         *eps_abs = (float)unit;
         *norm_mode = 0;
+    } else if (h->metric == HR_METRIC_L2) {
+        *eps_abs = (float)((unit + std::ldexp(1.0, -24) * 1.01) * (double)h->max_row_norm * 1.0001);
+        *norm_mode = 2;
     } else {
         *eps_abs = (float)(unit * (double)h->max_row_norm * 1.0001);
         *norm_mode = 1;
@@ -556,14 +573,15 @@ void dense_eps(const hr_index* h, float* eps_abs, int* norm_mode) {
 // ---- finishing steps shared by the single-modality chains and the hybrid chain --------------------------------
 int launch_refine_dense(hr_index* h, Workspace* ws, hipStream_t s, const float* d_q, int B, int C, int GR,
                         const uint8_t* d_mask) {
-    const int cosine = h->metric == HR_METRIC_COSINE;
+    const int cosine = h->metric;   // the kernel's `metric` argument
+    const bool l2 = h->metric == HR_METRIC_L2;
     if (h->dtype == HR_F16)
-        hipLaunchKernelGGL((refine_dense_kernel<_Float16>), dim3((C * GR + 63) / 64, B), dim3(64), 0, s,
+        hipLaunchKernelGGL((l2 ? refine_dense_kernel<_Float16, true> : refine_dense_kernel<_Float16, false>), dim3((C * GR + 63) / 64, B), dim3(64), 0, s,
                            h->tiles.as<chunk_t>(), h->KT, (int)h->dim, d_q, ws->qn2.as<double>(),
                            h->norm2.as<double>(), d_mask, ws->cand.as<int32_t>(), C, GR, h->n_rows, cosine,
                            ws->cscore.as<float>(), ws->crow.as<int32_t>());
     else
-        hipLaunchKernelGGL((refine_dense_kernel<float>), dim3((C * GR + 63) / 64, B), dim3(64), 0, s,
+        hipLaunchKernelGGL((l2 ? refine_dense_kernel<float, true> : refine_dense_kernel<float, false>), dim3((C * GR + 63) / 64, B), dim3(64), 0, s,
                            h->tiles.as<chunk_t>(), h->KT, (int)h->dim, d_q, ws->qn2.as<double>(),
                            h->norm2.as<double>(), d_mask, ws->cand.as<int32_t>(), C, GR, h->n_rows, cosine,
                            ws->cscore.as<float>(), ws->crow.as<int32_t>());
@@ -584,7 +602,7 @@ TopkArgs dense_topk_args(const hr_index* h, Workspace* ws, int C, int GR, int k,
     a.a_cut = ws->acut.as<float>();
     a.cut_floor = -INFINITY;
     a.eps_abs = eps_abs;
-    a.eps_abs_q = nullptr;
+    a.eps_abs_q = norm_mode == 2 ? ws->dqeps.as<float>() : nullptr;   // L2: the row term's share, 1 / |q| times a constant
     a.eps_rel = 0.0f;
     a.norm_mode = norm_mode;
     a.qn2 = ws->qn2.as<double>();
@@ -681,7 +699,7 @@ FinishMod finish_mod_dense(hr_index* h, Workspace* ws, const float* d_q, int B, 
     m.tiles = h->tiles.as<chunk_t>();
     m.KT = h->KT;
     m.dim = (int)h->dim;
-    m.cosine = h->metric == HR_METRIC_COSINE;
+    m.metric = h->metric;
     m.dtype = h->dtype;
     m.q = d_q;
     m.qn2 = ws->qn2.as<double>();
@@ -734,13 +752,23 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
                     (long long)h->dim);
     const bool prefer_gemm = (g_dense_kernels & 8) != 0;
     const bool use_qreg = qreg_supported(h) && !(prefer_gemm && gemm_supported(h));
-    const bool big256 = big && B > 128 && (use_qreg || gemm_supported(h));   // 256 queries per pass
+    // L2 shards: dense_scan_kernel up to 16 * Gsmall queries, dense_scan_bigq_kernel (128 queries per pass) beyond and for
+    // rows too long for the LDS-resident tile; the inline-asm 256-query forms serve COSINE / IP only
+    const bool l2 = h->metric == HR_METRIC_L2;
+    const bool big256 = big && B > 128 && !l2 && (use_qreg || gemm_supported(h));   // 256 queries per pass
     const int Gmax = big256 ? 16 : big ? 8 : Gsmall;
     const int chunk_q = 16 * Gmax;
     const int n_chunks = (B + chunk_q - 1) / chunk_q;
     const size_t chunk_frag = (size_t)Gmax * h->KT * kTileChunks;   // 16-byte chunks of one pass's query fragments
     HIP_TRY(h, ws->qfrag.ensure((size_t)n_chunks * chunk_frag * sizeof(chunk_t)));
     HIP_TRY(h, ws->qn2.ensure((size_t)B * sizeof(double)));
+    if (l2) {  // one entry per query SLOT (the scans read the padding slots of a pass too)
+        HIP_TRY(h, ws->qcoef.ensure((size_t)n_chunks * chunk_q * sizeof(float)));
+        HIP_TRY(h, ws->dqeps.ensure((size_t)n_chunks * chunk_q * sizeof(float)));
+    }
+    float* const d_coef = l2 ? ws->qcoef.as<float>() : nullptr;
+    float* const d_qeps = l2 ? ws->dqeps.as<float>() : nullptr;
+    const float rt_eps = l2 ? dense_l2_rt_eps(h) : 0.f;
     HIP_TRY(h, ws->gmax.ensure((size_t)B * n_groups * sizeof(float)));
     HIP_TRY(h, ws->cand.ensure((size_t)B * C * sizeof(int32_t)));
     HIP_TRY(h, ws->acut.ensure((size_t)B * sizeof(float)));
@@ -754,10 +782,10 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
         const int G_total = (n_chunks - 1) * Gmax + groups_of(B - (n_chunks - 1) * chunk_q);
         if (h->dtype == HR_F16)
             hipLaunchKernelGGL((prep_queries_kernel<_Float16>), dim3(16 * G_total), dim3(256), 0, s, d_q, B, (int)h->dim,
-                               h->KT, ws->qfrag.as<chunk_t>(), ws->qn2.as<double>());
+                               h->KT, ws->qfrag.as<chunk_t>(), ws->qn2.as<double>(), d_coef, d_qeps, rt_eps);
         else
             hipLaunchKernelGGL((prep_queries_kernel<float>), dim3(16 * G_total), dim3(256), 0, s, d_q, B, (int)h->dim,
-                               h->KT, ws->qfrag.as<chunk_t>(), ws->qn2.as<double>());
+                               h->KT, ws->qfrag.as<chunk_t>(), ws->qn2.as<double>(), d_coef, d_qeps, rt_eps);
         HIP_TRY(h, hipGetLastError());
     }
     for (int c0 = 0; (phases & PHASE_SCAN) && c0 < B; c0 += chunk_q) {
@@ -773,12 +801,18 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
                 e = (use_qreg && (g_dense_kernels & 16)) ? launch_scan_q64_g(h, s, qf, d_mask, gm, nq, n_super)
                     : use_qreg ? launch_scan_qreg_g(h, s, qf, d_mask, gm, nq, n_super)
                                : launch_scan_gemm_g<16>(h, s, qf, d_mask, gm, nq, n_super);
+            else if (big && l2)
+                e = (h->dtype == HR_F16) ? launch_scan_bigq_g<_Float16, true>(h, s, qf, d_mask, gm, nq, n_super, d_coef + c0)
+                                         : launch_scan_bigq_g<float, true>(h, s, qf, d_mask, gm, nq, n_super, d_coef + c0);
             else if (big)
-                e = (h->dtype == HR_F16) ? launch_scan_bigq_g<_Float16>(h, s, qf, d_mask, gm, nq, n_super)
-                                         : launch_scan_bigq_g<float>(h, s, qf, d_mask, gm, nq, n_super);
+                e = (h->dtype == HR_F16) ? launch_scan_bigq_g<_Float16, false>(h, s, qf, d_mask, gm, nq, n_super, nullptr)
+                                         : launch_scan_bigq_g<float, false>(h, s, qf, d_mask, gm, nq, n_super, nullptr);
+            else if (l2)
+                e = (h->dtype == HR_F16) ? launch_scan_g<_Float16, true>(h, s, G, qf, d_mask, gm, nq, n_super, d_coef + c0)
+                                         : launch_scan_g<float, true>(h, s, G, qf, d_mask, gm, nq, n_super, d_coef + c0);
             else
-                e = (h->dtype == HR_F16) ? launch_scan_g<_Float16>(h, s, G, qf, d_mask, gm, nq, n_super)
-                                         : launch_scan_g<float>(h, s, G, qf, d_mask, gm, nq, n_super);
+                e = (h->dtype == HR_F16) ? launch_scan_g<_Float16, false>(h, s, G, qf, d_mask, gm, nq, n_super, nullptr)
+                                         : launch_scan_g<float, false>(h, s, G, qf, d_mask, gm, nq, n_super, nullptr);
             HIP_TRY(h, e);
         }
     }
@@ -1187,7 +1221,7 @@ int build_sparse(hr_index* h) {
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 10400; }  // 1.4.0: round 4 (per-query fusion weights, encoder layer kernels, head-dim-64 attention)
+int hr_version(void) { return 10500; }  // 1.5.0: HR_METRIC_L2, hr_merge_topk_asc_dev, hr_post_args::asc_mask
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -1203,7 +1237,7 @@ int hr_create(int device, int64_t dim, int dtype, int metric, int64_t sparse_dim
         return fail(nullptr, HR_EINVAL, "need dim > 0 and/or sparse_dim > 0");
     if (dim > HR_MAX_DIM) return fail(nullptr, HR_ELIMIT, "dim=%lld exceeds HR_MAX_DIM=%d", (long long)dim, HR_MAX_DIM);
     if (dtype != HR_F32 && dtype != HR_F16) return fail(nullptr, HR_EINVAL, "unknown dtype %d", dtype);
-    if (metric != HR_METRIC_IP && metric != HR_METRIC_COSINE) return fail(nullptr, HR_EINVAL, "unknown metric %d", metric);
+    if (metric != HR_METRIC_IP && metric != HR_METRIC_COSINE && metric != HR_METRIC_L2) return fail(nullptr, HR_EINVAL, "unknown metric %d", metric);
     if (sparse_dim > (1ll << 24)) return fail(nullptr, HR_ELIMIT, "sparse_dim too large");
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
@@ -1360,14 +1394,14 @@ int hr_finalize(hr_index* h) {
     if (h->dim > 0 && h->n_normed < h->n_rows) {
         const int64_t n = h->n_rows - h->n_normed;
         const unsigned blocks = (unsigned)((n + 255) / 256);
-        const int cosine = h->metric == HR_METRIC_COSINE;
+        const int metric = h->metric;
         if (h->dtype == HR_F16)
             hipLaunchKernelGGL((row_norms_kernel<_Float16>), dim3(blocks), dim3(256), 0, s, h->tiles.as<chunk_t>(),
-                               h->KT, h->n_normed, n, cosine, h->norm2.as<double>(), h->scale.as<float>(),
+                               h->KT, h->n_normed, n, metric, h->norm2.as<double>(), h->scale.as<float>(),
                                h->max_norm.as<unsigned int>());
         else
             hipLaunchKernelGGL((row_norms_kernel<float>), dim3(blocks), dim3(256), 0, s, h->tiles.as<chunk_t>(), h->KT,
-                               h->n_normed, n, cosine, h->norm2.as<double>(), h->scale.as<float>(),
+                               h->n_normed, n, metric, h->norm2.as<double>(), h->scale.as<float>(),
                                h->max_norm.as<unsigned int>());
         HIP_TRY(h, hipGetLastError());
         unsigned int bits = 0;
@@ -1742,8 +1776,9 @@ int hr_fuse_rrf_dev(const int64_t* d_ids_a, int ka, const int64_t* d_ids_b, int 
     return HR_OK;
 }
 
-int hr_merge_topk_dev(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t score_stride, int64_t id_stride,
-                      int B, int k_in, int k_out, int64_t* d_out_ids, float* d_out_scores, void* stream) {
+namespace {
+int merge_topk_impl(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t score_stride, int64_t id_stride,
+                    int B, int k_in, int k_out, int64_t* d_out_ids, float* d_out_scores, void* stream, int asc) {
     if (n_lists <= 0 || B <= 0 || k_in <= 0 || k_out <= 0) return fail(nullptr, HR_EINVAL, "bad merge sizes");
     if (score_stride < (int64_t)B * k_in || id_stride < (int64_t)B * k_in)
         return fail(nullptr, HR_EINVAL, "list stride smaller than one list");
@@ -1751,18 +1786,29 @@ int hr_merge_topk_dev(const float* d_scores, const int64_t* d_ids, int n_lists, 
     const size_t lds = merge_lds_bytes(n_lists, k_in);
     if (lds <= kMergeLdsMax)
         hipLaunchKernelGGL(merge_topk_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, d_scores, d_ids, n_lists,
-                           score_stride, id_stride, k_in, k_out, d_out_ids, d_out_scores);
+                           score_stride, id_stride, k_in, k_out, d_out_ids, d_out_scores, asc);
     else
         hipLaunchKernelGGL(merge_topk_big_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, d_scores, d_ids, n_lists,
-                           score_stride, id_stride, k_in, k_out, d_out_ids, d_out_scores);
+                           score_stride, id_stride, k_in, k_out, d_out_ids, d_out_scores, asc);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "merge_topk_kernel: %s", hipGetErrorString(e));
     return HR_OK;
+}
+}  // namespace
+
+int hr_merge_topk_dev(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t score_stride, int64_t id_stride,
+                      int B, int k_in, int k_out, int64_t* d_out_ids, float* d_out_scores, void* stream) {
+    return merge_topk_impl(d_scores, d_ids, n_lists, score_stride, id_stride, B, k_in, k_out, d_out_ids, d_out_scores, stream, 0);
+}
+int hr_merge_topk_asc_dev(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t score_stride, int64_t id_stride,
+                          int B, int k_in, int k_out, int64_t* d_out_ids, float* d_out_scores, void* stream) {
+    return merge_topk_impl(d_scores, d_ids, n_lists, score_stride, id_stride, B, k_in, k_out, d_out_ids, d_out_scores, stream, 1);
 }
 
 int hr_post_lists_dev(const hr_post_args* a, int B, void* stream) {
     if (!a || B <= 0) return fail(nullptr, HR_EINVAL, "bad post-lists arguments");
     if (a->n_lists < 1 || a->top_k <= 0 || a->k_in[0] <= 0) return fail(nullptr, HR_EINVAL, "bad post-lists sizes");
+    if (a->asc_mask & ~7) return fail(nullptr, HR_EINVAL, "asc_mask has bits beyond the three modalities");
     size_t lds = 0;
     for (int m = 0; m < 3; ++m) {
         if (a->k_in[m] < 0 || a->k_in[m] > HR_MAX_TOPK || a->k_fuse[m] > HR_MAX_TOPK)

@@ -278,7 +278,11 @@ __global__ __launch_bounds__(1024) void select_groups_kernel(GroupSelPair p) {
 //   (a_cut <= floor, the floor lowered by the error bound where the bound is not a fraction of the score), or K rows were found and the K-th canonical score beats
 //   a_cut by more than the scan's error bound.
 // norm_mode: 0 = scores compare to a_cut as they are; 1 = divide by |q| first
-// (inner-product metric: the scan works on the unit-normalised query).
+// (inner-product metric: the scan works on the unit-normalised query); 2 = L2: the candidate scores are -D (negated
+// squared distances), written out as D, and the K-th one is carried into the scan's domain, t = (|q|^2 - D) c / 2 with
+// c = 1 / |q| (1 for a zero query), after D has been RAISED by 2^-22 D + 1e-30: a row outside the candidate groups is
+// then excluded only if its exact distance lies above every value that rounds to the K-th float or below, so it can
+// neither beat nor tie the K-th returned row.
 struct TopkArgs {
     const float* cscore;   // [B][n] canonical candidate scores
     const int32_t* crow;   // [B][n] candidate rows (< 0 = invalid)
@@ -327,7 +331,7 @@ __device__ inline void select_topk_block(const TopkArgs& a, int q, KeyFn key, Se
         int rank = 0;
         for (int j = 0; j < found; ++j) rank += sel[j] > me;
         out_ids[(int64_t)q * K + rank] = (int64_t)key_row(me) + row_offset;
-        out_scores[(int64_t)q * K + rank] = key_score(me);
+        out_scores[(int64_t)q * K + rank] = a.norm_mode == 2 ? -key_score(me) : key_score(me);
     }
     for (int i = found + threadIdx.x; i < K; i += blockDim.x) {
         out_ids[(int64_t)q * K + i] = -1;
@@ -346,6 +350,11 @@ __device__ inline void select_topk_block(const TopkArgs& a, int q, KeyFn key, Se
             if (a.norm_mode == 1) {
                 double nq = a.qn2[q];
                 sk = nq > 0.0 ? sk / sqrt(nq) : 0.0;
+            } else if (a.norm_mode == 2) {
+                const double nq = a.qn2[q];
+                const double dk = -sk * (1.0 + 0x1p-22) + 1e-30;
+                sk = (nq - dk) * 0.5 * (nq > 0.0 ? 1.0 / sqrt(nq) : 1.0);
+                sk -= 0x1p-40 * (fabs(sk) + nq * 0.5 * (nq > 0.0 ? 1.0 / sqrt(nq) : 1.0));  // fp64 rounding of this conversion
             }
             double bound = (double)cut + (double)a.eps_abs + (a.eps_abs_q ? (double)a.eps_abs_q[q] : 0.0) +
                            (double)a.eps_rel * fabs((double)cut);

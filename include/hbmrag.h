@@ -37,6 +37,15 @@
  *            sqrt(sum x^2 * sum q^2) (0 when either norm is 0).  Rows are
  *            ranked by (score32 desc, row id asc).  Milvus' HNSW(ef=64) is
  *            approximate; this is the exact FLAT answer of the same metric.
+ *   dense, HR_METRIC_L2 : score32 = (float) D, D = k-ordered sequential fp64 sum of
+ *            d_k * d_k with d_k = (double)x[k] - (double)q[k], every subtraction,
+ *            product and sum a separately rounded IEEE fp64 operation (no FMA),
+ *            k = 0 .. dim-1: Milvus' L2 "distance", squared, no root.  Rows are
+ *            ranked by (score32 ASCENDING, row id asc); lists are written smallest
+ *            distance first, padded with id -1 / score 0.  A row equal to the query
+ *            is a valid hit at distance exactly +0.  A zero query is legal
+ *            (D = |x|^2).  Row norms must stay inside the fp32 range squared
+ *            (|x|^2 / 2 is kept per row as a float).
  *   sparse : score32 = (float) sum over the row's stored entries, in stored
  *            (index) order, of value*query_value in fp64; only rows with
  *            score32 > 0 qualify; same ranking rule.
@@ -71,7 +80,7 @@ typedef enum hr_status {
 } hr_status;
 
 enum { HR_F32 = 0, HR_F16 = 1 };               /* storage dtype of the dense shard */
-enum { HR_METRIC_IP = 0, HR_METRIC_COSINE = 1 }; /* dense metric_type                */
+enum { HR_METRIC_IP = 0, HR_METRIC_COSINE = 1, HR_METRIC_L2 = 2 }; /* dense metric_type (Milvus: IP, COSINE, L2) */
 enum { HR_METHOD_SEMANTIC = 1, HR_METHOD_SPARSE = 2, HR_METHOD_DOMAIN = 4 };
 
 #define HR_MAX_TOPK 256  /* reference clamps top_k to 100 and over-retrieves 2x (constants.py:47, retrieval.py:351) */
@@ -232,6 +241,11 @@ HR_API int hr_fuse_rrf_dev(const int64_t* d_ids_a, int ka, const int64_t* d_ids_
 HR_API int hr_merge_topk_dev(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t score_stride,
                       int64_t id_stride, int B, int k_in, int k_out, int64_t* d_out_ids,
                       float* d_out_scores, void* stream);
+/* The same merge for lists sorted by score ASCENDING (the per-shard lists of an HR_METRIC_L2 collection): output the
+ * best k_out by (score asc, id asc). */
+HR_API int hr_merge_topk_asc_dev(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t score_stride,
+                          int64_t id_stride, int B, int k_in, int k_out, int64_t* d_out_ids,
+                          float* d_out_scores, void* stream);
 /* LearnedRanker.score + HybridRetriever.rerank's stable sort and cut
  * (reference ranker.py:109-125, retrieval.py:544-563) for a batch:
  *   new = base_w*score + method_bonus*popcount(methods) + recency_w*recency
@@ -273,7 +287,8 @@ typedef struct hr_post_args {
     double base_w, method_bonus, recency_w;
     const double* recency;
     int32_t k_out;
-    int32_t reserved;
+    int32_t asc_mask;          /* bit m = 1: the lists of modality m are sorted by score ASCENDING (the distances of an
+                                * HR_METRIC_L2 collection) and merged by (score asc, id asc); 0 = every list descending */
     int64_t* rr_ids;
     double* rr_scores;
     double* rr_orig;
@@ -454,7 +469,8 @@ HR_API int hr_debug_option(hr_index* h, int key, int value);
 #define HR_N_PHASES 10
 HR_API int hr_set_profiling(hr_index* h, int enabled);
 HR_API int hr_last_kernel_ms(hr_index* h, float* out_ms, int n);
-/* Algorithmic bytes one dense scan launch reads (rows*dim*sizeof(elem) + 4*rows). */
+/* Algorithmic bytes one dense scan launch reads (rows*dim*sizeof(elem) + 4*rows: the rows and one float per row —
+ * the scale of a COSINE / IP shard, the row term |x|^2 / 2 of an L2 shard, which takes the scale's place). */
 HR_API int64_t hr_dense_scan_bytes(const hr_index* h);
 
 #ifdef __cplusplus
