@@ -447,6 +447,7 @@ class MilvusIndexManager:
             # dense rows, sparse rows and payload columns of a chunk share one row number: the three are appended
             # together, and whatever fails afterwards is padded rather than left short
             dense_rows = device_rows(dense_dev, store_half) if dense_dev is not None else np.stack(rows_dense)
+            self._check_dense_rows(dense_rows, self._main)    # refused whole, before anything is appended
             try:
                 _, _, sparse_err = await asyncio.to_thread(self._main.add, dense_rows, sparse_csr)
             except PartialAppend as pa:
@@ -467,6 +468,7 @@ class MilvusIndexManager:
                 before = self._domain.num_rows
                 try:
                     dom_rows = device_rows(dom_dev, store_half) if dom_dev is not None else np.stack(rows_domain)
+                    self._check_dense_rows(dom_rows, self._domain)
                     await asyncio.to_thread(self._domain.add, dom_rows)
                     summary["indexed_domain"] = len(kept)
                 except Exception as e:  # zero rows never match (cosine 0): the domain collection stays row-aligned
@@ -504,6 +506,7 @@ class MilvusIndexManager:
         float16/float32, optional CSR triple (indptr, indices, values)."""
         if self._synthetic_rows:
             raise ValueError("shard is in synthetic-payload mode; use add_rows_synthetic")
+        self._check_dense_rows(dense, self._main)
         n = dense.shape[0]
         base = self.num_rows
         failed = None
@@ -535,6 +538,7 @@ class MilvusIndexManager:
         number on demand (10M-row benchmarks would otherwise hold GBs of Python strings)."""
         if len(self._cols["id"]):
             raise ValueError("shard already holds payload columns")
+        self._check_dense_rows(dense, self._main)
         n, failed = dense.shape[0], None
         try:
             _, _, sparse_err = self._main.add(dense, sparse_csr if "sparse_index" in self.collections else None)
@@ -639,6 +643,41 @@ class MilvusIndexManager:
             raise ValueError("sparse indices/values length mismatch")
         order = np.argsort(idx, kind="stable")
         return idx[order], val[order]
+
+    def _check_dense_rows(self, rows, shard_set) -> None:
+        """Refuse a dense batch before any shard, column or sparse collection is touched when some element, AS THE SHARD
+        STORES IT, is NaN or infinite (an fp32 value of 65520 or more becomes an infinity in an fp16 store): the library
+        refuses such a batch too (hr_add_dense, HR_EINVAL), but by then a multi-shard or collective append may have
+        given other pieces their row numbers.  numpy rows are checked on the host in bounded blocks, a CUDA tensor (an
+        encoder's output, already cast to the store's type) on its device.  ValueError names the first bad row."""
+        h = getattr(shard_set, "local", shard_set).handles[0]
+        code = getattr(h, "dtype", None)
+        half = code == 1 if isinstance(code, int) else self.dtype in ("float16", "fp16", "f16")
+        bad = None
+        if hasattr(rows, "is_cuda"):
+            import torch
+            ok = torch.isfinite(rows.to(torch.float16) if half else rows)
+            if not bool(ok.all()):
+                bad = int((~ok).reshape(ok.shape[0], -1).any(dim=1).nonzero()[0])
+        else:
+            a = np.asarray(rows)
+            if a.ndim != 2 or a.dtype not in (np.float16, np.float32):
+                return                      # the shard's own shape / dtype errors
+            step = max(1, (1 << 22) // max(1, a.shape[1]))
+            for lo in range(0, a.shape[0], step):
+                blk = np.ascontiguousarray(a[lo:lo + step])
+                if blk.dtype == np.float16:
+                    ok = (blk.view(np.uint16) & 0x7C00) != 0x7C00      # exponent all ones: NaN or infinity
+                elif half:
+                    ok = np.abs(blk) < np.float32(65520.0)             # false for NaN; 65520 is the tie that rounds to inf
+                else:
+                    ok = np.isfinite(blk)
+                if not ok.all():
+                    bad = lo + int(np.flatnonzero(~ok.all(axis=1))[0])
+                    break
+        if bad is not None:
+            raise ValueError(f"dense row {bad} of the batch holds a value that is NaN or infinite in the shard's "
+                             f"{'fp16' if half else 'fp32'} store")
 
     def _checked_sparse_csr(self, csr, n: int):
         """A batch hook's CSR as (indptr int64, indices int32, values float32) if it is what the shard accepts as it stands —

@@ -12,11 +12,16 @@ namespace hbmrag {
 
 // ---------------------------------------------------------------------------
 // ingest: row-major rows -> tiled shard layout (see chunk_index)
-// SRC = float (convert to the store type) or the store type itself.
+// SRC = float (convert to the store type) or the store type itself.  A stored element that is NaN or +-inf (an fp32
+// value that overflows fp16 included) records its row, as an index into the call's batch, in *bad_row: the lowest
+// such row wins.  The host refuses the batch when the word has left its initial all-ones value.
 template <typename STORE, typename SRC>
 __global__ void tile_rows_kernel(const SRC* __restrict__ src, int64_t n, int dim, int KT,
-                                 int64_t row0, chunk_t* __restrict__ tiles) {
+                                 int64_t row0, chunk_t* __restrict__ tiles, int64_t batch_row0,
+                                 unsigned long long* __restrict__ bad_row) {
     constexpr int EPC = kChunkBytes / (int)sizeof(STORE);
+    // all exponent bits set: NaN or infinity
+    constexpr unsigned kExp = sizeof(STORE) == 2 ? 0x7C007C00u : 0x7F800000u;
     const int kchunks = KT * 4;
     int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (tid >= n * kchunks) return;
@@ -29,6 +34,24 @@ __global__ void tile_rows_kernel(const SRC* __restrict__ src, int64_t n, int dim
         out.e[j] = (k < dim) ? (STORE)src[i * dim + k] : (STORE)0;
     }
     tiles[chunk_index(row0 + i, kc, KT)] = out.v;
+    bool bad = false;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const unsigned x = out.v[w] & kExp;
+        if (sizeof(STORE) == 2) bad |= (x & 0xFFFFu) == 0x7C00u || (x >> 16) == 0x7C00u;
+        else bad |= x == kExp;
+    }
+    if (bad) atomicMin(bad_row, (unsigned long long)(batch_row0 + i));
+}
+
+// Zero the tiles of rows [row0, row0 + n): what a refused batch wrote beyond the shard's last row.
+__global__ void zero_rows_kernel(int64_t n, int KT, int64_t row0, chunk_t* __restrict__ tiles) {
+    const int kchunks = KT * 4;
+    int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (tid >= n * kchunks) return;
+    int64_t i = tid / kchunks;
+    int kc = (int)(tid - i * kchunks);
+    tiles[chunk_index(row0 + i, kc, KT)] = chunk_t{0u, 0u, 0u, 0u};
 }
 
 // One thread per row: sum of squares in fp64, k-ordered (the canonical norm the

@@ -135,6 +135,7 @@ struct hr_index {
     int64_t cap_rows = 0, n_rows = 0, n_normed = 0;
     float max_row_norm = 0.f;
     DevBuf stage;  // ingest staging
+    DevBuf bad_row;  // one u64, all ones between calls: tile_rows_kernel lowers it to a batch row that is not finite
     hipStream_t ingest_stream = nullptr;
 
     // sparse shard: the CSR lives on the device; the host only stages the rows appended since the last hr_finalize
@@ -1036,6 +1037,8 @@ int grow_dense(hr_index* h, int64_t need_rows) {
     return HR_OK;
 }
 
+constexpr unsigned long long kNoBadRow = ~0ull;
+
 template <typename SRC>
 int add_dense_impl(hr_index* h, const SRC* rows, int64_t n, bool src_on_device, hipStream_t user_stream) {
     if (!h) return fail(nullptr, HR_EINVAL, "null handle");
@@ -1048,6 +1051,7 @@ int add_dense_impl(hr_index* h, const SRC* rows, int64_t n, bool src_on_device, 
     hipStream_t s = src_on_device && user_stream ? user_stream : h->ingest_stream;
     const int64_t chunk_rows = std::max<int64_t>(1, (64ll << 20) / (h->dim * (int64_t)sizeof(SRC)));
     const int kchunks = h->KT * 4;
+    unsigned long long* d_bad = h->bad_row.as<unsigned long long>();
     for (int64_t r0 = 0; r0 < n; r0 += chunk_rows) {
         const int64_t m = std::min(chunk_rows, n - r0);
         const SRC* src = rows + r0 * h->dim;
@@ -1061,20 +1065,35 @@ int add_dense_impl(hr_index* h, const SRC* rows, int64_t n, bool src_on_device, 
         if (h->dtype == HR_F16) {
             if constexpr (std::is_same<SRC, float>::value)
                 hipLaunchKernelGGL((tile_rows_kernel<_Float16, float>), dim3(blocks), dim3(256), 0, s, src, m,
-                                   (int)h->dim, h->KT, h->n_rows + r0, h->tiles.as<chunk_t>());
+                                   (int)h->dim, h->KT, h->n_rows + r0, h->tiles.as<chunk_t>(), r0, d_bad);
             else
                 hipLaunchKernelGGL((tile_rows_kernel<_Float16, _Float16>), dim3(blocks), dim3(256), 0, s,
                                    reinterpret_cast<const _Float16*>(src), m, (int)h->dim, h->KT, h->n_rows + r0,
-                                   h->tiles.as<chunk_t>());
+                                   h->tiles.as<chunk_t>(), r0, d_bad);
         } else {
             hipLaunchKernelGGL((tile_rows_kernel<float, float>), dim3(blocks), dim3(256), 0, s,
                                reinterpret_cast<const float*>(src), m, (int)h->dim, h->KT, h->n_rows + r0,
-                               h->tiles.as<chunk_t>());
+                               h->tiles.as<chunk_t>(), r0, d_bad);
         }
         HIP_TRY(h, hipGetLastError());
         if (!src_on_device) HIP_TRY(h, hipStreamSynchronize(s));  // staging buffer is reused
     }
+    // the flag rides on the synchronisation the append needs anyway
+    unsigned long long bad = kNoBadRow;
+    HIP_TRY(h, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
+    if (bad != kNoBadRow) {
+        // refused: the handle stays as it was.  The rows beyond n_rows go back to the zeros every scan and snapshot
+        // expects there, and the flag to its rest value.
+        const int64_t threads = n * kchunks;
+        hipLaunchKernelGGL(zero_rows_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, n, h->KT,
+                           h->n_rows, h->tiles.as<chunk_t>());
+        HIP_TRY(h, hipGetLastError());
+        HIP_TRY(h, hipMemsetAsync(d_bad, 0xFF, sizeof bad, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        return fail(h, HR_EINVAL, "dense row %lld of the batch holds a value that is NaN or infinite in the shard's %s store",
+                    (long long)bad, h->dtype == HR_F16 ? "fp16" : "fp32");
+    }
     h->n_rows += n;
     h->finalized = false;
     return HR_OK;
@@ -1221,7 +1240,7 @@ int build_sparse(hr_index* h) {
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 10500; }  // 1.5.0: HR_METRIC_L2, hr_merge_topk_asc_dev, hr_post_args::asc_mask
+int hr_version(void) { return 10501; }  // 1.5.1: dense rows that are not finite in the store's type are refused
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -1266,6 +1285,7 @@ int hr_create(int device, int64_t dim, int dtype, int metric, int64_t sparse_dim
     for (unsigned l = 0; l < 256; ++l) idle[l] = filler_posting(l / 4);
     if (hipStreamCreateWithFlags(&h->ingest_stream, hipStreamNonBlocking) != hipSuccess ||
         h->max_norm.ensure(4) != hipSuccess || hipMemset(h->max_norm.p, 0, 4) != hipSuccess ||
+        h->bad_row.ensure(8) != hipSuccess || hipMemset(h->bad_row.p, 0xFF, 8) != hipSuccess ||
         h->idle_post.ensure(sizeof idle) != hipSuccess ||
         hipMemcpy(h->idle_post.p, idle, sizeof idle, hipMemcpyHostToDevice) != hipSuccess) {
         int rc = fail(nullptr, HR_EHIP, "device %d initialisation failed: %s", device, hipGetErrorString(hipGetLastError()));
@@ -1288,7 +1308,7 @@ void hr_destroy(hr_index* h) {
                 if (w) { w->release(); delete w; }
         for (auto& sp : h->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
         for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
-        for (DevBuf* b : {&h->tiles, &h->scale, &h->norm2, &h->max_norm, &h->stage, &h->s_indptr, &h->s_idx, &h->s_val,
+        for (DevBuf* b : {&h->tiles, &h->scale, &h->norm2, &h->max_norm, &h->stage, &h->bad_row, &h->s_indptr, &h->s_idx, &h->s_val,
                           &h->rt_off, &h->range_base, &h->post, &h->idle_post})
             b->release();
         if (h->ingest_stream) (void)hipStreamDestroy(h->ingest_stream);
@@ -1513,7 +1533,8 @@ static int load_impl(const char* path, int device, hr_index** out) {
     if (fread(&hd, sizeof hd, 1, file.f) != 1 || std::memcmp(hd.magic, kSnapMagic, 8) != 0 || hd.version != 2)
         return fail(nullptr, HR_EINVAL, "%s is not a libhbmrag snapshot (version 2)", path);
     if (hd.n_rows < 0 || hd.n_sparse < 0 || hd.nnz < 0 || hd.cap_rows < hd.n_rows || hd.n_sparse > (1ll << 31) - 64 ||
-        hd.nnz > (1ll << 40) || !(hd.max_sparse_abs >= 0.f) || !(hd.max_row_norm >= 0.f))
+        hd.nnz > (1ll << 40) || !(hd.max_sparse_abs >= 0.f) || !(hd.max_row_norm >= 0.f) ||
+        !std::isfinite(hd.max_row_norm))
         return fail(nullptr, HR_EINVAL, "corrupt snapshot header");
     if (fseek(file.f, 0, SEEK_END) != 0 || (int64_t)ftell(file.f) != hd.file_bytes || fseek(file.f, (long)sizeof hd, SEEK_SET) != 0)
         return fail(nullptr, HR_EINVAL, "snapshot truncated or padded: %s does not hold the %lld bytes its header announces", path,

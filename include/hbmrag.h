@@ -111,7 +111,14 @@ HR_API int hr_reserve(hr_index* h, int64_t n_rows);
  * assigned in call order.  hr_add_dense takes row-major fp32 rows and stores
  * them in the shard's dtype (fp16: round-to-nearest-even, as numpy astype).
  * hr_add_dense_raw takes rows already in the shard's dtype (fp16 bits as
- * uint16).  The `_dev` forms take device pointers. */
+ * uint16).  The `_dev` forms take device pointers.
+ * Every element must be finite AS STORED: a batch that holds a NaN or an
+ * infinity, or on an fp16 shard an fp32 value that rounds to one (|x| >= 65520),
+ * is refused with HR_EINVAL by all three forms (Milvus rejects such vectors at
+ * insert).  hr_last_error names the lowest offending row as an index into the
+ * call's batch.  The check runs on the device beside the conversion.  A refused
+ * call appends nothing: hr_num_rows, the finalized state, the row norms and the
+ * bounds of the exactness proofs derived from them are what they were. */
 HR_API int hr_add_dense(hr_index* h, const float* rows, int64_t n);
 HR_API int hr_add_dense_raw(hr_index* h, const void* rows, int64_t n);
 HR_API int hr_add_dense_raw_dev(hr_index* h, const void* d_rows, int64_t n, void* stream);

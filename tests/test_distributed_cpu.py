@@ -368,6 +368,15 @@ def _ingest_worker(rank, world, port, ret, tmp):
         for a, b in zip(cuts[:-1], cuts[1:]):
             mgr.add_rows(X[a:b], (ptr[a:b + 1], idx, val), chunk_index=[r % 10 for r in range(a, b)])
         assert (cs.num_rows, cs.num_sparse_rows, mgr.num_rows) == (4100, 4100, 4100)
+        # a row that is not finite in the fp16 store is refused on the front end, before the batch is broadcast or cut:
+        # no rank hears of it, no row number is taken
+        own = (shard.num_rows, shard.num_sparse_rows)
+        spoiled = X[4100:4110].astype(np.float32)
+        spoiled[6, 3] = np.nan
+        with pytest.raises(ValueError, match=r"row 6\b"):
+            mgr.add_rows(spoiled, (ptr[4100:4111], idx, val))
+        assert (cs.num_rows, cs.num_sparse_rows, mgr.num_rows) == (4100, 4100, 4100)
+        assert (shard.num_rows, shard.num_sparse_rows) == own
         mgr.finalize()
         m = cuts[-1]
         keep = (np.arange(m) % 10) < 5

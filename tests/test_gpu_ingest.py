@@ -148,6 +148,11 @@ def test_snapshot_is_validated_on_load(gpu, tmp_path):
     bad = bytearray(good)
     bad[48:56] = struct.pack("<q", 1 << 62)                           # absurd n_rows in the header
     refused(bytes(bad), "header")
+    for name, value in (("inf_norm", float("inf")), ("nan_norm", float("nan"))):
+        bad = bytearray(good)
+        assert struct.unpack("<f", bad[80:84])[0] > 0                 # max_row_norm: the bound of every dense proof
+        bad[80:84] = struct.pack("<f", value)
+        refused(bytes(bad), name)
     h.close()
 
 
