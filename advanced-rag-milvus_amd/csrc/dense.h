@@ -168,6 +168,20 @@ struct Mfma<float> {
     }
 };
 
+
+// ---------------------------------------------------------------------------
+// Pieces the scan kernels share.  All of them are forced inline and take scalars by value: each was admitted only where
+// the kernel around it kept its registers, occupancy and k-loop (profiles/scan_refactor_resource_usage_*.txt).
+//
+// Group store.  A lane holds one query COLUMN of a 16 x 16 result tile for four of its rows; `v` is the lane's maximum
+// over the rows of one candidate group, the group's maximum is the maximum over the column's four lanes, and the lane of
+// the first quad writes it: gmax is [nq][gmax_stride], q the lane's query, q < nq a real one (not padding).
+__device__ __forceinline__ void store_group_max(float v, float* gmax, int64_t gmax_stride, int64_t group, int q, int nq,
+                                                int lane) {
+    v = col4_max(v);
+    if (lane < 16 && q < nq) gmax[(int64_t)q * gmax_stride + group] = v;
+}
+
 // PF = depth of the per-wave register prefetch ring (k-steps in flight); KT is
 // padded to a multiple of PF at hr_create so ring slots stay compile-time.
 // L2 = the squared-Euclidean form (compile time: the COSINE / IP instantiations are what they were): `scale` then holds
@@ -202,6 +216,8 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
     // Prefetch cursor: walks (group, pair, kt) exactly PF steps ahead of the
     // consumer, across pair and group boundaries, so the wave's HBM stream
     // never drains.  All of it is wave-uniform (scalar) state.
+    // (Stays a lambda here and in dense_scan_bigq_kernel: as a shared forced-inline struct it changed both kernels'
+    // k-loops and moved their registers by up to 25, tried.)
     int64_t pf_group = wave;
     int pf_pair = 0, pf_kt = 0;
     chunk_t ring[PF][RS];
@@ -251,7 +267,9 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
                     prefetch(j);  // refill the slot just consumed: PF-1 steps of lookahead
                 }
             }
-            // epilogue: lane holds rows row0..row0+3 of row block s for query 16g+(lane&15)
+            // epilogue: lane holds rows row0..row0+3 of row block s for query 16g+(lane&15).  The row validity `ok` and the
+            // masked maximum are written out in each of the four kernels that use this float form: as shared helpers
+            // (validity as a float array, a struct of floats, a struct of predicates) they cost registers, tried.
 #pragma unroll
             for (int s = 0; s < RS; ++s) {
                 const int64_t row0 = (group * kRowBlocksPerSuper + pair * RS + s) * kRowsPerBlock + quad * 4;
@@ -275,7 +293,8 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
                         v = (ok[r] != 0.f) ? v : NEG_INF;
                         mr = fmaxf(mr, v);
                     }
-                    if (NRB == 1) {  // this row block is a candidate group of its own
+                    if (NRB == 1) {  // this row block is a candidate group of its own (store_group_max, inline: as a call
+                        // it moved the registers of every 16-row-group instantiation and the occupancy of two, tried)
                         mr = col4_max(mr);
                         if (lane < 16 && 16 * g + lane < nq)
                             gmax[(int64_t)(16 * g + lane) * gmax_stride + group * kRowBlocksPerSuper + pair * RS + s] = mr;
@@ -287,11 +306,7 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
         }
         if (NRB != 1) {
 #pragma unroll
-            for (int g = 0; g < G; ++g) {
-                float v = m[g];
-                v = col4_max(v);
-                if (lane < 16 && 16 * g + lane < nq) gmax[(int64_t)(16 * g + lane) * gmax_stride + group] = v;
-            }
+            for (int g = 0; g < G; ++g) store_group_max(m[g], gmax, gmax_stride, group, 16 * g + lane, nq, lane);
         }
     }
 }
@@ -309,7 +324,7 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
 // L2: L2 : HBM traffic = 1 : 1.  MFMA work per corpus KiB is GQ x 16 cycles per
 // SIMD (GQ = 16: 64 cycles per KiB per CU against ~100 cycles per KiB of HBM
 // supply), so the pass stays HBM-bound.
-// L2: as in dense_scan_kernel.
+// L2, epilogue and output: those of dense_scan_kernel.
 template <typename STORE, int GQ, int NRB, bool L2 = false>
 __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
     const chunk_t* __restrict__ tiles, const chunk_t* __restrict__ qfrag, const float* __restrict__ scale,
@@ -335,7 +350,8 @@ __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
     for (int g = 0; g < GQ; ++g) cf[g] = L2 ? qcoef[16 * g + (lane & 15)] : 0.f;
     const int64_t n_rounds = (n_super + total_waves - 1) / total_waves;  // the same for every wave: lockstep
 
-    // corpus prefetch cursor (as in dense_scan_kernel); past the end (and for idle waves) re-read a valid group
+    // corpus prefetch cursor (the walk of dense_scan_kernel's); past the end, and for idle waves (every wave walks
+    // every round), re-read a valid group
     const int64_t safe_group = wave % n_super;
     int64_t pf_group = wave;
     int pf_pair = 0, pf_kt = 0;
@@ -442,9 +458,7 @@ __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
                             mr = fmaxf(mr, v);
                         }
                         if (NRB == 1) {
-                            mr = col4_max(mr);
-                            if (lane < 16 && 16 * g + lane < nq)
-                                gmax[(int64_t)(16 * g + lane) * gmax_stride + group * kRowBlocksPerSuper + pair * RS + s] = mr;
+                            store_group_max(mr, gmax, gmax_stride, group * kRowBlocksPerSuper + pair * RS + s, 16 * g + lane, nq, lane);
                         } else {
                             m[g] = fmaxf(m[g], mr);
                         }
@@ -454,11 +468,7 @@ __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
         }
         if (NRB != 1 && live) {
 #pragma unroll
-            for (int g = 0; g < GQ; ++g) {
-                float v = m[g];
-                v = col4_max(v);
-                if (lane < 16 && 16 * g + lane < nq) gmax[(int64_t)(16 * g + lane) * gmax_stride + group] = v;
-            }
+            for (int g = 0; g < GQ; ++g) store_group_max(m[g], gmax, gmax_stride, group, 16 * g + lane, nq, lane);
         }
     }
 }
@@ -482,7 +492,7 @@ __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
 //     vector-memory path.
 // The 64 row scales of the NEXT super-group travel the same way (one 256-byte LDS-DMA load by wave 0,
 // a whole super-group ahead): an ordinary register load inside the loop would make the compiler wait
-// for it with vmcnt(0), i.e. drain the ring.  Epilogue and output (per-group maxima) as in the other scans.
+// for it with vmcnt(0), i.e. drain the ring.  Epilogue and output (per-group maxima): those of dense_scan_kernel, scales from LDS.
 // Measured at 10M x 768: 3.77 ms per 256 queries (4.09 TB/s) against 2 x 2.6 ms for two 128-query passes (stages of
 // 8 tiles, i.e. three barriers per row block: 4.0 ms; a stage's refill loads issued in one burst: 3.82 ms).  The DMA stream alone (no LDS reads, no MFMAs) runs at
 // 5.06 TB/s with nontemporal loads (4.3 TB/s without the hint; ring depth changes nothing), and the LDS reads
@@ -494,6 +504,39 @@ constexpr int kQregStages = 5;        // ring depth in stages of one row block (
 typedef __attribute__((address_space(1))) const void* hr_gptr_t;
 typedef __attribute__((address_space(3))) void* hr_lptr_t;
 
+// LDS-DMA loader of the register-resident 256-query scans (dense_scan_qreg_kernel, dense_scan_q64_kernel).  A block of NW
+// waves walks the super-groups first, first + step, ... and brings their tiles HBM -> LDS in stages of T tiles (one row
+// block) into ring slots of T tiles each; wave w brings tiles w, w + NW, ... of every stage, all of which lie inside the
+// same super-group (TPS tiles, contiguous in the shard).  Past the block's last super-group the loader re-reads the
+// first: harmless, and it keeps the count of loads in flight fixed, which the counted vmcnt waits rely on.
+template <int T, int NW>
+struct StageLoader {
+    static constexpr int TPS = kRowBlocksPerSuper * T;
+    int64_t sg;   // super-group and first tile within it of the stage the loader is at
+    int within;
+    // tile wid + l * NW of that stage
+    __device__ __forceinline__ void issue_one(chunk_t* ring, int stage_slot, int l, const chunk_t* tiles, int64_t n_super,
+                                              int64_t first, int wid, int lane) const {
+        const int64_t sgc = sg < n_super ? sg : first;
+        const chunk_t* src = tiles + (sgc * TPS + within + l * NW) * kTileChunks + lane;
+        __builtin_amdgcn_global_load_lds((hr_gptr_t)src, (hr_lptr_t)(ring + (stage_slot * T + wid + l * NW) * kTileChunks), 16,
+                                         0, 2 /* nt: each byte is read once */);
+    }
+    __device__ __forceinline__ void advance(int64_t step) {
+        within += T;
+        if (within >= TPS) {
+            within -= TPS;
+            sg += step;
+        }
+    }
+};
+// The 64 row scales of super-group sg into LDS the same way (one 256-byte load by one wave; past the end: the first).
+__device__ __forceinline__ void issue_scale_lds(const float* scale, int64_t sg, int64_t n_super, int64_t first, int lane,
+                                                float* dst) {
+    const int64_t sgc = sg < n_super ? sg : first;
+    __builtin_amdgcn_global_load_lds((hr_gptr_t)(scale + sgc * kSuperRows + lane), (hr_lptr_t)dst, 4, 0, 0);
+}
+
 template <int KT, int NRB, int GW, int NW>  // NW waves x GW groups of 16 queries per pass
 __global__ __launch_bounds__(64 * NW) void dense_scan_qreg_kernel(
     const chunk_t* __restrict__ tiles, const chunk_t* __restrict__ qfrag, const float* __restrict__ scale,
@@ -501,7 +544,6 @@ __global__ __launch_bounds__(64 * NW) void dense_scan_qreg_kernel(
     constexpr int T = KT, NS = kQregStages;       // one stage = the KT tiles of one row block (one barrier per row block)
     constexpr int kRing = NS * T;
     constexpr int L = T / NW;                     // tiles a wave loads per stage
-    constexpr int TPS = kRowBlocksPerSuper * KT;  // tiles of one 64-row super-group, contiguous in the shard
     constexpr int H = 4;                          // tiles whose LDS reads are issued / awaited together
     static_assert(KT % T == 0 && T % NW == 0 && T % H == 0 && (T / H) % L == 0, "whole stages per row block, the same number of tiles per wave and stage");
     static_assert(NRB == 1 || NRB == kRowBlocksPerSuper, "group = one row block or one super-group");
@@ -533,35 +575,19 @@ __global__ __launch_bounds__(64 * NW) void dense_scan_qreg_kernel(
             asm volatile("" : "+v"(qf[gq][kt]), "+v"(qf[gq][kt + 1]), "+v"(qf[gq][kt + 2]), "+v"(qf[gq][kt + 3]),
                               "+v"(qf[gq][kt + 4]), "+v"(qf[gq][kt + 5]), "+v"(qf[gq][kt + 6]), "+v"(qf[gq][kt + 7]));
 
-    // loader: wave w brings tile w of every stage
-    int64_t ld_sg = first;
-    int ld_within = wid;
-    // tile wid + l * NW of the stage the loader is at (all L of them lie inside the same super-group)
-    auto issue_one = [&](int stage_slot, int l) {
-        const int64_t sg = ld_sg < n_super ? ld_sg : first;  // past the end: harmless re-read, keeps the count of loads in flight fixed
-        const chunk_t* src = tiles + (sg * TPS + ld_within + l * NW) * kTileChunks + lane;
-        __builtin_amdgcn_global_load_lds((hr_gptr_t)src, (hr_lptr_t)(ring + (stage_slot * T + wid + l * NW) * kTileChunks), 16,
-                                         0, 2 /* nt: each byte is read once */);
-    };
-    auto advance_loader = [&]() {
-        ld_within += T;
-        if (ld_within >= TPS) {
-            ld_within -= TPS;
-            ld_sg += step;
-        }
-    };
-    auto issue = [&](int stage_slot) {
-#pragma unroll
-        for (int l = 0; l < L; ++l) issue_one(stage_slot, l);
-        advance_loader();
-    };
+    StageLoader<T, NW> ld{first, wid};
+    auto issue_one = [&](int stage_slot, int l) { ld.issue_one(ring, stage_slot, l, tiles, n_super, first, wid, lane); };
+    auto advance_loader = [&]() { ld.advance(step); };
     auto issue_scale = [&](int64_t sg, int slot) {  // wave 0 only: one more (older) operation on its counter
-        const int64_t sgc = sg < n_super ? sg : first;
-        __builtin_amdgcn_global_load_lds((hr_gptr_t)(scale + sgc * kSuperRows + lane), (hr_lptr_t)&sc_lds[slot][0], 4, 0, 0);
+        issue_scale_lds(scale, sg, n_super, first, lane, reinterpret_cast<float*>(&sc_lds[slot][0]));
     };
     if (wid == 0) issue_scale(first, 0);
 #pragma unroll
-    for (int s = 0; s < NS - 1; ++s) issue(s);
+    for (int s = 0; s < NS - 1; ++s) {
+#pragma unroll
+        for (int l = 0; l < L; ++l) issue_one(s, l);
+        advance_loader();
+    }
 
     int st = 0;  // stage slot of the stage about to be consumed
     int64_t sg = first;
@@ -631,8 +657,7 @@ __global__ __launch_bounds__(64 * NW) void dense_scan_qreg_kernel(
                     mr = fmaxf(mr, v);
                 }
                 if (NRB == 1) {
-                    mr = col4_max(mr);
-                    if (lane < 16 && q < nq) gmax[(int64_t)q * gmax_stride + sg * kRowBlocksPerSuper + rbi] = mr;
+                    store_group_max(mr, gmax, gmax_stride, sg * kRowBlocksPerSuper + rbi, q, nq, lane);
                 } else {
                     m[gq] = fmaxf(m[gq], mr);
                 }
@@ -640,12 +665,8 @@ __global__ __launch_bounds__(64 * NW) void dense_scan_qreg_kernel(
         }
         if (NRB != 1) {
 #pragma unroll
-            for (int gq = 0; gq < GW; ++gq) {
-                const int q = 16 * (wid * GW + gq) + (lane & 15);
-                float v = m[gq];
-                v = col4_max(v);
-                if (lane < 16 && q < nq) gmax[(int64_t)q * gmax_stride + sg] = v;
-            }
+            for (int gq = 0; gq < GW; ++gq)
+                store_group_max(m[gq], gmax, gmax_stride, sg, 16 * (wid * GW + gq) + (lane & 15), nq, lane);
         }
     }
     // LDS DMA still in flight must land before the block's LDS is handed to another block
@@ -683,7 +704,6 @@ __global__ __launch_bounds__(256, 1) void dense_scan_q64_kernel(
     const uint8_t* __restrict__ rowmask, float* __restrict__ gmax, int nq, int64_t n_rows, int64_t n_super) {
     constexpr int GW = 4, NW = 4, T = KT, NS = kQregStages;
     constexpr int L = T / NW;                     // tiles a wave loads per stage
-    constexpr int TPS = kRowBlocksPerSuper * KT;  // tiles of one 64-row super-group, contiguous in the shard
     constexpr int H = 4;                          // tiles whose LDS reads are issued / awaited together
     static_assert(T % NW == 0 && T % H == 0 && (T / H) == L, "one refill tile per group of four");
     static_assert(NRB == 1 || NRB == kRowBlocksPerSuper, "group = one row block or one super-group");
@@ -715,25 +735,11 @@ __global__ __launch_bounds__(256, 1) void dense_scan_q64_kernel(
 #pragma unroll
         for (int kt = 0; kt < KT; ++kt) asm volatile("" : "+a"(qa[gq][kt]), "+v"(qv[gq][kt]));   // settled, and where they belong
 
-    // loader (as dense_scan_qreg_kernel): wave w brings tiles w, w + NW, ... of every stage
-    int64_t ld_sg = first;
-    int ld_within = wid;
-    auto issue_one = [&](int stage_slot, int l) {
-        const int64_t sg = ld_sg < n_super ? ld_sg : first;  // past the end: harmless re-read, keeps the count of loads in flight fixed
-        const chunk_t* src = tiles + (sg * TPS + ld_within + l * NW) * kTileChunks + lane;
-        __builtin_amdgcn_global_load_lds((hr_gptr_t)src, (hr_lptr_t)(ring + (stage_slot * T + wid + l * NW) * kTileChunks), 16,
-                                         0, 2 /* nt: each byte is read once */);
-    };
-    auto advance_loader = [&]() {
-        ld_within += T;
-        if (ld_within >= TPS) {
-            ld_within -= TPS;
-            ld_sg += step;
-        }
-    };
+    StageLoader<T, NW> ld{first, wid};
+    auto issue_one = [&](int stage_slot, int l) { ld.issue_one(ring, stage_slot, l, tiles, n_super, first, wid, lane); };
+    auto advance_loader = [&]() { ld.advance(step); };
     auto issue_scale = [&](int64_t sg, int slot) {  // wave 0 only: one more (older) operation on its counter
-        const int64_t sgc = sg < n_super ? sg : first;
-        __builtin_amdgcn_global_load_lds((hr_gptr_t)(scale + sgc * kSuperRows + lane), (hr_lptr_t)(sc_lds + slot * kSuperRows), 4, 0, 0);
+        issue_scale_lds(scale, sg, n_super, first, lane, sc_lds + slot * kSuperRows);
     };
     if (wid == 0) issue_scale(first, 0);
 #pragma unroll
@@ -825,8 +831,7 @@ __global__ __launch_bounds__(256, 1) void dense_scan_q64_kernel(
                     mr = fmaxf(mr, v);
                 }
                 if (NRB == 1) {
-                    mr = col4_max(mr);
-                    if (lane < 16 && q < nq) gmax[(int64_t)q * gmax_stride + sg * kRowBlocksPerSuper + rbi] = mr;
+                    store_group_max(mr, gmax, gmax_stride, sg * kRowBlocksPerSuper + rbi, q, nq, lane);
                 } else {
                     m[gq] = fmaxf(m[gq], mr);
                 }
@@ -834,12 +839,8 @@ __global__ __launch_bounds__(256, 1) void dense_scan_q64_kernel(
         }
         if (NRB != 1) {
 #pragma unroll
-            for (int gq = 0; gq < GW; ++gq) {
-                const int q = 16 * (wid * GW + gq) + (lane & 15);
-                float v = m[gq];
-                v = col4_max(v);
-                if (lane < 16 && q < nq) gmax[(int64_t)q * gmax_stride + sg] = v;
-            }
+            for (int gq = 0; gq < GW; ++gq)
+                store_group_max(m[gq], gmax, gmax_stride, sg, 16 * (wid * GW + gq) + (lane & 15), nq, lane);
         }
     }
     // LDS DMA still in flight must land before the block's LDS is handed to another block
@@ -848,7 +849,6 @@ __global__ __launch_bounds__(256, 1) void dense_scan_q64_kernel(
 
 // ---------------------------------------------------------------------------
 // 256-query scan as a tiled contraction (any KT >= 8, fp16 shards): BASELINE config 5's shape (D = 1024, B = 256).
-// (GQ = 8 is the same kernel for 65..128 queries: 64 accumulator registers per wave, half the query ring.)
 //
 // 256 queries x 1024 dims of fp16 are 512 KiB — as much as a CU's whole register file — so for this shape the queries
 // can be stationary neither in registers (dense_scan_qreg_kernel: D = 768 only) nor in LDS; two 128-query passes read
@@ -893,24 +893,20 @@ constexpr int kGemmRowBlocks = 16;               // row blocks per block tile (2
 #define HR_GEMM_DB 3
 #endif
 constexpr int kGemmDA = HR_GEMM_DA, kGemmDB = HR_GEMM_DB;  // ring depth (k-steps) of the corpus / query stream
-#ifndef HR_GEMM_DA128
-#define HR_GEMM_DA128 7
-#endif
 #ifndef HR_GEMM_READ_BURST
 #define HR_GEMM_READ_BURST 3
 #endif
 constexpr int kGemmReadBurst = HR_GEMM_READ_BURST;  // next-step fragment reads issued together between the MFMAs
-constexpr int kGemmDA128 = HR_GEMM_DA128;        // corpus ring depth of the 128-query form (its query ring is half the size)
 
-template <int GQ, int NRB>                       // GQ query groups of 16 per pass: 16 (256 queries) or 8 (128)
+template <int GQ, int NRB>                       // GQ query groups of 16 per pass: 16 (256 queries; a 128-query form gained nothing)
 __global__ __launch_bounds__(512) void dense_scan_gemm_kernel(
     const chunk_t* __restrict__ tiles, const chunk_t* __restrict__ qfrag, const float* __restrict__ scale,
     const uint8_t* __restrict__ rowmask, float* __restrict__ gmax, int nq, int KT, int64_t n_rows, int64_t n_super) {
     static_assert(NRB == 1 || NRB == kRowBlocksPerSuper, "group = one row block or one super-group");
-    static_assert(GQ == 16 || GQ == 8, "four query quarters of 4 or 2 groups");
-    constexpr int DA = GQ == 16 ? kGemmDA : kGemmDA128, DB = kGemmDB, RB = kGemmRowBlocks;
+    static_assert(GQ == 16, "four query quarters of 4 groups");
+    constexpr int DA = kGemmDA, DB = kGemmDB, RB = kGemmRowBlocks;
     constexpr int WA = RB / 2, WB = GQ / 4;      // fragments a wave reads per step: its row blocks, its query groups
-    constexpr int PB = GQ / 4;                   // 1 KiB pieces a query loader moves per step (a corpus loader: 4)
+    constexpr int PB = GQ / 4;                   // 1 KiB pieces a query loader moves per step: 4, as a corpus loader
     __shared__ chunk_t ringA[DA * RB * kTileChunks];
     __shared__ chunk_t ringB[DB * GQ * kTileChunks];
     __shared__ f32x4_t sc_lds[2][RB * kRowsPerBlock / 4];
@@ -956,6 +952,8 @@ __global__ __launch_bounds__(512) void dense_scan_gemm_kernel(
     if (loads_a) tile_setup();
     else src = reinterpret_cast<const char*>(qfrag) + (unsigned long long)lw * (unsigned long long)KT * 1024ull;
     auto piece = [&](int l) {  // 1 KiB of the loader's current step into its ring slot
+        // the test is always true (PB = 4), a leftover of the 128-query form: without it hipcc numbers five of the
+        // kernel's accumulator quads differently, and the kernel is kept instruction for instruction what was measured
         if (l < PB || loads_a)
             __builtin_amdgcn_global_load_lds((hr_gptr_t)(src + rel[l] + lane16),
                                              (hr_lptr_t)(ring_w + (l_slot * slot_tiles + 4 * l) * kTileChunks), 16, 0, 0);

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "attention.h"
 #include "encoder_layer.h"
+#include "scan_plan.h"
 #include "dense.h"
 #include "encoder_ops.h"
 #include "filter.h"
@@ -329,21 +330,27 @@ struct Span {
 // Compute units the scans may occupy: their persistent grids are sized to it (hr_set_scan_cus for a masked stream).
 inline int scan_cus(const hr_index* h) { return h->scan_cus > 0 ? std::min(h->scan_cus, h->cu_count) : h->cu_count; }
 
-// Rows (docs) per candidate group.  Small shards (a rank of a multi-GPU corpus) use 16-row
-// groups: 4x less refine traffic per query, and the 4x larger table of group maxima is
-// still small.  Big shards use 64-row groups, where selecting among 4x more maxima would
-// cost more than the refine saves (measured at 10M x 768: 3.88 ms/step vs 4.08).
-int group_rows_for(const hr_index* h, int64_t n) {
-    if (h->group_rows_override) return h->group_rows_override;
-    return n > 3000000 ? 64 : 16;
-}
+int group_rows_for(const hr_index* h, int64_t n) { return scan_group_rows(n, h->group_rows_override); }
 
 // ---- dense launch helpers ----------------------------------------------------
+// One launcher per scan kernel (grid and LDS sizing), then launch_scan: the one place that maps a ScanPlan
+// (scan_plan.h) onto the template instantiation.  n_super counts SUPER-groups (64 rows) = the scans' loop bound.
+struct ScanArgs {
+    const hr_index* h;
+    hipStream_t s;
+    const chunk_t* qfrag;
+    const uint8_t* mask;
+    float* gmax;
+    int nq;
+    int64_t n_super;
+    const float* qcoef;  // L2 passes: the coefficients of this pass's query slots
+};
+
 template <typename STORE, int G, int NRB, bool L2>
-hipError_t launch_scan(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask, float* gmax,
-                       int nq, int64_t n_groups, const float* qcoef) {
+hipError_t launch_scan_lds(const ScanArgs& a) {
     constexpr int RS = 2, PF = 4;
     auto kern = dense_scan_kernel<STORE, G, RS, PF, NRB, L2>;
+    const hr_index* h = a.h;
     const size_t lds = (size_t)G * h->KT * 1024;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -358,131 +365,106 @@ hipError_t launch_scan(const hr_index* h, hipStream_t s, const chunk_t* qfrag, c
         per_cu = (int)std::min<size_t>(8, (150 * 1024) / std::max<size_t>(lds, 1));
     }
     const int64_t waves_per_block = threads / 64;
-    int64_t blocks = std::min<int64_t>((n_groups + waves_per_block - 1) / waves_per_block,
+    int64_t blocks = std::min<int64_t>((a.n_super + waves_per_block - 1) / waves_per_block,
                                        (int64_t)scan_cus(h) * per_cu);
     blocks = std::max<int64_t>(blocks, 1);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), lds, s, h->tiles.as<chunk_t>(), qfrag,
-                       h->scale.as<float>(), mask, gmax, nq, h->KT, h->n_rows, n_groups, qcoef);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), lds, a.s, h->tiles.as<chunk_t>(), a.qfrag,
+                       h->scale.as<float>(), a.mask, a.gmax, a.nq, h->KT, h->n_rows, a.n_super, a.qcoef);
     return hipGetLastError();
-}
-
-template <typename STORE, bool L2>
-hipError_t launch_scan_g(const hr_index* h, hipStream_t s, int G, const chunk_t* qfrag, const uint8_t* mask,
-                         float* gmax, int nq, int64_t n_groups, const float* qcoef) {
-    // n_groups here counts SUPER-groups (64 rows) = the scan's loop bound
-    if (group_rows_for(h, h->n_rows) == 16) {
-        switch (G) {
-            case 1: return launch_scan<STORE, 1, 1, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
-            case 2: return launch_scan<STORE, 2, 1, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
-            case 3: return launch_scan<STORE, 3, 1, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
-            default: return launch_scan<STORE, 4, 1, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
-        }
-    }
-    switch (G) {
-        case 1: return launch_scan<STORE, 1, 4, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
-        case 2: return launch_scan<STORE, 2, 4, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
-        case 3: return launch_scan<STORE, 3, 4, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
-        default: return launch_scan<STORE, 4, 4, L2>(h, s, qfrag, mask, gmax, nq, n_groups, qcoef);
-    }
 }
 
 // Large-batch pass (dense_scan_bigq_kernel): GQ query groups streamed through LDS in k-chunks.
 template <typename STORE, int GQ, int NRB, bool L2>
-hipError_t launch_scan_bigq(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask, float* gmax,
-                            int nq, int64_t n_super, const float* qcoef) {
+hipError_t launch_scan_bigq(const ScanArgs& a) {
     auto kern = dense_scan_bigq_kernel<STORE, GQ, NRB, L2>;
+    const hr_index* h = a.h;
     const size_t lds = (size_t)2 * GQ * 2 * 1024;  // 2 buffers x GQ groups x BKT(2) fragments of 1 KiB
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    int64_t blocks = std::min<int64_t>((n_super + 7) / 8, (int64_t)scan_cus(h));
+    int64_t blocks = std::min<int64_t>((a.n_super + 7) / 8, (int64_t)scan_cus(h));
     blocks = std::max<int64_t>(blocks, 1);
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, s, h->tiles.as<chunk_t>(), qfrag,
-                       h->scale.as<float>(), mask, gmax, nq, h->KT, h->n_rows, n_super, qcoef);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, a.s, h->tiles.as<chunk_t>(), a.qfrag,
+                       h->scale.as<float>(), a.mask, a.gmax, a.nq, h->KT, h->n_rows, a.n_super, a.qcoef);
     return hipGetLastError();
-}
-template <typename STORE, bool L2>
-hipError_t launch_scan_bigq_g(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask,
-                              float* gmax, int nq, int64_t n_super, const float* qcoef) {
-    return group_rows_for(h, h->n_rows) == 16
-               ? launch_scan_bigq<STORE, 8, 1, L2>(h, s, qfrag, mask, gmax, nq, n_super, qcoef)
-               : launch_scan_bigq<STORE, 8, 4, L2>(h, s, qfrag, mask, gmax, nq, n_super, qcoef);
 }
 
 // 256-query pass with the queries in registers and the corpus streamed through LDS (dense_scan_qreg_kernel):
-// fp16 shards whose rows are 24 tiles long (D = 768 after padding; 2 x 24 x 4 fragment registers per wave).
-// hr_debug_option(HR_DEBUG_DENSE_KERNELS) bit mask (tests drive every scan kernel at every shape): 1 = no register-
-// resident 256-query pass, 2 = no tiled-contraction pass, 4 = no k-chunked large-batch pass, 8 = prefer the tiled
-// contraction to the register-resident pass where both apply
-int g_dense_kernels = 0;
-int g_sparse_rpb = 0;     // HR_DEBUG_SPARSE_RPB: doc ranges per sparse-scan block (0 = by shard size)
-int g_no_trim = 0;        // HR_DEBUG_NO_TRIM: 1 = refine all C candidate groups (A/B of the data-dependent candidate set)
-int g_group_rows = 0;     // HR_DEBUG_GROUP_ROWS: candidate-group size of handles created from now on (0 = by shard size)
-bool qreg_supported(const hr_index* h) {
-    return !(g_dense_kernels & 1) && h->dtype == HR_F16 && h->KT == 24;
-}
+// fp16 shards whose rows are 24 tiles long (D = 768 after padding; 2 x 24 x 4 fragment registers per wave);
+// 8 waves x 32 queries, one block per CU.
 template <int KT, int NRB, int GW, int NW>
-hipError_t launch_scan_qreg(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask, float* gmax,
-                            int nq, int64_t n_super) {
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(n_super, (int64_t)scan_cus(h) * (8 / NW)));
-    hipLaunchKernelGGL((dense_scan_qreg_kernel<KT, NRB, GW, NW>), dim3((unsigned)blocks), dim3(64 * NW), 0, s,
-                       h->tiles.as<chunk_t>(), qfrag, h->scale.as<float>(), mask, gmax, nq, h->n_rows, n_super);
+hipError_t launch_scan_qreg(const ScanArgs& a) {
+    const hr_index* h = a.h;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(a.n_super, (int64_t)scan_cus(h) * (8 / NW)));
+    hipLaunchKernelGGL((dense_scan_qreg_kernel<KT, NRB, GW, NW>), dim3((unsigned)blocks), dim3(64 * NW), 0, a.s,
+                       h->tiles.as<chunk_t>(), a.qfrag, h->scale.as<float>(), a.mask, a.gmax, a.nq, h->n_rows, a.n_super);
     return hipGetLastError();
-}
-// 256 queries per pass: 8 waves x 32 queries, one block per CU
-hipError_t launch_scan_qreg_g(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask, float* gmax,
-                              int nq, int64_t n_super) {
-    return group_rows_for(h, h->n_rows) == 16 ? launch_scan_qreg<24, 1, 2, 8>(h, s, qfrag, mask, gmax, nq, n_super)
-                                              : launch_scan_qreg<24, 4, 2, 8>(h, s, qfrag, mask, gmax, nq, n_super);
 }
 // 256 queries per pass, second form: 4 waves x 64 queries in registers (one wave per SIMD, the whole 512-entry register
 // file), the corpus through the same LDS-DMA ring with half the LDS reads (dense_scan_q64_kernel).
-// HR_DEBUG_DENSE_KERNELS bit 16 selects it.
-hipError_t launch_scan_q64_g(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask, float* gmax,
-                             int nq, int64_t n_super) {
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(n_super, (int64_t)scan_cus(h)));
+template <int NRB>
+hipError_t launch_scan_q64(const ScanArgs& a) {
+    const hr_index* h = a.h;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(a.n_super, (int64_t)scan_cus(h)));
     const size_t lds = (size_t)kQregStages * 24 * 1024 + 2 * kSuperRows * sizeof(float);
-    static bool ready = false;
+    static bool ready = false;  // per group size
     if (!ready) {
-        hipError_t e = hipFuncSetAttribute((const void*)dense_scan_q64_kernel<24, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute((const void*)dense_scan_q64_kernel<24, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute((const void*)dense_scan_q64_kernel<24, NRB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         ready = true;
     }
-    if (group_rows_for(h, h->n_rows) == 16)
-        hipLaunchKernelGGL((dense_scan_q64_kernel<24, 1>), dim3((unsigned)blocks), dim3(256), lds, s, h->tiles.as<chunk_t>(), qfrag,
-                           h->scale.as<float>(), mask, gmax, nq, h->n_rows, n_super);
-    else
-        hipLaunchKernelGGL((dense_scan_q64_kernel<24, 4>), dim3((unsigned)blocks), dim3(256), lds, s, h->tiles.as<chunk_t>(), qfrag,
-                           h->scale.as<float>(), mask, gmax, nq, h->n_rows, n_super);
+    hipLaunchKernelGGL((dense_scan_q64_kernel<24, NRB>), dim3((unsigned)blocks), dim3(256), lds, a.s, h->tiles.as<chunk_t>(),
+                       a.qfrag, h->scale.as<float>(), a.mask, a.gmax, a.nq, h->n_rows, a.n_super);
     return hipGetLastError();
 }
 // 256-query pass as a tiled contraction (dense_scan_gemm_kernel): fp16 shards of any row length from 8 tiles up;
 // serves the shapes the register-resident form cannot (D = 1024: BASELINE config 5).
-bool gemm_supported(const hr_index* h) {
-    return !(g_dense_kernels & 2) && h->dtype == HR_F16 && h->KT >= 8;
-}
-template <int GQ>
-hipError_t launch_scan_gemm_g(const hr_index* h, hipStream_t s, const chunk_t* qfrag, const uint8_t* mask, float* gmax,
-                              int nq, int64_t n_super) {
-    const int64_t n_tiles = (n_super * kRowBlocksPerSuper + kGemmRowBlocks - 1) / kGemmRowBlocks;
+template <int NRB>
+hipError_t launch_scan_gemm(const ScanArgs& a) {
+    const hr_index* h = a.h;
+    const int64_t n_tiles = (a.n_super * kRowBlocksPerSuper + kGemmRowBlocks - 1) / kGemmRowBlocks;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(n_tiles, scan_cus(h)));
-    if (group_rows_for(h, h->n_rows) == 16)
-        hipLaunchKernelGGL((dense_scan_gemm_kernel<GQ, 1>), dim3(blocks), dim3(512), 0, s, h->tiles.as<chunk_t>(), qfrag,
-                           h->scale.as<float>(), mask, gmax, nq, h->KT, h->n_rows, n_super);
-    else
-        hipLaunchKernelGGL((dense_scan_gemm_kernel<GQ, 4>), dim3(blocks), dim3(512), 0, s, h->tiles.as<chunk_t>(), qfrag,
-                           h->scale.as<float>(), mask, gmax, nq, h->KT, h->n_rows, n_super);
+    hipLaunchKernelGGL((dense_scan_gemm_kernel<16, NRB>), dim3(blocks), dim3(512), 0, a.s, h->tiles.as<chunk_t>(), a.qfrag,
+                       h->scale.as<float>(), a.mask, a.gmax, a.nq, h->KT, h->n_rows, a.n_super);
     return hipGetLastError();
 }
-constexpr int kScanTileKiB = 156;   // LDS the LDS-resident pass's query tile may take: G * KT KiB
-int max_groups_for_dim(const hr_index* h) {
-    int g = kScanTileKiB / std::max(h->KT, 1);
-    return std::max(1, std::min(4, g));
+
+// f(std::integral_constant<int, V>) for the V among Vs that equals v
+template <int... Vs, typename F>
+hipError_t with_constant(int v, F f) {
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == Vs ? (e = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+    return e;
 }
-// fp32 rows longer than 2496 (KT > 156) do not fit even one group of 16 queries: every batch of such a shard takes the
-// k-chunked pass, whose LDS does not grow with KT
-bool scan_tile_fits(const hr_index* h) { return max_groups_for_dim(h) * h->KT <= kScanTileKiB; }
+
+// The two generic kernels: STORE x L2 here, NRB x G below.
+template <typename STORE, bool L2>
+hipError_t launch_scan_generic(const ScanPlan& p, const ScanArgs& a) {
+    return with_constant<1, 4>(p.NRB, [&](auto nrb) {
+        if (p.kind == SCAN_BIGQ) return launch_scan_bigq<STORE, 8, decltype(nrb)::value, L2>(a);
+        return with_constant<1, 2, 3, 4>(
+            p.G, [&](auto g) { return launch_scan_lds<STORE, decltype(g)::value, decltype(nrb)::value, L2>(a); });
+    });
+}
+
+hipError_t launch_scan(const ScanPlan& p, const ScanArgs& a) {
+    switch (p.kind) {
+        case SCAN_QREG: return with_constant<1, 4>(p.NRB, [&](auto nrb) { return launch_scan_qreg<24, decltype(nrb)::value, 2, 8>(a); });
+        case SCAN_Q64: return with_constant<1, 4>(p.NRB, [&](auto nrb) { return launch_scan_q64<decltype(nrb)::value>(a); });
+        case SCAN_GEMM: return with_constant<1, 4>(p.NRB, [&](auto nrb) { return launch_scan_gemm<decltype(nrb)::value>(a); });
+        case SCAN_LDS:
+        case SCAN_BIGQ: {
+            const bool f16 = a.h->dtype == HR_F16;
+            if (p.l2) return f16 ? launch_scan_generic<_Float16, true>(p, a) : launch_scan_generic<float, true>(p, a);
+            return f16 ? launch_scan_generic<_Float16, false>(p, a) : launch_scan_generic<float, false>(p, a);
+        }
+        default: return hipErrorInvalidValue;
+    }
+}
+
+int g_dense_kernels = 0;  // HR_DEBUG_DENSE_KERNELS: bit mask that takes scan kernels out of the selection (scan_plan.h)
+int g_sparse_rpb = 0;     // HR_DEBUG_SPARSE_RPB: doc ranges per sparse-scan block (0 = by shard size)
+int g_no_trim = 0;        // HR_DEBUG_NO_TRIM: 1 = refine all C candidate groups (A/B of the data-dependent candidate set)
+int g_group_rows = 0;     // HR_DEBUG_GROUP_ROWS: candidate-group size of handles created from now on (0 = by shard size)
 
 // Two-level candidate selection: per-bucket maxima, then one block per query — for one modality or for both
 // modalities of a hybrid search in one pair of launches (select.h: GroupSelPair).
@@ -745,20 +727,16 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
     const int GR = group_rows_for(h, h->n_rows);
     const int64_t n_super = (h->n_rows + kSuperRows - 1) / kSuperRows;
     const int64_t n_groups = n_super * (kSuperRows / GR);  // group maxima per query (tail groups hold -inf)
-    const int Gsmall = max_groups_for_dim(h);
-    // batches beyond what fits LDS whole go through the k-chunked large-batch pass, 128 or 256 queries at a time
-    const bool big = (B > 16 * Gsmall || !scan_tile_fits(h)) && h->KT % 4 == 0 && !(g_dense_kernels & 4);
-    if (!big && !scan_tile_fits(h))
+    // one plan per pass (scan_plan.h); the full-batch plan gives the queries per pass
+    auto plan_for = [&](int nq) {
+        return scan_plan(h->KT, h->dtype, h->metric, h->n_rows, h->group_rows_override, g_dense_kernels, B, nq);
+    };
+    const ScanPlan first = plan_for(B);
+    if (first.kind == SCAN_NONE)
         return fail(h, HR_ELIMIT, "dim=%lld: the query tile does not fit LDS and the k-chunked pass is switched off",
                     (long long)h->dim);
-    const bool prefer_gemm = (g_dense_kernels & 8) != 0;
-    const bool use_qreg = qreg_supported(h) && !(prefer_gemm && gemm_supported(h));
-    // L2 shards: dense_scan_kernel up to 16 * Gsmall queries, dense_scan_bigq_kernel (128 queries per pass) beyond and for
-    // rows too long for the LDS-resident tile; the inline-asm 256-query forms serve COSINE / IP only
-    const bool l2 = h->metric == HR_METRIC_L2;
-    const bool big256 = big && B > 128 && !l2 && (use_qreg || gemm_supported(h));   // 256 queries per pass
-    const int Gmax = big256 ? 16 : big ? 8 : Gsmall;
-    const int chunk_q = 16 * Gmax;
+    const bool l2 = first.l2;
+    const int chunk_q = first.chunk_q, Gmax = chunk_q / 16;
     const int n_chunks = (B + chunk_q - 1) / chunk_q;
     const size_t chunk_frag = (size_t)Gmax * h->KT * kTileChunks;   // 16-byte chunks of one pass's query fragments
     HIP_TRY(h, ws->qfrag.ensure((size_t)n_chunks * chunk_frag * sizeof(chunk_t)));
@@ -776,11 +754,10 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
     HIP_TRY(h, ws->cscore.ensure((size_t)B * C * GR * sizeof(float)));
     HIP_TRY(h, ws->crow.ensure((size_t)B * C * GR * sizeof(int32_t)));
 
-    auto groups_of = [&](int nq) { return big ? ((big256 && nq > 128) ? 16 : 8) : (nq + 15) / 16; };
     if (phases & PHASE_PREP) {
         // every pass's queries in one launch: pass c owns fragment groups [c * Gmax, ...) of qfrag (slot = query number)
         Span sp(h, s, PH_PREP);
-        const int G_total = (n_chunks - 1) * Gmax + groups_of(B - (n_chunks - 1) * chunk_q);
+        const int G_total = (n_chunks - 1) * Gmax + plan_for(B - (n_chunks - 1) * chunk_q).G;
         if (h->dtype == HR_F16)
             hipLaunchKernelGGL((prep_queries_kernel<_Float16>), dim3(16 * G_total), dim3(256), 0, s, d_q, B, (int)h->dim,
                                h->KT, ws->qfrag.as<chunk_t>(), ws->qn2.as<double>(), d_coef, d_qeps, rt_eps);
@@ -791,31 +768,10 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
     }
     for (int c0 = 0; (phases & PHASE_SCAN) && c0 < B; c0 += chunk_q) {
         const int nq = std::min(chunk_q, B - c0);
-        const bool pass256 = big256 && nq > 128;   // a trailing chunk of <= 128 queries takes the 128-query pass
-        const int G = groups_of(nq);
-        const chunk_t* qf = ws->qfrag.as<chunk_t>() + (size_t)(c0 / chunk_q) * chunk_frag;
-        {
-            Span sp(h, s, PH_SCAN);
-            float* gm = ws->gmax.as<float>() + (int64_t)c0 * n_groups;
-            hipError_t e;
-            if (pass256)
-                e = (use_qreg && (g_dense_kernels & 16)) ? launch_scan_q64_g(h, s, qf, d_mask, gm, nq, n_super)
-                    : use_qreg ? launch_scan_qreg_g(h, s, qf, d_mask, gm, nq, n_super)
-                               : launch_scan_gemm_g<16>(h, s, qf, d_mask, gm, nq, n_super);
-            else if (big && l2)
-                e = (h->dtype == HR_F16) ? launch_scan_bigq_g<_Float16, true>(h, s, qf, d_mask, gm, nq, n_super, d_coef + c0)
-                                         : launch_scan_bigq_g<float, true>(h, s, qf, d_mask, gm, nq, n_super, d_coef + c0);
-            else if (big)
-                e = (h->dtype == HR_F16) ? launch_scan_bigq_g<_Float16, false>(h, s, qf, d_mask, gm, nq, n_super, nullptr)
-                                         : launch_scan_bigq_g<float, false>(h, s, qf, d_mask, gm, nq, n_super, nullptr);
-            else if (l2)
-                e = (h->dtype == HR_F16) ? launch_scan_g<_Float16, true>(h, s, G, qf, d_mask, gm, nq, n_super, d_coef + c0)
-                                         : launch_scan_g<float, true>(h, s, G, qf, d_mask, gm, nq, n_super, d_coef + c0);
-            else
-                e = (h->dtype == HR_F16) ? launch_scan_g<_Float16, false>(h, s, G, qf, d_mask, gm, nq, n_super, nullptr)
-                                         : launch_scan_g<float, false>(h, s, G, qf, d_mask, gm, nq, n_super, nullptr);
-            HIP_TRY(h, e);
-        }
+        Span sp(h, s, PH_SCAN);
+        const ScanArgs a{h, s, ws->qfrag.as<chunk_t>() + (size_t)(c0 / chunk_q) * chunk_frag, d_mask,
+                         ws->gmax.as<float>() + (int64_t)c0 * n_groups, nq, n_super, l2 ? d_coef + c0 : nullptr};
+        HIP_TRY(h, launch_scan(plan_for(nq), a));
     }
     if (scan_done) HIP_TRY(h, hipEventRecord(scan_done, s));
     if (!(phases & PHASE_FINISH)) return HR_OK;

@@ -100,3 +100,44 @@ def test_q64_pass_proves_its_lists_like_the_qreg_pass(gpu, options, group_rows):
     oids, osc = oracle.dense_search(X, q.cpu().numpy()[[0, 63, 64, 200, 255]], k, nat.HR_METRIC_COSINE)
     assert np.array_equal(out[16][0][[0, 63, 64, 200, 255]], oids)
     h.close()
+
+
+@pytest.mark.parametrize("group_rows", [16, 64])
+def test_every_scan_proves_its_lists_on_gaussian_rows(gpu, options, group_rows):
+    """A wrong group maximum out of a scan hides behind the canonical refine (the list comes out right, only not proven),
+    so this holds every scan to the exactness FLAGS of the device form: on random Gaussian rows every list is proven (as
+    the q64 test above relies on), whichever kernel scanned — the register-resident pass (0), the tiled contraction (8),
+    two 128-query passes (1|2), 64-query passes (4); at L2 the 128-query pass and a 2-query tail (0) and 64-query
+    passes (4).  Several super-groups per wave, a ragged last one, a 50 % row mask; ids and score bits against the
+    oracle on queries at both edges of every pass."""
+    torch = pytest.importorskip("torch")
+    from l2_yardstick import l2_search
+    options(nat.HR_DEBUG_GROUP_ROWS, group_rows)
+    rng = np.random.default_rng(100 + group_rows)
+    n, d, k = 5 * 64 * 7 + 37, 768, 40
+    X = rng.standard_normal((n, d)).astype(np.float32).astype(np.float16)
+    keep = np.packbits(rng.random(n) < 0.5, bitorder="little")
+    d_keep = torch.from_numpy(keep).cuda()
+    for metric, B, masks in ((nat.HR_METRIC_COSINE, 256, (0, 8, 1 | 2, 4)), (nat.HR_METRIC_L2, 130, (0, 4))):
+        Q = rng.standard_normal((B, d)).astype(np.float32)
+        pick = sorted({0, 63, 64, 127, 128, 129, B - 1})
+        if metric == nat.HR_METRIC_L2:
+            oids, osc = l2_search(X, Q[pick], k, keep)
+        else:
+            oids, osc = oracle.dense_search(X, Q[pick], k, metric, keep)
+        h = nat.ShardHandle(d, nat.HR_F16, metric)
+        h.add_dense(X)
+        h.finalize()
+        q = torch.from_numpy(Q).cuda()
+        for mask in masks:
+            options(nat.HR_DEBUG_DENSE_KERNELS, mask)
+            ids = torch.empty((B, k), dtype=torch.int64, device="cuda")
+            sc = torch.empty((B, k), dtype=torch.float32, device="cuda")
+            fl = torch.zeros((B,), dtype=torch.int32, device="cuda")
+            h.search_dense_dev(q.data_ptr(), B, k, ids.data_ptr(), sc.data_ptr(), fl.data_ptr(), d_keep.data_ptr(),
+                               torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            assert np.array_equal(fl.cpu().numpy(), np.ones(B, np.int32)), (metric, mask, np.nonzero(fl.cpu().numpy() != 1)[0][:8])
+            assert np.array_equal(ids.cpu().numpy()[pick], oids), (metric, mask)
+            assert np.array_equal(bits(sc.cpu().numpy()[pick]), bits(osc)), (metric, mask)
+        h.close()
