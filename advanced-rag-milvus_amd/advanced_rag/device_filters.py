@@ -94,7 +94,9 @@ class DeviceFilters:
 
     # ------------------------------------------------------------------ expression -> terms
     def _terms(self, expr: str, n: int) -> Tuple[List["nat.FilterTerm"], List[Tuple[str, str, str]]]:
-        terms, string_terms = [], []
+        # every term is checked and built before the first column is touched: an expression that is refused (a literal
+        # that would wrap in its field, a type mismatch, an unknown field, too many terms) uploads nothing
+        terms, string_terms, fields = [], [], []
         for field, op, value in _filters.parse(expr):
             if self.columns is None and field != "chunk_index":
                 raise ValueError("this shard was bulk-ingested without payload columns: only chunk_index (= row % 10) "
@@ -104,14 +106,15 @@ class DeviceFilters:
             if field in INT_COLUMNS:
                 if isinstance(value, str):
                     raise ValueError(f"field {field} is numeric; got string {value!r}")
+                value = _filters.numeric_literal(field, op, value, "i")   # ctypes would wrap an int beyond int64 silently
                 if isinstance(value, float):
-                    t.kind, t.dval = nat.HR_COL_I64_VS_F64, float(value)
+                    t.kind, t.dval = nat.HR_COL_I64_VS_F64, value
                 else:
-                    t.kind, t.ival = nat.HR_COL_I64, int(value)
+                    t.kind, t.ival = nat.HR_COL_I64, value
             elif field in FLOAT_COLUMNS:
                 if isinstance(value, str):
                     raise ValueError(f"field {field} is numeric; got string {value!r}")
-                t.kind, t.fval = nat.HR_COL_F32, float(np.float32(value))
+                t.kind, t.fval = nat.HR_COL_F32, float(_filters.numeric_literal(field, op, value, "f"))
             elif field in _STRING_FIELDS:
                 if not isinstance(value, str):
                     raise ValueError(f"field {field} is a string column; got {value!r}")
@@ -120,8 +123,12 @@ class DeviceFilters:
                 string_terms.append((_STRING_FIELDS[field], op, value))
             else:
                 raise ValueError(f"unknown filter field: {field}")
-            t.col = self._column(field, n).data_ptr()
             terms.append(t)
+            fields.append(field)
+        if len(terms) > 16:
+            raise ValueError("a filter expression may hold up to 16 terms")
+        for t, field in zip(terms, fields):
+            t.col = self._column(field, n).data_ptr()
         return terms, string_terms
 
     # ------------------------------------------------------------------ evaluation
@@ -134,8 +141,6 @@ class DeviceFilters:
         import torch
         dev = torch.device("cuda", self.device)
         terms, string_terms = self._terms(expr, n_rows) if expr else ([], [])
-        if len(terms) > 16:
-            raise ValueError("a filter expression may hold up to 16 terms")
         mask = torch.empty(mask_bytes(n_rows), dtype=torch.uint8, device=dev)
         und = torch.empty(mask_bytes(n_rows), dtype=torch.uint8, device=dev)
         counts = torch.zeros(2, dtype=torch.int32, device=dev)

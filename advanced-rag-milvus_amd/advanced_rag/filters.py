@@ -92,6 +92,30 @@ def parse(expr: str) -> List[Tuple[str, str, Any]]:
     return parsed
 
 
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def numeric_literal(field: str, op: str, value: Any, kind: str):
+    """The literal of `field op value` as the column compares it, or ValueError naming the term when the literal does not
+    fit (Milvus refuses such an expression; wrapping it into the field would answer another one).
+    kind "i" (INT64 field): an integer literal stays an int and must lie in [-2^63, 2^63 - 1]; a float literal stays a float
+    (the column is compared as float64, which holds every float literal).
+    kind "f" (FLOAT field): the literal rounded to float32; one beyond float32's range becomes +-inf, as numpy rounds it
+    (`entropy < 1e39` keeps every finite row), but an integer too large for a float at all is refused."""
+    if kind == "i":
+        if isinstance(value, float):
+            return value
+        if not INT64_MIN <= int(value) <= INT64_MAX:
+            raise ValueError(f"integer literal out of the int64 range in filter term: {field} {op} {value}")
+        return int(value)
+    try:
+        as_float = float(value)
+    except OverflowError:
+        raise ValueError(f"literal out of the floating-point range in filter term: {field} {op} {value}") from None
+    with np.errstate(over="ignore"):
+        return np.float32(as_float)
+
+
 def _compare(col: np.ndarray, op: str, value: Any) -> np.ndarray:
     if op == "==":
         return col == value
@@ -118,6 +142,11 @@ def evaluate(expr: str, columns: Dict[str, np.ndarray], n_rows: int) -> np.ndarr
                 raise ValueError(f"field {field} is a string column; got {value!r}")
         elif isinstance(value, str):
             raise ValueError(f"field {field} is numeric; got string {value!r}")
+        elif col.dtype.kind in "iu":
+            value = numeric_literal(field, op, value, "i")
+        elif col.dtype.kind == "f":
+            rounded = numeric_literal(field, op, value, "f")
+            value = rounded if col.dtype == np.float32 else float(value)
         keep &= _compare(col, op, value)
     return keep
 

@@ -282,7 +282,10 @@ def cpu_hybrid(Xn32, csr, Q, q_csr, top_k: int = 20, wa: float = 0.7, wb: float 
 #   * FLOAT fields (float32 columns) compare against the literal ROUNDED TO float32;
 #   * INT64 fields compare against an integer literal as integers (a bool counts as 0 / 1), against a float literal as float64;
 #   * VARCHAR fields compare by the UTF-8 bytes of the strings (= by code point); a string literal on a numeric field or a
-#     number on a string field is an error.
+#     number on a string field is an error;
+#   * a literal its field cannot hold is an error too (ValueError naming the term): an integer outside [-2^63, 2^63 - 1] on
+#     an INT64 field, an integer beyond every float on a FLOAT field.  A float literal beyond float32's range is no error:
+#     it rounds to +-inf (`entropy < 1e39` keeps every finite row).
 def _filter_terms(expr: str):
     """-> [(field, op, literal)] by a character scanner (no regular expressions): literal is str | bool | int | float."""
     i, n, out = 0, len(expr), []
@@ -363,9 +366,17 @@ def filter_mask(expr: str, columns, n_rows: int) -> np.ndarray:
             if isinstance(lit, str):
                 raise ValueError(f"field {field} is numeric; got string {lit!r}")
             if col.dtype.kind == "f":
-                keep &= cmp[op](col.astype(np.float32), np.float32(lit))
+                try:
+                    as_double = float(lit)
+                except OverflowError:      # an integer beyond every float: refused, like the int64 case below
+                    raise ValueError(f"literal out of range in {field} {op} {lit}") from None
+                with np.errstate(over="ignore"):      # beyond float32's range the literal rounds to +-inf, by intent
+                    lit32 = np.float32(as_double)
+                keep &= cmp[op](col.astype(np.float32), lit32)
             elif isinstance(lit, float):
                 keep &= cmp[op](col.astype(np.float64), np.float64(lit))
             else:
+                if not -(1 << 63) <= int(lit) < (1 << 63):      # Milvus refuses it; no int64 holds it
+                    raise ValueError(f"integer literal out of the int64 range in {field} {op} {lit}")
                 keep &= cmp[op](col.astype(np.int64), np.int64(int(lit)))
     return keep

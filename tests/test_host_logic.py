@@ -150,6 +150,78 @@ def test_filter_expression_evaluates_to_row_mask():
     assert filters.parse('doc_id == "a and b" and chunk_index == 3') == [("doc_id", "==", "a and b"), ("chunk_index", "==", 3)]
 
 
+_EDGE_COLS = {"chunk_index": np.array([0, 1, -1, 2**53, 2**63 - 1, -2**63], np.int64),
+              "token_count": np.array([5, 4, 3, 2, 1, 0], np.int64),
+              "entropy": np.array([0.0, np.nan, np.inf, -np.inf, 0.3, 1e-45], np.float32),
+              "doc_id": np.array(["a", "b", "c", "d", "e", "f"])}
+# literals no int64 / no float holds: Milvus refuses the expression, so every evaluator here does (it used to be three
+# answers: the oracle raised OverflowError, filters.evaluate kept every row, the device term wrapped to -2^63 and kept none)
+_OUT_OF_RANGE = [("chunk_index < 9223372036854775808", "chunk_index < 9223372036854775808"),
+                 ("chunk_index >= -9223372036854775809", "chunk_index >= -9223372036854775809"),
+                 ("token_count != 18446744073709551616", "token_count != 18446744073709551616"),
+                 ('doc_id == "a" and token_count == 9223372036854775808', "token_count == 9223372036854775808"),
+                 ("entropy < 1" + "0" * 400, "entropy < 1" + "0" * 400)]
+_OUT_OF_RANGE_IDS = ["2^63", "-2^63-1", "2^64", "in_the_second_term", "int_beyond_every_float"]
+
+
+@pytest.mark.parametrize("expr,term", _OUT_OF_RANGE, ids=_OUT_OF_RANGE_IDS)
+def test_out_of_range_literals_are_refused_by_both_host_evaluators(expr, term):
+    import oracle
+    for fn in (filters.evaluate, oracle.filter_mask):
+        with pytest.raises(ValueError) as ei:
+            fn(expr, _EDGE_COLS, 6)
+        assert term in str(ei.value), (fn.__module__, str(ei.value))     # the message names the term
+
+
+@pytest.mark.parametrize("expr,term", _OUT_OF_RANGE, ids=_OUT_OF_RANGE_IDS)
+def test_out_of_range_literals_are_refused_before_any_column_is_uploaded(expr, term):
+    """DeviceFilters._terms builds the kernel's terms on the host: the refusal needs no device, and must come before the
+    first column goes to HBM."""
+    from advanced_rag.columns import PayloadColumns
+    from advanced_rag.device_filters import DeviceFilters
+    dev = DeviceFilters(PayloadColumns(), 0)
+    dev._column = lambda field, n: pytest.fail(f"column {field} requested for a refused expression")
+    with pytest.raises(ValueError) as ei:
+        dev._terms(expr, 6)
+    assert term in str(ei.value)
+    assert dev._dev == {} and dev.stats["uploaded_bytes"] == 0
+
+
+def test_literals_at_the_ends_of_the_ranges_are_answered():
+    """The last literals that fit are not refused, and float literals beyond float32 compare as +-inf (pinned as it is):
+    all three statements agree, without a RuntimeWarning from the rounding."""
+    import warnings
+    import oracle
+    from advanced_rag import _native as nat
+    from advanced_rag.columns import PayloadColumns
+    from advanced_rag.device_filters import DeviceFilters
+    cases = {"chunk_index < 9223372036854775807": [1, 1, 1, 1, 0, 1],
+             "chunk_index > -9223372036854775808": [1, 1, 1, 1, 1, 0],
+             "chunk_index < 1e19": [1, 1, 1, 1, 1, 1],
+             "chunk_index >= 9223372036854775808.0": [0, 0, 0, 0, 1, 0],   # (double)INT64_MAX is 2^63
+             "chunk_index < inf": [1, 1, 1, 1, 1, 1],
+             "entropy < 1e39": [1, 0, 0, 1, 1, 1],                        # +inf after rounding: every finite row and -inf
+             "entropy > -1e39": [1, 0, 1, 0, 1, 1],
+             "entropy < 1e400": [1, 0, 0, 1, 1, 1],
+             "entropy <= 340282356779733661637539395458142568448": [1, 0, 1, 1, 1, 1],   # an int beyond float32: +inf too
+             "entropy > 0": [0, 0, 1, 0, 1, 1]}
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        for expr, want in cases.items():
+            assert oracle.filter_mask(expr, _EDGE_COLS, 6).astype(int).tolist() == want, expr
+            assert filters.evaluate(expr, _EDGE_COLS, 6).astype(int).tolist() == want, expr
+        dev = DeviceFilters(PayloadColumns(), 0)
+        dev._column = lambda field, n: type("Col", (), {"data_ptr": staticmethod(lambda: 64)})
+        (t,), _ = dev._terms("entropy < 1e39", 6)
+        assert (t.kind, t.fval) == (nat.HR_COL_F32, float("inf"))
+        (t,), _ = dev._terms("chunk_index <= 9223372036854775807", 6)
+        assert (t.kind, t.ival) == (nat.HR_COL_I64, 2**63 - 1)
+        (t,), _ = dev._terms("chunk_index >= -9223372036854775808", 6)
+        assert (t.kind, t.ival) == (nat.HR_COL_I64, -2**63)
+        (t,), _ = dev._terms("chunk_index < 1e19", 6)
+        assert (t.kind, t.dval) == (nat.HR_COL_I64_VS_F64, 1e19)
+
+
 def test_mmr_diversification():  # reference test_extended.py:189-213
     cfg = RetrievalConfig(hybrid_alpha=0.7, top_k=3, enable_mmr=True, mmr_lambda=0.6)
     r = HybridRetriever(index_manager=None, config=cfg)
