@@ -468,24 +468,7 @@ int g_group_rows = 0;     // HR_DEBUG_GROUP_ROWS: candidate-group size of handle
 
 // Two-level candidate selection: per-bucket maxima, then one block per query — for one modality or for both
 // modalities of a hybrid search in one pair of launches (select.h: GroupSelPair).
-int group_sel_args(hr_index* h, Workspace* ws, int B, int64_t n_groups, int C, GroupSelArgs* a, const TopkArgs* t = nullptr) {
-    const int64_t n_buckets = (n_groups + kBucketGroups - 1) / kBucketGroups;
-    HIP_TRY(h, ws->bmax.ensure((size_t)B * n_buckets * sizeof(float)));
-    a->gmax = ws->gmax.as<float>();
-    a->bmax = ws->bmax.as<float>();
-    a->n_groups = n_groups;
-    a->n_buckets = n_buckets;
-    a->C = C;
-    a->two_level = n_groups > C && n_buckets > C;
-    a->cand = ws->cand.as<int32_t>();
-    a->a_cut = ws->acut.as<float>();
-    // the data-dependent candidate set: trim against the K-th largest group maximum with the error bound of the list's proof
-    a->K_trim = (t && !g_no_trim) ? t->K : 0;
-    a->eps_abs = t ? t->eps_abs : 0.f;
-    a->eps_rel = t ? t->eps_rel : 0.f;
-    a->eps_abs_q = t ? t->eps_abs_q : nullptr;
-    return HR_OK;
-}
+inline int64_t bucket_count(int64_t n_groups) { return (n_groups + kBucketGroups - 1) / kBucketGroups; }
 int launch_group_select_pair(hr_index* h, hipStream_t s, int B, const GroupSelPair& p) {
     int64_t blocks = 0;
     for (int m = 0; m < p.n; ++m)
@@ -497,12 +480,6 @@ int launch_group_select_pair(hr_index* h, hipStream_t s, int B, const GroupSelPa
     hipLaunchKernelGGL(select_groups_kernel, dim3(B, p.n), dim3(1024), 0, s, p);
     HIP_TRY(h, hipGetLastError());
     return HR_OK;
-}
-int launch_group_select(hr_index* h, Workspace* ws, hipStream_t s, int B, int64_t n_groups, int C, const TopkArgs* t = nullptr) {
-    GroupSelPair p{};
-    p.n = 1;
-    HR_TRY(group_sel_args(h, ws, B, n_groups, C, &p.m[0], t));
-    return launch_group_select_pair(h, s, B, p);
 }
 int launch_topk_pair(hr_index* h, hipStream_t s, int B, const TopkPair& p) {
     hipLaunchKernelGGL(select_topk_kernel, dim3(B, p.n), dim3(1024), 0, s, p);
@@ -553,88 +530,166 @@ void dense_eps(const hr_index* h, float* eps_abs, int* norm_mode) {
     }
 }
 
-// ---- finishing steps shared by the single-modality chains and the hybrid chain --------------------------------
-int launch_refine_dense(hr_index* h, Workspace* ws, hipStream_t s, const float* d_q, int B, int C, int GR,
-                        const uint8_t* d_mask) {
-    const int cosine = h->metric;   // the kernel's `metric` argument
-    const bool l2 = h->metric == HR_METRIC_L2;
-    if (h->dtype == HR_F16)
-        hipLaunchKernelGGL((l2 ? refine_dense_kernel<_Float16, true> : refine_dense_kernel<_Float16, false>), dim3((C * GR + 63) / 64, B), dim3(64), 0, s,
-                           h->tiles.as<chunk_t>(), h->KT, (int)h->dim, d_q, ws->qn2.as<double>(),
-                           h->norm2.as<double>(), d_mask, ws->cand.as<int32_t>(), C, GR, h->n_rows, cosine,
-                           ws->cscore.as<float>(), ws->crow.as<int32_t>());
-    else
-        hipLaunchKernelGGL((l2 ? refine_dense_kernel<float, true> : refine_dense_kernel<float, false>), dim3((C * GR + 63) / 64, B), dim3(64), 0, s,
-                           h->tiles.as<chunk_t>(), h->KT, (int)h->dim, d_q, ws->qn2.as<double>(),
-                           h->norm2.as<double>(), d_mask, ws->cand.as<int32_t>(), C, GR, h->n_rows, cosine,
-                           ws->cscore.as<float>(), ws->crow.as<int32_t>());
-    HIP_TRY(h, hipGetLastError());
+// ---- the finish of one modality ---------------------------------------------------------------------------------
+// "Finishing" = select the candidate groups from the scan's group maxima, refine them exactly, take the top k and set the
+// exactness flag.  A FinishSide says what that takes for one modality of one call.  dense_side / sparse_side fill it
+// once; the selection arguments, the fused kernel's FinishMod, the refine launch and the chain's TopkArgs all come from it.
+struct OutLists {  // where a call's lists go: [B][k] ids and scores, [B] exactness flags (may be null)
+    int64_t* ids;
+    float* scores;
+    int32_t* flags;
+};
+struct FinishSide {
+    Workspace* ws;
+    bool sparse;
+    int GR;            // rows per candidate group
+    int64_t n_groups;  // group SLOTS the scan wrote per query (dense: a whole number of super-groups, the tail slots hold -inf)
+    int C;             // candidate groups per query
+    const uint8_t* mask;
+    TopkArgs topk;
+    const float* d_q;  // dense refine
+    const int64_t* q_ptr;  // sparse refine: the query CSR and the fixed stride of the scan's query layout
+    const int32_t* q_idx;
+    const float* q_val;
+    int stride;
+    int ph_select, ph_refine, ph_topk;  // profiling phases of the side on its own
+};
+
+// What both modalities fill alike.  Ensures the workspace buffers the finish reads and writes — here, before the call's
+// first launch and before TopkArgs takes their addresses.  dense_side / sparse_side rely on the enqueue functions
+// having sized what the prep and scan phases write (qn2, dqeps; qeps, qfloor): a finish follows a scan on the same
+// workspace.
+int side_common(hr_index* h, Workspace* ws, int B, int k, int C, int GR, int64_t n_groups, const uint8_t* d_mask,
+                const OutLists& out, FinishSide* f) {
+    HIP_TRY(h, ws->gmax.ensure((size_t)B * n_groups * sizeof(float)));
+    HIP_TRY(h, ws->bmax.ensure((size_t)B * bucket_count(n_groups) * sizeof(float)));
+    HIP_TRY(h, ws->cand.ensure((size_t)B * C * sizeof(int32_t)));
+    HIP_TRY(h, ws->acut.ensure((size_t)B * sizeof(float)));
+    HIP_TRY(h, ws->cscore.ensure((size_t)B * C * GR * sizeof(float)));
+    HIP_TRY(h, ws->crow.ensure((size_t)B * C * GR * sizeof(int32_t)));
+    *f = FinishSide{};
+    f->ws = ws;
+    f->GR = GR;
+    f->n_groups = n_groups;
+    f->C = C;
+    f->mask = d_mask;
+    TopkArgs& t = f->topk;
+    t.cscore = ws->cscore.as<float>();
+    t.crow = ws->crow.as<int32_t>();
+    t.n = C * GR;
+    t.K = k;
+    t.row_offset = h->row_offset;
+    t.a_cut = ws->acut.as<float>();
+    t.out_ids = out.ids;
+    t.out_scores = out.scores;
+    t.flags = out.flags;
     return HR_OK;
 }
-TopkArgs dense_topk_args(const hr_index* h, Workspace* ws, int C, int GR, int k, int64_t* d_ids, float* d_scores,
-                         int32_t* d_flags) {
-    float eps_abs;
-    int norm_mode;
-    dense_eps(h, &eps_abs, &norm_mode);
-    TopkArgs a{};
-    a.cscore = ws->cscore.as<float>();
-    a.crow = ws->crow.as<int32_t>();
-    a.n = C * GR;
-    a.K = k;
-    a.row_offset = h->row_offset;
-    a.a_cut = ws->acut.as<float>();
-    a.cut_floor = -INFINITY;
-    a.eps_abs = eps_abs;
-    a.eps_abs_q = norm_mode == 2 ? ws->dqeps.as<float>() : nullptr;   // L2: the row term's share, 1 / |q| times a constant
-    a.eps_rel = 0.0f;
-    a.norm_mode = norm_mode;
-    a.qn2 = ws->qn2.as<double>();
-    a.out_ids = d_ids;
-    a.out_scores = d_scores;
-    a.flags = d_flags;
-    return a;
-}
-int launch_refine_sparse(hr_index* h, Workspace* ws, hipStream_t s, const int64_t* d_qptr, const int32_t* d_qidx,
-                         const float* d_qval, int B, int C, int GR, int stride, const uint8_t* d_mask) {
-    // 64 docs per wave: shorter chains finish this kernel sooner (0.60 -> 0.55 ms at 10M docs, 0.168 -> 0.136 ms at 1.25M
-    // with 16) but the step does not gain — the kernel runs beside the scans, and what it takes from the HBM sooner they
-    // get later (round 2 A/B).
-    const int dpw = 64;
-    const bool hashed = stride <= kHashMaxTerms;   // the query's terms as a hash table behind the filter (sparse.h)
-    const size_t lds = (size_t)kFilterBits / 8 + (hashed ? (size_t)sparse_hash_slots(stride) * 8 : (size_t)stride * 8);
-    hipLaunchKernelGGL(hashed ? refine_sparse_kernel<true> : refine_sparse_kernel<false>,
-                       dim3((C * GR + 4 * dpw - 1) / (4 * dpw), B), dim3(256), lds, s, h->s_indptr.as<int64_t>(),
-                       h->s_idx.as<int32_t>(), h->s_val.as<float>(), d_qptr, d_qidx, d_qval, d_mask,
-                       ws->cand.as<int32_t>(), C, GR, h->n_sparse, stride, dpw, ws->cscore.as<float>(),
-                       ws->crow.as<int32_t>());
-    HIP_TRY(h, hipGetLastError());
+inline int64_t dense_super_groups(const hr_index* h) { return (h->n_rows + kSuperRows - 1) / kSuperRows; }
+int dense_side(hr_index* h, Workspace* ws, const float* d_q, int B, int k, int C, const uint8_t* d_mask, const OutLists& out,
+               FinishSide* f) {
+    const int GR = group_rows_for(h, h->n_rows);
+    HR_TRY(side_common(h, ws, B, k, C, GR, dense_super_groups(h) * (kSuperRows / GR), d_mask, out, f));
+    f->d_q = d_q;
+    f->ph_select = PH_GSEL, f->ph_refine = PH_REFINE, f->ph_topk = PH_TOPK;
+    TopkArgs& t = f->topk;
+    dense_eps(h, &t.eps_abs, &t.norm_mode);
+    t.cut_floor = -INFINITY;
+    t.eps_abs_q = t.norm_mode == 2 ? ws->dqeps.as<float>() : nullptr;   // L2: the row term's share, 1 / |q| times a constant
+    t.qn2 = ws->qn2.as<double>();
     return HR_OK;
 }
-TopkArgs sparse_topk_args(const hr_index* h, Workspace* ws, int C, int GR, int k, int64_t* d_ids, float* d_scores,
-                          int32_t* d_flags) {
+int sparse_side(hr_index* h, Workspace* ws, const int64_t* d_qptr, const int32_t* d_qidx, const float* d_qval, int B,
+                int max_q_nnz, int k, int C, const uint8_t* d_mask, const OutLists& out, FinishSide* f) {
+    const int GR = group_rows_for(h, h->n_sparse);
+    HR_TRY(side_common(h, ws, B, k, C, GR, (h->n_sparse + GR - 1) / GR, d_mask, out, f));
+    f->sparse = true;
+    f->q_ptr = d_qptr;
+    f->q_idx = d_qidx;
+    f->q_val = d_qval;
+    f->stride = (int)round_up(std::max(max_q_nnz, 1), 64);  // fixed-stride query layout for the scan
+    f->ph_select = PH_SGSEL, f->ph_refine = PH_SREFINE, f->ph_topk = PH_STOPK;
     // scan error = fixed-point rounding ((nnz+1)/scale per query, from the prep kernel) + fp32 rounding of w*scale, of
     // the product and of the int->float conversion (relative, 2^-22 with margin).
-    TopkArgs a{};
-    a.cscore = ws->cscore.as<float>();
-    a.crow = ws->crow.as<int32_t>();
-    a.n = C * GR;
-    a.K = k;
-    a.row_offset = h->row_offset;
-    a.a_cut = ws->acut.as<float>();
-    a.cut_floor = 0.0f;
-    a.cut_floor_q = ws->qfloor.as<float>();   // 0, or -q_eps when products can be negative (sparse_query_prep_kernel)
-    a.eps_abs = 0.0f;
-    a.eps_abs_q = ws->qeps.as<float>();
-    a.eps_rel = (float)(std::ldexp(1.0, -11) * 1.01 + std::ldexp(1.0, -22));  // fp16 posting weights
-    a.norm_mode = 0;
-    a.qn2 = nullptr;
-    a.out_ids = d_ids;
-    a.out_scores = d_scores;
-    a.flags = d_flags;
-    return a;
+    TopkArgs& t = f->topk;
+    t.cut_floor_q = ws->qfloor.as<float>();   // 0, or -q_eps when products can be negative (sparse_query_prep_kernel)
+    t.eps_abs_q = ws->qeps.as<float>();
+    t.eps_rel = (float)(std::ldexp(1.0, -11) * 1.01 + std::ldexp(1.0, -22));  // fp16 posting weights
+    return HR_OK;
 }
 
-// Enqueue a complete dense search on stream s.  All pointers are device pointers.
+GroupSelArgs sel_args(const FinishSide& f) {
+    GroupSelArgs a{};
+    a.gmax = f.ws->gmax.as<float>();
+    a.bmax = f.ws->bmax.as<float>();
+    a.n_groups = f.n_groups;
+    a.n_buckets = bucket_count(f.n_groups);
+    a.C = f.C;
+    a.two_level = f.n_groups > f.C && a.n_buckets > f.C;
+    a.cand = f.ws->cand.as<int32_t>();
+    a.a_cut = f.ws->acut.as<float>();
+    // the data-dependent candidate set: trim against the K-th largest group maximum with the error bound of the list's proof
+    a.K_trim = g_no_trim ? 0 : f.topk.K;
+    a.eps_abs = f.topk.eps_abs;
+    a.eps_rel = f.topk.eps_rel;
+    a.eps_abs_q = f.topk.eps_abs_q;
+    return a;
+}
+FinishMod finish_mod(const hr_index* h, const FinishSide& f) {
+    FinishMod m{};
+    m.kind = f.sparse;
+    m.group_rows = f.GR;
+    m.sel = sel_args(f);
+    m.topk = f.topk;
+    m.rowmask = f.mask;
+    if (f.sparse) {
+        m.indptr = h->s_indptr.as<int64_t>();
+        m.idx = h->s_idx.as<int32_t>();
+        m.val = h->s_val.as<float>();
+        m.q_indptr = f.q_ptr;
+        m.q_idx = f.q_idx;
+        m.q_val = f.q_val;
+        m.q_cap = f.stride;
+        m.n_rows = h->n_sparse;
+    } else {
+        m.tiles = h->tiles.as<chunk_t>();
+        m.KT = h->KT;
+        m.dim = (int)h->dim;
+        m.metric = h->metric;
+        m.dtype = h->dtype;
+        m.q = f.d_q;
+        m.qn2 = f.ws->qn2.as<double>();
+        m.norm2 = h->norm2.as<double>();
+        m.n_rows = h->n_rows;
+    }
+    return m;
+}
+int launch_refine(hr_index* h, hipStream_t s, int B, const FinishSide& f) {
+    Workspace* ws = f.ws;
+    if (!f.sparse) {
+        const bool f16 = h->dtype == HR_F16, l2 = h->metric == HR_METRIC_L2;
+        auto kern = f16 ? (l2 ? refine_dense_kernel<_Float16, true> : refine_dense_kernel<_Float16, false>)
+                        : (l2 ? refine_dense_kernel<float, true> : refine_dense_kernel<float, false>);
+        hipLaunchKernelGGL(kern, dim3((f.C * f.GR + 63) / 64, B), dim3(64), 0, s, h->tiles.as<chunk_t>(), h->KT, (int)h->dim,
+                           f.d_q, ws->qn2.as<double>(), h->norm2.as<double>(), f.mask, ws->cand.as<int32_t>(), f.C, f.GR,
+                           h->n_rows, h->metric, ws->cscore.as<float>(), ws->crow.as<int32_t>());
+    } else {
+        // 64 docs per wave: shorter chains finish this kernel sooner (0.60 -> 0.55 ms at 10M docs, 0.168 -> 0.136 ms at 1.25M
+        // with 16) but the step does not gain — the kernel runs beside the scans, and what it takes from the HBM sooner they
+        // get later (round 2 A/B).
+        const int dpw = 64;
+        const bool hashed = f.stride <= kHashMaxTerms;   // the query's terms as a hash table behind the filter (sparse.h)
+        const size_t lds = (size_t)kFilterBits / 8 + (hashed ? (size_t)sparse_hash_slots(f.stride) * 8 : (size_t)f.stride * 8);
+        hipLaunchKernelGGL(hashed ? refine_sparse_kernel<true> : refine_sparse_kernel<false>,
+                           dim3((f.C * f.GR + 4 * dpw - 1) / (4 * dpw), B), dim3(256), lds, s, h->s_indptr.as<int64_t>(),
+                           h->s_idx.as<int32_t>(), h->s_val.as<float>(), f.q_ptr, f.q_idx, f.q_val, f.mask,
+                           ws->cand.as<int32_t>(), f.C, f.GR, h->n_sparse, f.stride, dpw, ws->cscore.as<float>(),
+                           ws->crow.as<int32_t>());
+    }
+    HIP_TRY(h, hipGetLastError());
+    return HR_OK;
+}
+
 enum { PHASE_SCAN = 1, PHASE_FINISH = 2, PHASE_PREP = 4, PHASE_ALL = 7 };
 
 // ---- the finishing chain as one launch (finish.h) --------------------------------------------------------------
@@ -642,11 +697,10 @@ enum { PHASE_SCAN = 1, PHASE_FINISH = 2, PHASE_PREP = 4, PHASE_ALL = 7 };
 // set fits LDS; otherwise the multi-launch chain, whose refine kernels spread ONE query over many compute units
 // (single-query latency path, escalated searches with hundreds of candidate groups).
 int g_finish_mode = 0;  // hr_debug_option(HR_DEBUG_FINISH_MODE): 0 = by batch size, 1 = always the chain, 2 = fused whenever it fits
-bool finish_fused_ok(int B, int n_mod, int C, int GR, int64_t n_groups) {
-    const int64_t n_buckets = (n_groups + kBucketGroups - 1) / kBucketGroups;
+bool finish_fused_ok(int B, int n_mod, const FinishSide& f) {
     if (g_finish_mode == 1) return false;
-    return ((int64_t)B * n_mod >= 64 || g_finish_mode == 2) && C <= kFinishMaxCand && (int64_t)C * GR <= kFinishMaxSlots &&
-           n_buckets <= kFinishMaxBuckets;
+    return ((int64_t)B * n_mod >= 64 || g_finish_mode == 2) && f.C <= kFinishMaxCand && (int64_t)f.C * f.GR <= kFinishMaxSlots &&
+           bucket_count(f.n_groups) <= kFinishMaxBuckets;
 }
 int launch_finish(hr_index* h, hipStream_t s, int B, FinishPair& p) {
     p.key_slots = 0;
@@ -662,71 +716,45 @@ int launch_finish(hr_index* h, hipStream_t s, int B, FinishPair& p) {
     return HR_OK;
 }
 
-FinishMod finish_mod_dense(hr_index* h, Workspace* ws, const float* d_q, int B, int C, int GR, int64_t n_groups, int k,
-                           const uint8_t* d_mask, int64_t* d_ids, float* d_scores, int32_t* d_flags) {
-    FinishMod m{};
-    m.kind = 0;
-    m.group_rows = GR;
-    m.sel.gmax = ws->gmax.as<float>();
-    m.sel.n_groups = n_groups;
-    m.sel.n_buckets = (n_groups + kBucketGroups - 1) / kBucketGroups;
-    m.sel.C = C;
-    m.sel.two_level = n_groups > C && m.sel.n_buckets > C;
-    m.sel.a_cut = ws->acut.as<float>();
-    m.topk = dense_topk_args(h, ws, C, GR, k, d_ids, d_scores, d_flags);
-    m.sel.K_trim = g_no_trim ? 0 : k;
-    m.sel.eps_abs = m.topk.eps_abs;
-    m.sel.eps_rel = m.topk.eps_rel;
-    m.sel.eps_abs_q = m.topk.eps_abs_q;
-    m.rowmask = d_mask;
-    m.tiles = h->tiles.as<chunk_t>();
-    m.KT = h->KT;
-    m.dim = (int)h->dim;
-    m.metric = h->metric;
-    m.dtype = h->dtype;
-    m.q = d_q;
-    m.qn2 = ws->qn2.as<double>();
-    m.norm2 = h->norm2.as<double>();
-    m.n_rows = h->n_rows;
-    return m;
-}
-FinishMod finish_mod_sparse(hr_index* h, Workspace* ws, const int64_t* d_qptr, const int32_t* d_qidx, const float* d_qval,
-                            int B, int C, int GR, int64_t n_groups, int stride, int k, const uint8_t* d_mask,
-                            int64_t* d_ids, float* d_scores, int32_t* d_flags) {
-    FinishMod m{};
-    m.kind = 1;
-    m.group_rows = GR;
-    m.sel.gmax = ws->gmax.as<float>();
-    m.sel.n_groups = n_groups;
-    m.sel.n_buckets = (n_groups + kBucketGroups - 1) / kBucketGroups;
-    m.sel.C = C;
-    m.sel.two_level = n_groups > C && m.sel.n_buckets > C;
-    m.sel.a_cut = ws->acut.as<float>();
-    m.topk = sparse_topk_args(h, ws, C, GR, k, d_ids, d_scores, d_flags);
-    m.sel.K_trim = g_no_trim ? 0 : k;
-    m.sel.eps_abs = m.topk.eps_abs;
-    m.sel.eps_rel = m.topk.eps_rel;
-    m.sel.eps_abs_q = m.topk.eps_abs_q;
-    m.rowmask = d_mask;
-    m.indptr = h->s_indptr.as<int64_t>();
-    m.idx = h->s_idx.as<int32_t>();
-    m.val = h->s_val.as<float>();
-    m.q_indptr = d_qptr;
-    m.q_idx = d_qidx;
-    m.q_val = d_qval;
-    m.q_cap = stride;
-    m.n_rows = h->n_sparse;
-    return m;
+// Finish one modality, or both modalities of a hybrid search (dense first), on stream s: the fused kernel when every side
+// fits it, else the chain with the selection steps of all sides in one launch each — with two sides 5 dependent launches
+// (+ bucket_max) instead of 8, their spans booked on the first side's phases (group_select, topk).
+int finish_enqueue(hr_index* h, hipStream_t s, int B, const FinishSide* f, int n) {
+    bool fused = true;
+    for (int i = 0; i < n; ++i) fused = fused && finish_fused_ok(B, n, f[i]);
+    if (fused) {
+        Span sp(h, s, PH_FINISH);
+        FinishPair p{};
+        p.n = n;
+        for (int i = 0; i < n; ++i) p.m[i] = finish_mod(h, f[i]);
+        return launch_finish(h, s, B, p);
+    }
+    {
+        Span sp(h, s, f[0].ph_select);
+        GroupSelPair p{};
+        p.n = n;
+        for (int i = 0; i < n; ++i) p.m[i] = sel_args(f[i]);
+        HR_TRY(launch_group_select_pair(h, s, B, p));
+    }
+    for (int i = 0; i < n; ++i) {
+        Span sp(h, s, f[i].ph_refine);
+        HR_TRY(launch_refine(h, s, B, f[i]));
+    }
+    {
+        Span sp(h, s, f[0].ph_topk);
+        TopkPair p{};
+        p.n = n;
+        for (int i = 0; i < n; ++i) p.m[i] = f[i].topk;
+        HR_TRY(launch_topk_pair(h, s, B, p));
+    }
+    return HR_OK;
 }
 
-// Enqueue a dense search on stream s: PHASE_PREP = query prep, PHASE_SCAN = the shard scan (leaves the group
-// maxima in ws), PHASE_FINISH = candidate select + refine + top-k from those maxima.
+// Enqueue a dense search on stream s (all pointers are device pointers): PHASE_PREP = query prep, PHASE_SCAN = the
+// shard scan (leaves the group maxima in ws), PHASE_FINISH = candidate select + refine + top-k from those maxima.
 int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float* d_q, int B, int k,
-                         const uint8_t* d_mask, int64_t* d_ids, float* d_scores, int32_t* d_flags, int C,
-                         hipEvent_t scan_done = nullptr, int phases = PHASE_ALL) {
-    const int GR = group_rows_for(h, h->n_rows);
-    const int64_t n_super = (h->n_rows + kSuperRows - 1) / kSuperRows;
-    const int64_t n_groups = n_super * (kSuperRows / GR);  // group maxima per query (tail groups hold -inf)
+                         const uint8_t* d_mask, const OutLists& out, int C, hipEvent_t scan_done = nullptr,
+                         int phases = PHASE_ALL) {
     // one plan per pass (scan_plan.h); the full-batch plan gives the queries per pass
     auto plan_for = [&](int nq) {
         return scan_plan(h->KT, h->dtype, h->metric, h->n_rows, h->group_rows_override, g_dense_kernels, B, nq);
@@ -748,57 +776,27 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
     float* const d_coef = l2 ? ws->qcoef.as<float>() : nullptr;
     float* const d_qeps = l2 ? ws->dqeps.as<float>() : nullptr;
     const float rt_eps = l2 ? dense_l2_rt_eps(h) : 0.f;
-    HIP_TRY(h, ws->gmax.ensure((size_t)B * n_groups * sizeof(float)));
-    HIP_TRY(h, ws->cand.ensure((size_t)B * C * sizeof(int32_t)));
-    HIP_TRY(h, ws->acut.ensure((size_t)B * sizeof(float)));
-    HIP_TRY(h, ws->cscore.ensure((size_t)B * C * GR * sizeof(float)));
-    HIP_TRY(h, ws->crow.ensure((size_t)B * C * GR * sizeof(int32_t)));
+    FinishSide f;
+    HR_TRY(dense_side(h, ws, d_q, B, k, C, d_mask, out, &f));
 
     if (phases & PHASE_PREP) {
         // every pass's queries in one launch: pass c owns fragment groups [c * Gmax, ...) of qfrag (slot = query number)
         Span sp(h, s, PH_PREP);
         const int G_total = (n_chunks - 1) * Gmax + plan_for(B - (n_chunks - 1) * chunk_q).G;
-        if (h->dtype == HR_F16)
-            hipLaunchKernelGGL((prep_queries_kernel<_Float16>), dim3(16 * G_total), dim3(256), 0, s, d_q, B, (int)h->dim,
-                               h->KT, ws->qfrag.as<chunk_t>(), ws->qn2.as<double>(), d_coef, d_qeps, rt_eps);
-        else
-            hipLaunchKernelGGL((prep_queries_kernel<float>), dim3(16 * G_total), dim3(256), 0, s, d_q, B, (int)h->dim,
-                               h->KT, ws->qfrag.as<chunk_t>(), ws->qn2.as<double>(), d_coef, d_qeps, rt_eps);
+        hipLaunchKernelGGL(h->dtype == HR_F16 ? prep_queries_kernel<_Float16> : prep_queries_kernel<float>, dim3(16 * G_total),
+                           dim3(256), 0, s, d_q, B, (int)h->dim, h->KT, ws->qfrag.as<chunk_t>(), ws->qn2.as<double>(), d_coef,
+                           d_qeps, rt_eps);
         HIP_TRY(h, hipGetLastError());
     }
     for (int c0 = 0; (phases & PHASE_SCAN) && c0 < B; c0 += chunk_q) {
         const int nq = std::min(chunk_q, B - c0);
         Span sp(h, s, PH_SCAN);
         const ScanArgs a{h, s, ws->qfrag.as<chunk_t>() + (size_t)(c0 / chunk_q) * chunk_frag, d_mask,
-                         ws->gmax.as<float>() + (int64_t)c0 * n_groups, nq, n_super, l2 ? d_coef + c0 : nullptr};
+                         ws->gmax.as<float>() + (int64_t)c0 * f.n_groups, nq, dense_super_groups(h), l2 ? d_coef + c0 : nullptr};
         HIP_TRY(h, launch_scan(plan_for(nq), a));
     }
     if (scan_done) HIP_TRY(h, hipEventRecord(scan_done, s));
-    if (!(phases & PHASE_FINISH)) return HR_OK;
-    if (finish_fused_ok(B, 1, C, GR, n_groups)) {
-        Span sp(h, s, PH_FINISH);
-        FinishPair p{};
-        p.n = 1;
-        p.m[0] = finish_mod_dense(h, ws, d_q, B, C, GR, n_groups, k, d_mask, d_ids, d_scores, d_flags);
-        return launch_finish(h, s, B, p);
-    }
-    {
-        Span sp(h, s, PH_GSEL);
-        const TopkArgs t = dense_topk_args(h, ws, C, GR, k, d_ids, d_scores, d_flags);
-        HR_TRY(launch_group_select(h, ws, s, B, n_groups, C, &t));
-    }
-    {
-        Span sp(h, s, PH_REFINE);
-        HR_TRY(launch_refine_dense(h, ws, s, d_q, B, C, GR, d_mask));
-    }
-    {
-        Span sp(h, s, PH_TOPK);
-        TopkPair p{};
-        p.n = 1;
-        p.m[0] = dense_topk_args(h, ws, C, GR, k, d_ids, d_scores, d_flags);
-        HR_TRY(launch_topk_pair(h, s, B, p));
-    }
-    return HR_OK;
+    return (phases & PHASE_FINISH) ? finish_enqueue(h, s, B, &f, 1) : HR_OK;
 }
 
 // Doc ranges one scan block walks (sparse_scan_kernel pipelines over them): as many as leave the chip
@@ -812,28 +810,21 @@ int sparse_ranges_per_block(const hr_index* h, int B) {
 }
 
 int sparse_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const int64_t* d_qptr, const int32_t* d_qidx,
-                          const float* d_qval, int B, int max_q_nnz, int k, const uint8_t* d_mask, int64_t* d_ids,
-                          float* d_scores, int32_t* d_flags, int C, int phases = PHASE_ALL) {
-    const int GR = group_rows_for(h, h->n_sparse);
-    const int64_t n_groups = (h->n_sparse + GR - 1) / GR;
-    HIP_TRY(h, ws->gmax.ensure((size_t)B * n_groups * sizeof(float)));
-    HIP_TRY(h, ws->cand.ensure((size_t)B * C * sizeof(int32_t)));
-    HIP_TRY(h, ws->acut.ensure((size_t)B * sizeof(float)));
-    HIP_TRY(h, ws->cscore.ensure((size_t)B * C * GR * sizeof(float)));
-    HIP_TRY(h, ws->crow.ensure((size_t)B * C * GR * sizeof(int32_t)));
+                          const float* d_qval, int B, int max_q_nnz, int k, const uint8_t* d_mask, const OutLists& out,
+                          int C, int phases = PHASE_ALL) {
     HIP_TRY(h, ws->qscale.ensure((size_t)B * sizeof(float)));
     HIP_TRY(h, ws->qeps.ensure((size_t)B * sizeof(float)));
     HIP_TRY(h, ws->qfloor.ensure((size_t)B * sizeof(float)));
-    const int64_t V1 = h->sparse_dim + 1;
-    const int stride = (int)round_up(std::max(max_q_nnz, 1), 64);  // fixed-stride query layout for the scan
+    FinishSide f;
+    HR_TRY(sparse_side(h, ws, d_qptr, d_qidx, d_qval, B, max_q_nnz, k, C, d_mask, out, &f));
     if (phases & PHASE_PREP) {
         HIP_TRY(h, ws->pq_n.ensure((size_t)B * 4));
-        HIP_TRY(h, ws->pq_idx.ensure((size_t)B * stride * 4));
-        HIP_TRY(h, ws->pq_w.ensure((size_t)B * stride * 4));
+        HIP_TRY(h, ws->pq_idx.ensure((size_t)B * f.stride * 4));
+        HIP_TRY(h, ws->pq_w.ensure((size_t)B * f.stride * 4));
         // the largest posting weight after fp16 rounding: a nonzero weight below 2^-24 is stored as 2^-24 (sparse.h)
         const float max_post_w = h->max_sparse_abs > 0.f ? std::max(h->max_sparse_abs, 0x1p-24f) : 0.f;
         hipLaunchKernelGGL(sparse_query_prep_kernel, dim3(B), dim3(256), 0, s, d_qptr, d_qidx, d_qval, max_post_w,
-                           (int)h->sparse_signed, stride, (int)h->sparse_dim, ws->qscale.as<float>(),
+                           (int)h->sparse_signed, f.stride, (int)h->sparse_dim, ws->qscale.as<float>(),
                            ws->qeps.as<float>(), ws->qfloor.as<float>(), ws->pq_n.as<int32_t>(),
                            ws->pq_idx.as<int32_t>(), ws->pq_w.as<float>());
         HIP_TRY(h, hipGetLastError());
@@ -842,101 +833,15 @@ int sparse_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const int64
         Span sp(h, s, PH_SSCAN);
         const int rpb = sparse_ranges_per_block(h, B);
         const unsigned chunks = (unsigned)((h->n_ranges + rpb - 1) / rpb);
-        if (h->n_dense_runs > 0)
-            hipLaunchKernelGGL(sparse_scan_kernel<true>, dim3((unsigned)B, chunks), dim3(kScanThreads), 0, s,
-                               h->rt_off.as<unsigned int>(), V1, h->range_base.as<int64_t>(), h->post.as<uint32_t>(),
-                               ws->pq_n.as<int32_t>(), ws->pq_idx.as<int32_t>(), ws->pq_w.as<float>(), stride,
-                               ws->qscale.as<float>(), d_mask, h->n_sparse, n_groups, GR, h->n_ranges, rpb,
-                               h->idle_post.as<uint32_t>(), ws->gmax.as<float>());
-        else
-            hipLaunchKernelGGL(sparse_scan_kernel<false>, dim3((unsigned)B, chunks), dim3(kScanThreads), 0, s,
-                               h->rt_off.as<unsigned int>(), V1, h->range_base.as<int64_t>(), h->post.as<uint32_t>(),
-                               ws->pq_n.as<int32_t>(), ws->pq_idx.as<int32_t>(), ws->pq_w.as<float>(), stride,
-                               ws->qscale.as<float>(), d_mask, h->n_sparse, n_groups, GR, h->n_ranges, rpb,
-                               h->idle_post.as<uint32_t>(), ws->gmax.as<float>());
+        hipLaunchKernelGGL(h->n_dense_runs > 0 ? sparse_scan_kernel<true> : sparse_scan_kernel<false>,
+                           dim3((unsigned)B, chunks), dim3(kScanThreads), 0, s, h->rt_off.as<unsigned int>(),
+                           h->sparse_dim + 1, h->range_base.as<int64_t>(), h->post.as<uint32_t>(), ws->pq_n.as<int32_t>(),
+                           ws->pq_idx.as<int32_t>(), ws->pq_w.as<float>(), f.stride, ws->qscale.as<float>(), d_mask,
+                           h->n_sparse, f.n_groups, f.GR, h->n_ranges, rpb, h->idle_post.as<uint32_t>(),
+                           ws->gmax.as<float>());
         HIP_TRY(h, hipGetLastError());
     }
-    if (!(phases & PHASE_FINISH)) return HR_OK;
-    if (finish_fused_ok(B, 1, C, GR, n_groups)) {
-        Span sp(h, s, PH_FINISH);
-        FinishPair p{};
-        p.n = 1;
-        p.m[0] = finish_mod_sparse(h, ws, d_qptr, d_qidx, d_qval, B, C, GR, n_groups, stride, k, d_mask, d_ids, d_scores, d_flags);
-        return launch_finish(h, s, B, p);
-    }
-    {
-        Span sp(h, s, PH_SGSEL);
-        const TopkArgs t = sparse_topk_args(h, ws, C, GR, k, d_ids, d_scores, d_flags);
-        HR_TRY(launch_group_select(h, ws, s, B, n_groups, C, &t));
-    }
-    {
-        Span sp(h, s, PH_SREFINE);
-        HR_TRY(launch_refine_sparse(h, ws, s, d_qptr, d_qidx, d_qval, B, C, GR, stride, d_mask));
-    }
-    {
-        Span sp(h, s, PH_STOPK);
-        TopkPair p{};
-        p.n = 1;
-        p.m[0] = sparse_topk_args(h, ws, C, GR, k, d_ids, d_scores, d_flags);
-        HR_TRY(launch_topk_pair(h, s, B, p));
-    }
-    return HR_OK;
-}
-
-// Finishing chain of a hybrid search (both modalities non-empty): the same kernels as the two single chains, with the
-// selection steps of both modalities in one launch each — 5 dependent launches (+ 2 refines) instead of 8.
-// The profiling spans of the merged launches are booked on the dense phases (group_select, topk).
-int hybrid_finish_enqueue(hr_index* h, Workspace* wd, Workspace* wsp, hipStream_t s, const float* d_q,
-                          const int64_t* d_qptr, const int32_t* d_qidx, const float* d_qval, int B, int max_q_nnz, int k,
-                          const uint8_t* d_mask, int64_t* d_ids, float* d_scores, int32_t* d_flags, int64_t* s_ids,
-                          float* s_scores, int32_t* s_flags, int C) {
-    const int GRd = group_rows_for(h, h->n_rows), GRs = group_rows_for(h, h->n_sparse);
-    const int64_t n_super = (h->n_rows + kSuperRows - 1) / kSuperRows;
-    const int64_t ng_d = n_super * (kSuperRows / GRd), ng_s = (h->n_sparse + GRs - 1) / GRs;
-    const int stride = (int)round_up(std::max(max_q_nnz, 1), 64);
-    if (finish_fused_ok(B, 2, C, GRd, ng_d) && finish_fused_ok(B, 2, C, GRs, ng_s)) {
-        for (Workspace* ws : {wd, wsp}) HIP_TRY(h, ws->acut.ensure((size_t)B * sizeof(float)));
-        Span sp(h, s, PH_FINISH);
-        FinishPair p{};
-        p.n = 2;
-        p.m[0] = finish_mod_dense(h, wd, d_q, B, C, GRd, ng_d, k, d_mask, d_ids, d_scores, d_flags);
-        p.m[1] = finish_mod_sparse(h, wsp, d_qptr, d_qidx, d_qval, B, C, GRs, ng_s, stride, k, d_mask, s_ids, s_scores, s_flags);
-        return launch_finish(h, s, B, p);
-    }
-    for (Workspace* ws : {wd, wsp}) {
-        const int GR = ws == wd ? GRd : GRs;
-        HIP_TRY(h, ws->cand.ensure((size_t)B * C * sizeof(int32_t)));
-        HIP_TRY(h, ws->acut.ensure((size_t)B * sizeof(float)));
-        HIP_TRY(h, ws->cscore.ensure((size_t)B * C * GR * sizeof(float)));
-        HIP_TRY(h, ws->crow.ensure((size_t)B * C * GR * sizeof(int32_t)));
-    }
-    {
-        Span sp(h, s, PH_GSEL);
-        GroupSelPair p{};
-        p.n = 2;
-        const TopkArgs td = dense_topk_args(h, wd, C, GRd, k, d_ids, d_scores, d_flags);
-        const TopkArgs ts = sparse_topk_args(h, wsp, C, GRs, k, s_ids, s_scores, s_flags);
-        HR_TRY(group_sel_args(h, wd, B, ng_d, C, &p.m[0], &td));
-        HR_TRY(group_sel_args(h, wsp, B, ng_s, C, &p.m[1], &ts));
-        HR_TRY(launch_group_select_pair(h, s, B, p));
-    }
-    {
-        Span sp(h, s, PH_REFINE);
-        HR_TRY(launch_refine_dense(h, wd, s, d_q, B, C, GRd, d_mask));
-    }
-    {
-        Span sp(h, s, PH_SREFINE);
-        HR_TRY(launch_refine_sparse(h, wsp, s, d_qptr, d_qidx, d_qval, B, C, GRs, stride, d_mask));
-    }
-    {
-        Span sp(h, s, PH_TOPK);
-        TopkPair p{};
-        p.n = 2;
-        p.m[0] = dense_topk_args(h, wd, C, GRd, k, d_ids, d_scores, d_flags);
-        p.m[1] = sparse_topk_args(h, wsp, C, GRs, k, s_ids, s_scores, s_flags);
-        HR_TRY(launch_topk_pair(h, s, B, p));
-    }
-    return HR_OK;
+    return (phases & PHASE_FINISH) ? finish_enqueue(h, s, B, &f, 1) : HR_OK;
 }
 
 int check_search_args(hr_index* h, int B, int k, bool dense) {
@@ -959,6 +864,66 @@ int fill_empty(hr_index* h, hipStream_t s, int B, int k, int64_t* d_ids, float* 
         HIP_TRY(h, hipMemcpyAsync(d_flags, ones.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipStreamSynchronize(s));
     }
+    return HR_OK;
+}
+
+// ---- the host-buffer forms' shared run ---------------------------------------------------------------------------
+struct PooledWs {  // a workspace of the handle's pool for the length of one host-form call
+    hr_index* h;
+    Workspace* w;
+    explicit PooledWs(hr_index* h_) : h(h_), w(take_ws(h_)) {}
+    ~PooledWs() {
+        if (w) give_ws(h, w);
+    }
+};
+
+// What the host forms share, after their own argument checks.  rows names the modality's row count (n_rows or
+// n_sparse), read here under the handle's lock.  stage_queries(ws, s) uploads the queries; enqueue(ws, s, d_mask, out,
+// C) enqueues one search with C candidate groups per query, and is repeated with more of them until every list is
+// proven exact or every group that holds rows was a candidate.
+template <typename Stage, typename Enqueue>
+int search_host(hr_index* h, int B, int k, int64_t hr_index::*rows, const uint8_t* rowmask, bool mask_on_device,
+                int64_t* out_ids, float* out_scores, Stage stage_queries, Enqueue enqueue) {
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    DeviceGuard dg(h->device);
+    const int64_t n_rows = h->*rows;
+    if (n_rows == 0) {
+        std::fill(out_ids, out_ids + (size_t)B * k, (int64_t)-1);
+        std::fill(out_scores, out_scores + (size_t)B * k, 0.f);
+        return HR_OK;
+    }
+    PooledWs pooled(h);
+    Workspace* ws = pooled.w;
+    if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
+    hipStream_t s = ws->stream;
+    HR_TRY(stage_queries(ws, s));
+    HIP_TRY(h, ws->d_ids.ensure((size_t)B * k * 8));
+    HIP_TRY(h, ws->d_scores.ensure((size_t)B * k * 4));
+    HIP_TRY(h, ws->flags.ensure((size_t)B * 4));
+    const uint8_t* d_mask = mask_on_device ? rowmask : nullptr;
+    if (rowmask && !mask_on_device) {
+        const size_t mb = (size_t)(n_rows + 7) / 8;
+        HIP_TRY(h, ws->d_mask.ensure(mb));
+        HIP_TRY(h, hipMemcpyAsync(ws->d_mask.p, rowmask, mb, hipMemcpyHostToDevice, s));
+        d_mask = ws->d_mask.as<uint8_t>();
+    }
+    const OutLists out{ws->d_ids.as<int64_t>(), ws->d_scores.as<float>(), ws->flags.as<int32_t>()};
+    // the groups that hold rows — not the group slots of FinishSide::n_groups, which for dense include the -inf tail
+    const int GR = group_rows_for(h, n_rows);
+    const int64_t n_row_groups = (n_rows + GR - 1) / GR;
+    int C = candidate_groups_for_k(k);
+    std::vector<int32_t> flags(B);
+    for (;;) {
+        HR_TRY(enqueue(ws, s, d_mask, out, C));
+        HIP_TRY(h, hipMemcpyAsync(flags.data(), ws->flags.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        const bool all_exact = std::all_of(flags.begin(), flags.end(), [](int32_t f) { return f != 0; });
+        if (all_exact || C >= n_row_groups) break;
+        C = next_candidate_count(C, n_row_groups);  // widen the candidate set and redo
+    }
+    HIP_TRY(h, hipMemcpyAsync(out_ids, out.ids, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out_scores, out.scores, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
     return HR_OK;
 }
 
@@ -1576,6 +1541,11 @@ int64_t hr_dense_scan_bytes(const hr_index* h) {
 }
 
 // ---- device-pointer, asynchronous forms -----------------------------------------
+static int check_query_nnz(hr_index* h, int max_q_nnz) {
+    if (max_q_nnz < 0 || max_q_nnz > HR_MAX_QUERY_NNZ) return fail(h, HR_ELIMIT, "query nnz exceeds HR_MAX_QUERY_NNZ");
+    return HR_OK;
+}
+
 int hr_search_dense_dev(hr_index* h, const float* d_q, int B, int k, const uint8_t* d_rowmask, int64_t* d_ids,
                         float* d_scores, int32_t* d_flags, void* stream) {
     HR_TRY(check_search_args(h, B, k, true));
@@ -1587,7 +1557,7 @@ int hr_search_dense_dev(hr_index* h, const float* d_q, int B, int k, const uint8
     StreamWs ws_held;
     Workspace* ws = ws_for_stream(h, stream, ws_held);
     if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
-    return dense_search_enqueue(h, ws, s, d_q, B, k, d_rowmask, d_ids, d_scores, d_flags, candidate_groups_for_k(k));
+    return dense_search_enqueue(h, ws, s, d_q, B, k, d_rowmask, {d_ids, d_scores, d_flags}, candidate_groups_for_k(k));
 }
 
 int hr_search_sparse_dev(hr_index* h, const int64_t* d_q_indptr, const int32_t* d_q_idx, const float* d_q_val, int B,
@@ -1596,7 +1566,7 @@ int hr_search_sparse_dev(hr_index* h, const int64_t* d_q_indptr, const int32_t* 
     HR_TRY(check_search_args(h, B, k, false));
     if (!d_q_indptr || !d_ids || !d_scores || (q_nnz_total > 0 && (!d_q_idx || !d_q_val)))
         return fail(h, HR_EINVAL, "null buffer");
-    if (max_q_nnz < 0 || max_q_nnz > HR_MAX_QUERY_NNZ) return fail(h, HR_ELIMIT, "query nnz exceeds HR_MAX_QUERY_NNZ");
+    HR_TRY(check_query_nnz(h, max_q_nnz));
     std::shared_lock<std::shared_mutex> lk(h->rw);
     DeviceGuard dg(h->device);
     hipStream_t s = (hipStream_t)stream;
@@ -1604,24 +1574,31 @@ int hr_search_sparse_dev(hr_index* h, const int64_t* d_q_indptr, const int32_t* 
     StreamWs ws_held;
     Workspace* ws = ws_for_stream(h, stream, ws_held);
     if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
-    return sparse_search_enqueue(h, ws, s, d_q_indptr, d_q_idx, d_q_val, B, max_q_nnz, k, d_rowmask, d_ids, d_scores,
-                                 d_flags, candidate_groups_for_k(k));
+    return sparse_search_enqueue(h, ws, s, d_q_indptr, d_q_idx, d_q_val, B, max_q_nnz, k, d_rowmask,
+                                 {d_ids, d_scores, d_flags}, candidate_groups_for_k(k));
+}
+
+// The hybrid forms' shared preamble.  buffers_ok: the entry point's own null-buffer rule (those that produce lists need
+// somewhere to put them; the finish takes no q_nnz_total to judge the query arrays by).
+static int check_hybrid_args(hr_index* h, int B, int k, bool buffers_ok) {
+    HR_TRY(check_search_args(h, B, k, true));
+    HR_TRY(check_search_args(h, B, k, false));
+    return buffers_ok ? HR_OK : fail(h, HR_EINVAL, "null buffer");
+}
+// [2][B][k] outputs, dense first: the sparse half
+static OutLists sparse_half(int B, int k, int64_t* d_ids, float* d_scores, int32_t* d_flags) {
+    return {d_ids + (size_t)B * k, d_scores + (size_t)B * k, d_flags ? d_flags + B : nullptr};
 }
 
 int hr_search_hybrid_dev(hr_index* h, const float* d_q, const int64_t* d_q_indptr, const int32_t* d_q_idx,
                          const float* d_q_val, int B, int64_t q_nnz_total, int max_q_nnz, int k,
                          const uint8_t* d_rowmask, int64_t* d_ids, float* d_scores, int32_t* d_flags, void* stream) {
-    HR_TRY(check_search_args(h, B, k, true));
-    HR_TRY(check_search_args(h, B, k, false));
-    if (!d_q || !d_q_indptr || !d_ids || !d_scores || (q_nnz_total > 0 && (!d_q_idx || !d_q_val)))
-        return fail(h, HR_EINVAL, "null buffer");
-    if (max_q_nnz < 0 || max_q_nnz > HR_MAX_QUERY_NNZ) return fail(h, HR_ELIMIT, "query nnz exceeds HR_MAX_QUERY_NNZ");
+    HR_TRY(check_hybrid_args(h, B, k, d_q && d_q_indptr && d_ids && d_scores && (q_nnz_total <= 0 || (d_q_idx && d_q_val))));
+    HR_TRY(check_query_nnz(h, max_q_nnz));
     std::shared_lock<std::shared_mutex> lk(h->rw);
     DeviceGuard dg(h->device);
     hipStream_t s = (hipStream_t)stream;
-    int64_t* s_ids = d_ids + (size_t)B * k;
-    float* s_scores = d_scores + (size_t)B * k;
-    int32_t* s_flags = d_flags ? d_flags + B : nullptr;
+    const OutLists so = sparse_half(B, k, d_ids, d_scores, d_flags);
     StreamWs ws_held;
     Workspace* ws = ws_for_stream(h, stream, ws_held);
     if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
@@ -1637,31 +1614,39 @@ int hr_search_hybrid_dev(hr_index* h, const float* d_q, const int64_t* d_q_indpt
         HR_TRY(fill_empty(h, s, B, k, d_ids, d_scores, d_flags));
         HIP_TRY(h, hipEventRecord(ws->ev_scan, s));
     } else {
-        HR_TRY(dense_search_enqueue(h, ws, s, d_q, B, k, d_rowmask, d_ids, d_scores, d_flags, C, ws->ev_scan));
+        HR_TRY(dense_search_enqueue(h, ws, s, d_q, B, k, d_rowmask, {d_ids, d_scores, d_flags}, C, ws->ev_scan));
     }
     // sparse chain: starts when the dense scan is done, overlaps the dense tail
     HIP_TRY(h, hipStreamWaitEvent(ws->side, ws->ev_scan, 0));
     if (h->n_sparse == 0) {
-        HR_TRY(fill_empty(h, ws->side, B, k, s_ids, s_scores, s_flags));
+        HR_TRY(fill_empty(h, ws->side, B, k, so.ids, so.scores, so.flags));
     } else {
         HR_TRY(sparse_search_enqueue(h, ws->sparse_ws, ws->side, d_q_indptr, d_q_idx, d_q_val, B, max_q_nnz, k,
-                                     d_rowmask, s_ids, s_scores, s_flags, C));
+                                     d_rowmask, so, C));
     }
     HIP_TRY(h, hipEventRecord(ws->ev_side, ws->side));
     HIP_TRY(h, hipStreamWaitEvent(s, ws->ev_side, 0));
     return HR_OK;
 }
 
-static int slot_workspaces(hr_index* h, int slot, Workspace** dense, Workspace** sparse) {
+// The two workspaces of a slot of the two-phase forms, locked while one call enqueues
+struct SlotWs {
+    Workspace *dense = nullptr, *sparse = nullptr;
+    std::unique_lock<std::mutex> held;
+};
+static int lock_slot(hr_index* h, int slot, SlotWs* out) {
     if (slot < 0 || slot >= HR_MAX_SLOTS) return fail(h, HR_EINVAL, "slot %d out of range [0,%d)", slot, HR_MAX_SLOTS);
-    std::lock_guard<std::mutex> g(h->pool_mu);
-    for (int m = 0; m < 2; ++m)
-        if (!h->slot_ws[slot][m]) {
-            h->slot_ws[slot][m] = new (std::nothrow) Workspace();
-            if (!h->slot_ws[slot][m]) return fail(h, HR_ENOMEM, "workspace allocation failed");
-        }
-    *dense = h->slot_ws[slot][0];
-    *sparse = h->slot_ws[slot][1];
+    {
+        std::lock_guard<std::mutex> g(h->pool_mu);
+        for (int m = 0; m < 2; ++m)
+            if (!h->slot_ws[slot][m]) {
+                h->slot_ws[slot][m] = new (std::nothrow) Workspace();
+                if (!h->slot_ws[slot][m]) return fail(h, HR_ENOMEM, "workspace allocation failed");
+            }
+        out->dense = h->slot_ws[slot][0];
+        out->sparse = h->slot_ws[slot][1];
+    }
+    out->held = std::unique_lock<std::mutex>(out->dense->mu);
     return HR_OK;
 }
 
@@ -1669,16 +1654,12 @@ static int slot_workspaces(hr_index* h, int slot, Workspace** dense, Workspace**
 static int hybrid_scan_phases(hr_index* h, const float* d_q, const int64_t* d_q_indptr, const int32_t* d_q_idx,
                               const float* d_q_val, int B, int64_t q_nnz_total, int max_q_nnz, int k,
                               const uint8_t* d_rowmask, int slot, void* stream, bool prep_only) {
-    HR_TRY(check_search_args(h, B, k, true));
-    HR_TRY(check_search_args(h, B, k, false));
-    if (!d_q || !d_q_indptr || (q_nnz_total > 0 && (!d_q_idx || !d_q_val))) return fail(h, HR_EINVAL, "null buffer");
-    if (max_q_nnz < 0 || max_q_nnz > HR_MAX_QUERY_NNZ) return fail(h, HR_ELIMIT, "query nnz exceeds HR_MAX_QUERY_NNZ");
+    HR_TRY(check_hybrid_args(h, B, k, d_q && d_q_indptr && (q_nnz_total <= 0 || (d_q_idx && d_q_val))));
+    HR_TRY(check_query_nnz(h, max_q_nnz));
     std::shared_lock<std::shared_mutex> lk(h->rw);
     DeviceGuard dg(h->device);
-    Workspace *wd = nullptr, *wsp = nullptr;
-    HR_TRY(slot_workspaces(h, slot, &wd, &wsp));
-    if (!wd || !wsp) return fail(h, HR_ENOMEM, "no workspace for slot %d", slot);
-    std::lock_guard<std::mutex> slot_held(wd->mu);
+    SlotWs w;
+    HR_TRY(lock_slot(h, slot, &w));
     hipStream_t s = (hipStream_t)stream;
     const int C = candidate_groups_for_k(k);
     int phases = PHASE_PREP;
@@ -1686,11 +1667,9 @@ static int hybrid_scan_phases(hr_index* h, const float* d_q, const int64_t* d_q_
         phases = h->slot_prepped[slot] ? PHASE_SCAN : (PHASE_PREP | PHASE_SCAN);
         h->slot_prepped[slot] = false;
     }
-    if (h->n_rows > 0)
-        HR_TRY(dense_search_enqueue(h, wd, s, d_q, B, k, d_rowmask, nullptr, nullptr, nullptr, C, nullptr, phases));
+    if (h->n_rows > 0) HR_TRY(dense_search_enqueue(h, w.dense, s, d_q, B, k, d_rowmask, {}, C, nullptr, phases));
     if (h->n_sparse > 0)
-        HR_TRY(sparse_search_enqueue(h, wsp, s, d_q_indptr, d_q_idx, d_q_val, B, max_q_nnz, k, d_rowmask, nullptr,
-                                     nullptr, nullptr, C, phases));
+        HR_TRY(sparse_search_enqueue(h, w.sparse, s, d_q_indptr, d_q_idx, d_q_val, B, max_q_nnz, k, d_rowmask, {}, C, phases));
     if (prep_only) h->slot_prepped[slot] = true;
     return HR_OK;
 }
@@ -1706,36 +1685,30 @@ int hr_hybrid_scan_dev(hr_index* h, const float* d_q, const int64_t* d_q_indptr,
     return hybrid_scan_phases(h, d_q, d_q_indptr, d_q_idx, d_q_val, B, q_nnz_total, max_q_nnz, k, d_rowmask, slot, stream, false);
 }
 
+// Finish of the slot's scans: both modalities in one finish_enqueue; an empty collection's lists are all padding, and
+// the other modality then finishes as a single side.
 int hr_hybrid_finish_dev(hr_index* h, const float* d_q, const int64_t* d_q_indptr, const int32_t* d_q_idx,
                          const float* d_q_val, int B, int max_q_nnz, int k, const uint8_t* d_rowmask, int slot,
                          int64_t* d_ids, float* d_scores, int32_t* d_flags, void* stream) {
-    HR_TRY(check_search_args(h, B, k, true));
-    HR_TRY(check_search_args(h, B, k, false));
-    if (!d_q || !d_q_indptr || !d_ids || !d_scores) return fail(h, HR_EINVAL, "null buffer");
+    HR_TRY(check_hybrid_args(h, B, k, d_q && d_q_indptr && d_ids && d_scores));
     std::shared_lock<std::shared_mutex> lk(h->rw);
     DeviceGuard dg(h->device);
-    Workspace *wd = nullptr, *wsp = nullptr;
-    HR_TRY(slot_workspaces(h, slot, &wd, &wsp));
-    if (!wd || !wsp) return fail(h, HR_ENOMEM, "no workspace for slot %d", slot);
-    std::lock_guard<std::mutex> slot_held(wd->mu);
+    SlotWs w;
+    HR_TRY(lock_slot(h, slot, &w));
     hipStream_t s = (hipStream_t)stream;
     const int C = candidate_groups_for_k(k);
-    int64_t* s_ids = d_ids + (size_t)B * k;
-    float* s_scores = d_scores + (size_t)B * k;
-    int32_t* s_flags = d_flags ? d_flags + B : nullptr;
-    if (h->n_rows > 0 && h->n_sparse > 0)
-        return hybrid_finish_enqueue(h, wd, wsp, s, d_q, d_q_indptr, d_q_idx, d_q_val, B, max_q_nnz, k, d_rowmask, d_ids,
-                                     d_scores, d_flags, s_ids, s_scores, s_flags, C);
+    const OutLists so = sparse_half(B, k, d_ids, d_scores, d_flags);
+    FinishSide f[2];
+    int n = 0;
     if (h->n_rows > 0)
-        HR_TRY(dense_search_enqueue(h, wd, s, d_q, B, k, d_rowmask, d_ids, d_scores, d_flags, C, nullptr, PHASE_FINISH));
+        HR_TRY(dense_side(h, w.dense, d_q, B, k, C, d_rowmask, {d_ids, d_scores, d_flags}, &f[n++]));
     else
         HR_TRY(fill_empty(h, s, B, k, d_ids, d_scores, d_flags));
     if (h->n_sparse > 0)
-        HR_TRY(sparse_search_enqueue(h, wsp, s, d_q_indptr, d_q_idx, d_q_val, B, max_q_nnz, k, d_rowmask, s_ids,
-                                     s_scores, s_flags, C, PHASE_FINISH));
+        HR_TRY(sparse_side(h, w.sparse, d_q_indptr, d_q_idx, d_q_val, B, max_q_nnz, k, C, d_rowmask, so, &f[n++]));
     else
-        HR_TRY(fill_empty(h, s, B, k, s_ids, s_scores, s_flags));
-    return HR_OK;
+        HR_TRY(fill_empty(h, s, B, k, so.ids, so.scores, so.flags));
+    return n ? finish_enqueue(h, s, B, f, n) : HR_OK;
 }
 
 int hr_fuse_rrf_dev(const int64_t* d_ids_a, int ka, const int64_t* d_ids_b, int kb, const int64_t* d_ids_c, int kc,
@@ -2172,45 +2145,16 @@ static int search_dense_host(hr_index* h, const float* q, int B, int k, const ui
     if (!q || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
     for (int64_t i = 0; i < (int64_t)B * h->dim; ++i)   // the scan's bound (and the ranking) assume finite queries
         if (!std::isfinite(q[i])) return fail(h, HR_EINVAL, "non-finite value in query %lld", (long long)(i / h->dim));
-    std::shared_lock<std::shared_mutex> lk(h->rw);
-    DeviceGuard dg(h->device);
-    if (h->n_rows == 0) {
-        std::fill(out_ids, out_ids + (size_t)B * k, (int64_t)-1);
-        std::fill(out_scores, out_scores + (size_t)B * k, 0.f);
-        return HR_OK;
-    }
-    Workspace* ws = take_ws(h);
-    if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
-    struct Giver { hr_index* h; Workspace* w; ~Giver() { give_ws(h, w); } } giver{h, ws};
-    hipStream_t s = ws->stream;
-    HIP_TRY(h, ws->d_q.ensure((size_t)B * h->dim * 4));
-    HIP_TRY(h, ws->d_ids.ensure((size_t)B * k * 8));
-    HIP_TRY(h, ws->d_scores.ensure((size_t)B * k * 4));
-    HIP_TRY(h, ws->flags.ensure((size_t)B * 4));
-    HIP_TRY(h, hipMemcpyAsync(ws->d_q.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, s));
-    const uint8_t* d_mask = mask_on_device ? rowmask : nullptr;
-    if (rowmask && !mask_on_device) {
-        const size_t mb = (size_t)(h->n_rows + 7) / 8;
-        HIP_TRY(h, ws->d_mask.ensure(mb));
-        HIP_TRY(h, hipMemcpyAsync(ws->d_mask.p, rowmask, mb, hipMemcpyHostToDevice, s));
-        d_mask = ws->d_mask.as<uint8_t>();
-    }
-    const int64_t n_groups = (h->n_rows + group_rows_for(h, h->n_rows) - 1) / group_rows_for(h, h->n_rows);
-    int C = candidate_groups_for_k(k);
-    std::vector<int32_t> flags(B);
-    for (;;) {
-        HR_TRY(dense_search_enqueue(h, ws, s, ws->d_q.as<float>(), B, k, d_mask, ws->d_ids.as<int64_t>(),
-                                    ws->d_scores.as<float>(), ws->flags.as<int32_t>(), C));
-        HIP_TRY(h, hipMemcpyAsync(flags.data(), ws->flags.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        const bool all_exact = std::all_of(flags.begin(), flags.end(), [](int32_t f) { return f != 0; });
-        if (all_exact || C >= n_groups) break;
-        C = next_candidate_count(C, n_groups);  // widen the candidate set and redo
-    }
-    HIP_TRY(h, hipMemcpyAsync(out_ids, ws->d_ids.p, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(out_scores, ws->d_scores.p, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return HR_OK;
+    return search_host(
+        h, B, k, &hr_index::n_rows, rowmask, mask_on_device, out_ids, out_scores,
+        [&](Workspace* ws, hipStream_t s) {
+            HIP_TRY(h, ws->d_q.ensure((size_t)B * h->dim * 4));
+            HIP_TRY(h, hipMemcpyAsync(ws->d_q.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, s));
+            return (int)HR_OK;
+        },
+        [&](Workspace* ws, hipStream_t s, const uint8_t* d_mask, const OutLists& out, int C) {
+            return dense_search_enqueue(h, ws, s, ws->d_q.as<float>(), B, k, d_mask, out, C);
+        });
 }
 
 int hr_search_dense(hr_index* h, const float* q, int B, int k, const uint8_t* rowmask, int64_t* out_ids,
@@ -2265,53 +2209,24 @@ static int search_sparse_host(hr_index* h, const int64_t* q_indptr, const int32_
     }
     if (max_nnz > HR_MAX_QUERY_NNZ) return fail(h, HR_ELIMIT, "query nnz %d exceeds HR_MAX_QUERY_NNZ", max_nnz);
 
-    std::shared_lock<std::shared_mutex> lk(h->rw);
-    DeviceGuard dg(h->device);
-    if (h->n_sparse == 0) {
-        std::fill(out_ids, out_ids + (size_t)B * k, (int64_t)-1);
-        std::fill(out_scores, out_scores + (size_t)B * k, 0.f);
-        return HR_OK;
-    }
-    Workspace* ws = take_ws(h);
-    if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
-    struct Giver { hr_index* h; Workspace* w; ~Giver() { give_ws(h, w); } } giver{h, ws};
-    hipStream_t s = ws->stream;
-    const size_t nnz = idx.size();
-    HIP_TRY(h, ws->d_qptr.ensure((size_t)(B + 1) * 8));
-    HIP_TRY(h, ws->d_qidx.ensure(std::max<size_t>(nnz, 1) * 4));
-    HIP_TRY(h, ws->d_qval.ensure(std::max<size_t>(nnz, 1) * 4));
-    HIP_TRY(h, ws->d_ids.ensure((size_t)B * k * 8));
-    HIP_TRY(h, ws->d_scores.ensure((size_t)B * k * 4));
-    HIP_TRY(h, ws->flags.ensure((size_t)B * 4));
-    HIP_TRY(h, hipMemcpyAsync(ws->d_qptr.p, ptr.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, s));
-    if (nnz) {
-        HIP_TRY(h, hipMemcpyAsync(ws->d_qidx.p, idx.data(), nnz * 4, hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(ws->d_qval.p, val.data(), nnz * 4, hipMemcpyHostToDevice, s));
-    }
-    const uint8_t* d_mask = mask_on_device ? rowmask : nullptr;
-    if (rowmask && !mask_on_device) {
-        const size_t mb = (size_t)(h->n_sparse + 7) / 8;
-        HIP_TRY(h, ws->d_mask.ensure(mb));
-        HIP_TRY(h, hipMemcpyAsync(ws->d_mask.p, rowmask, mb, hipMemcpyHostToDevice, s));
-        d_mask = ws->d_mask.as<uint8_t>();
-    }
-    const int64_t n_groups = (h->n_sparse + group_rows_for(h, h->n_sparse) - 1) / group_rows_for(h, h->n_sparse);
-    int C = candidate_groups_for_k(k);
-    std::vector<int32_t> flags(B);
-    for (;;) {
-        HR_TRY(sparse_search_enqueue(h, ws, s, ws->d_qptr.as<int64_t>(), ws->d_qidx.as<int32_t>(),
-                                     ws->d_qval.as<float>(), B, max_nnz, k, d_mask, ws->d_ids.as<int64_t>(),
-                                     ws->d_scores.as<float>(), ws->flags.as<int32_t>(), C));
-        HIP_TRY(h, hipMemcpyAsync(flags.data(), ws->flags.p, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        const bool all_exact = std::all_of(flags.begin(), flags.end(), [](int32_t f) { return f != 0; });
-        if (all_exact || C >= n_groups) break;
-        C = next_candidate_count(C, n_groups);
-    }
-    HIP_TRY(h, hipMemcpyAsync(out_ids, ws->d_ids.p, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(out_scores, ws->d_scores.p, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipStreamSynchronize(s));
-    return HR_OK;
+    return search_host(
+        h, B, k, &hr_index::n_sparse, rowmask, mask_on_device, out_ids, out_scores,
+        [&](Workspace* ws, hipStream_t s) {
+            const size_t nnz = idx.size();
+            HIP_TRY(h, ws->d_qptr.ensure((size_t)(B + 1) * 8));
+            HIP_TRY(h, ws->d_qidx.ensure(std::max<size_t>(nnz, 1) * 4));
+            HIP_TRY(h, ws->d_qval.ensure(std::max<size_t>(nnz, 1) * 4));
+            HIP_TRY(h, hipMemcpyAsync(ws->d_qptr.p, ptr.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, s));
+            if (nnz) {
+                HIP_TRY(h, hipMemcpyAsync(ws->d_qidx.p, idx.data(), nnz * 4, hipMemcpyHostToDevice, s));
+                HIP_TRY(h, hipMemcpyAsync(ws->d_qval.p, val.data(), nnz * 4, hipMemcpyHostToDevice, s));
+            }
+            return (int)HR_OK;
+        },
+        [&](Workspace* ws, hipStream_t s, const uint8_t* d_mask, const OutLists& out, int C) {
+            return sparse_search_enqueue(h, ws, s, ws->d_qptr.as<int64_t>(), ws->d_qidx.as<int32_t>(),
+                                         ws->d_qval.as<float>(), B, max_nnz, k, d_mask, out, C);
+        });
 }
 
 int hr_search_sparse(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B, int k,
@@ -2335,9 +2250,9 @@ int hr_fuse_rrf(hr_index* h, const int64_t* ids_a, int na, const int64_t* ids_b,
         return fail(h, HR_ELIMIT, "list longer than HR_MAX_TOPK=%d", HR_MAX_TOPK);
     if (!out_ids || !out_scores || !out_methods || !n_out) return fail(h, HR_EINVAL, "null buffer");
     DeviceGuard dg(h->device);
-    Workspace* ws = take_ws(h);
+    PooledWs pooled(h);
+    Workspace* ws = pooled.w;
     if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
-    struct Giver { hr_index* h; Workspace* w; ~Giver() { give_ws(h, w); } } giver{h, ws};
     hipStream_t s = ws->stream;
     const int total = na + nb + nc;
     const int ka = std::max(na, 1);  // kernel wants a readable first list

@@ -9,7 +9,7 @@ outside the candidates (`cut`) by more than the scan's error bound, or when `cut
   * the query weights are scaled by scale = 2^30 / (sum|w_q| * max|posting weight|) and each posting adds
     trunc(fma(w16, w_q * scale, 1)) to an int32 accumulator (sparse_scan_kernel);
   * a group's maximum is max(0, acc) * (1 / scale);
-  * q_eps, the per-query floor and eps_rel as sparse_query_prep_kernel and sparse_topk_args compute them.
+  * q_eps, the per-query floor and eps_rel as sparse_query_prep_kernel and sparse_side compute them.
 
 For random unsigned, signed and extreme families it asserts the two facts the proof and the candidate trim rest on:
 |approx - exact| stays within q_eps + eps_rel * |approx| for every row, and a row whose clamped maximum lies at or below
@@ -18,7 +18,7 @@ the model is sharp enough to notice an edit that makes the bound unsound."""
 import numpy as np
 import pytest
 
-EPS_REL = 2.0 ** -11 * 1.01 + 2.0 ** -22          # sparse_topk_args: fp16 postings + fp32 rounding
+EPS_REL = 2.0 ** -11 * 1.01 + 2.0 ** -22          # sparse_side: fp16 postings + fp32 rounding
 SUBNORMAL_MIN = 2.0 ** -24
 INF = np.float32(np.inf)
 
