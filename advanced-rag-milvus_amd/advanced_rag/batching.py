@@ -28,7 +28,8 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
-from .engine import pack_sparse_queries
+from .engine import EngineConfig, HybridSearchEngine, pack_sparse_queries
+from .staging import dense_rows_device, dense_rows_host, list_buffers, upload_sparse
 
 
 def _deliver(fut: Future, value) -> None:
@@ -48,6 +49,14 @@ def _fail(fut: Future, exc: BaseException) -> None:
             fut.set_exception(exc)
     except Exception:
         pass
+
+
+def _answer(fut: Future, fn, *args) -> None:
+    """Answer a request with the value of fn(*args), or fail it with what the call raised."""
+    try:
+        _deliver(fut, fn(*args))
+    except Exception as e:
+        _fail(fut, e)
 
 
 def _set_many(items) -> None:
@@ -121,8 +130,7 @@ class SearchCoalescer:
         self._outbox: Dict[Any, list] = {}     # event loop -> [(asyncio future, ok, value)] of the round in progress
 
     # ------------------------------------------------------------------ front
-    def submit(self, kind: str, key: Tuple, payload: Any) -> Future:
-        req = _Request(kind, key, payload)
+    def _put(self, req: _Request) -> None:
         with self._lock:
             if self._closed:
                 raise RuntimeError("search front is closed")
@@ -130,6 +138,10 @@ class SearchCoalescer:
                 self._thread = threading.Thread(target=self._guarded, name="search-coalescer", daemon=True)
                 self._thread.start()
         self._q.put(req)
+
+    def submit(self, kind: str, key: Tuple, payload: Any) -> Future:
+        req = _Request(kind, key, payload)
+        self._put(req)
         return req.future
 
     def _guarded(self):
@@ -161,14 +173,7 @@ class SearchCoalescer:
         import asyncio
         loop = asyncio.get_running_loop()
         afut = loop.create_future()
-        req = _Request(kind, key, payload, _LoopFuture(loop, afut, self._outbox))
-        with self._lock:
-            if self._closed:
-                raise RuntimeError("search front is closed")
-            if self._thread is None or not self._thread.is_alive():
-                self._thread = threading.Thread(target=self._guarded, name="search-coalescer", daemon=True)
-                self._thread.start()
-        self._q.put(req)
+        self._put(_Request(kind, key, payload, _LoopFuture(loop, afut, self._outbox)))
         return afut
 
     def _flush(self):
@@ -223,12 +228,9 @@ class SearchCoalescer:
         self._inflight = live
         return live
 
-    def _run(self):
-        import torch
-        dev = torch.device("cuda", self.mgr.device)
-        # one stream per kind of work: the dense and the sparse searches of a round run side by side (a lone retrieve()
-        # overlaps its two scans, as its two worker threads did before the front existed)
-        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "hybrid", "encode")}
+    def _rounds(self):
+        """The frame both worker loops share: yields each non-empty round's requests until close() and keeps the books around
+        it (stats, `_inflight`, the answers for the event loops).  A round that raises leaves `_inflight` to _guarded."""
         while True:
             reqs = self._collect()
             if reqs is None:
@@ -236,15 +238,26 @@ class SearchCoalescer:
             if not reqs:
                 continue
             t0 = time.perf_counter()
+            self.stats["rounds"] += 1
+            self.stats["requests"] += len(reqs)
+            yield reqs
+            self._inflight = []
+            self._flush()
+            self.stats["busy_s"] += time.perf_counter() - t0
+
+    def _run(self):
+        import torch
+        dev = torch.device("cuda", self.mgr.device)
+        # one stream per kind of work: the dense and the sparse searches of a round run side by side (a lone retrieve()
+        # overlaps its two scans, as its two worker threads did before the front existed)
+        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "hybrid", "encode")}
+        for reqs in self._rounds():
             groups: Dict[Tuple, List[_Request]] = {}
             for r in reqs:
                 groups.setdefault((r.kind, r.key), []).append(r)
-            self.stats["rounds"] += 1
-            self.stats["requests"] += len(reqs)
-            launched, used = [], set()
+            launched = []
             for (kind, key), rs in groups.items():
                 stream = streams[kind]
-                used.add(kind)
                 with torch.cuda.stream(stream):
                     step = min(self.max_batch, 128) if kind == "hybrid" else self.max_batch
                     for c0 in range(0, len(rs), step):
@@ -254,7 +267,7 @@ class SearchCoalescer:
                             launched.append((kind, key, chunk, getattr(self, "_enqueue_" + kind)(torch, dev, stream, key, chunk)))
                         except Exception as e:   # a bad batch must not take the other groups down: one by one
                             launched.append((kind, key, chunk, e))
-            for kind in used:
+            for kind in {kind for kind, _ in groups}:
                 streams[kind].synchronize()
             for kind, key, chunk, state in launched:
                 if isinstance(state, Exception):
@@ -265,9 +278,6 @@ class SearchCoalescer:
                 except Exception as e:  # never leave a caller waiting
                     for r in chunk:
                         _fail(r.future, e)
-            self._inflight = []
-            self._flush()
-            self.stats["busy_s"] += time.perf_counter() - t0
 
     def _run_collective(self):
         """Rounds of the torchrun form: the dense and the sparse searches of the callers that share (top_k, filter
@@ -276,15 +286,7 @@ class SearchCoalescer:
         if getattr(cs.dev, "type", "cpu") == "cuda":   # the current device is a per-thread setting: the collectives of this
             import torch                                # thread must run on the rank's GPU
             torch.cuda.set_device(cs.dev)
-        while True:
-            reqs = self._collect()
-            if reqs is None:
-                return
-            if not reqs:
-                continue
-            t0 = time.perf_counter()
-            self.stats["rounds"] += 1
-            self.stats["requests"] += len(reqs)
+        for reqs in self._rounds():
             groups: Dict[Tuple, Dict[str, List[_Request]]] = {}
             hybrid: Dict[Tuple, List[_Request]] = {}
             for r in reqs:
@@ -292,19 +294,13 @@ class SearchCoalescer:
                     hybrid.setdefault(r.key, []).append(r)
                     continue
                 if r.kind == "fuse":
-                    try:
-                        _deliver(r.future, self.mgr._fuse_rows_blocking(r.payload, r.key))
-                    except Exception as e:
-                        _fail(r.future, e)
+                    _answer(r.future, self.mgr._fuse_rows_blocking, r.payload, r.key)
                     continue
                 coll_name, top_k, expr, params_key = r.key
                 if self.mgr.collections[coll_name].handle is not cs:
                     # a collection that is NOT spread over the ranks (the local domain shard): its searches have nothing
                     # to do with the shard set's rounds — the blocking single-shard path answers them
-                    try:
-                        _deliver(r.future, self.mgr._search_lists_blocking(r.payload, coll_name, top_k, expr, dict(params_key)))
-                    except Exception as e:
-                        _fail(r.future, e)
+                    _answer(r.future, self._lists_blocking, r, r.key)
                     continue
                 drop = float(dict(params_key).get("drop_ratio_search", 0.0)) if r.kind == "sparse" else None
                 groups.setdefault((top_k, expr), {}).setdefault((r.kind, drop), []).append(r)
@@ -314,8 +310,7 @@ class SearchCoalescer:
                     chunk = rs[c0:c0 + 64]
                     try:
                         keep = self.mgr._row_mask(expr)
-                        q = np.stack([np.asarray(r.payload[0].detach().cpu().numpy() if hasattr(r.payload[0], "detach") else r.payload[0],
-                                                 dtype=np.float32).reshape(-1) for r in chunk])
+                        q = dense_rows_host([r.payload[0] for r in chunk])
                         res = cs.round_hybrid(q, [r.payload[1] for r in chunk], top_k, drop, rrf_k,
                                               np.array([[r.payload[2], r.payload[3]] for r in chunk], dtype=np.float64), keep)
                         self.stats["hybrid_launches"] += 1
@@ -336,8 +331,7 @@ class SearchCoalescer:
                             continue
                         try:
                             keep = self.mgr._row_mask(expr)
-                            q = np.stack([np.asarray(r.payload.detach().cpu().numpy() if hasattr(r.payload, "detach") else r.payload,
-                                                     dtype=np.float32).reshape(-1) for r in d_chunk]) if d_chunk else None
+                            q = dense_rows_host([r.payload for r in d_chunk]) if d_chunk else None
                             res = cs.round(q, [r.payload for r in s_chunk] if s_chunk else None, top_k, drop or 0.0, keep)
                             self.stats["dense_launches"] += 1 if d_chunk else 0
                             self.stats["sparse_launches"] += 1 if s_chunk else 0
@@ -348,90 +342,68 @@ class SearchCoalescer:
                         except Exception as e:
                             for r in d_chunk + s_chunk:
                                 _fail(r.future, e)
-            self._inflight = []
-            self._flush()
-            self.stats["busy_s"] += time.perf_counter() - t0
+
+    def _lists_blocking(self, r: _Request, key: Tuple):
+        """The lists of one dense or sparse request through the manager's blocking single-query path."""
+        coll_name, top_k, expr, params_key = key
+        return self.mgr._search_lists_blocking(r.payload, coll_name, top_k, expr, dict(params_key))
 
     def _one_by_one(self, kind: str, key: Tuple, chunk: List[_Request]):
         """Fallback when a batched launch was refused: each request through the blocking single-query path, so that
         only the request that is actually at fault fails."""
         for r in chunk:
-            try:
-                if kind == "fuse":
-                    _deliver(r.future, self.mgr._fuse_rows_blocking(r.payload, key))
-                elif kind == "hybrid":
-                    _deliver(r.future, None)   # the caller falls back to two searches + a fusion
-                elif kind == "encode":
-                    _deliver(r.future, self.mgr.embedding_generator.encode_to_device([r.payload[1]])[0])
-                else:
-                    coll_name, top_k, expr, params_key = key
-                    _deliver(r.future, self.mgr._search_lists_blocking(r.payload, coll_name, top_k, expr, dict(params_key)))
-            except Exception as e:
-                _fail(r.future, e)
+            if kind == "fuse":
+                _answer(r.future, self.mgr._fuse_rows_blocking, r.payload, key)
+            elif kind == "hybrid":
+                _deliver(r.future, None)   # the caller falls back to two searches + a fusion
+            elif kind == "encode":
+                _answer(r.future, lambda: self.mgr.embedding_generator.encode_to_device([r.payload[1]])[0])
+            else:
+                _answer(r.future, self._lists_blocking, r, key)
 
     # ------------------------------------------------------------------ dense
     def _enqueue_dense(self, torch, dev, stream, key, chunk):
         coll_name, top_k, expr, _ = key
         handle = self.mgr.collections[coll_name].handle.first
         B = len(chunk)
-        on_dev = [hasattr(r.payload, "is_cuda") and r.payload.is_cuda for r in chunk]
-        if all(on_dev):
-            q = torch.stack([r.payload.reshape(-1).to(torch.float32) for r in chunk]).contiguous()
-        else:
-            host = np.stack([np.asarray(r.payload.detach().cpu().numpy() if hasattr(r.payload, "detach") else r.payload,
-                                        dtype=np.float32).reshape(-1) for r in chunk])
-            if host.shape[1] != handle.dim:
-                raise ValueError(f"query dim {host.shape[1]} != shard dim {handle.dim}")
-            q = torch.from_numpy(host).to(dev)
-        ids = torch.empty((B, top_k), dtype=torch.int64, device=dev)
-        sc = torch.empty((B, top_k), dtype=torch.float32, device=dev)
-        fl = torch.zeros((B,), dtype=torch.int32, device=dev)
+        q = dense_rows_device([r.payload for r in chunk], dev, handle.dim)
+        ids, sc, fl = list_buffers(B, top_k, dev)
         mask = self.mgr._device_row_mask(expr, "dense")
         handle.search_dense_dev(q.data_ptr(), B, top_k, ids.data_ptr(), sc.data_ptr(), fl.data_ptr(),
                                 mask.data_ptr() if mask is not None else 0, stream.cuda_stream)
         self.stats["dense_launches"] += 1
         return {"ids": ids, "sc": sc, "fl": fl, "keep": (q, mask)}
 
-    def _scatter_dense(self, key, chunk, st):
-        self._scatter_lists(key, chunk, st)
-
     # ------------------------------------------------------------------ sparse
     def _enqueue_sparse(self, torch, dev, stream, key, chunk):
         coll_name, top_k, expr, params_key = key
         handle = self.mgr.collections[coll_name].handle.first
         drop = float(dict(params_key).get("drop_ratio_search", 0.0))
-        ptr, idx, val, max_nnz = pack_sparse_queries([r.payload for r in chunk], drop, handle.sparse_dim)
         B = len(chunk)
-        d_ptr, d_idx, d_val = torch.from_numpy(ptr).to(dev), torch.from_numpy(idx).to(dev), torch.from_numpy(val).to(dev)
-        ids = torch.empty((B, top_k), dtype=torch.int64, device=dev)
-        sc = torch.empty((B, top_k), dtype=torch.float32, device=dev)
-        fl = torch.zeros((B,), dtype=torch.int32, device=dev)
+        d_ptr, d_idx, d_val, max_nnz = upload_sparse(
+            pack_sparse_queries([r.payload for r in chunk], drop, handle.sparse_dim), dev)
+        nnz = int(d_idx.shape[0])
+        ids, sc, fl = list_buffers(B, top_k, dev)
         mask = self.mgr._device_row_mask(expr, "sparse")
-        handle.search_sparse_dev(d_ptr.data_ptr(), d_idx.data_ptr() if idx.size else 0, d_val.data_ptr() if idx.size else 0, B,
-                                 int(idx.shape[0]), int(max_nnz), top_k, ids.data_ptr(), sc.data_ptr(), fl.data_ptr(),
+        handle.search_sparse_dev(d_ptr.data_ptr(), d_idx.data_ptr() if nnz else 0, d_val.data_ptr() if nnz else 0, B,
+                                 nnz, int(max_nnz), top_k, ids.data_ptr(), sc.data_ptr(), fl.data_ptr(),
                                  mask.data_ptr() if mask is not None else 0, stream.cuda_stream)
         self.stats["sparse_launches"] += 1
         return {"ids": ids, "sc": sc, "fl": fl, "keep": (d_ptr, d_idx, d_val, mask)}
 
-    def _scatter_sparse(self, key, chunk, st):
-        self._scatter_lists(key, chunk, st)
-
     def _scatter_lists(self, key, chunk, st):
-        coll_name, top_k, expr, params_key = key
         ids, sc, fl = st["ids"].cpu().numpy(), st["sc"].cpu().numpy(), st["fl"].cpu().numpy()
         for i, r in enumerate(chunk):
-            try:
-                if fl[i] != 1:  # ties at the candidate cut: the host form widens the candidate set until the proof holds
-                    self.stats["redone_unproven"] += 1
-                    _deliver(r.future, self.mgr._search_lists_blocking(r.payload, coll_name, top_k, expr, dict(params_key)))
-                else:
-                    _deliver(r.future, (ids[i], sc[i]))
-            except Exception as e:
-                _fail(r.future, e)
+            if fl[i] != 1:  # ties at the candidate cut: the host form widens the candidate set until the proof holds
+                self.stats["redone_unproven"] += 1
+                _answer(r.future, self._lists_blocking, r, key)
+            else:
+                _deliver(r.future, (ids[i], sc[i]))
+
+    _scatter_dense = _scatter_sparse = _scatter_lists     # what _run looks up as "_scatter_" + kind
 
     # ------------------------------------------------------------------ hybrid (both searches + RRF of a request)
     def _enqueue_hybrid(self, torch, dev, stream, key, chunk):
-        from .engine import EngineConfig, HybridSearchEngine
         top_k, expr, drop, rrf_k = key
         handle = self.mgr.collections["semantic_index"].handle.first
         ekey = (top_k, rrf_k)
@@ -441,23 +413,14 @@ class SearchCoalescer:
                 self._engines.clear()
             eng = self._engines[ekey] = HybridSearchEngine(
                 handle, EngineConfig(top_k=top_k, rrf_k=rrf_k, enable_reranking=False), device=str(dev))
-        B = len(chunk)
-        dense = [r.payload[0] for r in chunk]
         # the fusion weights are per REQUEST (a weight_adapter may pick them per query, reference retrieval.py:251-262):
         # they travel as a [B, 3] operand of the post kernel, so requests with different weights still share the round
         wq = torch.from_numpy(np.array([[r.payload[2], r.payload[3], 0.0] for r in chunk], dtype=np.float64)).to(dev)
-        if all(hasattr(q, "is_cuda") and q.is_cuda for q in dense):
-            q = torch.stack([x.reshape(-1).to(torch.float32) for x in dense]).contiguous()
-        else:
-            host = np.stack([np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float32).reshape(-1)
-                             for x in dense])
-            q = torch.from_numpy(host).to(dev)
-        if q.shape[1] != handle.dim:
-            raise ValueError(f"query dim {q.shape[1]} != shard dim {handle.dim}")
-        ptr, idx, val, max_nnz = pack_sparse_queries([r.payload[1] for r in chunk], drop, handle.sparse_dim)
-        if not idx.size:
+        q = dense_rows_device([r.payload[0] for r in chunk], dev, handle.dim)
+        packed = pack_sparse_queries([r.payload[1] for r in chunk], drop, handle.sparse_dim)
+        if not packed[1].size:
             raise ValueError("no sparse terms in the batch")   # -> one by one through the general path
-        d_sparse = (torch.from_numpy(ptr).to(dev), torch.from_numpy(idx).to(dev), torch.from_numpy(val).to(dev), int(max_nnz))
+        d_sparse = upload_sparse(packed, dev)
         mask = self.mgr._device_row_mask(expr, "dense")
         b = eng.search(q, d_sparse, rowmask=mask, weights=wq)
         self.stats["hybrid_launches"] += 1

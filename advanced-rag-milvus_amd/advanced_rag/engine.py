@@ -28,6 +28,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
+from .staging import upload_sparse
 
 
 def shard_range(n_rows: int, rank: int, world: int, align: int = 1) -> Tuple[int, int]:
@@ -398,10 +399,7 @@ class HybridSearchEngine:
         return redone
 
     def upload_sparse(self, packed):
-        t = self.torch
-        indptr, idx, val, max_nnz = packed
-        return (t.from_numpy(indptr).to(self.device), t.from_numpy(idx).to(self.device),
-                t.from_numpy(val).to(self.device), max_nnz)
+        return upload_sparse(packed, self.device)
 
 
 class PipelinedSearchEngine(HybridSearchEngine):

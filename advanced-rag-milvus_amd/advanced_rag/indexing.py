@@ -37,19 +37,12 @@ import numpy as np
 from . import filters as _filters
 from .columns import FLOAT_COLUMNS, PayloadColumns
 from .constants import IndexingConstants
-from .embedding_cache import get_semantic_cache
+from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache, get_semantic_cache
 from ._native import HR_MAX_TOPK   # importing the binding module does not load the library
 from .shards import PartialAppend, ShardSet
+from .staging import dense_rows_device, dense_rows_host, list_buffers
 
 logger = logging.getLogger(__name__)
-
-# FLOAT fields of the collection schema (reference indexing.py:200-202) hold float32; a search hands them back as
-# Python floats of the float32-rounded value, which is what the payload columns store
-_FLOAT_FIELDS = ("entropy", "redundancy", "domain_density")
-
-
-def _f32(v) -> float:
-    return float(np.float32(v))
 
 
 class IndexType(Enum):
@@ -174,20 +167,51 @@ class MilvusIndexManager:
         self._native = _native
         _native.load_library()
 
-    def _initialize_collections(self):
-        nat = self._native
-        store = nat.HR_F16 if self.dtype in ("float16", "fp16", "f16") else nat.HR_F32
-        sparse_on = os.getenv("ENABLE_SPARSE", "1") == "1"
-        self._main = ShardSet([nat.ShardHandle(self.semantic_dim, store, metric_code(self.semantic_metric),
-                                               self.sparse_dim if sparse_on else 0, d) for d in self.devices])
+    @property
+    def _store_half(self) -> bool:
+        return self.dtype in ("float16", "fp16", "f16")
+
+    @property
+    def _store_code(self) -> int:
+        return self._native.HR_F16 if self._store_half else self._native.HR_F32
+
+    @staticmethod
+    def _sparse_enabled() -> bool:
+        return os.getenv("ENABLE_SPARSE", "1") == "1"
+
+    def _shard_handle(self, kind: str, device: int, path: Optional[str] = None, sparse_on: Optional[bool] = None):
+        """A shard handle of the "main" (semantic + sparse) or the "domain" collection on `device`: a new, empty one, or
+        the one saved at `path`.  sparse_on: whether a main handle carries the sparse collection (default: the environment)."""
+        if kind == "main":
+            sparse_on = self._sparse_enabled() if sparse_on is None else sparse_on
+            args = (self.semantic_dim, self._store_code, metric_code(self.semantic_metric),
+                    self.sparse_dim if sparse_on else 0, device)
+        else:
+            args = (self.domain_dim, self._store_code, metric_code(self.domain_metric), 0, device)
+        make = self._native.ShardHandle
+        return make(*args) if path is None else make.load(path, *args)
+
+    def _register_main_collections(self, sparse: bool):
         self.collections["semantic_index"] = ShardCollection(self, "semantic_index", "dense", self._main,
                                                              self.semantic_dim, self.semantic_metric)
-        if sparse_on:
+        if sparse:
             self.collections["sparse_index"] = ShardCollection(self, "sparse_index", "sparse", self._main,
                                                                self.sparse_dim, "IP")
+
+    def _forget_masks(self, rebuild_filters: bool):
+        """Drop every cached row mask, host and HBM: the rows changed.  After an APPEND (_append_payload, add_rows) the device
+        filter columns stay: they grow in place, every row is uploaded once.  After the row space was REPLACED (attach_shards,
+        add_rows_synthetic, load_snapshot) they go too (rebuild_filters) and are rebuilt on first use.  close() drops HBM masks only."""
+        self._mask_cache.clear()
+        self._dev_masks.clear()
+        if rebuild_filters:
+            self._dev_filters = None
+
+    def _initialize_collections(self):
+        self._main = ShardSet([self._shard_handle("main", d) for d in self.devices])
+        self._register_main_collections(self._sparse_enabled())
         if self.enable_domain:
-            self._domain = ShardSet([nat.ShardHandle(self.domain_dim, store, metric_code(self.domain_metric), 0, d)
-                                     for d in self.devices])
+            self._domain = ShardSet([self._shard_handle("domain", d) for d in self.devices])
             self.collections["domain_index"] = ShardCollection(self, "domain_index", "dense", self._domain,
                                                                self.domain_dim, self.domain_metric)
 
@@ -225,15 +249,9 @@ class MilvusIndexManager:
         self.devices = [h.device for h in handles]
         # the collection's metric is the handles' own (COSINE for a handle that carries none)
         self.semantic_metric = metric_name(getattr(handles[0], "metric", None))
-        self.collections["semantic_index"] = ShardCollection(self, "semantic_index", "dense", self._main,
-                                                             self.semantic_dim, self.semantic_metric)
-        if handles[0].sparse_dim:
-            self.collections["sparse_index"] = ShardCollection(self, "sparse_index", "sparse", self._main,
-                                                               self.sparse_dim, "IP")
+        self._register_main_collections(bool(handles[0].sparse_dim))
         self._synthetic_rows = int(synthetic_rows)
-        self._dev_filters = None
-        self._dev_masks.clear()
-        self._mask_cache.clear()
+        self._forget_masks(rebuild_filters=True)
 
     def serve(self):
         """Ranks > 0 of the torchrun form: answer rank 0's searches until it calls stop_workers()."""
@@ -355,7 +373,7 @@ class MilvusIndexManager:
         summary = {"total_chunks": len(chunks), "indexed_semantic": 0, "indexed_sparse": 0, "indexed_domain": 0,
                    "errors": []}
         timing = {"encode": 0.0, "append": 0.0, "flush": 0.0}
-        use_sparse = "sparse_index" in self.collections and os.getenv("ENABLE_SPARSE", "1") == "1"
+        use_sparse = "sparse_index" in self.collections and self._sparse_enabled()
         gen = self.embedding_generator
         on_device = gen is not None and hasattr(gen, "encode_to_device") and self._main is not None and \
             hasattr(self._main, "handles")
@@ -428,12 +446,12 @@ class MilvusIndexManager:
         if not kept:
             return summary
 
-        def device_rows(t, store_half: bool):
+        def device_rows(t):
             """The kept rows of an encoder output, in the shard's storage type, still on the device."""
             import torch
             if len(kept_idx) != t.shape[0]:
                 t = t.index_select(0, torch.as_tensor(kept_idx, device=t.device))
-            return t.to(torch.float16 if store_half else torch.float32).contiguous()
+            return t.to(torch.float16 if self._store_half else torch.float32).contiguous()
 
         try:
             if "semantic_index" not in self.collections:
@@ -442,11 +460,10 @@ class MilvusIndexManager:
             if use_sparse:
                 sparse_csr = (np.asarray(sp_ptr, np.int64), np.concatenate(sp_idx) if sp_idx else np.zeros(0, np.int32),
                               np.concatenate(sp_val) if sp_val else np.zeros(0, np.float32))
-            store_half = self.dtype in ("float16", "fp16", "f16")
             t1 = _time.perf_counter()
             # dense rows, sparse rows and payload columns of a chunk share one row number: the three are appended
             # together, and whatever fails afterwards is padded rather than left short
-            dense_rows = device_rows(dense_dev, store_half) if dense_dev is not None else np.stack(rows_dense)
+            dense_rows = device_rows(dense_dev) if dense_dev is not None else np.stack(rows_dense)
             self._check_dense_rows(dense_rows, self._main)    # refused whole, before anything is appended
             try:
                 _, _, sparse_err = await asyncio.to_thread(self._main.add, dense_rows, sparse_csr)
@@ -467,7 +484,7 @@ class MilvusIndexManager:
             if "domain_index" in self.collections:
                 before = self._domain.num_rows
                 try:
-                    dom_rows = device_rows(dom_dev, store_half) if dom_dev is not None else np.stack(rows_domain)
+                    dom_rows = device_rows(dom_dev) if dom_dev is not None else np.stack(rows_domain)
                     self._check_dense_rows(dom_rows, self._domain)
                     await asyncio.to_thread(self._domain.add, dom_rows)
                     summary["indexed_domain"] = len(kept)
@@ -497,8 +514,17 @@ class MilvusIndexManager:
             c[name].extend([getattr(m, name) for m in metas])
         c["timestamp"].extend(str(m.timestamp) for m in metas)
         c["metadata_json"].extend(str(m.to_dict())[:10000] for m in metas)
-        self._mask_cache.clear()
-        self._dev_masks.clear()
+        self._forget_masks(rebuild_filters=False)
+
+    def _add_to_main(self, dense, sparse_csr):
+        """Append a bulk batch to the main shard set -> (rows the shards numbered, what stopped the append or None, the sparse
+        collection's error or None).  Rows numbered before a shard refused (PartialAppend) still need their payload: the caller adds it."""
+        self._check_dense_rows(dense, self._main)
+        try:
+            _, _, sparse_err = self._main.add(dense, sparse_csr if "sparse_index" in self.collections else None)
+        except PartialAppend as pa:
+            return pa.end - pa.base, pa.cause, None
+        return dense.shape[0], None, sparse_err
 
     def add_rows(self, dense: np.ndarray, sparse_csr=None, ids: Optional[Sequence[str]] = None,
                  contents: Optional[Sequence[str]] = None, **scalar_columns):
@@ -506,14 +532,8 @@ class MilvusIndexManager:
         float16/float32, optional CSR triple (indptr, indices, values)."""
         if self._synthetic_rows:
             raise ValueError("shard is in synthetic-payload mode; use add_rows_synthetic")
-        self._check_dense_rows(dense, self._main)
-        n = dense.shape[0]
         base = self.num_rows
-        failed = None
-        try:
-            _, _, sparse_err = self._main.add(dense, sparse_csr if "sparse_index" in self.collections else None)
-        except PartialAppend as pa:    # the shards numbered pa.end - pa.base rows: their payload goes in, then the caller hears
-            n, failed, sparse_err = pa.end - pa.base, pa.cause, None
+        n, failed, sparse_err = self._add_to_main(dense, sparse_csr)
         c = self._cols
         defaults = {"doc_id": lambda r: f"doc{r // 10}", "chunk_index": lambda r: r % 10, "token_count": lambda r: 0,
                     "entropy": lambda r: 0.0, "redundancy": lambda r: 0.0, "domain_density": lambda r: 0.0,
@@ -526,8 +546,7 @@ class MilvusIndexManager:
             for name, fn in defaults.items():
                 given = scalar_columns.get(name)
                 c[name].extend(given[lo:hi] if given is not None else [fn(base + r) for r in range(lo, hi)])
-        self._mask_cache.clear()
-        self._dev_masks.clear()
+        self._forget_masks(rebuild_filters=False)
         if failed is not None:
             raise failed
         if sparse_err is not None:  # the rows are in (with empty sparse rows); the caller still hears about it
@@ -538,16 +557,9 @@ class MilvusIndexManager:
         number on demand (10M-row benchmarks would otherwise hold GBs of Python strings)."""
         if len(self._cols["id"]):
             raise ValueError("shard already holds payload columns")
-        self._check_dense_rows(dense, self._main)
-        n, failed = dense.shape[0], None
-        try:
-            _, _, sparse_err = self._main.add(dense, sparse_csr if "sparse_index" in self.collections else None)
-        except PartialAppend as pa:
-            n, failed, sparse_err = pa.end - pa.base, pa.cause, None
+        n, failed, sparse_err = self._add_to_main(dense, sparse_csr)
         self._synthetic_rows += n
-        self._dev_filters = None
-        self._dev_masks.clear()
-        self._mask_cache.clear()
+        self._forget_masks(rebuild_filters=True)
         if failed is not None:
             raise failed
         if sparse_err is not None:
@@ -576,29 +588,28 @@ class MilvusIndexManager:
     def load_snapshot(self, directory: str) -> None:
         """Replace this manager's (empty) collections with the ones saved by `save_snapshot`; the manager must have
         been created with as many devices as the snapshot has shards."""
-        nat = self._native
-        store = nat.HR_F16 if self.dtype in ("float16", "fp16", "f16") else nat.HR_F32
-        sparse_on = "sparse_index" in self.collections
+        sparse_on = "sparse_index" in self.collections     # what this manager was created with, not the environment of today
+        path = lambda kind, s: os.path.join(directory, f"{kind}.{s}.hbmrag")
         with np.load(os.path.join(directory, "payload.npz"), allow_pickle=False) as z:
             n_shards = int(z["n_shards"])
             if n_shards != len(self.devices):
                 raise ValueError(f"snapshot has {n_shards} shards, this manager was created with {len(self.devices)} devices")
-            main = [nat.ShardHandle.load(os.path.join(directory, f"main.{s}.hbmrag"), self.semantic_dim, store,
-                                         metric_code(self.semantic_metric), self.sparse_dim if sparse_on else 0, d)
-                    for s, d in enumerate(self.devices)]
+            main = [self._shard_handle("main", d, path("main", s), sparse_on) for s, d in enumerate(self.devices)]
             self._main.adopt(main, [z[f"rows_main_{s}"] for s in range(n_shards)])
-            if self._domain is not None and os.path.exists(os.path.join(directory, "domain.0.hbmrag")):
-                dom = [nat.ShardHandle.load(os.path.join(directory, f"domain.{s}.hbmrag"), self.domain_dim, store,
-                                            metric_code(self.domain_metric), 0, d) for s, d in enumerate(self.devices)]
+            if self._domain is not None and os.path.exists(path("domain", 0)):
+                dom = [self._shard_handle("domain", d, path("domain", s)) for s, d in enumerate(self.devices)]
                 self._domain.adopt(dom, [z[f"rows_domain_{s}"] for s in range(n_shards)])
-            self._synthetic_rows = int(z["synthetic_rows"])
+            self._load_payload(z, with_columns=True)
+        self._forget_masks(rebuild_filters=True)
+
+    def _load_payload(self, z, with_columns: bool):
+        """The host half of a snapshot (payload.npz): the synthetic-row count and, with_columns, the tombstones and the columns."""
+        self._synthetic_rows = int(z["synthetic_rows"])
+        if with_columns:
             self._deleted = z["deleted"].copy() if z["deleted"].size else None
             self._cols = PayloadColumns()
             for k in self._cols:
                 self._cols[k].extend(z[f"col_{k}"].tolist())
-        self._dev_filters = None
-        self._mask_cache.clear()
-        self._dev_masks.clear()
 
     def load_snapshot_rank(self, directory: str, process_group=True, device: Optional[int] = None) -> None:
         """Resume the torchrun form from a snapshot rank 0 wrote with save_snapshot(): EVERY rank calls this — it loads
@@ -606,27 +617,18 @@ class MilvusIndexManager:
         import torch.distributed as dist
         if not hasattr(self, "_native"):
             self._connect()
-        nat = self._native
         group = None if process_group is True else process_group
         rank, world = dist.get_rank(group), dist.get_world_size(group)
-        store = nat.HR_F16 if self.dtype in ("float16", "fp16", "f16") else nat.HR_F32
         with np.load(os.path.join(directory, "payload.npz"), allow_pickle=False) as z:
             if int(z["n_shards"]) != world:
                 raise ValueError(f"snapshot has {int(z['n_shards'])} shards, the process group has {world} ranks")
             rows = z[f"rows_main_{rank}"].astype(np.int64)
-            sparse_on = os.getenv("ENABLE_SPARSE", "1") == "1"
-            dev = self.devices[0] if device is None else device
-            h = nat.ShardHandle.load(os.path.join(directory, f"main.{rank}.hbmrag"), self.semantic_dim, store,
-                                     metric_code(self.semantic_metric), self.sparse_dim if sparse_on else 0, dev)
-            synthetic = int(z["synthetic_rows"])
-            if rank == 0:
-                self._deleted = z["deleted"].copy() if z["deleted"].size else None
-                self._cols = PayloadColumns()
-                for k in self._cols:
-                    self._cols[k].extend(z[f"col_{k}"].tolist())
+            h = self._shard_handle("main", self.devices[0] if device is None else device,
+                                   os.path.join(directory, f"main.{rank}.hbmrag"))
+            self._load_payload(z, with_columns=rank == 0)
         if self._main is not None:
             self._main.close()
-        self.attach_shards([h], rows_of=[rows], synthetic_rows=synthetic, process_group=process_group, local_ids=True)
+        self.attach_shards([h], rows_of=[rows], synthetic_rows=self._synthetic_rows, process_group=process_group, local_ids=True)
 
     # ------------------------------------------------------------------ search
     @staticmethod
@@ -652,7 +654,7 @@ class MilvusIndexManager:
         encoder's output, already cast to the store's type) on its device.  ValueError names the first bad row."""
         h = getattr(shard_set, "local", shard_set).handles[0]
         code = getattr(h, "dtype", None)
-        half = code == 1 if isinstance(code, int) else self.dtype in ("float16", "fp16", "f16")
+        half = code == 1 if isinstance(code, int) else self._store_half
         bad = None
         if hasattr(rows, "is_cuda"):
             import torch
@@ -756,17 +758,13 @@ class MilvusIndexManager:
             elif hasattr(query, "is_cuda") and query.is_cuda and d_mask is None:
                 ids, sc = self._search_dense_device(h, query, top_k)
             else:
-                if hasattr(query, "detach"):
-                    query = query.detach().cpu().numpy()
-                ids, sc = h.search_dense(np.asarray(query, dtype=np.float32).reshape(1, -1), top_k, None, ptr)
+                ids, sc = h.search_dense(dense_rows_host([query]), top_k, None, ptr)
             return ids[0], sc[0]
         mask = self._row_mask(filters)
         if coll.kind == "sparse":
             ids, sc = coll.handle.search_sparse([query], top_k, drop, mask)
         else:
-            if hasattr(query, "detach"):
-                query = query.detach().cpu().numpy()
-            ids, sc = coll.handle.search_dense(np.asarray(query, dtype=np.float32).reshape(1, -1), top_k, mask)
+            ids, sc = coll.handle.search_dense(dense_rows_host([query]), top_k, mask)
         return ids[0], sc[0]
 
     def _search_blocking(self, query_embedding, collection_name: str, top_k: int, filters: Optional[str],
@@ -781,10 +779,8 @@ class MilvusIndexManager:
         """Query already in HBM (device-resident embedding cache): device form, no upload; an unproven
         list (ties at the candidate cut) is redone through the host form."""
         import torch
-        q = q_dev.reshape(1, -1).to(torch.float32).contiguous()
-        ids = torch.empty((1, top_k), dtype=torch.int64, device=q.device)
-        sc = torch.empty((1, top_k), dtype=torch.float32, device=q.device)
-        flag = torch.zeros((1,), dtype=torch.int32, device=q.device)
+        q = dense_rows_device([q_dev], q_dev.device, handle.dim)
+        ids, sc, flag = list_buffers(1, top_k, q.device)
         stream = torch.cuda.current_stream(q.device)
         handle.search_dense_dev(q.data_ptr(), 1, top_k, ids.data_ptr(), sc.data_ptr(), flag.data_ptr(), 0, stream.cuda_stream)
         stream.synchronize()
@@ -963,18 +959,24 @@ class MilvusIndexManager:
                 out[i] = np.random.randn(self.semantic_dim).astype(np.float32)
         return out  # type: ignore[return-value]
 
-    def _device_query_embedding(self, text: str):
-        """float32 [dim] CUDA tensor for `text` from the device-resident table (filled on a miss)."""
-        from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache
+    def _device_table(self):
+        """The device-resident table of semantic query embeddings, created on first use together with its counters."""
         if self._dev_cache is None:
             self._dev_cache = DeviceEmbeddingTable(self._dev_cache_slots, self.semantic_dim, f"cuda:{self.device}")
             self.device_cache_stats = {"hits": 0, "misses": 0}
+        return self._dev_cache
+
+    def _count_device_lookup(self, vec):
+        """Book a lookup in the device table as a hit (a row) or a miss (None); hands `vec` back."""
+        self.device_cache_stats["hits" if vec is not None else "misses"] += 1
+        return vec
+
+    def _device_query_embedding(self, text: str):
+        """float32 [dim] CUDA tensor for `text` from the device-resident table (filled on a miss)."""
         key = EmbeddingCache._materialize_key(text)
-        vec = self._dev_cache.lookup(key)
+        vec = self._count_device_lookup(self._device_table().lookup(key))
         if vec is not None:
-            self.device_cache_stats["hits"] += 1
             return vec
-        self.device_cache_stats["misses"] += 1
         gen = self.embedding_generator
         if gen is not None and hasattr(gen, "encode_to_device"):
             fresh = gen.encode_to_device([text])[0]
@@ -988,23 +990,17 @@ class MilvusIndexManager:
         gen = self.embedding_generator
         if self._dev_cache_slots > 0 and self._main is not None and not (
                 gen is not None and asyncio.iscoroutinefunction(gen.encode_semantic)):
-            from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache
-            if self._dev_cache is None:
-                self._dev_cache = DeviceEmbeddingTable(self._dev_cache_slots, self.semantic_dim, f"cuda:{self.device}")
-                self.device_cache_stats = {"hits": 0, "misses": 0}
             key = EmbeddingCache._materialize_key(text)
-            hit = self._dev_cache.lookup(key)
+            hit = self._device_table().lookup(key)
             if hit is not None:          # a hit is a dictionary lookup: no executor hop, no task
-                self.device_cache_stats["hits"] += 1
-                return hit
+                return self._count_device_lookup(hit)
             front = self._encode_front(gen)
             if front is not None:        # the misses of a round share ONE encoder forward (batching.py::_enqueue_encode)
-                self.device_cache_stats["misses"] += 1
+                self._count_device_lookup(None)
                 return await front.submit_async("encode", ("encode",), (key, text))
             return await asyncio.get_event_loop().run_in_executor(self.embedding_executor, self._device_query_embedding, text)
         front = self._encode_front(gen)
         if front is not None:
-            from .embedding_cache import EmbeddingCache
             key = EmbeddingCache._materialize_key(text)
 
             async def compute_batched() -> np.ndarray:   # the host cache holds host arrays (reference indexing.py:601-627)

@@ -135,3 +135,27 @@ def test_ingest_documents_refuses_a_batch_whose_encoder_returned_an_inf():
     assert rep["indexing_summary"]["indexed_semantic"] == m and after[:3] == (n + m, n + m, n + m)
     assert set(after[5]) == {n + m}
     asyncio.run(p.close())
+
+
+def test_appending_rows_keeps_the_device_filter_columns_and_replacing_the_row_space_drops_them():
+    """Every ingest forgets the cached row masks (they cover the old rows).  The device filter columns grow in place when
+    rows are appended (add_rows), so that object stays; a row space that is replaced (add_rows_synthetic) drops it."""
+    rng = np.random.default_rng(3)
+    X, csr = _batch(rng, 6)
+
+    def prime(mgr):
+        mgr._mask_cache[("e", 0, 0)] = np.ones(0, bool)
+        mgr._dev_masks[("global", "e", 0, 0)] = object()
+        mgr._dev_filters = object()
+        return mgr._dev_filters
+
+    mgr = _manager()
+    filters = prime(mgr)
+    mgr.add_rows(X, csr)
+    assert mgr._mask_cache == {} and mgr._dev_masks == {} and mgr._dev_filters is filters
+    asyncio.run(mgr.close())
+    mgr = _manager()
+    prime(mgr)
+    mgr.add_rows_synthetic(X, csr)
+    assert mgr._mask_cache == {} and mgr._dev_masks == {} and mgr._dev_filters is None
+    asyncio.run(mgr.close())

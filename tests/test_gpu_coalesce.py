@@ -417,3 +417,38 @@ def test_concurrent_retrieves_share_encoder_forwards(gpu, long_timeout, device_c
         assert torch.allclose(got, lone, atol=3e-3), (got - lone).abs().max()
     finally:
         asyncio.run(pipe.close())
+
+
+def test_one_round_takes_device_and_host_queries_and_refuses_a_device_query_of_the_wrong_width(gpu, long_timeout):
+    """The same vector as a CUDA tensor, a numpy array and a CPU tensor in ONE round: one launch, identical lists.  A CUDA
+    query one element short is refused for its caller alone, with the message a host query of that width gets, instead of
+    reaching the kernel as a buffer of the wrong size; its batch mate is answered."""
+    rng = np.random.default_rng(29)
+    n, d, V = 300, 64, 50
+    X = rng.standard_normal((n, d)).astype(np.float32)
+    ptr = np.arange(n + 1, dtype=np.int64) * 2
+    idx = np.tile(np.array([3, 17], np.int32), n)
+    val = np.abs(rng.standard_normal(2 * n)).astype(np.float32) + 0.1
+    mgr = MilvusIndexManager(semantic_dim=d, sparse_dim=V, dtype="float32", enable_domain=False)
+    mgr.add_rows(X, (ptr, idx, val))
+    mgr.finalize()
+    q = rng.standard_normal(d).astype(np.float32)
+    forms = [torch.from_numpy(q).cuda(), q, torch.from_numpy(q.copy())]
+
+    def lists(hits):
+        return [(h["id"], float(h["score"]).hex()) for h in hits]
+
+    async def together(queries):
+        return await asyncio.gather(*[mgr.search(x, "semantic_index", 10) for x in queries], return_exceptions=True)
+
+    try:
+        outs = asyncio.run(together(forms))
+        st = mgr._front.stats
+        assert st["dense_launches"] == 1 and st["rounds"] == 1 and st["requests"] == 3, st
+        assert len(outs[0]) == 10 and lists(outs[0]) == lists(outs[1]) == lists(outs[2])
+        bad, good = asyncio.run(together([forms[0][:d - 1], forms[0]]))
+        assert isinstance(bad, ValueError) and str(bad) == f"query dim {d - 1} != shard dim {d}", bad
+        assert lists(good) == lists(outs[0])
+        assert st.get("worker_failures", 0) == 0
+    finally:
+        asyncio.run(mgr.close())
