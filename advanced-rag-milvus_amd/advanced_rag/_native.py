@@ -13,6 +13,8 @@ from typing import Optional, Sequence, Tuple
 
 import numpy as np
 
+from .staging import csr_of_queries
+
 HR_F32, HR_F16 = 0, 1
 HR_METRIC_IP, HR_METRIC_COSINE, HR_METRIC_L2 = 0, 1, 2
 HR_METHOD_SEMANTIC, HR_METHOD_SPARSE, HR_METHOD_DOMAIN = 1, 2, 4
@@ -309,13 +311,7 @@ class ShardHandle:
                       drop_ratio: float = 0.0, rowmask: Optional[np.ndarray] = None,
                       d_rowmask: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         B = len(queries)
-        indptr = np.zeros(B + 1, dtype=np.int64)
-        for b, (qi, _) in enumerate(queries):
-            indptr[b + 1] = indptr[b] + len(qi)
-        idx = np.concatenate([np.asarray(qi, dtype=np.int32) for qi, _ in queries]) if indptr[-1] else np.zeros(0, np.int32)
-        val = np.concatenate([np.asarray(qv, dtype=np.float32) for _, qv in queries]) if indptr[-1] else np.zeros(0, np.float32)
-        idx = np.ascontiguousarray(idx, dtype=np.int32)
-        val = np.ascontiguousarray(val, dtype=np.float32)
+        indptr, idx, val = csr_of_queries(queries)
         ids = np.empty((B, k), dtype=np.int64)
         sc = np.empty((B, k), dtype=np.float32)
         if d_rowmask:

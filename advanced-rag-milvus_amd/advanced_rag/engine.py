@@ -28,6 +28,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
+from .shards import dense_ascending
 from .staging import upload_sparse
 
 
@@ -307,8 +308,7 @@ class HybridSearchEngine:
                 a.ids[slot], a.k_in[slot] = b["ids"][m].data_ptr(), kp
         a.n_lists, a.rrf_k, a.top_k = n_lists, cfg.rrf_k, cfg.top_k
         # the lists of an L2 shard are distances, smallest first: the merge of that modality runs ascending
-        l2 = lambda h: getattr(h, "metric", None) == nat.HR_METRIC_L2
-        a.asc_mask = (1 if l2(self.h) else 0) | (4 if self.hd is not None and l2(self.hd) else 0)
+        a.asc_mask = (1 if dense_ascending(self.h) else 0) | (4 if self.hd is not None and dense_ascending(self.hd) else 0)
         a.w[0], a.w[1], a.w[2] = cfg.dense_weight, cfg.sparse_weight, cfg.domain_weight
         a.fused_ids, a.fused_scores = b["fused_ids"].data_ptr(), b["fused_scores"].data_ptr()
         a.fused_methods, a.fused_n = b["fused_methods"].data_ptr(), b["fused_n"].data_ptr()

@@ -23,14 +23,32 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-
-HR_METRIC_L2 = 2   # include/hbmrag.h; a handle of that metric returns squared distances, smallest first
+from . import wire
+from ._native import HR_METRIC_L2   # a handle of that metric returns squared distances, smallest first
+from .staging import csr_of_queries
 
 
 def dense_ascending(handle) -> bool:
     """True when `handle`'s dense lists are distances (ascending): an L2 shard.  Handles without a `metric` (test stubs)
     are similarity shards."""
     return getattr(handle, "metric", None) == HR_METRIC_L2
+
+
+def is_native_handle(handle) -> bool:
+    """True for a libhbmrag shard (row masks are kept in its HBM, the device forms exist); False for a test stand-in."""
+    return getattr(handle, "_h", None) is not None
+
+
+def empty_lists(B: int, k: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The [B, k] lists of a shard that holds no row: ids all -1, scores 0."""
+    return np.full((B, k), -1, np.int64), np.zeros((B, k), np.float32)
+
+
+def to_global(local_ids: np.ndarray, rows: np.ndarray) -> np.ndarray:
+    """A handle's lists of LOCAL rows -> global rows through its row map `rows`; the -1 padding stays -1."""
+    if not len(rows):
+        return np.full(local_ids.shape, -1, np.int64)
+    return np.where(local_ids >= 0, rows[np.maximum(local_ids, 0)], -1).astype(np.int64)
 
 
 def merge_lists(ids: Sequence[np.ndarray], scores: Sequence[np.ndarray], k: int,
@@ -194,7 +212,7 @@ class ShardSet:
             own = keep if (self.n_shards == 1 and len(self.rows_of[0]) == len(keep)) else keep[self.rows_of[s]]
             packed = np.packbits(own, bitorder="little")
             h = self.handles[s]
-            if getattr(h, "_h", None) is not None:   # a libhbmrag shard: keep the mask in its HBM
+            if is_native_handle(h):   # keep the mask in its HBM
                 import torch
                 hit = (None, torch.from_numpy(packed).to(f"cuda:{h.device}"))
             else:
@@ -215,26 +233,21 @@ class ShardSet:
     def _gather(self, parts, k: int, ascending: bool = False):
         if self.n_shards == 1:
             return parts[0]
-        ids, scores = [], []
-        for s, (li, sc) in enumerate(parts):
-            gi = np.where(li >= 0, self.rows_of[s][np.maximum(li, 0)] if len(self.rows_of[s]) else -1, -1)
-            ids.append(gi.astype(np.int64))
-            scores.append(sc)
-        return merge_lists(ids, scores, k, ascending)
+        ids = [to_global(li, self.rows_of[s]) for s, (li, _) in enumerate(parts)]
+        return merge_lists(ids, [sc for _, sc in parts], k, ascending)
 
     def search_dense(self, q: np.ndarray, k: int, keep: Optional[np.ndarray] = None):
         """q [B, dim] float32; keep = boolean filter over GLOBAL rows (or None) -> (ids [B,k] global rows, scores)."""
         def one(s):
             if self.handles[s].num_rows == 0:
-                B = np.atleast_2d(q).shape[0]
-                return np.full((B, k), -1, np.int64), np.zeros((B, k), np.float32)
+                return empty_lists(np.atleast_2d(q).shape[0], k)
             return self.handles[s].search_dense(q, k, *self._local_mask(s, keep))
         return self._gather(self._fan_out(one), k, self.dense_ascending)
 
     def search_sparse(self, queries, k: int, drop_ratio: float = 0.0, keep: Optional[np.ndarray] = None):
         def one(s):
             if self.handles[s].num_sparse_rows == 0:
-                return np.full((len(queries), k), -1, np.int64), np.zeros((len(queries), k), np.float32)
+                return empty_lists(len(queries), k)
             return self.handles[s].search_sparse(queries, k, drop_ratio, *self._local_mask(s, keep))
         return self._gather(self._fan_out(one), k)
 
@@ -256,24 +269,87 @@ class ShardSet:
         self._n = int(sum(len(r) for r in self.rows_of))
 
 
+class MaskCache:
+    """The row filters a CollectiveShardSet has sent round: MAX_MASKS entries, first in first out.  Every rank `put`s the
+    same mask ids in the same order, so the ranks evict alike and rank 0's `lookup` knows what the others still hold.  An
+    entry is this rank's boolean slice of the mask and, made on first use by a hybrid round, its packed copy on the device;
+    they leave together."""
+
+    def __init__(self, capacity: int):
+        self.capacity = capacity
+        self._entries = {}          # mask id -> [boolean slice, device copy | None], oldest first
+        self._ids = {}              # rank 0: id(filter array) -> (mask id, the array: keeps the id() unique)
+        self._next_id = 1
+
+    def lookup(self, keep: Optional[np.ndarray]):
+        """rank 0: (mask id, 1 if the mask must travel with this round, its packed bytes or None) of a filter array; the
+        id 0 is "no filter"."""
+        if keep is None:
+            return 0, 0, None
+        ent = self._ids.get(id(keep))
+        if ent is not None and ent[0] in self._entries:
+            return ent[0], 0, None
+        mask_id = self._next_id
+        self._next_id += 1
+        self._ids = {key: v for key, v in self._ids.items() if v[0] in self._entries}
+        self._ids[id(keep)] = (mask_id, keep)
+        return mask_id, 1, np.packbits(np.asarray(keep, dtype=bool), bitorder="little")
+
+    def put(self, mask_id: int, bits_slice: np.ndarray):
+        if len(self._entries) >= self.capacity:
+            self._entries.pop(next(iter(self._entries)))
+        self._entries[mask_id] = [bits_slice, None]
+
+    def get(self, mask_id: int) -> np.ndarray:
+        return self._entries[mask_id][0]
+
+    def device(self, mask_id: int, upload):
+        """The entry's device copy: upload(boolean slice), made once."""
+        ent = self._entries[mask_id]
+        if ent[1] is None:
+            ent[1] = upload(ent[0])
+        return ent[1]
+
+    def __contains__(self, mask_id: int) -> bool:
+        return mask_id in self._entries
+
+    def clear(self):
+        self._entries.clear()
+        self._ids.clear()
+
+
 class CollectiveShardSet:
     """The torchrun form: one PROCESS per GPU, each owning the shard of a contiguous global row range, searched as one
     collection from rank 0 — the reference's `num_shards` are invisible to the caller and cost it one RPC
     (indexing.py:232-239, :439-551); here a round of searches costs TWO collectives:
 
-      1. ONE broadcast of a fixed-size packet (header + dense queries + sparse queries as CSR + the id of the filter
-         mask): every rank learns what to search;
+      1. ONE broadcast of a fixed-size packet: every rank learns what to search;
       2. every rank runs the dense and / or the sparse search of the round on its shard (device forms on a GPU shard,
          unproven lists repaired locally through the host form);
       3. ONE gather of the packed per-rank lists (both modalities) to rank 0, which merges them by (score desc, row asc).
 
+    The packet (wire.py holds the layout; no position is spelt out here) is a header — the op, the op's fields, the mask
+    triple, the payload's byte count — and a payload of typed sections, 8-byte items first:
+
+      OP_ROUND   Bd, Bs, k, dim, nnz, drop + mask_id, mask_new, mask_len;  sparse indptr [Bs + 1], dense queries [Bd, dim],
+                 sparse indices [nnz], sparse values [nnz]
+      OP_HYBRID  B, top_k, dim, nnz, rrf_k, max_nnz + the mask triple;  indptr [B + 1], fusion weights [B, 3], dense
+                 queries [B, dim], indices [nnz], values [nnz]
+      OP_ADD     nrows, dim, has_dense, has_sparse, nnz;  no payload (the batch follows in broadcasts of its own)
+      OP_SAVE    no fields;  the ranks' shard paths, one per line
+      OP_FLUSH, OP_ROWMAPS, OP_STOP   neither
+
     A round carries the searches of one or many retrieve() calls (the manager's batching front packs concurrent
     callers), so a lone retrieve() = 1 broadcast + 1 gather.  A filter's packed row mask travels ONCE, in an extra
-    broadcast of the round that first uses it; every rank keeps its slice under the mask's id (same LRU on all ranks).
-    Rank 0 validates and packs the whole round BEFORE the first collective and every rank always reaches the gather — a
-    failing rank contributes empty lists and an error flag that rank 0 raises — so nobody is left waiting in a
-    collective.  Collectives are torch.distributed's (backend "nccl" = RCCL over xGMI on a GPU node; "gloo" in the CPU
-    tests and one-GPU rehearsals); rounds are serialised by a lock, so every rank sees the same sequence.
+    broadcast of the round that first uses it; every rank keeps its slice under the mask's id (MaskCache: first in first
+    out, the same order on all ranks).  Rank 0 validates and packs the whole round BEFORE the first collective, and
+    rounds are serialised by a lock, so every rank sees the same sequence.  Collectives are torch.distributed's (backend
+    "nccl" = RCCL over xGMI on a GPU node; "gloo" in the CPU tests and one-GPU rehearsals).
+
+    Who is guaranteed to reach the collective.  A search round (OP_ROUND) and every control operation: a rank whose own
+    part fails still enters the gather / the status all-reduce, with empty lists and an error flag that rank 0 raises, so
+    nobody is left waiting.  A hybrid round (OP_HYBRID) is NOT: its collective is the all-gather inside the engine's
+    search, and a rank that raises before it (a mask shorter than its rows, say) never enters it — the other ranks wait.
 
     Two forms of the local shard (a local ShardSet of one handle).  Pre-built: the rank filled its shard itself with one
     contiguous global row range; the handle carries the numbers (ShardHandle.set_row_offset(first_row)) and `first_row`
@@ -283,9 +359,7 @@ class CollectiveShardSet:
     shard file), row_maps (one gather) — which rank 0 calls while the other ranks sit in serve(); each is one control
     packet + its payload broadcasts + one all-reduce of a status flag, so that rank 0 hears of a failure anywhere."""
 
-    OP_STOP, OP_ROUND, OP_ADD, OP_FLUSH, OP_SAVE, OP_ROWMAPS, OP_HYBRID = 0, 1, 2, 3, 4, 5, 6
-    HEADER = 16                     # int64 words
-    PACKET_BYTES = 1 << 20          # header + queries of one round (128 x (768-d dense + 100-term sparse) = 0.5 MB)
+    PACKET_BYTES = wire.PACKET_BYTES
     MAX_MASKS = 8
     hybrid_on_device = True         # False: retrieve() takes the two-searches-then-fuse rounds through the host forms (round 3)
 
@@ -309,13 +383,15 @@ class CollectiveShardSet:
         dist.all_reduce(n, group=group)
         self._n_rows, self._n_sparse = int(n[0]), int(n[1])
         self._packet = torch.zeros(self.PACKET_BYTES, dtype=torch.uint8, device=self.dev)
-        self._masks = {}            # mask id -> this rank's boolean slice (LRU, same order on every rank)
-        self._mask_ids = {}         # rank 0: id(filter array) -> (mask id, the array: keeps the id alive)
-        self._next_mask_id = 1
+        self._masks = MaskCache(self.MAX_MASKS)
         self.n_collectives = 0      # broadcasts + gathers issued (tests count them)
         self._side = None           # one worker thread: the dense search of a round that also carries sparse queries
         self._hyb_engines = {}      # (top_k, rrf_k) -> engine.HybridSearchEngine over the group (hybrid rounds on the device)
-        self._dev_masks = {}        # mask id -> this rank's packed row mask in HBM
+        self._serving = False
+        # what every rank runs when a packet of that op arrives: handler(fields, packet bytes, **what only rank 0 has)
+        self._handlers = {wire.OP_ROUND: self._op_round, wire.OP_HYBRID: self._op_hybrid, wire.OP_ADD: self._op_add,
+                          wire.OP_FLUSH: self._op_flush, wire.OP_SAVE: self._op_save, wire.OP_ROWMAPS: self._op_rowmaps,
+                          wire.OP_STOP: self._op_stop}
 
     # shape, as ShardSet
     n_shards = property(lambda self: self.world)
@@ -334,17 +410,49 @@ class CollectiveShardSet:
             return self.local.rows_of[0]
         return np.arange(self.first_row, self.first_row + max(self.local.num_rows, self.local.num_sparse_rows), dtype=np.int64)
 
-    # ------------------------------------------------------------------ collective control operations (rank 0 calls, the others serve())
-    def _control(self, op: int, words=(), blob: bytes = b""):
-        """rank 0: send a control packet (header words + an optional byte blob) — the workers pick it up in serve()."""
-        hdr = np.zeros(self.HEADER, dtype=np.int64)
-        hdr[0] = op
-        hdr[1: 1 + len(words)] = list(words)
-        hdr[self.HEADER - 1] = len(blob)
-        body = np.concatenate([hdr.view(np.uint8), np.frombuffer(blob, dtype=np.uint8)]) if blob else hdr.view(np.uint8)
-        if body.size > self.PACKET_BYTES:
-            raise ValueError("control packet too large")
-        return self._send_packet(body, whole=True)
+    # ------------------------------------------------------------------ protocol
+    def _bcast(self, t):
+        self.n_collectives += 1
+        self.dist.broadcast(t, src=0, group=self.group)
+        return t
+
+    def _send_packet(self, body: Optional[np.ndarray]) -> np.ndarray:
+        """ONE broadcast of the fixed-size packet; returns the bytes in use (header + payload) as numpy on every rank."""
+        t = self.torch
+        if self.rank == 0:
+            self._packet[: body.size].copy_(t.from_numpy(body))
+        self._bcast(self._packet)
+        if self.rank == 0:
+            return body
+        n = wire.unpack_header(self._packet[: wire.HEADER_BYTES].cpu().numpy())[2]
+        return self._packet[: wire.HEADER_BYTES + n].cpu().numpy()
+
+    def _dispatch(self, body: Optional[np.ndarray], **rank0):
+        """Both sides of one packet: rank 0 sends `body` (the workers pick it up in serve()), every rank reads the header
+        and runs the op's handler; `rank0` is what only the sender has (a new mask's bytes, the batch of an add)."""
+        pkt = self._send_packet(body)
+        op, fields, _ = wire.unpack_header(pkt)
+        return self._handlers[op](fields, pkt, **rank0)
+
+    def _control(self, op: int, fields=(), blob: bytes = b"", **rank0):
+        """rank 0, under the lock: one control operation = its packet (header fields + an optional byte blob), then the
+        handler every rank runs."""
+        return self._dispatch(wire.pack(op, fields, [np.frombuffer(blob, dtype=np.uint8)], self.PACKET_BYTES), **rank0)
+
+    @staticmethod
+    def _guarded(fn):
+        """Run this rank's part of a collective operation -> (result, None) or (None, the exception): a rank that fails
+        must still reach the collective that follows, nobody may be left waiting in it."""
+        try:
+            return fn(), None
+        except Exception as e:
+            return None, e
+
+    def _log_worker_failure(self, what: str, err: Optional[Exception]):
+        """A worker rank has nobody to raise to: its error goes to the log, rank 0 learns of it through the collective."""
+        if err is not None and self.rank != 0:
+            import logging
+            logging.getLogger(__name__).error("rank %d failed %s: %s", self.rank, what, err)
 
     def _status(self, err: Optional[Exception]):
         """Every rank reports whether its part of a control operation worked; rank 0 raises if any did not."""
@@ -352,15 +460,14 @@ class CollectiveShardSet:
         flag = t.tensor([0 if err is None else 1], dtype=t.int64, device=self.dev)
         self.n_collectives += 1
         self.dist.all_reduce(flag, group=self.group)
-        if err is not None and self.rank != 0:
-            import logging
-            logging.getLogger(__name__).error("rank %d failed a collective control operation: %s", self.rank, err)
+        self._log_worker_failure("a collective control operation", err)
         if self.rank == 0:
             if err is not None:
                 raise err
             if int(flag.item()):
                 raise RuntimeError("a collective control operation failed on another rank (see its log)")
 
+    # ------------------------------------------------------------------ collective control operations (rank 0 calls, the others serve())
     def add(self, dense, sparse_csr=None, n: Optional[int] = None):
         """Collective append (rank 0 calls it with the batch, the other ranks are in serve()): the batch travels in ONE
         broadcast per part (dense rows, CSR), every rank keeps the contiguous block shard_range(n, rank, world) of it and
@@ -372,34 +479,33 @@ class CollectiveShardSet:
             if dense is not None and hasattr(dense, "detach"):
                 dense = dense.detach().float().cpu().numpy()
             nrows = dense.shape[0] if dense is not None else (len(sparse_csr[0]) - 1 if sparse_csr is not None else int(n or 0))
-            dim = 0 if dense is None else int(dense.shape[1])
             if sparse_csr is not None:      # positions from 0 and exactly nnz entries: the receivers size their buffers by it
                 ptr = np.asarray(sparse_csr[0], dtype=np.int64)
                 sparse_csr = (ptr - ptr[0], np.asarray(sparse_csr[1])[ptr[0]:ptr[-1]], np.asarray(sparse_csr[2])[ptr[0]:ptr[-1]])
-            nnz = 0 if sparse_csr is None else int(sparse_csr[0][-1])
-            self._control(self.OP_ADD, (nrows, dim, 1 if dense is not None else 0, 1 if sparse_csr is not None else 0, nnz))
-            return self._add_collective(nrows, dim, dense is not None, sparse_csr is not None, nnz, dense, sparse_csr)
+            fields = dict(nrows=nrows, dim=0 if dense is None else dense.shape[1], has_dense=dense is not None,
+                          has_sparse=sparse_csr is not None, nnz=0 if sparse_csr is None else sparse_csr[0][-1])
+            return self._control(wire.OP_ADD, fields, dense=dense, sparse_csr=sparse_csr)
 
-    def _add_collective(self, nrows, dim, has_dense, has_sparse, nnz, dense=None, sparse_csr=None):
+    def _op_add(self, f, pkt, dense=None, sparse_csr=None):
         from .engine import shard_range
         t = self.torch
+        nrows, has_dense, has_sparse = f.nrows, bool(f.has_dense), bool(f.has_sparse)
+        base = self._n_rows if has_dense or not has_sparse else self._n_sparse
 
         def bcast_array(arr, count, dtype):
             buf = (t.from_numpy(np.ascontiguousarray(arr, dtype=dtype)).to(self.dev) if self.rank == 0
                    else t.empty(count, dtype=getattr(t, np.dtype(dtype).name), device=self.dev))
             return self._bcast(buf.reshape(-1)).cpu().numpy()
 
-        err, out = None, (0, 0, None)
-        try:
-            d = bcast_array(dense, nrows * dim, np.float32).reshape(nrows, dim) if has_dense else None
+        def my_part():
+            d = bcast_array(dense, nrows * f.dim, np.float32).reshape(nrows, f.dim) if has_dense else None
             csr = None
             if has_sparse:
                 ptr = bcast_array(sparse_csr[0] if self.rank == 0 else None, nrows + 1, np.int64)
-                idx = bcast_array(sparse_csr[1] if self.rank == 0 else None, nnz, np.int32) if nnz else np.zeros(0, np.int32)
-                val = bcast_array(sparse_csr[2] if self.rank == 0 else None, nnz, np.float32) if nnz else np.zeros(0, np.float32)
+                idx = bcast_array(sparse_csr[1] if self.rank == 0 else None, f.nnz, np.int32) if f.nnz else np.zeros(0, np.int32)
+                val = bcast_array(sparse_csr[2] if self.rank == 0 else None, f.nnz, np.float32) if f.nnz else np.zeros(0, np.float32)
                 csr = (ptr, idx, val)
             lo, hi = shard_range(nrows, self.rank, self.world)
-            base = self._n_rows if has_dense or not has_sparse else self._n_sparse
             # the global row numbers are taken on every rank BEFORE the local append: a rank whose append fails leaves a
             # hole (rows no search returns) instead of ranks that disagree about the numbering
             if has_dense or not has_sparse:
@@ -407,23 +513,20 @@ class CollectiveShardSet:
             if has_sparse or not has_dense:
                 self._n_sparse += nrows
             self._masks.clear()          # row slices of cached filters are stale on every rank
-            self._mask_ids.clear()
-            self._dev_masks.clear()
             sparse_err = None
             if hi > lo:
                 piece_csr = None if csr is None else (csr[0][lo:hi + 1], csr[1], csr[2])
                 b0 = self.local._n
                 _, _, sparse_err = self.local.add(None if d is None else d[lo:hi], piece_csr, hi - lo)
                 self.local.rows_of[0][b0:] = np.arange(base + lo, base + hi, dtype=np.int64)   # global rows of the block
-            out = (base, base + nrows, sparse_err)
-        except Exception as e:
-            err = e
+            return base, base + nrows, sparse_err
+
+        out, err = self._guarded(my_part)
         try:
             self._status(err)
         except Exception as e:
             # the row numbers [base, base + nrows) are taken on every rank whatever failed: the caller keeps its payload
             # columns aligned with them (the failing rank's block stays a hole no search returns)
-            base = out[0] if err is None else (self._n_rows if has_dense or not has_sparse else self._n_sparse) - nrows
             raise PartialAppend(base, base + nrows, e) from e
         return out
 
@@ -433,144 +536,115 @@ class CollectiveShardSet:
             self.local.finalize()
             return
         with self._lock:
-            self._control(self.OP_FLUSH)
-            self._flush_collective()
+            self._control(wire.OP_FLUSH)
 
-    def _flush_collective(self):
-        err = None
-        try:
-            self.local.finalize()
-        except Exception as e:
-            err = e
-        self._status(err)
+    def _op_flush(self, f, pkt):
+        self._status(self._guarded(self.local.finalize)[1])
 
     def save(self, path_of_shard) -> None:
         """Every rank writes its shard to path_of_shard(rank) (rank 0 calls it; the paths travel in the control packet)."""
         with self._lock:
-            paths = "\n".join(path_of_shard(r) for r in range(self.world)).encode("utf-8")
-            self._control(self.OP_SAVE, (), paths)
-            self._save_collective(paths)
+            self._control(wire.OP_SAVE, blob="\n".join(path_of_shard(r) for r in range(self.world)).encode("utf-8"))
 
-    def _save_collective(self, paths: bytes):
-        err = None
-        try:
-            mine = paths.decode("utf-8").split("\n")[self.rank]
+    def _op_save(self, f, pkt):
+        def my_part():
+            mine = wire.payload(pkt).tobytes().decode("utf-8").split("\n")[self.rank]
             self.local.save(lambda s: mine)
-        except Exception as e:
-            err = e
-        self._status(err)
+        self._status(self._guarded(my_part)[1])
 
     def row_maps(self):
         """The global rows every rank's shard holds, in rank order (rank 0 calls it: one gather)."""
         with self._lock:
-            self._control(self.OP_ROWMAPS)
-            return self._rowmaps_collective()
+            return self._control(wire.OP_ROWMAPS)
 
-    def _rowmaps_collective(self):
+    def _op_rowmaps(self, f, pkt):
         rows = self._global_rows()
         parts = [None] * self.world if self.rank == 0 else None
         self.n_collectives += 1
         self.dist.gather_object(rows, parts, dst=0, group=self.group)
         return [np.asarray(r, dtype=np.int64) for r in parts] if self.rank == 0 else None
 
-    # ------------------------------------------------------------------ protocol
-    def _bcast(self, t):
-        self.n_collectives += 1
-        self.dist.broadcast(t, src=0, group=self.group)
-        return t
+    def stop_workers(self):
+        with self._lock:
+            self._control(wire.OP_STOP)
 
-    def _pack_round(self, dense_q, sparse_queries, k: int, drop: float, keep):
-        """rank 0: the whole round as one byte packet (numpy); raises BEFORE any collective if something is wrong."""
-        Bd = 0 if dense_q is None else int(dense_q.shape[0])
-        Bs = 0 if sparse_queries is None else len(sparse_queries)
-        parts, dim = [], 0
-        if Bd:
-            dense_q = np.ascontiguousarray(dense_q, dtype=np.float32)
-            dim = dense_q.shape[1]
-            parts.append(dense_q.view(np.uint8).reshape(-1))
-        nnz = 0
-        if Bs:
-            ptr = np.zeros(Bs + 1, dtype=np.int64)
-            for b, (qi, _) in enumerate(sparse_queries):
-                ptr[b + 1] = ptr[b] + len(qi)
-            nnz = int(ptr[-1])
-            idx = np.concatenate([np.asarray(qi, np.int32) for qi, _ in sparse_queries]) if nnz else np.zeros(0, np.int32)
-            val = np.concatenate([np.asarray(qv, np.float32) for _, qv in sparse_queries]) if nnz else np.zeros(0, np.float32)
-            if idx.shape != val.shape:
-                raise ValueError("sparse query indices/values length mismatch")
-            parts += [ptr.view(np.uint8), idx.view(np.uint8), val.view(np.uint8)]
-        mask_id, mask_new, mask_bytes = self._mask_for(keep)
-        hdr = np.zeros(self.HEADER, dtype=np.int64)
-        hdr[:10] = [self.OP_ROUND, Bd, Bs, k, dim, nnz, int(np.array([drop], dtype=np.float64).view(np.int64)[0]), mask_id,
-                    mask_new, 0 if mask_bytes is None else mask_bytes.size]
-        body = np.concatenate([hdr.view(np.uint8)] + parts) if parts else hdr.view(np.uint8)
-        if body.size > self.PACKET_BYTES:
-            raise ValueError(f"a round of {Bd} dense + {Bs} sparse queries needs {body.size} bytes; the packet holds {self.PACKET_BYTES}")
-        return body, mask_bytes
+    def _op_stop(self, f, pkt):
+        self._serving = False
+        if self._side is not None:
+            self._side.shutdown(wait=False)
+            self._side = None
 
-    def _send_packet(self, body: Optional[np.ndarray], whole: bool = False):
-        """ONE broadcast of the fixed-size packet; returns its bytes as numpy on every rank."""
-        t = self.torch
-        if self.rank == 0:
-            host = np.zeros(self.PACKET_BYTES, dtype=np.uint8)
-            host[: body.size] = body
-            self._packet.copy_(t.from_numpy(host))
-        self._bcast(self._packet)
-        if self.rank == 0:
-            return host
-        hdr = self._packet[: self.HEADER * 8].cpu().numpy().view(np.int64)   # then only the bytes the round uses
-        if int(hdr[0]) != self.OP_ROUND:                                      # a control packet: header + its blob
-            return self._packet[: self.HEADER * 8 + int(hdr[self.HEADER - 1])].cpu().numpy()
-        need = self.HEADER * 8 + int(hdr[1]) * int(hdr[4]) * 4 + (int(hdr[2]) + 1) * 8 * (1 if hdr[2] else 0) + int(hdr[5]) * 8
-        return self._packet[: min(need, self.PACKET_BYTES)].cpu().numpy()
+    # ------------------------------------------------------------------ ranks > 0
+    def serve(self):
+        """Answer rank 0's packets until it sends OP_STOP."""
+        self._serving = True
+        while self._serving:
+            self._dispatch(None)
 
-    def _mask_slice(self, hdr, mask_bytes_rank0):
+    # ------------------------------------------------------------------ search rounds
+    def round(self, dense_q: Optional[np.ndarray], sparse_queries, k: int, drop_ratio: float = 0.0, keep: Optional[np.ndarray] = None):
+        """One round = one broadcast + one gather: dense_q [Bd, dim] and / or Bs sparse queries, all with the same k and
+        filter -> ((dense ids, scores) | None, (sparse ids, scores) | None), global rows, merged over the ranks.  Raises
+        BEFORE any collective if the round cannot be packed."""
+        fields = dict(Bd=0, Bs=0, k=k, dim=0, nnz=0, drop=drop_ratio)
+        ptr = idx = val = None
+        if dense_q is not None:
+            dense_q = np.ascontiguousarray(np.atleast_2d(dense_q), dtype=np.float32)
+            fields.update(Bd=dense_q.shape[0], dim=dense_q.shape[1] if dense_q.shape[0] else 0)
+        if sparse_queries is not None and len(sparse_queries):
+            ptr, idx, val = csr_of_queries(sparse_queries)
+            fields.update(Bs=len(sparse_queries), nnz=idx.size)
+        sections = [a for a in (ptr, dense_q if fields["Bd"] else None, idx, val) if a is not None]   # 8-byte items first
+        with self._lock:
+            mask_id, mask_new, mask_bytes = self._masks.lookup(keep)
+            body = wire.pack(wire.OP_ROUND, {**fields, **wire.mask_fields(mask_id, mask_new, mask_bytes)}, sections, self.PACKET_BYTES)
+            return self._dispatch(body, mask_bytes=mask_bytes)
+
+    def search_dense(self, q: np.ndarray, k: int, keep: Optional[np.ndarray] = None):
+        return self.round(q, None, k, 0.0, keep)[0]
+
+    def search_sparse(self, queries, k: int, drop_ratio: float = 0.0, keep: Optional[np.ndarray] = None):
+        return self.round(None, list(queries), k, drop_ratio, keep)[1]
+
+    def _mask_slice(self, f, mask_bytes_rank0):
         """This rank's boolean slice of the round's filter (None = no filter); receives a new mask if the round carries one."""
         t = self.torch
-        mask_id, mask_new, mask_len = int(hdr[7]), int(hdr[8]), int(hdr[9])
-        if mask_id == 0:
+        if f.mask_id == 0:
             return None
-        if mask_new:
-            buf = t.from_numpy(mask_bytes_rank0).to(self.dev) if self.rank == 0 else t.empty(mask_len, dtype=t.uint8, device=self.dev)
+        if f.mask_new:
+            buf = t.from_numpy(mask_bytes_rank0).to(self.dev) if self.rank == 0 else t.empty(f.mask_len, dtype=t.uint8, device=self.dev)
             bits = np.unpackbits(self._bcast(buf).cpu().numpy(), bitorder="little").astype(bool)
             rows = self._global_rows()
             if rows.size and bits.size <= int(rows.max()):
                 raise ValueError(f"filter mask covers {bits.size} rows, this rank holds rows up to {int(rows.max()) + 1}")
-            if len(self._masks) >= self.MAX_MASKS:
-                self._masks.pop(next(iter(self._masks)))
-            self._masks[mask_id] = bits[rows]
-        return self._masks[mask_id]
+            self._masks.put(f.mask_id, bits[rows])
+        return self._masks.get(f.mask_id)
 
-    def _local_round(self, pkt: np.ndarray, hdr, keep_local):
-        """Run this rank's part of a round -> int64 [2 + n_mod * B * k * 2]: status, then ids and score bits per modality."""
-        Bd, Bs, k, dim, nnz = (int(x) for x in hdr[1:6])
-        drop = float(np.array([hdr[6]], dtype=np.int64).view(np.float64)[0])
-        off = self.HEADER * 8
+    def _local_round(self, f, pkt: np.ndarray, keep_local):
+        """Run this rank's part of a round -> [(ids, scores)] per modality in the round, global rows."""
+        s = wire.Sections(pkt)
         out = []
         dense_job = None
-        if Bd:
-            q = pkt[off: off + Bd * dim * 4].view(np.float32).reshape(Bd, dim)
-            off += Bd * dim * 4
+        if f.Bs:
+            ptr = s.take(f.Bs + 1, np.int64)
+        if f.Bd:
+            q = s.take(f.Bd * f.dim, np.float32).reshape(f.Bd, f.dim)
             # the slice object itself when it fits: the local ShardSet keeps a filter's packed (device) mask by identity
             kd = None if keep_local is None else (keep_local if keep_local.size == self.local.num_rows else keep_local[: self.local.num_rows])
-            if Bs:   # both modalities in the round: the dense search runs beside the sparse one (ctypes releases the GIL)
+            if f.Bs:   # both modalities in the round: the dense search runs beside the sparse one (ctypes releases the GIL)
                 if self._side is None:
                     self._side = ThreadPoolExecutor(max_workers=1, thread_name_prefix="round-dense-")
-                dense_job = self._side.submit(self.local.search_dense, q, k, kd)
+                dense_job = self._side.submit(self.local.search_dense, q, f.k, kd)
                 out.append(None)
             else:
-                out.append(self.local.search_dense(q, k, kd))
-        if Bs:
-            ptr = pkt[off: off + (Bs + 1) * 8].view(np.int64)
-            off += (Bs + 1) * 8
-            idx = pkt[off: off + nnz * 4].view(np.int32)
-            off += nnz * 4
-            val = pkt[off: off + nnz * 4].view(np.float32)
-            queries = [(idx[ptr[b]:ptr[b + 1]], val[ptr[b]:ptr[b + 1]]) for b in range(Bs)]
+                out.append(self.local.search_dense(q, f.k, kd))
+        if f.Bs:
+            idx, val = s.take(f.nnz, np.int32), s.take(f.nnz, np.float32)
+            queries = [(idx[ptr[b]:ptr[b + 1]], val[ptr[b]:ptr[b + 1]]) for b in range(f.Bs)]
             ks = None if keep_local is None else (keep_local if keep_local.size == self.local.num_sparse_rows
                                                   else keep_local[: self.local.num_sparse_rows])
             try:
-                out.append(self.local.search_sparse(queries, k, drop, ks))
+                out.append(self.local.search_sparse(queries, f.k, f.drop, ks))
             finally:
                 if dense_job is not None:   # never leave the side thread running into the next round
                     dense_err = dense_job.exception()
@@ -579,69 +653,28 @@ class CollectiveShardSet:
                     raise dense_err
                 out[0] = dense_job.result()
         if self.local_ids:
-            rows = self.local.rows_of[0]
-            out = [(np.where(li >= 0, rows[np.maximum(li, 0)] if rows.size else -1, -1).astype(np.int64), sc) for li, sc in out]
+            out = [(to_global(li, self.local.rows_of[0]), sc) for li, sc in out]
         return out
 
-    def _round(self, body, mask_bytes):
-        """Both sides of a round after rank 0 has packed it.  Returns the merged lists on rank 0."""
+    def _op_round(self, f, pkt, mask_bytes=None):
+        """Every rank's part of a search round after rank 0 has packed it.  Returns the merged lists on rank 0."""
         t = self.torch
-        pkt = self._send_packet(body)
-        hdr = pkt[: self.HEADER * 8].view(np.int64)
-        if int(hdr[0]) == self.OP_STOP:
-            return False
-        if int(hdr[0]) == self.OP_HYBRID:
-            return self._hybrid_round(pkt, hdr, mask_bytes)
-        if int(hdr[0]) != self.OP_ROUND:     # a worker picked up a control operation of rank 0
-            op = int(hdr[0])
-            if op == self.OP_ADD:
-                self._add_collective(int(hdr[1]), int(hdr[2]), bool(hdr[3]), bool(hdr[4]), int(hdr[5]))
-            elif op == self.OP_FLUSH:
-                self._flush_collective()
-            elif op == self.OP_SAVE:
-                self._save_collective(pkt[self.HEADER * 8: self.HEADER * 8 + int(hdr[self.HEADER - 1])].tobytes())
-            elif op == self.OP_ROWMAPS:
-                self._rowmaps_collective()
-            return True
-        Bd, Bs, k = int(hdr[1]), int(hdr[2]), int(hdr[3])
-        n_vals = (Bd + Bs) * k
-        mine = np.zeros(2 + 2 * n_vals, dtype=np.int64)
-        mine[2: 2 + n_vals] = -1
-        err = None
-        try:
-            lists = self._local_round(pkt, hdr, self._mask_slice(hdr, mask_bytes))
-            ids = np.concatenate([li.reshape(-1) for li, _ in lists]).astype(np.int64)
-            sc = np.concatenate([s.reshape(-1) for _, s in lists]).astype(np.float32)
-            mine[2: 2 + n_vals] = ids
-            mine[2 + n_vals:] = sc.view(np.int32).astype(np.int64)
-        except Exception as e:   # still reach the gather: nobody may be left waiting in a collective
-            err = e
-            mine[0] = 1
-        mine_t = t.from_numpy(mine).to(self.dev)
+        n_vals = (f.Bd + f.Bs) * f.k
+        mine, err = self._guarded(lambda: wire.pack_lists(self._local_round(f, pkt, self._mask_slice(f, mask_bytes)), n_vals))
+        mine_t = t.from_numpy(wire.pack_lists(None, n_vals) if err is not None else mine).to(self.dev)
         parts = [t.empty_like(mine_t) for _ in range(self.world)] if self.rank == 0 else None
         self.n_collectives += 1
         self.dist.gather(mine_t, parts, dst=0, group=self.group)
-        if err is not None and self.rank != 0:
-            import logging
-            logging.getLogger(__name__).error("rank %d failed its part of a search round: %s", self.rank, err)
+        self._log_worker_failure("its part of a search round", err)
         if self.rank != 0:
-            return True
+            return None
         if err is not None:
             raise err
-        parts = [p.cpu().numpy() for p in parts]
-        bad = [r for r, p in enumerate(parts) if p[0] != 0]
+        bad, lists = wire.unpack_lists([p.cpu().numpy() for p in parts], (f.Bd, f.Bs), f.k)
         if bad:
             raise RuntimeError(f"search round failed on rank(s) {bad}")
-        out, o = [], 2
-        for B, asc in ((Bd, self.local.dense_ascending), (Bs, False)):
-            if not B:
-                out.append(None)
-                continue
-            ids = [p[o: o + B * k].reshape(B, k) for p in parts]
-            scs = [p[2 + n_vals + (o - 2): 2 + n_vals + (o - 2) + B * k].astype(np.int32).view(np.float32).reshape(B, k) for p in parts]
-            out.append(merge_lists(ids, scs, k, asc))
-            o += B * k
-        return out
+        return [None if m is None else merge_lists(m[0], m[1], f.k, asc)
+                for m, asc in zip(lists, (self.local.dense_ascending, False))]
 
     # ------------------------------------------------------------------ hybrid rounds on the device
     @property
@@ -649,8 +682,7 @@ class CollectiveShardSet:
         """The device form of a hybrid round needs real shards whose handles return GLOBAL rows (pre-built contiguous
         shards: the engine merges the ranks' lists by the ids the scans wrote) and the sparse modality."""
         h = self.local.first
-        return (self.hybrid_on_device and not self.local_ids and getattr(h, "_h", None) is not None
-                and getattr(h, "sparse_dim", 0) > 0)
+        return self.hybrid_on_device and not self.local_ids and is_native_handle(h) and getattr(h, "sparse_dim", 0) > 0
 
     def round_hybrid(self, dense_q: np.ndarray, sparse_queries, top_k: int, drop_ratio: float, rrf_k: int,
                      weights: np.ndarray, keep: Optional[np.ndarray] = None):
@@ -674,108 +706,38 @@ class CollectiveShardSet:
         w = np.zeros((B, 3), dtype=np.float64)
         w[:, :2] = np.asarray(weights, dtype=np.float64).reshape(B, 2)
         with self._lock:
-            mask_id, mask_new, mask_bytes = self._mask_for(keep)
-            # 8-byte items first: every view of the packet is aligned for its type
-            blob = np.concatenate([ptr.astype(np.int64).view(np.uint8), w.view(np.uint8).reshape(-1), dense_q.view(np.uint8).reshape(-1),
-                                   idx.astype(np.int32).view(np.uint8), val.astype(np.float32).view(np.uint8)])
-            hdr = np.zeros(self.HEADER, dtype=np.int64)
-            hdr[:11] = [self.OP_HYBRID, B, int(top_k), dim, int(idx.size), int(rrf_k), 0, mask_id, mask_new,
-                        0 if mask_bytes is None else mask_bytes.size, int(max_nnz)]
-            hdr[self.HEADER - 1] = blob.size
-            body = np.concatenate([hdr.view(np.uint8), blob])
-            if body.size > self.PACKET_BYTES:
-                raise ValueError(f"a hybrid round of {B} requests needs {body.size} bytes; the packet holds {self.PACKET_BYTES}")
-            return self._round(body, mask_bytes)
+            mask_id, mask_new, mask_bytes = self._masks.lookup(keep)
+            fields = dict(B=B, top_k=top_k, dim=dim, nnz=idx.size, rrf_k=rrf_k, max_nnz=max_nnz,
+                          **wire.mask_fields(mask_id, mask_new, mask_bytes))
+            body = wire.pack(wire.OP_HYBRID, fields, [ptr.astype(np.int64), w, dense_q, idx.astype(np.int32), val.astype(np.float32)],
+                             self.PACKET_BYTES)
+            return self._dispatch(body, mask_bytes=mask_bytes)
 
-    def _hybrid_round(self, pkt: np.ndarray, hdr, mask_bytes):
+    def _op_hybrid(self, f, pkt: np.ndarray, mask_bytes=None):
         """Every rank's part of a hybrid round (collective: the engine's all-gather is inside)."""
         from .engine import EngineConfig, HybridSearchEngine
         t = self.torch
-        B, top_k, dim, nnz, rrf_k = (int(x) for x in hdr[1:6])
-        max_nnz = int(hdr[10])
-        keep_local = self._mask_slice(hdr, mask_bytes)
+        keep_local = self._mask_slice(f, mask_bytes)
         dev = t.device("cuda", self.local.first.device)
-        eng = self._hyb_engines.get((top_k, rrf_k))
+        eng = self._hyb_engines.get((f.top_k, f.rrf_k))
         if eng is None:
             if len(self._hyb_engines) >= 8:
                 self._hyb_engines.clear()
-            eng = self._hyb_engines[(top_k, rrf_k)] = HybridSearchEngine(
-                self.local.first, EngineConfig(top_k=top_k, rrf_k=rrf_k, enable_reranking=False), process_group=self.group, device=str(dev))
-        # the operands are views of the packet where it lives on the device (nccl), uploads of its host copy otherwise
-        src = self._packet if self._packet.is_cuda else t.from_numpy(pkt[: self.HEADER * 8 + int(hdr[self.HEADER - 1])]).to(dev)
-        o = self.HEADER * 8
-
-        def view(n_bytes, dtype):
-            nonlocal o
-            v = src[o: o + n_bytes].view(dtype)
-            o += n_bytes
-            return v
-        ptr = view((B + 1) * 8, t.int64)
-        wq = view(B * 24, t.float64).view(B, 3)
-        q = view(B * dim * 4, t.float32).view(B, dim)
-        idx = view(nnz * 4, t.int32)
-        val = view(nnz * 4, t.float32)
-        mask = None
-        if keep_local is not None:
-            mid = int(hdr[7])
-            mask = self._dev_masks.get(mid)
-            if mask is None:
-                if len(self._dev_masks) >= self.MAX_MASKS:
-                    self._dev_masks.pop(next(iter(self._dev_masks)))
-                mask = self._dev_masks[mid] = t.from_numpy(np.packbits(keep_local, bitorder="little")).to(dev)
+            eng = self._hyb_engines[(f.top_k, f.rrf_k)] = HybridSearchEngine(
+                self.local.first, EngineConfig(top_k=f.top_k, rrf_k=f.rrf_k, enable_reranking=False), process_group=self.group, device=str(dev))
+        # the operands are views of the packet where it lives on the device (nccl), of an upload of its host copy otherwise
+        s = wire.Sections(self._packet if self._packet.is_cuda else t.from_numpy(pkt).to(dev))
+        ptr = s.take(f.B + 1, np.int64)
+        wq = s.take(f.B * 3, np.float64).view(f.B, 3)
+        q = s.take(f.B * f.dim, np.float32).view(f.B, f.dim)
+        idx, val = s.take(f.nnz, np.int32), s.take(f.nnz, np.float32)
+        mask = None if keep_local is None else self._masks.device(
+            f.mask_id, lambda bits: t.from_numpy(np.packbits(bits, bitorder="little")).to(dev))
         with t.cuda.device(dev):
-            b = eng.search(q, (ptr, idx, val, max_nnz), rowmask=mask, weights=wq)
+            b = eng.search(q, (ptr, idx, val, f.max_nnz), rowmask=mask, weights=wq)
             t.cuda.current_stream(dev).synchronize()      # the packet may be rewritten by the next round
         if self.rank != 0:
-            return True
+            return None
         out = {k: b[k].cpu().numpy() for k in ("fused_ids", "fused_scores", "fused_methods", "fused_n", "list_ids", "list_scores")}
         out["proven"] = b["agg_flags"].cpu().numpy().min(axis=0) == 1
         return out
-
-    def _mask_for(self, keep):
-        """rank 0: (mask id, 1 if the mask must travel with this round, its packed bytes or None) of a filter array."""
-        if keep is None:
-            return 0, 0, None
-        ent = self._mask_ids.get(id(keep))
-        if ent is not None and ent[0] in self._masks:
-            return ent[0], 0, None
-        mask_id = self._next_mask_id
-        self._next_mask_id += 1
-        self._mask_ids = {key: v for key, v in self._mask_ids.items() if v[0] in self._masks}
-        self._mask_ids[id(keep)] = (mask_id, keep)
-        return mask_id, 1, np.packbits(np.asarray(keep, dtype=bool), bitorder="little")
-
-    # ------------------------------------------------------------------ rank 0
-    def round(self, dense_q: Optional[np.ndarray], sparse_queries, k: int, drop_ratio: float = 0.0, keep: Optional[np.ndarray] = None):
-        """One round = one broadcast + one gather: dense_q [Bd, dim] and / or Bs sparse queries, all with the same k and
-        filter -> ((dense ids, scores) | None, (sparse ids, scores) | None), global rows, merged over the ranks."""
-        if dense_q is not None:
-            dense_q = np.ascontiguousarray(np.atleast_2d(dense_q), dtype=np.float32)
-        with self._lock:
-            body, mask_bytes = self._pack_round(dense_q, sparse_queries, int(k), float(drop_ratio), keep)   # may raise: no collective yet
-            return self._round(body, mask_bytes)
-
-    def search_dense(self, q: np.ndarray, k: int, keep: Optional[np.ndarray] = None):
-        return self.round(q, None, k, 0.0, keep)[0]
-
-    def search_sparse(self, queries, k: int, drop_ratio: float = 0.0, keep: Optional[np.ndarray] = None):
-        return self.round(None, list(queries), k, drop_ratio, keep)[1]
-
-    def stop_workers(self):
-        with self._lock:
-            hdr = np.zeros(self.HEADER, dtype=np.int64)
-            hdr[0] = self.OP_STOP
-            self._send_packet(hdr.view(np.uint8))
-        self._close_side()
-
-    def _close_side(self):
-        if self._side is not None:
-            self._side.shutdown(wait=False)
-            self._side = None
-
-    # ------------------------------------------------------------------ ranks > 0
-    def serve(self):
-        """Answer rank 0's rounds until it sends OP_STOP."""
-        while self._round(None, None):
-            pass
-        self._close_side()

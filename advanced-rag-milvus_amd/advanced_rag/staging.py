@@ -27,6 +27,20 @@ def dense_rows_device(payloads, dev, dim):
     return torch.from_numpy(dense_rows_host(payloads, dim)).to(dev)
 
 
+def csr_of_queries(queries):
+    """B sparse queries [(indices, values)] -> their raw CSR (indptr int64 [B + 1], idx int32 [nnz], val float32 [nnz]), the
+    entries as they came: nothing dropped, nothing sorted (engine.pack_sparse_queries does both, for the device forms)."""
+    indptr = np.zeros(len(queries) + 1, dtype=np.int64)
+    for b, (qi, qv) in enumerate(queries):
+        if len(qi) != len(qv):
+            raise ValueError(f"sparse query {b} has {len(qi)} indices and {len(qv)} values")
+        indptr[b + 1] = indptr[b] + len(qi)
+    if not indptr[-1]:
+        return indptr, np.zeros(0, np.int32), np.zeros(0, np.float32)
+    return (indptr, np.concatenate([np.asarray(qi, dtype=np.int32) for qi, _ in queries]),
+            np.concatenate([np.asarray(qv, dtype=np.float32) for _, qv in queries]))
+
+
 def upload_sparse(packed, dev):
     """engine.pack_sparse_queries' (indptr, idx, val, max_nnz) -> the three arrays as tensors on `dev`, max_nnz as it came."""
     import torch

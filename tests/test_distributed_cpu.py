@@ -21,15 +21,15 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _corpus(n=5003, d=48, V=400, nnz=9, B=6):
+def _corpus(n=5003, d=48, V=400, nnz=9, B=6, tie=(100, 4000)):
     rng = np.random.default_rng(99)
     X = rng.standard_normal((n, d)).astype(np.float16)
-    X[100] = X[4000]  # an exact cross-shard tie
+    X[tie[0]] = X[tie[1]]  # an exact cross-shard tie
     idx = np.sort(np.argpartition(rng.random((n, V)), nnz - 1, axis=1)[:, :nnz], axis=1).astype(np.int32).reshape(-1)
     val = np.abs(rng.standard_normal(n * nnz)).astype(np.float32)
     ptr = np.arange(n + 1, dtype=np.int64) * nnz
     Q = rng.standard_normal((B, d)).astype(np.float32)
-    Q[0] = X[100].astype(np.float32)
+    Q[0] = X[tie[0]].astype(np.float32)
     SQ = [(np.sort(rng.choice(V, 30, replace=False)).astype(np.int32), np.abs(rng.standard_normal(30)).astype(np.float32))
           for _ in range(B)]
     return X, ptr, idx, val, Q, SQ
@@ -473,3 +473,113 @@ def test_collective_ingest_fills_two_ranks_and_matches_the_single_shard_answer(t
     assert set(ret.keys()) == {0, 1}
     assert ret[0][0] + ret[1][0] == 5003 - 250          # rank 1 refused its 250-row block of the 500-row batch
     assert ret[0][1] + ret[1][1] == 5003 - 250
+
+
+class _FailingOracleShard(_OracleShard):
+    """An oracle shard that refuses ONE search: the next one asked for `fail_k` results."""
+    fail_k = None
+
+    def _maybe_fail(self, k):
+        if k == self.fail_k:
+            self.fail_k = None
+            raise MemoryError(f"the shard of rows [{self.lo}, {self.hi}) is out of memory")
+
+    def search_dense(self, q, k, mask=None):
+        self._maybe_fail(k)
+        return super().search_dense(q, k, mask)
+
+    def search_sparse(self, queries, k, drop, mask=None):
+        self._maybe_fail(k)
+        return super().search_sparse(queries, k, drop, mask)
+
+
+def _rounds_worker(rank, world, port, ret):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "advanced-rag-milvus_amd"))
+    import oracle
+    from advanced_rag import MilvusIndexManager
+    from advanced_rag.engine import shard_range
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        V, k = 120, 10
+        X, ptr, idx, val, Q, SQ = _corpus(n=389, V=V, nnz=7, B=3, tie=(100, 300))
+        n = X.shape[0]
+        lo, hi = shard_range(n, rank, world, align=64)
+        shard = _FailingOracleShard(X, ptr, idx, val, lo, hi, V)
+        if rank == 1:
+            shard.fail_k = 37
+        mgr = MilvusIndexManager(semantic_dim=X.shape[1], sparse_dim=V, connect=False)
+        mgr._native = None
+        mgr.attach_shards([shard], rows_of=[np.arange(hi - lo)], synthetic_rows=n, process_group=True, first_row=lo)
+        if rank != 0:
+            mgr.serve()
+            ret[rank] = shard.fail_k is None        # it did refuse that one search
+            return
+        cs = mgr._main
+
+        def same(got, want):
+            assert np.array_equal(got[0], want[0]), (got[0], want[0])
+            assert np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
+
+        def check(dense_q, sparse_q, keep=None, kk=k, collectives=None):
+            packed = None if keep is None else np.packbits(keep, bitorder="little")
+            c0 = cs.n_collectives
+            d, s = cs.round(dense_q, sparse_q, kk, 0.2, keep)
+            if collectives is not None:
+                assert cs.n_collectives - c0 == collectives, (cs.n_collectives - c0, collectives)
+            assert (d is None) == (dense_q is None) and (s is None) == (not sparse_q)
+            if d is not None:
+                same(d, oracle.dense_search(X, np.atleast_2d(dense_q), kk, oracle.COSINE, packed))
+            if s is not None:
+                same(s, oracle.sparse_search(ptr, idx, val, sparse_q, kk, 0.2, packed))
+
+        # ---- the shapes a round takes
+        none = (np.zeros(0, np.int32), np.zeros(0, np.float32))
+        check(Q, None, collectives=2)                           # dense only
+        check(None, SQ, collectives=2)                          # sparse only
+        check(Q, SQ, collectives=2)                             # both
+        check(Q[:1], SQ[:1])                                    # B = 1
+        check(Q[0], None)                                       # ... handed in as one row
+        check(Q[:2], [SQ[0], none, SQ[2]])                      # one query of the batch is empty
+        check(Q[:1], [none, none], collectives=2)               # nnz = 0
+        check(None, [none])
+        assert cs.round(Q[:1], None, k)[0][0][0, :2].tolist() == [100, 300]      # the cross-rank tie: lower row first
+
+        # ---- more filters than the ranks keep: the oldest masks leave first, on every rank alike
+        rng = np.random.default_rng(3)
+        keeps = [rng.random(n) < 0.5 for _ in range(cs.MAX_MASKS + 2)]
+        for keep in keeps:
+            check(Q, SQ, keep, collectives=3)                   # + the mask
+        check(Q, SQ, keeps[0], collectives=3)                   # rolled out: it travels again
+        check(Q, SQ, keeps[-1], collectives=2)                  # still there
+        check(Q, SQ, keeps[3], collectives=2)
+        check(None, SQ, keeps[1], collectives=3)                # the second oldest went with the first
+
+        # ---- a rank whose search fails: everybody reaches the gather, rank 0 raises, the next round is whole again
+        c0 = cs.n_collectives
+        with pytest.raises(RuntimeError, match=r"rank\(s\) \[1\]"):
+            cs.round(Q, None, 37)
+        assert cs.n_collectives - c0 == 2
+        check(Q, None, kk=37, collectives=2)
+        shard.fail_k = 38
+        with pytest.raises(MemoryError, match=r"rows \[0, "):     # rank 0's own error, not a report about others
+            cs.round(Q, SQ, 38, 0.2, keeps[-1])
+        check(Q, SQ, keeps[-1], kk=38, collectives=2)
+        mgr.stop_workers()
+        ret[rank] = True
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(120)
+def test_collective_rounds_mask_roll_over_and_failing_ranks():
+    """The protocol of CollectiveShardSet.round() on two gloo ranks of oracle shards, held to the whole-corpus oracle bit
+    for bit: every shape of a round (one modality, both, B = 1, empty sparse queries), more distinct filters than the
+    mask cache keeps (an evicted mask travels again, a live one does not), and a rank whose shard fails one search."""
+    world = 2
+    port = _free_port()
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_rounds_worker, args=(world, port, ret), nprocs=world, join=True)
+    assert dict(ret) == {0: True, 1: True}

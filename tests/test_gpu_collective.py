@@ -20,15 +20,17 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _corpus(n=20011, d=64, V=500, nnz=9, B=5):
+def _corpus(n=20011, d=64, V=500, nnz=9, B=5, tie=(300, 15000)):
     rng = np.random.default_rng(5)
     X = rng.standard_normal((n, d)).astype(np.float16)
-    X[300] = X[15000]                       # an exact tie across the ranks
+    if tie:
+        X[tie[0]] = X[tie[1]]               # an exact tie across the ranks
     idx = np.sort(np.argpartition(rng.random((n, V)), nnz - 1, axis=1)[:, :nnz], axis=1).astype(np.int32).reshape(-1)
     val = np.abs(rng.standard_normal(n * nnz)).astype(np.float32)
     ptr = np.arange(n + 1, dtype=np.int64) * nnz
     Q = rng.standard_normal((B, d)).astype(np.float32)
-    Q[0] = X[300].astype(np.float32)
+    if tie:
+        Q[0] = X[tie[0]].astype(np.float32)
     SQ = [(np.sort(rng.choice(V, 30, replace=False)).astype(np.int32), np.abs(rng.standard_normal(30)).astype(np.float32))
           for _ in range(B)]
     return X, ptr, idx, val, Q, SQ
@@ -232,6 +234,87 @@ def test_hybrid_rounds_on_the_device_across_two_gpu_processes(gpu):
     mgr = mp.Manager()
     ret = mgr.dict()
     mp.spawn(_hybrid_worker, args=(world, port, ret), nprocs=world, join=True)
+    assert dict(ret) == {0: True, 1: True}
+
+
+def _hybrid_rounds_worker(rank, world, port, ret):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "advanced-rag-milvus_amd"))
+    import torch.distributed as dist
+
+    import oracle
+    from advanced_rag import MilvusIndexManager, _native
+    from advanced_rag.engine import pack_sparse_queries, shard_range
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        top_k, kp, drop, rrf_k, w = 20, 40, 0.2, 60, (0.7, 0.3)
+        X, ptr, idx, val, Q, SQ = _corpus(n=1500, B=3, tie=None)
+        n, d, V = X.shape[0], X.shape[1], 500
+        # 31 terms in the first query: 25 + 24 + 24 survive the drop, so the packet's idx / val sections have an odd length
+        # for B = 1 and for B = 3
+        SQ[0] = (np.arange(0, 31 * 16, 16, dtype=np.int32), np.linspace(0.5, 2.0, 31).astype(np.float32))
+        assert all(pack_sparse_queries(SQ[:B], drop, V)[1].size % 2 == 1 for B in (1, 3))
+        lo, hi = shard_range(n, rank, world, align=64)
+        h = _native.ShardHandle(d, _native.HR_F16, _native.HR_METRIC_COSINE, V, 0)
+        h.set_row_offset(lo)
+        h.add_dense(X[lo:hi])
+        h.add_sparse(ptr[lo:hi + 1] - ptr[lo], idx[ptr[lo]:ptr[hi]], val[ptr[lo]:ptr[hi]])
+        h.finalize()
+        mgr = MilvusIndexManager(semantic_dim=d, sparse_dim=V, connect=False, dtype="float16")
+        mgr._connect()
+        mgr.attach_shards([h], rows_of=[np.arange(hi - lo)], synthetic_rows=n, process_group=True, first_row=lo)
+        cs = mgr._main
+        assert cs.supports_hybrid_round
+        if rank != 0:
+            mgr.serve()
+            ret[rank] = True
+            return
+
+        def check(B, keep, collectives):
+            packed = None if keep is None else np.packbits(keep, bitorder="little")
+            c0 = cs.n_collectives
+            res = cs.round_hybrid(Q[:B], SQ[:B], top_k, drop, rrf_k, np.tile(w, (B, 1)), keep)
+            assert cs.n_collectives - c0 == collectives, (cs.n_collectives - c0, collectives)
+            # one entry past the lists: no tie at the cut and no short list, so the oracle alone says every list is provable
+            di, ds = oracle.dense_search(X, Q[:B], kp + 1, oracle.COSINE, packed)
+            si, ss = oracle.sparse_search(ptr, idx, val, SQ[:B], kp + 1, drop, packed)
+            for li, ls in ((di, ds), (si, ss)):
+                assert (li[:, kp] >= 0).all() and (ls[:, kp - 1] != ls[:, kp]).all()
+            assert res["proven"].shape == (B,) and res["proven"].all()
+            assert np.array_equal(res["list_ids"][0], di[:, :kp]) and np.array_equal(res["list_ids"][1], si[:, :kp])
+            for q in range(B):
+                fi, fs, _ = oracle.rrf(di[q, :kp], si[q, :kp], (), w[0], w[1], 0.2, rrf_k)
+                assert res["fused_n"][q] == top_k and np.array_equal(res["fused_ids"][q], fi[:top_k]), (B, q)
+                assert np.allclose(res["fused_scores"][q], fs[:top_k], rtol=1e-12)
+
+        rng = np.random.default_rng(11)
+        keeps = [rng.random(n) < 0.5 for _ in range(cs.MAX_MASKS + 2)]
+        check(3, None, 1)
+        check(1, None, 1)
+        for i, keep in enumerate(keeps):
+            check((1, 3)[i % 2], keep, 2)           # the packet + the new mask
+        check(3, keeps[0], 2)                       # rolled out of every rank's cache (slice and device copy): travels again
+        check(1, keeps[-1], 1)                      # still there
+        check(3, keeps[-1], 1)
+        mgr.stop_workers()
+        ret[rank] = True
+    finally:
+        dist.destroy_process_group()
+
+
+@pytest.mark.timeout(300)
+def test_hybrid_rounds_read_the_packet_and_roll_masks_over_on_the_device(gpu):
+    """round_hybrid() on two processes sharing the card: the operands of hr_search_hybrid_dev are typed views of the packet
+    where it was uploaded (B = 1 and 3, idx / val sections of odd length), more distinct filters pass than the mask cache
+    keeps and the first comes back.  Every fused list and both modality lists equal the oracle chain (dense 2k, sparse 2k,
+    RRF) over the whole corpus, every list is proven, a new mask costs one extra collective and a known one none."""
+    import torch.multiprocessing as mp
+    world = 2
+    port = _free_port()
+    mgr = mp.Manager()
+    ret = mgr.dict()
+    mp.spawn(_hybrid_rounds_worker, args=(world, port, ret), nprocs=world, join=True)
     assert dict(ret) == {0: True, 1: True}
 
 
