@@ -19,6 +19,7 @@
 #include <shared_mutex>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -40,39 +41,45 @@ namespace {
 
 thread_local std::string g_last_error;  // for calls without a handle
 
+// A device allocation and its owner: freed when the buffer goes out of scope, movable, never copied.  hipFree needs the
+// buffer's device to be current (every holder is destroyed under a DeviceGuard) and waits for work that still uses it.
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    // Exactly `bytes` (no growth slack), whatever the buffer held before; empty on failure.
+    hipError_t alloc_exact(size_t bytes) {
+        release();
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) cap = bytes;
+        else p = nullptr;
         return e;
     }
+    hipError_t ensure(size_t bytes) { return bytes <= cap ? hipSuccess : alloc_exact(bytes + bytes / 8 + 256); }
     // Capacity for `bytes`, KEEPING the first `keep` bytes (device-to-device copy on stream s into a buffer 1.5x the
     // size asked for, so that repeated appends cost amortised O(appended bytes)).
     hipError_t grow(size_t bytes, size_t keep, hipStream_t s) {
         if (bytes <= cap) return hipSuccess;
-        void* np_ = nullptr;
-        const size_t want = bytes + bytes / 2 + 256;
-        hipError_t e = hipMalloc(&np_, want);
-        if (e != hipSuccess) return e;
-        if (p && keep) {
-            e = hipMemcpyAsync(np_, p, keep, hipMemcpyDeviceToDevice, s);
+        DevBuf nb;
+        hipError_t e = nb.alloc_exact(bytes + bytes / 2 + 256);
+        if (e == hipSuccess && p && keep) {
+            e = hipMemcpyAsync(nb.p, p, keep, hipMemcpyDeviceToDevice, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) {
-                (void)hipFree(np_);
-                return e;
-            }
         }
-        if (p) (void)hipFree(p);
-        p = np_;
-        cap = want;
-        return hipSuccess;
+        if (e == hipSuccess) *this = std::move(nb);
+        return e;
     }
     void release() {
         if (p) (void)hipFree(p);
@@ -85,35 +92,31 @@ struct DevBuf {
 enum Phase { PH_PREP = 0, PH_SCAN, PH_GSEL, PH_REFINE, PH_TOPK, PH_SSCAN, PH_SGSEL, PH_SREFINE, PH_STOPK, PH_FINISH, PH_COUNT };
 static_assert(PH_COUNT == HR_N_PHASES, "phase table and ABI out of step");
 
-struct Workspace {
-    std::mutex mu;                 // held while one call enqueues: calls sharing a workspace must not interleave their kernels
-    int users = 0;                 // calls that hold or wait for this workspace (guarded by hr_index::pool_mu): never pruned while > 0
+// A workspace's streams and events.  A base of Workspace so that they outlive its buffers: members are destroyed first,
+// and the hipFree of a buffer waits for the work that still uses it, on these streams included.
+struct WorkspaceQueues {
     hipStream_t stream = nullptr;  // own stream (host-form calls)
     hipStream_t side = nullptr;    // side stream + events of hr_search_hybrid_dev
     hipEvent_t ev_scan = nullptr, ev_side = nullptr;
+    ~WorkspaceQueues() {
+        if (stream) (void)hipStreamDestroy(stream);
+        if (side) (void)hipStreamDestroy(side);
+        if (ev_scan) (void)hipEventDestroy(ev_scan);
+        if (ev_side) (void)hipEventDestroy(ev_side);
+    }
+};
+
+// `delete w`, with the workspace's device current, is the whole release.
+struct Workspace : WorkspaceQueues {
+    std::mutex mu;                 // held while one call enqueues: calls sharing a workspace must not interleave their kernels
+    int users = 0;                 // calls that hold or wait for this workspace (guarded by hr_index::pool_mu): never pruned while > 0
     struct Workspace* sparse_ws = nullptr;  // private buffers of the sparse chain when it runs concurrently
     DevBuf qfrag, qn2, gmax, bmax, cand, acut, cscore, crow, flags, qscale, qeps, qfloor, pq_n, pq_idx, pq_w;
     DevBuf qcoef, dqeps;   // L2 shards: per query slot, the row term's coefficient 1 / |q| and the per-query error term
     DevBuf d_q, d_ids, d_scores, d_mask;          // host-form staging
     DevBuf d_qptr, d_qidx, d_qval;                // sparse query staging
     DevBuf f_ids, f_out_ids, f_out_scores, f_out_meth, f_n;  // hr_fuse_rrf staging
-    void release() {
-        for (DevBuf* b : {&qcoef, &dqeps, &qfrag, &qn2, &gmax, &bmax, &qscale, &qeps, &qfloor, &pq_n, &pq_idx, &pq_w, &cand, &acut, &cscore, &crow, &flags, &d_q, &d_ids, &d_scores,
-                          &d_mask, &d_qptr, &d_qidx, &d_qval, &f_ids, &f_out_ids, &f_out_scores, &f_out_meth, &f_n})
-            b->release();
-        if (stream) (void)hipStreamDestroy(stream);
-        stream = nullptr;
-        if (side) (void)hipStreamDestroy(side);
-        side = nullptr;
-        if (ev_scan) (void)hipEventDestroy(ev_scan);
-        if (ev_side) (void)hipEventDestroy(ev_side);
-        ev_scan = ev_side = nullptr;
-        if (sparse_ws) {
-            sparse_ws->release();
-            delete sparse_ws;
-            sparse_ws = nullptr;
-        }
-    }
+    ~Workspace() { delete sparse_ws; }
 };
 
 struct EventSpan {
@@ -171,6 +174,18 @@ struct hr_index {
     std::vector<hipEvent_t> event_pool;
     mutable std::mutex err_mu;
     mutable std::string err;
+
+    // Deleted with the device current and idle (hr_destroy; hr_create's failure path).  The workspaces go before the
+    // handle's own stream; the buffers above free themselves after this body.
+    ~hr_index() {
+        for (Workspace* w : free_ws) delete w;
+        for (auto& kv : stream_ws) delete kv.second;
+        for (auto& pair : slot_ws)
+            for (Workspace* w : pair) delete w;
+        for (auto& sp : spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
+        for (hipEvent_t e : event_pool) (void)hipEventDestroy(e);
+        if (ingest_stream) (void)hipStreamDestroy(ingest_stream);
+    }
 };
 
 namespace {
@@ -284,10 +299,7 @@ Workspace* ws_for_stream(hr_index* h, void* stream, StreamWs& out) {
         }
         if (w) ++w->users;
     }
-    for (Workspace* old : pruned) {
-        old->release();  // hipFree waits for the work that still uses the buffers
-        delete old;
-    }
+    for (Workspace* old : pruned) delete old;  // hipFree waits for the work that still uses the buffers
     if (!w) return nullptr;
     out.h = h;
     out.w = w;
@@ -436,6 +448,13 @@ hipError_t with_constant(int v, F f) {
     return e;
 }
 
+// f(STORE{}) for the element type of a dense store of `dtype`: _Float16 or float
+template <typename F>
+auto with_store(int dtype, F f) {
+    if (dtype == HR_F16) return f(_Float16{});
+    return f(float{});
+}
+
 // The two generic kernels: STORE x L2 here, NRB x G below.
 template <typename STORE, bool L2>
 hipError_t launch_scan_generic(const ScanPlan& p, const ScanArgs& a) {
@@ -452,11 +471,11 @@ hipError_t launch_scan(const ScanPlan& p, const ScanArgs& a) {
         case SCAN_Q64: return with_constant<1, 4>(p.NRB, [&](auto nrb) { return launch_scan_q64<decltype(nrb)::value>(a); });
         case SCAN_GEMM: return with_constant<1, 4>(p.NRB, [&](auto nrb) { return launch_scan_gemm<decltype(nrb)::value>(a); });
         case SCAN_LDS:
-        case SCAN_BIGQ: {
-            const bool f16 = a.h->dtype == HR_F16;
-            if (p.l2) return f16 ? launch_scan_generic<_Float16, true>(p, a) : launch_scan_generic<float, true>(p, a);
-            return f16 ? launch_scan_generic<_Float16, false>(p, a) : launch_scan_generic<float, false>(p, a);
-        }
+        case SCAN_BIGQ:
+            return with_store(a.h->dtype, [&](auto store) {
+                using STORE = decltype(store);
+                return p.l2 ? launch_scan_generic<STORE, true>(p, a) : launch_scan_generic<STORE, false>(p, a);
+            });
         default: return hipErrorInvalidValue;
     }
 }
@@ -927,35 +946,48 @@ int search_host(hr_index* h, int B, int k, int64_t hr_index::*rows, const uint8_
     return HR_OK;
 }
 
-int grow_dense(hr_index* h, int64_t need_rows) {
-    if (need_rows <= h->cap_rows) return HR_OK;
-    int64_t new_cap = std::max<int64_t>(round_up(need_rows, kSuperRows),
-                                        round_up(h->cap_rows + h->cap_rows / 2, kSuperRows));
-    new_cap = std::max<int64_t>(new_cap, 1024);
-    DevBuf nt, ns, nn;
-    const size_t tb = tile_bytes_for_rows(h, new_cap);
-    if (hipMalloc(&nt.p, tb) != hipSuccess || hipMalloc(&ns.p, (size_t)new_cap * 4) != hipSuccess ||
-        hipMalloc(&nn.p, (size_t)new_cap * 8) != hipSuccess) {
+// ---- the dense store's capacity ------------------------------------------------------------------------------------
+// The one rule.  Capacity is a whole number of super-groups (kSuperRows).  hr_reserve on an EMPTY handle gets exactly
+// what it asks for, one super-group at least.  Every other growth — an append, and hr_reserve on a handle that already
+// has a store — takes at least 1.5x the old capacity and at least 1024 rows, so that repeated appends copy amortised
+// O(rows appended).
+int64_t dense_capacity_for(int64_t cap_rows, int64_t need_rows, bool reserving) {
+    const int64_t need = round_up(need_rows, kSuperRows);
+    if (reserving && cap_rows == 0) return std::max<int64_t>(need, kSuperRows);
+    return std::max<int64_t>({need, round_up(cap_rows + cap_rows / 2, kSuperRows), 1024});
+}
+
+// Gives the dense store `rows` rows of capacity (a multiple of kSuperRows, not below cap_rows): the old contents in
+// front, zeros behind them — every scan and snapshot expects zeros beyond n_rows.  The handle changes only after the
+// last call that can fail; until then the new buffers belong to this scope, and an early return frees them.
+int set_dense_capacity(hr_index* h, int64_t rows) {
+    DevBuf tiles, scale, norm2;
+    const size_t tb = tile_bytes_for_rows(h, rows);
+    if (tiles.alloc_exact(tb) != hipSuccess || scale.alloc_exact((size_t)rows * 4) != hipSuccess ||
+        norm2.alloc_exact((size_t)rows * 8) != hipSuccess) {
         (void)hipGetLastError();
-        nt.cap = ns.cap = nn.cap = 1;
-        nt.release(); ns.release(); nn.release();
-        return fail(h, HR_ENOMEM, "cannot allocate dense shard for %lld rows (%zu bytes)", (long long)new_cap, tb);
+        return fail(h, HR_ENOMEM, "cannot allocate dense shard for %lld rows (%zu bytes)", (long long)rows, tb);
     }
-    nt.cap = tb; ns.cap = (size_t)new_cap * 4; nn.cap = (size_t)new_cap * 8;
     hipStream_t s = h->ingest_stream;
-    HIP_TRY(h, hipMemsetAsync(nt.p, 0, tb, s));
-    HIP_TRY(h, hipMemsetAsync(ns.p, 0, ns.cap, s));
-    HIP_TRY(h, hipMemsetAsync(nn.p, 0, nn.cap, s));
+    HIP_TRY(h, hipMemsetAsync(tiles.p, 0, tiles.cap, s));
+    HIP_TRY(h, hipMemsetAsync(scale.p, 0, scale.cap, s));
+    HIP_TRY(h, hipMemsetAsync(norm2.p, 0, norm2.cap, s));
     if (h->cap_rows > 0) {
-        HIP_TRY(h, hipMemcpyAsync(nt.p, h->tiles.p, tile_bytes_for_rows(h, h->cap_rows), hipMemcpyDeviceToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(ns.p, h->scale.p, (size_t)h->cap_rows * 4, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(h, hipMemcpyAsync(nn.p, h->norm2.p, (size_t)h->cap_rows * 8, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(tiles.p, h->tiles.p, tile_bytes_for_rows(h, h->cap_rows), hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(scale.p, h->scale.p, (size_t)h->cap_rows * 4, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(h, hipMemcpyAsync(norm2.p, h->norm2.p, (size_t)h->cap_rows * 8, hipMemcpyDeviceToDevice, s));
     }
     HIP_TRY(h, hipStreamSynchronize(s));
-    h->tiles.release(); h->scale.release(); h->norm2.release();
-    h->tiles = nt; h->scale = ns; h->norm2 = nn;
-    h->cap_rows = new_cap;
+    h->tiles = std::move(tiles);
+    h->scale = std::move(scale);
+    h->norm2 = std::move(norm2);
+    h->cap_rows = rows;
     return HR_OK;
+}
+
+int grow_dense(hr_index* h, int64_t need_rows) {
+    if (need_rows <= h->cap_rows) return HR_OK;
+    return set_dense_capacity(h, dense_capacity_for(h->cap_rows, need_rows, false));
 }
 
 constexpr unsigned long long kNoBadRow = ~0ull;
@@ -983,19 +1015,13 @@ int add_dense_impl(hr_index* h, const SRC* rows, int64_t n, bool src_on_device, 
         }
         const int64_t threads = m * kchunks;
         const unsigned blocks = (unsigned)((threads + 255) / 256);
-        if (h->dtype == HR_F16) {
-            if constexpr (std::is_same<SRC, float>::value)
-                hipLaunchKernelGGL((tile_rows_kernel<_Float16, float>), dim3(blocks), dim3(256), 0, s, src, m,
-                                   (int)h->dim, h->KT, h->n_rows + r0, h->tiles.as<chunk_t>(), r0, d_bad);
-            else
-                hipLaunchKernelGGL((tile_rows_kernel<_Float16, _Float16>), dim3(blocks), dim3(256), 0, s,
-                                   reinterpret_cast<const _Float16*>(src), m, (int)h->dim, h->KT, h->n_rows + r0,
-                                   h->tiles.as<chunk_t>(), r0, d_bad);
-        } else {
-            hipLaunchKernelGGL((tile_rows_kernel<float, float>), dim3(blocks), dim3(256), 0, s,
-                               reinterpret_cast<const float*>(src), m, (int)h->dim, h->KT, h->n_rows + r0,
-                               h->tiles.as<chunk_t>(), r0, d_bad);
-        }
+        with_store(h->dtype, [&](auto store) {
+            using STORE = decltype(store);
+            // an fp32 store is only ever fed fp32 rows (hr_add_dense_raw*); an fp16 store takes fp32 or fp16 ones
+            using IN = std::conditional_t<std::is_same<STORE, float>::value, float, SRC>;
+            hipLaunchKernelGGL((tile_rows_kernel<STORE, IN>), dim3(blocks), dim3(256), 0, s, reinterpret_cast<const IN*>(src), m,
+                               (int)h->dim, h->KT, h->n_rows + r0, h->tiles.as<chunk_t>(), r0, d_bad);
+        });
         HIP_TRY(h, hipGetLastError());
         if (!src_on_device) HIP_TRY(h, hipStreamSynchronize(s));  // staging buffer is reused
     }
@@ -1107,16 +1133,13 @@ int build_sparse(hr_index* h) {
     hipLaunchKernelGGL(sparse_count_kernel, dim3(doc_blocks), dim3(256), 0, s, h->s_indptr.as<int64_t>(),
                        h->s_idx.as<int32_t>(), doc0, n, V1, h->rt_off.as<unsigned int>());
     HIP_TRY(h, hipGetLastError());
-    struct Scratch {  // released on every return path
-        DevBuf totals, cursor;
-        ~Scratch() { totals.release(); cursor.release(); }
-    } tmp;
-    HIP_TRY(h, tmp.totals.ensure((size_t)dirty * 8));
+    DevBuf totals, cursor;  // scratch of this call
+    HIP_TRY(h, totals.ensure((size_t)dirty * 8));
     hipLaunchKernelGGL(sparse_scan_offsets_kernel, dim3((unsigned)dirty), dim3(1024), 0, s,
-                       h->rt_off.as<unsigned int>(), V1, r_d, tmp.totals.as<unsigned long long>());
+                       h->rt_off.as<unsigned int>(), V1, r_d, totals.as<unsigned long long>());
     HIP_TRY(h, hipGetLastError());
     std::vector<unsigned long long> ht(dirty);
-    HIP_TRY(h, hipMemcpyAsync(ht.data(), tmp.totals.p, (size_t)dirty * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(ht.data(), totals.p, (size_t)dirty * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipStreamSynchronize(s));
     h->h_range_base.resize(n_ranges + 1);
     h->h_range_dense.resize(n_ranges);
@@ -1128,8 +1151,8 @@ int build_sparse(hr_index* h) {
     HIP_TRY(h, h->post.grow((size_t)h->h_range_base[n_ranges] * 4 + 64, (size_t)h->h_range_base[r_d] * 4, s));
     HIP_TRY(h, h->range_base.grow((size_t)(n_ranges + 1) * 8, 0, s));
     HIP_TRY(h, hipMemcpyAsync(h->range_base.p, h->h_range_base.data(), (size_t)(n_ranges + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(h, tmp.cursor.ensure((size_t)dirty * V1 * 4));
-    HIP_TRY(h, hipMemcpyAsync(tmp.cursor.p, h->rt_off.as<unsigned int>() + r_d * V1, (size_t)dirty * V1 * 4,
+    HIP_TRY(h, cursor.ensure((size_t)dirty * V1 * 4));
+    HIP_TRY(h, hipMemcpyAsync(cursor.p, h->rt_off.as<unsigned int>() + r_d * V1, (size_t)dirty * V1 * 4,
                               hipMemcpyDeviceToDevice, s));
     // dense runs (sparse.h) hold one fp16 weight per doc of the range: every word of the rebuilt blocks starts as "absent /
     // absent"; sparse runs and their fillers are overwritten whole by the two kernels below
@@ -1140,12 +1163,12 @@ int build_sparse(hr_index* h) {
     }
     // (the fill kernel permutes docs inside aligned blocks of 128: its grid covers whole blocks)
     hipLaunchKernelGGL(sparse_fill_kernel, dim3((unsigned)((round_up(n - doc0, 128) + 255) / 256)), dim3(256), 0, s, h->s_indptr.as<int64_t>(),
-                       h->s_idx.as<int32_t>(), h->s_val.as<float>(), doc0, n, V1, tmp.cursor.as<unsigned int>(),
+                       h->s_idx.as<int32_t>(), h->s_val.as<float>(), doc0, n, V1, cursor.as<unsigned int>(),
                        h->rt_off.as<unsigned int>(), h->range_base.as<int64_t>(), h->post.as<uint32_t>());
     HIP_TRY(h, hipGetLastError());
     const int64_t pairs = dirty * h->sparse_dim;
     hipLaunchKernelGGL(sparse_pad_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s,
-                       h->rt_off.as<unsigned int>(), tmp.cursor.as<unsigned int>(), V1, r_d, n_ranges,
+                       h->rt_off.as<unsigned int>(), cursor.as<unsigned int>(), V1, r_d, n_ranges,
                        h->range_base.as<int64_t>(), h->post.as<uint32_t>());
     HIP_TRY(h, hipGetLastError());
     HIP_TRY(h, hipStreamSynchronize(s));
@@ -1205,12 +1228,12 @@ int hr_create(int device, int64_t dim, int dtype, int metric, int64_t sparse_dim
     uint32_t idle[256];  // idle postings of scan lane l: weight 0, accumulator pad word l
     for (unsigned l = 0; l < 256; ++l) idle[l] = filler_posting(l / 4);
     if (hipStreamCreateWithFlags(&h->ingest_stream, hipStreamNonBlocking) != hipSuccess ||
-        h->max_norm.ensure(4) != hipSuccess || hipMemset(h->max_norm.p, 0, 4) != hipSuccess ||
-        h->bad_row.ensure(8) != hipSuccess || hipMemset(h->bad_row.p, 0xFF, 8) != hipSuccess ||
-        h->idle_post.ensure(sizeof idle) != hipSuccess ||
+        h->max_norm.alloc_exact(4) != hipSuccess || hipMemset(h->max_norm.p, 0, 4) != hipSuccess ||
+        h->bad_row.alloc_exact(8) != hipSuccess || hipMemset(h->bad_row.p, 0xFF, 8) != hipSuccess ||
+        h->idle_post.alloc_exact(sizeof idle) != hipSuccess ||
         hipMemcpy(h->idle_post.p, idle, sizeof idle, hipMemcpyHostToDevice) != hipSuccess) {
         int rc = fail(nullptr, HR_EHIP, "device %d initialisation failed: %s", device, hipGetErrorString(hipGetLastError()));
-        delete h;
+        delete h;  // under dg: the handle frees what it got so far on its own device
         return rc;
     }
     *out = h;
@@ -1219,21 +1242,8 @@ int hr_create(int device, int64_t dim, int dtype, int metric, int64_t sparse_dim
 
 void hr_destroy(hr_index* h) {
     if (!h) return;
-    {
-        DeviceGuard dg(h->device);
-        (void)hipDeviceSynchronize();
-        for (Workspace* w : h->free_ws) { w->release(); delete w; }
-        for (auto& kv : h->stream_ws) { kv.second->release(); delete kv.second; }
-        for (auto& pair : h->slot_ws)
-            for (Workspace* w : pair)
-                if (w) { w->release(); delete w; }
-        for (auto& sp : h->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
-        for (hipEvent_t e : h->event_pool) (void)hipEventDestroy(e);
-        for (DevBuf* b : {&h->tiles, &h->scale, &h->norm2, &h->max_norm, &h->stage, &h->bad_row, &h->s_indptr, &h->s_idx, &h->s_val,
-                          &h->rt_off, &h->range_base, &h->post, &h->idle_post})
-            b->release();
-        if (h->ingest_stream) (void)hipStreamDestroy(h->ingest_stream);
-    }
+    DeviceGuard dg(h->device);  // outlives the handle: every buffer is freed on its own device
+    (void)hipDeviceSynchronize();
     delete h;
 }
 
@@ -1251,31 +1261,7 @@ int hr_reserve(hr_index* h, int64_t n_rows) {
     std::unique_lock<std::shared_mutex> lk(h->rw);
     DeviceGuard dg(h->device);
     if (n_rows <= h->cap_rows) return HR_OK;
-    // exact-size allocation: temporarily defeat the 1.5x growth policy
-    const int64_t want = round_up(n_rows, kSuperRows);
-    const int64_t saved = h->cap_rows;
-    if (saved == 0) {
-        h->cap_rows = 0;
-        DevBuf nt, ns, nn;
-        const size_t tb = tile_bytes_for_rows(h, std::max<int64_t>(want, kSuperRows));
-        const int64_t rows = std::max<int64_t>(want, kSuperRows);
-        if (hipMalloc(&nt.p, tb) != hipSuccess || hipMalloc(&ns.p, (size_t)rows * 4) != hipSuccess ||
-            hipMalloc(&nn.p, (size_t)rows * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            nt.cap = ns.cap = nn.cap = 1;
-            nt.release(); ns.release(); nn.release();
-            return fail(h, HR_ENOMEM, "cannot reserve %lld rows", (long long)n_rows);
-        }
-        nt.cap = tb; ns.cap = (size_t)rows * 4; nn.cap = (size_t)rows * 8;
-        HIP_TRY(h, hipMemsetAsync(nt.p, 0, tb, h->ingest_stream));
-        HIP_TRY(h, hipMemsetAsync(ns.p, 0, ns.cap, h->ingest_stream));
-        HIP_TRY(h, hipMemsetAsync(nn.p, 0, nn.cap, h->ingest_stream));
-        HIP_TRY(h, hipStreamSynchronize(h->ingest_stream));
-        h->tiles = nt; h->scale = ns; h->norm2 = nn;
-        h->cap_rows = rows;
-        return HR_OK;
-    }
-    return grow_dense(h, want);
+    return set_dense_capacity(h, dense_capacity_for(h->cap_rows, n_rows, true));
 }
 
 int hr_add_dense(hr_index* h, const float* rows, int64_t n) {
@@ -1335,15 +1321,11 @@ int hr_finalize(hr_index* h) {
     if (h->dim > 0 && h->n_normed < h->n_rows) {
         const int64_t n = h->n_rows - h->n_normed;
         const unsigned blocks = (unsigned)((n + 255) / 256);
-        const int metric = h->metric;
-        if (h->dtype == HR_F16)
-            hipLaunchKernelGGL((row_norms_kernel<_Float16>), dim3(blocks), dim3(256), 0, s, h->tiles.as<chunk_t>(),
-                               h->KT, h->n_normed, n, metric, h->norm2.as<double>(), h->scale.as<float>(),
+        with_store(h->dtype, [&](auto store) {
+            hipLaunchKernelGGL((row_norms_kernel<decltype(store)>), dim3(blocks), dim3(256), 0, s, h->tiles.as<chunk_t>(), h->KT,
+                               h->n_normed, n, h->metric, h->norm2.as<double>(), h->scale.as<float>(),
                                h->max_norm.as<unsigned int>());
-        else
-            hipLaunchKernelGGL((row_norms_kernel<float>), dim3(blocks), dim3(256), 0, s, h->tiles.as<chunk_t>(), h->KT,
-                               h->n_normed, n, metric, h->norm2.as<double>(), h->scale.as<float>(),
-                               h->max_norm.as<unsigned int>());
+        });
         HIP_TRY(h, hipGetLastError());
         unsigned int bits = 0;
         HIP_TRY(h, hipMemcpyAsync(&bits, h->max_norm.p, 4, hipMemcpyDeviceToHost, s));
@@ -1391,6 +1373,36 @@ int stream_in(hr_index* h, FILE* f, void* dptr, size_t bytes) {
     return HR_OK;
 }
 
+// The snapshot's body, the one definition of its layout: the sections that follow the header, in file order, each the
+// device buffer it is read from (written to, on load) and its length.  Dense shards with rows hold tiles, scale and
+// norm2 up to the header's row capacity; sparse shards with rows hold the device CSR.
+struct Section {
+    void* dev;
+    size_t bytes;
+};
+struct Sections {
+    Section s[6];
+    int n_dense = 0, n = 0;  // s[0 .. n_dense) dense, s[n_dense .. n) sparse
+    Sections(const hr_index* h, const SnapHeader& hd) {
+        if (hd.dim > 0 && hd.n_rows > 0) {
+            s[n++] = {h->tiles.p, tile_bytes_for_rows(h, hd.cap_rows)};
+            s[n++] = {h->scale.p, (size_t)hd.cap_rows * 4};
+            s[n++] = {h->norm2.p, (size_t)hd.cap_rows * 8};
+        }
+        n_dense = n;
+        if (hd.n_sparse > 0) {
+            s[n++] = {h->s_indptr.p, (size_t)(hd.n_sparse + 1) * 8};
+            s[n++] = {h->s_idx.p, (size_t)hd.nnz * 4};
+            s[n++] = {h->s_val.p, (size_t)hd.nnz * 4};
+        }
+    }
+    int64_t bytes() const {
+        int64_t t = 0;
+        for (int i = 0; i < n; ++i) t += (int64_t)s[i].bytes;
+        return t;
+    }
+};
+
 int save_to(hr_index* h, FILE* f) {
     SnapHeader hd{};
     std::memcpy(hd.magic, kSnapMagic, 8);
@@ -1399,21 +1411,16 @@ int save_to(hr_index* h, FILE* f) {
     hd.cap_rows = h->dim ? round_up(std::max<int64_t>(h->n_rows, 1), kSuperRows) : 0;
     hd.n_sparse = h->n_sparse; hd.nnz = h->nnz_csr; hd.row_offset = h->row_offset;
     hd.max_row_norm = h->max_row_norm; hd.max_sparse_abs = h->max_sparse_abs;
-    const bool dense = h->dim > 0 && h->n_rows > 0;
-    hd.file_bytes = (int64_t)sizeof hd + (dense ? (int64_t)tile_bytes_for_rows(h, hd.cap_rows) + hd.cap_rows * 12 : 0) +
-                    (h->n_sparse > 0 ? (h->n_sparse + 1) * 8 + hd.nnz * 8 : 0);
+    const Sections body(h, hd);  // the CSR too is read back from the device: the host keeps no copy of it
+    hd.file_bytes = (int64_t)sizeof hd + body.bytes();
     if (fwrite(&hd, sizeof hd, 1, f) != 1) return fail(h, HR_EINVAL, "snapshot write failed");
-    if (dense) {
-        HR_TRY(stream_out(h, f, h->tiles.p, tile_bytes_for_rows(h, hd.cap_rows)));
-        HR_TRY(stream_out(h, f, h->scale.p, (size_t)hd.cap_rows * 4));
-        HR_TRY(stream_out(h, f, h->norm2.p, (size_t)hd.cap_rows * 8));
-    }
-    if (h->n_sparse > 0) {  // the CSR is read back from the device: the host keeps no copy of it
-        HR_TRY(stream_out(h, f, h->s_indptr.p, (size_t)(h->n_sparse + 1) * 8));
-        HR_TRY(stream_out(h, f, h->s_idx.p, (size_t)hd.nnz * 4));
-        HR_TRY(stream_out(h, f, h->s_val.p, (size_t)hd.nnz * 4));
-    }
+    for (int i = 0; i < body.n; ++i) HR_TRY(stream_out(h, f, body.s[i].dev, body.s[i].bytes));
     return HR_OK;
+}
+
+// A handle's error, for a caller that never gets the handle (hr_load destroys it on failure)
+int forward_error(const hr_index* h, int rc, const char* prefix = "") {
+    return fail(nullptr, rc, "%s%s", prefix, hr_last_error(h));
 }
 }  // namespace
 
@@ -1466,13 +1473,17 @@ static int load_impl(const char* path, int device, hr_index** out) {
     if (h->KT != hd.KT) return fail(nullptr, HR_EINVAL, "snapshot tile layout (KT=%d) differs from this build (KT=%d)", hd.KT, h->KT);
     h->row_offset = hd.row_offset;
     DeviceGuard dg(device);
-    if (hd.dim > 0 && hd.n_rows > 0) {
+    const bool dense = hd.dim > 0 && hd.n_rows > 0;
+    if (dense) {
         if (hd.cap_rows != round_up(hd.n_rows, kSuperRows)) return fail(nullptr, HR_EINVAL, "corrupt snapshot header (row capacity)");
         HR_TRY(hr_reserve(h, hd.cap_rows));
-        int rc = stream_in(h, file.f, h->tiles.p, tile_bytes_for_rows(h, hd.cap_rows));
-        if (rc == HR_OK) rc = stream_in(h, file.f, h->scale.p, (size_t)hd.cap_rows * 4);
-        if (rc == HR_OK) rc = stream_in(h, file.f, h->norm2.p, (size_t)hd.cap_rows * 8);
-        if (rc != HR_OK) return fail(nullptr, rc, "%s", hr_last_error(h));
+    }
+    const Sections body(h, hd);
+    for (int i = 0; i < body.n_dense; ++i) {
+        const int rc = stream_in(h, file.f, body.s[i].dev, body.s[i].bytes);
+        if (rc != HR_OK) return forward_error(h, rc);
+    }
+    if (dense) {
         h->n_rows = h->n_normed = hd.n_rows;
         h->max_row_norm = hd.max_row_norm;
         unsigned int bits;
@@ -1482,22 +1493,24 @@ static int load_impl(const char* path, int device, hr_index** out) {
     }
     if (hd.n_sparse > 0) {
         if (hd.sparse_dim <= 0) return fail(nullptr, HR_EINVAL, "corrupt snapshot header (sparse rows without a sparse collection)");
-        // the file is not trusted: the CSR goes through the same checks as hr_add_sparse before any kernel indexes with it
-        std::vector<int64_t> ptr((size_t)hd.n_sparse + 1);
-        std::vector<int32_t> idx((size_t)hd.nnz);
-        std::vector<float> val((size_t)hd.nnz);
-        const bool ok = fread(ptr.data(), 8, ptr.size(), file.f) == ptr.size() &&
-                        fread(idx.data(), 4, idx.size(), file.f) == idx.size() &&
-                        fread(val.data(), 4, val.size(), file.f) == val.size();
+        // the file is not trusted: the CSR goes through the host and the same checks as hr_add_sparse before any kernel
+        // indexes with it (the sections name only its lengths here: the device CSR does not exist yet)
+        const Section* sp = body.s + body.n_dense;
+        std::vector<int64_t> ptr(sp[0].bytes / 8);
+        std::vector<int32_t> idx(sp[1].bytes / 4);
+        std::vector<float> val(sp[2].bytes / 4);
+        const bool ok = fread(ptr.data(), 1, sp[0].bytes, file.f) == sp[0].bytes &&
+                        fread(idx.data(), 1, sp[1].bytes, file.f) == sp[1].bytes &&
+                        fread(val.data(), 1, sp[2].bytes, file.f) == sp[2].bytes;
         if (!ok || ptr.front() != 0 || ptr.back() != hd.nnz)
             return fail(nullptr, HR_EINVAL, "snapshot truncated or corrupt (sparse section)");
         for (int64_t r = 0; r < hd.n_sparse; ++r)
             if (ptr[r + 1] < ptr[r] || ptr[r + 1] > hd.nnz) return fail(nullptr, HR_EINVAL, "snapshot corrupt (sparse row pointers)");
-        int rc = hr_add_sparse(h, ptr.data(), idx.data(), val.data(), hd.n_sparse);  // validates; recomputes max |weight|
-        if (rc != HR_OK) return fail(nullptr, rc, "snapshot corrupt (sparse section): %s", hr_last_error(h));
+        const int rc = hr_add_sparse(h, ptr.data(), idx.data(), val.data(), hd.n_sparse);  // validates; recomputes max |weight|
+        if (rc != HR_OK) return forward_error(h, rc, "snapshot corrupt (sparse section): ");
     }
-    int rc = hr_finalize(h);
-    if (rc != HR_OK) return fail(nullptr, rc, "%s", hr_last_error(h));
+    const int rc = hr_finalize(h);
+    if (rc != HR_OK) return forward_error(h, rc);
     guard.keep = true;
     *out = h;
     return HR_OK;
