@@ -108,6 +108,8 @@ _SIGNATURES = {
     "hr_rerank_linear_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int,
                                         _c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_int, _c.c_void_p,
                                         _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_mmr_select_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                     _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_add_layernorm_f16_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                             _c.c_int, _c.c_float, _c.c_void_p]),
     "hr_embed_layernorm_f16_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -419,6 +421,19 @@ def _raise_global(L, rc: int):
     if rc == 1:
         raise ValueError(msg)
     raise HbmRagError(rc, msg)
+
+
+def mmr_select_dev(d_ids: int, d_scores: int, d_n: int, B: int, k_in: int, d_tok_indptr: int, d_tok: int, tok_rows: int,
+                   first_row: int, d_lambda: int, k_out: int, d_out_pos: int, d_out_n: int, stream: int = 0):
+    """hr_mmr_select_dev: greedy MMR over a batch of fused lists (device pointers; 0 = NULL)."""
+    L = load_library()
+    rc = L.hr_mmr_select_dev(_vp(d_ids) if d_ids else None, _vp(d_scores) if d_scores else None, _vp(d_n) if d_n else None,
+                             B, k_in, _vp(d_tok_indptr) if d_tok_indptr else None, _vp(d_tok) if d_tok else None,
+                             tok_rows, first_row, _vp(d_lambda) if d_lambda else None, k_out,
+                             _vp(d_out_pos) if d_out_pos else None, _vp(d_out_n) if d_out_n else None,
+                             _vp(stream) if stream else None)
+    if rc != 0:
+        _raise_global(L, rc)
 
 
 def merge_topk_dev(d_scores: int, d_ids: int, n_lists: int, B: int, k_in: int, k_out: int, d_out_ids: int,

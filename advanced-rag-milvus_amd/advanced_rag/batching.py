@@ -13,7 +13,10 @@ could not prove exact are redone through the host form, which widens the candida
 A caller that has BOTH embeddings of a request in hand (HybridRetriever._retrieve_inner via
 MilvusIndexManager.hybrid_search) submits one "hybrid" request instead of two searches and a fusion: the batch runs as
 one `hr_search_hybrid_dev` (both scans, the fused finishing kernel) + one `hr_post_lists_dev` (RRF) — the engine's own
-step — and the caller gets the fused top-k with the per-modality scores in ONE round instead of two.
+step — and the caller gets the fused top-k with the per-modality scores in ONE round instead of two.  A request of a
+diversifying profile (MMR; only from a manager created with mmr_on_device=True) takes the same round with the WHOLE fused
+list kept (4 x top_k entries) and one `hr_mmr_select_dev` behind it on the same stream; lambda is a per-query operand, so
+profiles that differ only in lambda share the round.
 
 One worker thread per manager; the event loop never blocks on the GPU.
 """
@@ -123,9 +126,9 @@ class SearchCoalescer:
             # hundred microseconds for the other search of the same retrieve() (and for other callers) halves the collectives
             self.window_s = max(self.window_s, 250e-6)
         self.stats = {"rounds": 0, "requests": 0, "dense_launches": 0, "sparse_launches": 0, "fuse_launches": 0,
-                      "hybrid_launches": 0, "encode_launches": 0, "encoded_texts": 0, "max_batch_seen": 0, "redone_unproven": 0,
+                      "hybrid_launches": 0, "mmr_launches": 0, "encode_launches": 0, "encoded_texts": 0, "max_batch_seen": 0, "redone_unproven": 0,
                       "busy_s": 0.0}
-        self._engines: Dict[Tuple, Any] = {}   # hybrid engines per (top_k, rrf_k)
+        self._engines: Dict[Tuple, Any] = {}   # hybrid engines per (top_k, rrf_k, mmr)
         self._inflight: List[_Request] = []    # the requests of the round in progress (failed as a whole if the worker dies)
         self._outbox: Dict[Any, list] = {}     # event loop -> [(asyncio future, ok, value)] of the round in progress
 
@@ -304,7 +307,7 @@ class SearchCoalescer:
                     continue
                 drop = float(dict(params_key).get("drop_ratio_search", 0.0)) if r.kind == "sparse" else None
                 groups.setdefault((top_k, expr), {}).setdefault((r.kind, drop), []).append(r)
-            for (top_k, expr, drop, rrf_k), rs in hybrid.items():
+            for (top_k, expr, drop, rrf_k, _mmr), rs in hybrid.items():   # (MMR requests never get here: hybrid_search declines)
                 # both searches and the fusion of these requests as ONE collective round on the device (shards.round_hybrid)
                 for c0 in range(0, len(rs), 64):
                     chunk = rs[c0:c0 + 64]
@@ -404,15 +407,16 @@ class SearchCoalescer:
 
     # ------------------------------------------------------------------ hybrid (both searches + RRF of a request)
     def _enqueue_hybrid(self, torch, dev, stream, key, chunk):
-        top_k, expr, drop, rrf_k = key
+        top_k, expr, drop, rrf_k, mmr = key
         handle = self.mgr.collections["semantic_index"].handle.first
-        ekey = (top_k, rrf_k)
+        ekey = (top_k, rrf_k, mmr)
         eng = self._engines.get(ekey)
         if eng is None:
             if len(self._engines) >= 16:
                 self._engines.clear()
             eng = self._engines[ekey] = HybridSearchEngine(
-                handle, EngineConfig(top_k=top_k, rrf_k=rrf_k, enable_reranking=False), device=str(dev))
+                handle, EngineConfig(top_k=top_k, rrf_k=rrf_k, enable_reranking=False,
+                                     fused_k=4 * top_k if mmr else None), device=str(dev))   # MMR: two 2 * top_k lists, whole
         # the fusion weights are per REQUEST (a weight_adapter may pick them per query, reference retrieval.py:251-262):
         # they travel as a [B, 3] operand of the post kernel, so requests with different weights still share the round
         wq = torch.from_numpy(np.array([[r.payload[2], r.payload[3], 0.0] for r in chunk], dtype=np.float64)).to(dev)
@@ -428,8 +432,29 @@ class SearchCoalescer:
         self.stats["sparse_launches"] += 1
         # the engine reuses ONE buffer set per batch size: another group (or the next chunk of this one) with the same B
         # is enqueued before this round is read back, so the results are copied out here, in stream order
+        if mmr:
+            return {"b": self._mmr_select(torch, dev, stream, top_k, chunk, b), "keep": (q, d_sparse, mask, wq)}
         out = {k: b[k].clone() for k in ("fused_ids", "fused_scores", "fused_methods", "fused_n", "ids", "scores", "flags")}
         return {"b": out, "keep": (q, d_sparse, mask, wq)}
+
+    def _mmr_select(self, torch, dev, stream, top_k, chunk, b):
+        """HybridRetriever._mmr_diversify over the whole fused lists of the batch (hr_mmr_select_dev, same stream) -> the
+        buffers _scatter_hybrid reads, with fused_* = the selected entries in selection order and fused_n = their number."""
+        from . import _native as nat
+        B = len(chunk)
+        lam = torch.from_numpy(np.array([r.payload[4] for r in chunk], dtype=np.float64)).to(dev)
+        indptr, tok, rows = self.mgr._token_sets_on_device().tensors()
+        pos = torch.empty((B, top_k), dtype=torch.int32, device=dev)
+        n_sel = torch.empty((B,), dtype=torch.int32, device=dev)
+        nat.mmr_select_dev(b["fused_ids"].data_ptr(), b["fused_scores"].data_ptr(), b["fused_n"].data_ptr(), B,
+                           int(b["fused_ids"].shape[1]), indptr.data_ptr() if rows else 0, tok.data_ptr() if rows else 0,
+                           rows, 0, lam.data_ptr(), top_k, pos.data_ptr(), n_sel.data_ptr(), stream.cuda_stream)
+        self.stats["mmr_launches"] += 1
+        at = pos.clamp(min=0).to(torch.int64)      # (-1 padding lies beyond fused_n: never read)
+        out = {k: b[k].gather(1, at) for k in ("fused_ids", "fused_scores", "fused_methods")}
+        out.update(fused_n=n_sel, **{k: b[k].clone() for k in ("ids", "scores", "flags")})
+        out["keep"] = (lam, indptr, tok, pos)
+        return out
 
     def _scatter_hybrid(self, key, chunk, st):
         b = st["b"]

@@ -12,6 +12,10 @@ For filter expressions (filters.py / device_filters.py) a string column can hand
 prefix key per row (two big-endian uint64 words of the zero-padded UTF-8 bytes; UTF-8 byte order is code-point
 order): `key < key(v)` decides `s < v` for every row whose first 16 bytes differ from v's, and only the rows that tie
 on the prefix need the full strings.  Keys are built lazily, per column, on first use, and extended by later appends.
+
+For MMR diversification on the device (csrc/mmr.h) the `content` column can hand out its rows' TOKEN SETS
+(`TokenSetColumn`): the reference compares `set(content.lower().split())` of two hits; here every distinct token of the
+collection gets an int32 id and a row keeps its ids, sorted — built lazily as well, and never part of a snapshot.
 """
 from __future__ import annotations
 
@@ -178,6 +182,71 @@ class StringColumn:
         return out
 
 
+class TokenSetColumn:
+    """Append-only CSR over global rows: row r holds the sorted, unique int32 ids of `set(content.lower().split())`
+    (Python's own lower / split: Unicode case mapping and whitespace are the reference's, retrieval.py:495).  Ids come
+    from one dictionary per collection, token -> id in first-seen order: equal ids mean equal tokens (nothing is hashed).
+    Rows are tokenised once; an id, once given, never changes."""
+    MAX_TOKENS = (1 << 31) - 1     # ids are int32
+
+    def __init__(self):
+        self.ids: Dict[str, int] = {}
+        self._indptr = np.zeros(1, dtype=np.int64)
+        self._tok = np.empty(0, dtype=np.int32)
+        self._n = 0
+
+    def __len__(self) -> int:
+        return self._n
+
+    def extend(self, contents: Iterable[str]) -> None:
+        ids, rows, lens = self.ids, [], []
+        for text in contents:
+            row = []
+            for t in set(text.lower().split()):
+                i = ids.get(t)
+                if i is None:
+                    if len(ids) >= self.MAX_TOKENS:
+                        raise ValueError(f"more than {self.MAX_TOKENS} distinct tokens: token ids are int32")
+                    i = ids[t] = len(ids)
+                row.append(i)
+            row.sort()
+            rows.extend(row)
+            lens.append(len(row))
+        if not lens:
+            return
+        used = int(self._indptr[self._n])
+        self._tok = _grown(self._tok, used + len(rows))
+        self._tok[used: used + len(rows)] = rows
+        self._indptr = _grown(self._indptr, self._n + len(lens) + 1)
+        np.cumsum(lens, out=self._indptr[self._n + 1: self._n + len(lens) + 1])
+        self._indptr[self._n + 1: self._n + len(lens) + 1] += used
+        self._n += len(lens)
+
+    def sync(self, content: "StringColumn") -> "TokenSetColumn":
+        """Tokenise the rows of `content` this column does not hold yet."""
+        step = 1 << 16       # bounded temporaries
+        for a in range(self._n, len(content), step):
+            self.extend(content[a: min(len(content), a + step)])
+        return self
+
+    def indptr(self) -> np.ndarray:
+        """int64 [rows + 1] view (no copy)."""
+        return self._indptr[: self._n + 1]
+
+    def tokens(self) -> np.ndarray:
+        """int32 view of every row's ids, row after row (no copy)."""
+        return self._tok[: int(self._indptr[self._n])]
+
+    def row(self, r: int) -> np.ndarray:
+        if not 0 <= r < self._n:
+            raise IndexError(r)
+        return self._tok[self._indptr[r]: self._indptr[r + 1]]
+
+    @property
+    def nbytes(self) -> int:
+        return self._indptr.nbytes + self._tok.nbytes
+
+
 class PayloadColumns:
     """dict-like: columns["id"][row], columns["entropy"].array(), len(columns["id"])."""
 
@@ -185,6 +254,7 @@ class PayloadColumns:
         self._c: Dict[str, Any] = {k: StringColumn() for k in STRING_COLUMNS}
         self._c.update({k: NumericColumn(np.int64) for k in INT_COLUMNS})
         self._c.update({k: NumericColumn(np.float32) for k in FLOAT_COLUMNS})
+        self._token_sets: Optional[TokenSetColumn] = None    # derived from "content" on first use; not a payload field
 
     def __getitem__(self, name: str):
         return self._c["id" if name == "chunk_id" else name]
@@ -211,6 +281,12 @@ class PayloadColumns:
     @property
     def nbytes(self) -> int:
         return sum(c.nbytes for c in self._c.values())
+
+    def token_sets(self) -> TokenSetColumn:
+        """The token sets of every row's content: built on first use, extended by what later appends added."""
+        if self._token_sets is None:
+            self._token_sets = TokenSetColumn()
+        return self._token_sets.sync(self._c["content"])
 
     def filter_columns(self) -> Dict[str, np.ndarray]:
         """What filters.evaluate takes: numpy arrays per field (string fields as unicode arrays — fine for small

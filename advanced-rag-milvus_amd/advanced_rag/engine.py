@@ -153,6 +153,10 @@ class EngineConfig:
     recency_weight: float = 0.0
     use_sparse: bool = True
     domain_weight: float = 0.2    # weight of the optional domain list (reference retrieval.py:455-468)
+    # entries of the fused list that are kept (None = top_k).  A caller that goes on with the WHOLE fused list (MMR over the
+    # 4 * top_k entries of two 2 * top_k lists, batching.py) asks for more; the rerank step reads fused[:top_k], so this is
+    # only valid with enable_reranking=False
+    fused_k: Optional[int] = None
 
 
 class HybridSearchEngine:
@@ -166,6 +170,8 @@ class HybridSearchEngine:
         # rows (sharded the same way when the corpus is), searched with k = top_k (not 2k) and fused with weight 0.2
         self.hd = domain_handle
         self.cfg = config or EngineConfig()
+        if self.cfg.fused_k is not None and (self.cfg.enable_reranking or self.cfg.fused_k <= 0):
+            raise ValueError("fused_k must be positive and needs enable_reranking=False")
         self.group = process_group
         self.dist = None
         self.world, self.rank = 1, 0
@@ -194,6 +200,7 @@ class HybridSearchEngine:
             return b
         t, dev, cfg = self.torch, self.device, self.cfg
         kp = 2 * cfg.top_k
+        fk = cfg.fused_k or cfg.top_k
         n_main = 2 if cfg.use_sparse else 1
         n_mod = n_main + (1 if self.hd is not None else 0)
         layout = ListPack(n_mod, B, kp)
@@ -203,9 +210,9 @@ class HybridSearchEngine:
         b = {
             "kp": kp, "n_mod": n_mod, "n_main": n_main, "pack": pack, "layout": layout,
             "ids": ids_v, "scores": scores_v, "flags": layout.flags_view(pack),
-            "fused_ids": t.empty((B, cfg.top_k), dtype=t.int64, device=dev),
-            "fused_scores": t.empty((B, cfg.top_k), dtype=t.float64, device=dev),
-            "fused_methods": t.empty((B, cfg.top_k), dtype=t.int32, device=dev),
+            "fused_ids": t.empty((B, fk), dtype=t.int64, device=dev),
+            "fused_scores": t.empty((B, fk), dtype=t.float64, device=dev),
+            "fused_methods": t.empty((B, fk), dtype=t.int32, device=dev),
             "fused_n": t.empty((B,), dtype=t.int32, device=dev),
             "rr_ids": t.empty((B, cfg.rerank_top_k), dtype=t.int64, device=dev),
             "rr_scores": t.empty((B, cfg.rerank_top_k), dtype=t.float64, device=dev),
@@ -306,7 +313,7 @@ class HybridSearchEngine:
                 a.ids[slot], a.k_in[slot] = b["dom_ids"].data_ptr(), cfg.top_k
             else:
                 a.ids[slot], a.k_in[slot] = b["ids"][m].data_ptr(), kp
-        a.n_lists, a.rrf_k, a.top_k = n_lists, cfg.rrf_k, cfg.top_k
+        a.n_lists, a.rrf_k, a.top_k = n_lists, cfg.rrf_k, cfg.fused_k or cfg.top_k
         # the lists of an L2 shard are distances, smallest first: the merge of that modality runs ascending
         a.asc_mask = (1 if dense_ascending(self.h) else 0) | (4 if self.hd is not None and dense_ascending(self.hd) else 0)
         a.w[0], a.w[1], a.w[2] = cfg.dense_weight, cfg.sparse_weight, cfg.domain_weight

@@ -122,8 +122,11 @@ class MilvusIndexManager:
                  semantic_dim: int = 1536, sparse_dim: int = 10000, domain_dim: int = 768, connect: bool = True,
                  *, dtype: str = "float16", device: int = 0, devices: Optional[Sequence[int]] = None,
                  enable_domain: bool = True, device_embedding_cache: int = 0, coalesce: bool = True,
-                 semantic_metric: str = "COSINE", domain_metric: str = "COSINE"):
+                 semantic_metric: str = "COSINE", domain_metric: str = "COSINE", mmr_on_device: bool = False):
         self.host, self.port = host, port
+        # MMR profiles (troubleshooting, analysis) through the one-round path: the rows' token sets are mirrored into HBM
+        # and hr_mmr_select_dev diversifies the fused lists there (hybrid_search(mmr_lambda=...)); off = the general path
+        self.mmr_on_device = bool(mmr_on_device)
         metric_code(semantic_metric), metric_code(domain_metric)   # ValueError for anything but L2 / IP / COSINE
         self.semantic_metric, self.domain_metric = semantic_metric, domain_metric
         self.enable_sharding, self.num_shards = enable_sharding, num_shards
@@ -141,6 +144,7 @@ class MilvusIndexManager:
         # filterable ones are mirrored into HBM on first use (device_filters.py)
         self._cols = PayloadColumns()
         self._dev_filters = None
+        self._dev_tokens = None    # device_tokens.DeviceTokenSets: the token sets of "content" in HBM, on first use
         self._deleted: Optional[np.ndarray] = None
         self._mask_cache: Dict[Any, Optional[np.ndarray]] = {}   # (expr, rows, delete epoch) -> boolean row filter
         self._delete_epoch = 0
@@ -200,12 +204,14 @@ class MilvusIndexManager:
 
     def _forget_masks(self, rebuild_filters: bool):
         """Drop every cached row mask, host and HBM: the rows changed.  After an APPEND (_append_payload, add_rows) the device
-        filter columns stay: they grow in place, every row is uploaded once.  After the row space was REPLACED (attach_shards,
-        add_rows_synthetic, load_snapshot) they go too (rebuild_filters) and are rebuilt on first use.  close() drops HBM masks only."""
+        filter columns and the token sets stay: they grow in place, every row is uploaded once.  After the row space was REPLACED
+        (attach_shards, add_rows_synthetic, load_snapshot) they go too (rebuild_filters) and are rebuilt on first use.  close() drops
+        HBM masks only."""
         self._mask_cache.clear()
         self._dev_masks.clear()
         if rebuild_filters:
             self._dev_filters = None
+            self._dev_tokens = None
 
     def _initialize_collections(self):
         self._main = ShardSet([self._shard_handle("main", d) for d in self.devices])
@@ -286,6 +292,13 @@ class MilvusIndexManager:
             from .device_filters import DeviceFilters
             self._dev_filters = DeviceFilters(None if self._synthetic_rows else self._cols, main.first.device)
         return self._dev_filters
+
+    def _token_sets_on_device(self):
+        """The HBM mirror of the rows' token sets (what hr_mmr_select_dev reads), on the main shard's device."""
+        if self._dev_tokens is None:
+            from .device_tokens import DeviceTokenSets
+            self._dev_tokens = DeviceTokenSets(None if self._synthetic_rows else self._cols, self._main.first.device)
+        return self._dev_tokens
 
     def _global_device_mask(self, expr: Optional[str]):
         """Packed mask over GLOBAL rows of `expr` + tombstones as a CUDA tensor (None = all rows), evaluated on the
@@ -842,20 +855,28 @@ class MilvusIndexManager:
 
     async def hybrid_search(self, dense_embedding, sparse_embedding, top_k: int, filters: Optional[str],
                             weights: Sequence[float], rrf_k: int = 60, semantic_params: Optional[Dict] = None,
-                            sparse_params: Optional[Dict] = None):
+                            sparse_params: Optional[Dict] = None, mmr_lambda: Optional[float] = None):
         """The semantic search (2 x top_k), the sparse search (2 x top_k) and their rank fusion for ONE request in ONE
         round of the batching front: what `search` + `search` + `fuse_rank_lists_async` return, cut to the fused top_k.
 
         -> [(hit dict as `search` formats it, with "score" = the score in the list the payload comes from (the semantic
         list if the row is in it, else the sparse one), float64 fused score, method bit mask)] in fused order, or None
         when this manager cannot answer that way (no front, sharded collection, a list the device form could not prove
-        exact, bad parameters ...) — the caller then takes the general path, which also owns the error behaviour."""
+        exact, bad parameters ...) — the caller then takes the general path, which also owns the error behaviour.
+
+        With `mmr_lambda` the fused list is diversified before the cut (HybridRetriever._mmr_diversify over all of its up to
+        4 x top_k entries, on the device): at most top_k entries in MMR order.  Only a manager created with
+        mmr_on_device=True whose collection lies on one shard answers that; every other one declines."""
+        if mmr_lambda is not None and not self.mmr_on_device:
+            return None
         sem, spa = self.collections.get("semantic_index"), self.collections.get("sparse_index")
         if sem is None or spa is None or sem.handle is not spa.handle or 2 * int(top_k) > HR_MAX_TOPK:
             return None
         front = self._coalescer(sem)
         if front is None or (front.collective and not getattr(self._main, "supports_hybrid_round", False)):
             return None        # (the torchrun form answers in one round when its shards allow it: shards.round_hybrid)
+        if mmr_lambda is not None and front.collective:
+            return None
         try:
             self._search_params(sem, semantic_params)
             sp = self._search_params(spa, sparse_params)
@@ -866,7 +887,9 @@ class MilvusIndexManager:
         if not len(payload[0]):
             return None
         w = list(weights) + [0.0] * (2 - len(weights))
-        fut = front.submit_async("hybrid", (int(top_k), filters, drop, int(rrf_k)), (dense_embedding, payload, float(w[0]), float(w[1])))
+        mmr = mmr_lambda is not None
+        fut = front.submit_async("hybrid", (int(top_k), filters, drop, int(rrf_k), mmr),
+                                 (dense_embedding, payload, float(w[0]), float(w[1]), float(mmr_lambda) if mmr else 0.0))
         try:
             # no timer of its own: the caller (HybridRetriever.retrieve) already bounds the whole request with
             # RetrievalConstants.TIMEOUT_SECONDS, and a wait_for here is a task + a timer handle per request on the event

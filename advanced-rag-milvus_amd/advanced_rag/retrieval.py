@@ -216,20 +216,23 @@ class HybridRetriever:
         """Both searches and their rank fusion as ONE request to an index manager that offers `hybrid_search` (the HBM
         manager's batching front: one device round per retrieve() instead of two, and only the fused top_k hits are
         ever formatted).  Same lists, same arithmetic, same hit dicts as the general path below; None = take that path
-        (MMR needs the whole fused list; a manager without the entry point; a request it declined)."""
+        (a manager without the entry point; a request it declined; MMR, which needs the whole fused list, unless the
+        manager diversifies on the device: `mmr_on_device`)."""
         one_round = getattr(self.index_manager, "hybrid_search", None)
-        if one_round is None or self.config.enable_mmr:
+        if one_round is None or (self.config.enable_mmr and not getattr(self.index_manager, "mmr_on_device", False)):
             return None
         known = getattr(self.index_manager, "collections", None)
         if known is None or "sparse_index" not in known or "semantic_index" not in known:
             return None
         cfg = self.config
+        extra = {"mmr_lambda": cfg.mmr_lambda} if cfg.enable_mmr else {}
         saved = (cfg.dense_weight, cfg.sparse_weight)
         self._adapt_weights(query)   # the adapter sees only the query: applying it before the searches changes nothing
         try:
             ranked = await one_round(dense_q, sparse_q, top_k=cfg.top_k, filters=expr,
                                      weights=(cfg.dense_weight, cfg.sparse_weight), rrf_k=self.RRF_K,
-                                     semantic_params=cfg.semantic_search_params, sparse_params=cfg.sparse_search_params)
+                                     semantic_params=cfg.semantic_search_params, sparse_params=cfg.sparse_search_params,
+                                     **extra)
         except Exception:  # pragma: no cover - the general path owns the error behaviour
             logger.exception("one-round hybrid search failed; taking the general path")
             ranked = None

@@ -31,6 +31,7 @@
 #include "filter.h"
 #include "finish.h"
 #include "fuse.h"
+#include "mmr.h"
 #include "text.h"
 #include "select.h"
 #include "sparse.h"
@@ -1184,7 +1185,7 @@ int build_sparse(hr_index* h) {
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 10501; }  // 1.5.1: dense rows that are not finite in the store's type are refused
+int hr_version(void) { return 10600; }  // 1.6.0: hr_mmr_select_dev
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -1948,6 +1949,21 @@ int hr_rerank_linear_dev(const int64_t* d_ids, const double* d_scores, const int
                        d_recency, k_in, base_w, method_bonus, recency_w, k_out, d_out_ids, d_out_scores, d_out_orig);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "rerank_linear_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+int hr_mmr_select_dev(const int64_t* d_ids, const double* d_scores, const int32_t* d_n, int B, int k_in,
+                      const int64_t* d_tok_indptr, const int32_t* d_tok, int64_t tok_rows, int64_t first_row,
+                      const double* d_lambda, int k_out, int32_t* d_out_pos, int32_t* d_out_n, void* stream) {
+    if (B <= 0 || k_in <= 0 || k_out <= 0 || k_out > k_in || tok_rows < 0) return fail(nullptr, HR_EINVAL, "bad mmr sizes");
+    if (k_in > kFuseMax) return fail(nullptr, HR_ELIMIT, "k_in exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+    if (!d_ids || !d_scores || !d_n || !d_lambda || !d_out_pos || !d_out_n) return fail(nullptr, HR_EINVAL, "null buffer");
+    if (tok_rows > 0 ? (!d_tok_indptr || !d_tok) : (d_tok_indptr || d_tok))   // a column without rows has no arrays, and only it
+        return fail(nullptr, HR_EINVAL, "token arrays must be given exactly when tok_rows > 0");
+    hipLaunchKernelGGL(mmr_select_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, d_ids, d_scores, d_n, k_in, d_tok_indptr,
+                       d_tok, tok_rows, first_row, d_lambda, k_out, d_out_pos, d_out_n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "mmr_select_kernel: %s", hipGetErrorString(e));
     return HR_OK;
 }
 

@@ -264,6 +264,20 @@ HR_API int hr_rerank_linear_dev(const int64_t* d_ids, const double* d_scores, co
                          double method_bonus, double recency_w, int k_out, int64_t* d_out_ids,
                          double* d_out_scores, double* d_out_orig, void* stream);
 
+/* HybridRetriever._mmr_diversify (reference retrieval.py:493-516) for a batch of fused lists: greedy MMR on the token
+ * Jaccard similarity of the rows' contents, value = lambda * score - (1 - lambda) * max similarity to the selected
+ * (float64, every operation rounded on its own); the first candidate in fused order with the largest value wins, only
+ * values > -1e9 can be selected, and the selection stops at min(k_out, d_n[q]) or when no candidate qualifies.
+ * d_ids / d_scores [B][k_in], d_n[B] valid entries: the outputs of hr_fuse_rrf_dev / hr_post_lists_dev.
+ * Token sets: row r = d_tok[d_tok_indptr[r - first_row] .. d_tok_indptr[r - first_row + 1]), int32, ascending, unique;
+ * an id outside [first_row, first_row + tok_rows) has the empty set.  d_tok_indptr / d_tok are NULL iff tok_rows == 0.
+ * Rows may be of any length.  k_out <= k_in <= 3 * HR_MAX_TOPK (HR_ELIMIT beyond).
+ * d_lambda[B]: mmr_lambda per query.
+ * Out: d_out_pos [B][k_out] positions into the query's fused list in selection order (-1 padded), d_out_n[B]. */
+HR_API int hr_mmr_select_dev(const int64_t* d_ids, const double* d_scores, const int32_t* d_n, int B, int k_in,
+                      const int64_t* d_tok_indptr, const int32_t* d_tok, int64_t tok_rows, int64_t first_row,
+                      const double* d_lambda, int k_out, int32_t* d_out_pos, int32_t* d_out_n, void* stream);
+
 /* Everything after the per-shard lists of a query batch in ONE launch (one block per query): [hr_merge_topk_dev of
  * every modality's exchanged lists] -> hr_fuse_rrf_dev -> [hr_rerank_linear_dev]; results are bit-identical to the
  * separate calls (reference retrieval.py:421-491 fusion, :518-563 rerank, after the server-side shard merge of
