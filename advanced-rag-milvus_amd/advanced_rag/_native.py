@@ -53,6 +53,7 @@ _SIGNATURES = {
     "hr_add_dense_raw_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "hr_add_sparse": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64]),
     "hr_finalize": (_c.c_int, [_c.c_void_p]),
+    "hr_compact": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     "hr_save": (_c.c_int, [_c.c_void_p, _c.c_char_p]),
     "hr_load": (_c.c_int, [_c.c_char_p, _c.c_int, _c.POINTER(_c.c_void_p)]),
     "hr_get_info": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int32), _c.POINTER(_c.c_int32),
@@ -128,6 +129,7 @@ _SIGNATURES = {
                                            _c.c_int64, _c.c_int, _c.c_int, _c.c_float, _c.c_int, _c.c_void_p]),
     "hr_set_profiling": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "hr_last_kernel_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
+    "hr_last_compact_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -266,6 +268,27 @@ class ShardHandle:
     def finalize(self):
         self._check(self._lib.hr_finalize(self._h))
 
+    def compact(self, keep=None, d_keep: int = 0) -> Tuple[int, int]:
+        """hr_compact: remove the rows whose keep bit is 0 for good; returns (dense rows, sparse rows) left.
+        keep = boolean array (one entry per local row) or packed uint8 mask (bit r % 8 of byte r // 8), or d_keep =
+        device pointer of a packed mask of 8 * ceil(n / 64) bytes, n = max(num_rows, num_sparse_rows).  The handle must
+        be finalized; no search may run meanwhile, and row numbers and row masks held by the caller are void afterwards."""
+        kd, ks = ctypes.c_int64(0), ctypes.c_int64(0)
+        if d_keep:
+            self._check(self._lib.hr_compact(self._h, _vp(d_keep), 1, ctypes.byref(kd), ctypes.byref(ks)))
+            return kd.value, ks.value
+        if keep is None:
+            raise ValueError("compact needs a keep mask")
+        n = max(self.num_rows, self.num_sparse_rows)
+        m = np.asarray(keep)
+        if m.dtype == np.bool_:
+            if m.ndim != 1 or m.shape[0] != n:
+                raise ValueError(f"boolean keep mask has shape {m.shape}, the shard holds {n} rows")
+            m = np.packbits(m, bitorder="little")
+        m = self._mask(m, n)
+        self._check(self._lib.hr_compact(self._h, _vp(m), 0, ctypes.byref(kd), ctypes.byref(ks)))
+        return kd.value, ks.value
+
     @property
     def num_rows(self) -> int:
         return int(self._lib.hr_num_rows(self._h))
@@ -400,6 +423,13 @@ class ShardHandle:
         buf = np.zeros(2 * HR_N_PHASES, dtype=np.float32)
         self._check(self._lib.hr_last_kernel_ms(self._h, _vp(buf), buf.shape[0]))
         return {PHASE_NAMES[p]: (float(buf[p]), int(buf[HR_N_PHASES + p])) for p in range(HR_N_PHASES)}
+
+    def compact_ms(self):
+        """The last compact() that changed the shard: ms of the tile gather (device events; 0 without set_profiling), of
+        the whole call and of the posting rebuild inside it (host wall time)."""
+        buf = np.zeros(3, dtype=np.float32)
+        self._check(self._lib.hr_last_compact_ms(self._h, _vp(buf), 3))
+        return {"tile_gather": float(buf[0]), "call": float(buf[1]), "posting_rebuild": float(buf[2])}
 
 
 def fuse_rrf_dev(d_a: int, ka: int, d_b: int, kb: int, d_c: int, kc: int, B: int, wa: float, wb: float, wc: float,

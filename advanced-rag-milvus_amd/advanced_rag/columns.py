@@ -29,6 +29,23 @@ FLOAT_COLUMNS = ("entropy", "redundancy", "domain_density")
 KEY_BYTES = 16
 
 
+def _keep_mask(keep, n: int) -> np.ndarray:
+    keep = np.asarray(keep, dtype=bool)
+    if keep.shape != (n,):
+        raise ValueError(f"keep mask has shape {keep.shape}, the column holds {n} rows")
+    return keep
+
+
+def _gather_csr(off: np.ndarray, data: np.ndarray, keep: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """The rows of a CSR (off [n + 1], data) that `keep` names -> (new offsets from 0, their data back to back)."""
+    lens = (off[1:] - off[:-1])[keep]
+    new_off = np.zeros(lens.shape[0] + 1, dtype=np.int64)
+    np.cumsum(lens, out=new_off[1:])
+    # element e of the output lies in kept row j: it comes from start[j] + (e - new_off[j])
+    shift = np.repeat(off[:-1][keep] - new_off[:-1], lens)
+    return new_off, data[np.arange(int(new_off[-1]), dtype=np.int64) + shift]
+
+
 def _grown(arr: np.ndarray, need: int) -> np.ndarray:
     if need <= arr.shape[0]:
         return arr
@@ -71,6 +88,11 @@ class NumericColumn:
 
     def __eq__(self, other) -> bool:
         return list(self) == list(other)
+
+    def compact(self, keep: np.ndarray) -> None:
+        """Drop the rows whose entry of the boolean `keep` is False; the others move up in order."""
+        self._a = self._a[: self._n][_keep_mask(keep, self._n)]
+        self._n = self._a.shape[0]
 
     def array(self) -> np.ndarray:
         """The column as a numpy view (no copy): what the filters compare against."""
@@ -132,6 +154,17 @@ class StringColumn:
 
     def tolist(self) -> List[str]:
         return list(self)
+
+    def compact(self, keep: np.ndarray) -> None:
+        """Drop the rows whose entry of the boolean `keep` is False: the byte buffer is gathered and the offsets are
+        rebuilt; the prefix keys are gathered with them."""
+        keep = _keep_mask(keep, self._n)
+        self._off, self._buf = _gather_csr(self._off[: self._n + 1], self._buf, keep)
+        if self._keys is not None:
+            self._keys = self._keys[: self._n_keyed][keep[: self._n_keyed]]
+            self._n_keyed = self._keys.shape[0]
+        self._used = int(self._off[-1])
+        self._n = self._off.shape[0] - 1
 
     def as_str_array(self) -> np.ndarray:
         """numpy unicode array (fixed width = the longest row): only for small collections and tests."""
@@ -222,6 +255,12 @@ class TokenSetColumn:
         self._indptr[self._n + 1: self._n + len(lens) + 1] += used
         self._n += len(lens)
 
+    def compact(self, keep: np.ndarray) -> None:
+        """Drop the rows whose entry of the boolean `keep` is False.  The dictionary stays: an id never changes."""
+        keep = _keep_mask(keep, self._n)
+        self._indptr, self._tok = _gather_csr(self._indptr[: self._n + 1], self._tok, keep)
+        self._n = self._indptr.shape[0] - 1
+
     def sync(self, content: "StringColumn") -> "TokenSetColumn":
         """Tokenise the rows of `content` this column does not hold yet."""
         step = 1 << 16       # bounded temporaries
@@ -287,6 +326,16 @@ class PayloadColumns:
         if self._token_sets is None:
             self._token_sets = TokenSetColumn()
         return self._token_sets.sync(self._c["content"])
+
+    def compact(self, keep: np.ndarray) -> None:
+        """Drop the rows whose entry of the boolean `keep` (one per row) is False from every column, one column at a
+        time (the peak extra memory is one column), and from the token sets as far as they are built."""
+        keep = _keep_mask(keep, self.n_rows)
+        for col in self._c.values():
+            col.compact(keep)
+        if self._token_sets is not None:
+            n = len(self._token_sets)
+            self._token_sets.compact(keep[:n])
 
     def filter_columns(self) -> Dict[str, np.ndarray]:
         """What filters.evaluate takes: numpy arrays per field (string fields as unicode arrays — fine for small

@@ -116,6 +116,11 @@ class ShardCollection:
     def delete(self, expr: str):
         self.manager._tombstone(expr)
 
+    def compact(self) -> Dict[str, int]:
+        """pymilvus' Collection.compact(): drop the deleted rows from the store for good (MilvusIndexManager.compact —
+        the collections of a manager share their rows, so all of them are compacted)."""
+        return self.manager.compact()
+
 
 class MilvusIndexManager:
     def __init__(self, host: str = "localhost", port: int = 19530, enable_sharding: bool = True, num_shards: int = 4,
@@ -370,6 +375,49 @@ class MilvusIndexManager:
             self._deleted = grown
         self._deleted[:n] |= hit
         self._delete_epoch += 1
+
+    # ------------------------------------------------------------------ compaction
+    def compact(self) -> Dict[str, int]:
+        """Remove every tombstoned row (delete_by_filter / Collection.delete) from the shards, the domain shards and the
+        payload columns for good, and give the HBM back: hr_compact per shard (include/hbmrag.h).  The scans stop streaming
+        the dead rows, num_entities counts the survivors, and the survivors are renumbered in order — a hit's "_row"
+        changes, its "id" and everything else does not.
+
+        A maintenance call like load_snapshot: it REPLACES the row space, nothing calls it by itself, and the caller
+        issues no search while it runs.  It is out of place: until it returns, a shard's old and new store are in HBM
+        together.  A collection whose payload is derived from the row number (add_rows_synthetic) cannot be compacted:
+        its ids would change.  -> rows_before, rows_after, device_bytes_before, device_bytes_after."""
+        if self._synthetic_rows:
+            raise ValueError("a synthetic-payload collection cannot be compacted: its ids are a function of the row number")
+        sets = [s for s in (self._main, self._domain) if s is not None]
+        n = self.num_rows
+        bytes_before = sum(int(getattr(s, "device_bytes", 0)) for s in sets)
+        out = {"rows_before": n, "rows_after": n, "device_bytes_before": bytes_before, "device_bytes_after": bytes_before}
+        if self._deleted is None or not self._deleted[:n].any():
+            return out
+        for s in sets:      # refuse before anything is touched
+            if not hasattr(s, "handles"):
+                s.compact(None)          # the torchrun form: NotImplementedError
+        # the front's engines and buffers are sized for the old shard: the next search builds a new one
+        if self._front is not None:
+            self._front.close()
+            self._front = None
+        keep = np.ones(n, dtype=bool)
+        keep[: self._deleted.shape[0]] = ~self._deleted[:n]
+        d_keep = 0
+        if self._filters_on_device() is not None and self._main.n_shards == 1:
+            d_mask = self._global_device_mask(None)      # alive rows, packed, already in HBM
+            d_keep = d_mask.data_ptr() if d_mask is not None else 0
+        # the same mask over the rows each set has: row r of one stays row r of the other
+        for s in sets:
+            s.compact(keep, d_keep if s.device == self._main.device else 0)
+        self._cols.compact(keep)     # only after every shard set succeeded
+        self._deleted = None
+        self._delete_epoch += 1
+        self._forget_masks(rebuild_filters=True)
+        out["rows_after"] = self.num_rows
+        out["device_bytes_after"] = sum(int(getattr(s, "device_bytes", 0)) for s in sets)
+        return out
 
     # ------------------------------------------------------------------ ingest
     async def index_chunks(self, chunks: List["Chunk"], domain: Optional[str] = None) -> Dict[str, Any]:

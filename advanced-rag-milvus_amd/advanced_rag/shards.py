@@ -189,6 +189,33 @@ class ShardSet:
         for h in self.handles:
             h.finalize()
 
+    def compact(self, keep_global: np.ndarray, d_keep: int = 0) -> int:
+        """Remove the rows whose entry of `keep_global` (boolean, over GLOBAL rows) is False from every shard for good
+        (hr_compact) and renumber the survivors: new global row = kept rows before it.  Returns the rows left.
+        d_keep: the same mask packed in HBM; used instead of an upload when the set is one native shard whose local rows
+        are the global rows.  While the shards are processed every row map is cut down but keeps the OLD numbers; the maps
+        are renumbered only after the last shard has succeeded.  If a shard fails the error is raised with the set still
+        consistent under the old numbering: the shards done so far have merely lost rows the mask hides anyway.
+        A maintenance call: no search may run meanwhile."""
+        keep = np.asarray(keep_global, dtype=bool)
+        if keep.ndim != 1 or any(len(r) and int(r[-1]) >= len(keep) for r in self.rows_of):
+            raise ValueError(f"keep mask covers {keep.shape} rows, the set holds rows up to {self._n}")
+        self._packed = None     # packed copies of filters are cut by local row: stale from the first shard on
+        for s, h in enumerate(self.handles):
+            rows = self.rows_of[s]
+            own = keep[rows]
+            if own.all():
+                continue
+            if d_keep and self.n_shards == 1 and is_native_handle(h) and np.array_equal(rows, np.arange(len(rows))):
+                h.compact(d_keep=d_keep)
+            else:
+                h.compact(own)
+            self.rows_of[s] = rows[own]
+        new_of = np.cumsum(keep, dtype=np.int64) - 1
+        self.rows_of = [new_of[r] for r in self.rows_of]
+        self._n = int(np.count_nonzero(keep[:self._n]))
+        return self._n
+
     def close(self):
         for h in self.handles:
             h.close()
@@ -403,6 +430,10 @@ class CollectiveShardSet:
 
     def close(self):
         self.local.close()
+
+    def compact(self, keep_global, d_keep: int = 0):
+        """Not in the torchrun form: every rank would have to compact its shard and renumber in step."""
+        raise NotImplementedError("compaction of a torchrun collection (CollectiveShardSet) is not implemented")
 
     def _global_rows(self) -> np.ndarray:
         """Global row of every local row of this rank."""

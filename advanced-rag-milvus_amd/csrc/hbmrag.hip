@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -24,6 +25,7 @@
 
 #include "common.h"
 #include "attention.h"
+#include "compact.h"
 #include "encoder_layer.h"
 #include "scan_plan.h"
 #include "dense.h"
@@ -163,6 +165,7 @@ struct hr_index {
     int cu_count = 256;
     int scan_cus = 0;              // compute units the scans' stream may use (hr_set_scan_cus); 0 = all
     int fault_inject = 0;          // hr_debug_inject_fault: fail the next build_sparse after its CSR upload (tests)
+    float compact_ms[3] = {};      // the last hr_compact under profiling: tile gather (events), whole call, posting rebuild (wall)
     bool slot_prepped[HR_MAX_SLOTS] = {};  // hr_hybrid_prep_dev has prepared the slot's queries for the next scan
 
     mutable std::shared_mutex rw;  // searches shared, add/finalize exclusive
@@ -1180,12 +1183,128 @@ int build_sparse(hr_index* h) {
     return HR_OK;
 }
 
+// ---- compaction (compact.h) ------------------------------------------------------------------------------------------
+// Exclusive scan of f(0 .. n) on stream s: on return (enqueued) block_off holds the exclusive prefix of the sums of
+// blocks of kCompactBlock elements, d_total[0] their total.
+template <typename F>
+int compact_scan_blocks(hr_index* h, hipStream_t s, F f, int64_t n, DevBuf& block_off, unsigned long long* d_total) {
+    const int64_t nb = (n + kCompactBlock - 1) / kCompactBlock;
+    if (block_off.alloc_exact((size_t)std::max<int64_t>(nb, 1) * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, HR_ENOMEM, "cannot allocate the compaction scan (%lld blocks)", (long long)nb);
+    }
+    hipLaunchKernelGGL((compact_block_sums_kernel<F>), dim3((unsigned)nb), dim3(kCompactBlock), 0, s, f, n,
+                       block_off.as<unsigned long long>());
+    HIP_TRY(h, hipGetLastError());
+    hipLaunchKernelGGL(compact_scan_sums_kernel, dim3(1), dim3(kCompactBlock), 0, s, block_off.as<unsigned long long>(), nb, d_total);
+    HIP_TRY(h, hipGetLastError());
+    return HR_OK;
+}
+
+// The row map of the first n rows under the keep mask: src_of[new row] = old row (ascending), *kept = its length.
+int compact_row_map(hr_index* h, hipStream_t s, const unsigned long long* d_mask, int64_t n, DevBuf& src_of, int64_t* kept) {
+    *kept = 0;
+    if (n == 0) return HR_OK;
+    const int64_t n_words = (n + 63) / 64;
+    DevBuf block_off, total;
+    if (total.alloc_exact(8) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, HR_ENOMEM, "cannot allocate the compaction scan");
+    }
+    HR_TRY(compact_scan_blocks(h, s, KeepCount{d_mask, n}, n_words, block_off, total.as<unsigned long long>()));
+    unsigned long long n_kept = 0;
+    HIP_TRY(h, hipMemcpyAsync(&n_kept, total.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    *kept = (int64_t)n_kept;
+    if (n_kept == 0 || (int64_t)n_kept == n) return HR_OK;  // nothing to gather / nothing to drop: no map needed
+    if (src_of.alloc_exact((size_t)n_kept * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, HR_ENOMEM, "cannot allocate the row map of %llu rows", n_kept);
+    }
+    const unsigned blocks = (unsigned)((n_words + kCompactBlock - 1) / kCompactBlock);
+    hipLaunchKernelGGL(compact_row_map_kernel, dim3(blocks), dim3(kCompactBlock), 0, s, d_mask, n, n_words,
+                       block_off.as<unsigned long long>(), (int64_t)n_kept, src_of.as<uint32_t>());
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(s));  // block_off is scratch of this scope
+    return HR_OK;
+}
+
+// The new dense store of the survivors (the handle is not touched): gathered tiles, per-row values and the maximum norm.
+struct CompactDense {
+    DevBuf tiles, scale, norm2, max_norm;
+    int64_t cap_rows = 0;
+};
+int compact_dense(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t kept, CompactDense* out, hipEvent_t* span) {
+    out->cap_rows = dense_capacity_for(0, kept, true);
+    const size_t tb = tile_bytes_for_rows(h, out->cap_rows);
+    if (out->tiles.alloc_exact(tb) != hipSuccess || out->scale.alloc_exact((size_t)out->cap_rows * 4) != hipSuccess ||
+        out->norm2.alloc_exact((size_t)out->cap_rows * 8) != hipSuccess || out->max_norm.alloc_exact(4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, HR_ENOMEM, "cannot allocate the compacted dense shard for %lld rows (%zu bytes) beside the old one",
+                    (long long)out->cap_rows, tb);
+    }
+    // zeros beyond the last row block that holds a survivor (the gather writes that block whole, its ragged lanes as zeros)
+    const int64_t n_dst_blocks = (kept + kRowsPerBlock - 1) / kRowsPerBlock;
+    const size_t written = (size_t)n_dst_blocks * h->KT * 1024;
+    if (tb > written) HIP_TRY(h, hipMemsetAsync((char*)out->tiles.p + written, 0, tb - written, s));
+    HIP_TRY(h, hipMemsetAsync(out->scale.p, 0, out->scale.cap, s));
+    HIP_TRY(h, hipMemsetAsync(out->norm2.p, 0, out->norm2.cap, s));
+    HIP_TRY(h, hipMemsetAsync(out->max_norm.p, 0, 4, s));
+    if (kept == 0) return HR_OK;
+    if (span) HIP_TRY(h, hipEventRecord(span[0], s));
+    hipLaunchKernelGGL(compact_tiles_kernel, dim3((unsigned)((n_dst_blocks + kCompactWaves - 1) / kCompactWaves)),
+                       dim3(kCompactWaves * 64), 0, s, h->tiles.as<chunk_t>(), d_src_of, kept, h->KT, n_dst_blocks,
+                       out->tiles.as<chunk_t>());
+    HIP_TRY(h, hipGetLastError());
+    if (span) HIP_TRY(h, hipEventRecord(span[1], s));
+    hipLaunchKernelGGL(compact_row_values_kernel, dim3((unsigned)((kept + 255) / 256)), dim3(256), 0, s, h->scale.as<float>(),
+                       h->norm2.as<double>(), d_src_of, kept, out->scale.as<float>(), out->norm2.as<double>(),
+                       out->max_norm.as<unsigned int>());
+    HIP_TRY(h, hipGetLastError());
+    return HR_OK;
+}
+
+// The new CSR of the surviving sparse rows (the handle is not touched), exactly as large as it has to be.
+struct CompactSparse {
+    DevBuf indptr, idx, val, stats;
+    int64_t nnz = 0;
+};
+int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t kept, CompactSparse* out) {
+    if (kept == 0) return HR_OK;
+    DevBuf block_off, total;
+    if (out->indptr.alloc_exact((size_t)(kept + 1) * 8) != hipSuccess || out->stats.alloc_exact(8) != hipSuccess ||
+        total.alloc_exact(8) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, HR_ENOMEM, "cannot allocate the compacted sparse rows (%lld) beside the old ones", (long long)kept);
+    }
+    const RowLength len{h->s_indptr.as<int64_t>(), d_src_of};
+    HR_TRY(compact_scan_blocks(h, s, len, kept, block_off, total.as<unsigned long long>()));
+    hipLaunchKernelGGL(compact_indptr_kernel, dim3((unsigned)((kept + kCompactBlock - 1) / kCompactBlock)), dim3(kCompactBlock), 0, s,
+                       len, kept, block_off.as<unsigned long long>(), out->indptr.as<int64_t>());
+    HIP_TRY(h, hipGetLastError());
+    unsigned long long nnz = 0;
+    HIP_TRY(h, hipMemcpyAsync(&nnz, total.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));  // the entry buffers are sized by it
+    out->nnz = (int64_t)nnz;
+    if (out->idx.alloc_exact((size_t)std::max<int64_t>(out->nnz, 1) * 4) != hipSuccess ||
+        out->val.alloc_exact((size_t)std::max<int64_t>(out->nnz, 1) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, HR_ENOMEM, "cannot allocate the compacted sparse entries (%lld) beside the old ones", (long long)out->nnz);
+    }
+    HIP_TRY(h, hipMemsetAsync(out->stats.p, 0, 8, s));
+    hipLaunchKernelGGL(compact_csr_kernel, dim3((unsigned)((kept + 3) / 4)), dim3(256), 0, s, h->s_indptr.as<int64_t>(),
+                       h->s_idx.as<int32_t>(), h->s_val.as<float>(), d_src_of, kept, out->indptr.as<int64_t>(),
+                       out->idx.as<int32_t>(), out->val.as<float>(), out->stats.as<unsigned int>());
+    HIP_TRY(h, hipGetLastError());
+    return HR_OK;
+}
+
 }  // namespace
 
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 10600; }  // 1.6.0: hr_mmr_select_dev
+int hr_version(void) { return 10700; }  // 1.7.0: hr_compact
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -1336,6 +1455,108 @@ int hr_finalize(hr_index* h) {
     }
     if (h->sparse_dim > 0 && (h->n_sparse_built != h->n_sparse || h->n_csr != h->n_sparse)) HR_TRY(build_sparse(h));
     h->finalized = true;
+    return HR_OK;
+}
+
+int hr_compact(hr_index* h, const uint8_t* keep, int on_device, int64_t* kept_dense, int64_t* kept_sparse) {
+    if (!h) return fail(nullptr, HR_EINVAL, "null handle");
+    if (!keep) return fail(h, HR_EINVAL, "null keep mask");
+    std::unique_lock<std::shared_mutex> lk(h->rw);
+    DeviceGuard dg(h->device);
+    if (!h->finalized) return fail(h, HR_ESTATE, "hr_compact before hr_finalize (pending rows must be flushed first)");
+    using clk = std::chrono::steady_clock;
+    const clk::time_point t_call = clk::now();
+    struct Events {  // hr_set_profiling: the tile gather between two events
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    } ev;
+    bool timed = false;
+    if (h->profiling && (hipEventCreate(&ev.e[0]) != hipSuccess || hipEventCreate(&ev.e[1]) != hipSuccess))
+        return fail(h, HR_EHIP, "cannot create the profiling events");
+    // `*_dev` searches drop their shared lock once their kernels are enqueued: none may still read the old store
+    HIP_TRY(h, hipDeviceSynchronize());
+    hipStream_t s = h->ingest_stream;
+    const bool dense = h->dim > 0 && h->n_rows > 0, sparse = h->sparse_dim > 0 && h->n_sparse > 0;
+    const int64_t n = std::max(h->n_rows, h->n_sparse);
+    if (kept_dense) *kept_dense = h->n_rows;
+    if (kept_sparse) *kept_sparse = h->n_sparse;
+    if (n == 0) return HR_OK;
+
+    // ---- everything new is built beside the old store; the handle is untouched until the commit below ----
+    DevBuf mask_buf;
+    const unsigned long long* d_mask = reinterpret_cast<const unsigned long long*>(keep);
+    if (!on_device) {
+        const size_t words = (size_t)((n + 63) / 64);
+        if (mask_buf.alloc_exact(words * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, HR_ENOMEM, "cannot allocate the keep mask");
+        }
+        HIP_TRY(h, hipMemsetAsync(mask_buf.p, 0, words * 8, s));
+        HIP_TRY(h, hipMemcpyAsync(mask_buf.p, keep, (size_t)((n + 7) / 8), hipMemcpyHostToDevice, s));
+        d_mask = mask_buf.as<unsigned long long>();
+    }
+    DevBuf map_d, map_s;  // one map serves both collections when they hold the same rows
+    int64_t kd = 0, ks = 0;
+    if (dense) HR_TRY(compact_row_map(h, s, d_mask, h->n_rows, map_d, &kd));
+    if (sparse) {
+        if (dense && h->n_sparse == h->n_rows) ks = kd;
+        else HR_TRY(compact_row_map(h, s, d_mask, h->n_sparse, map_s, &ks));
+    }
+    if (kd == h->n_rows && ks == h->n_sparse) return HR_OK;  // every row stays: nothing changes, capacity included
+    const uint32_t* src_d = map_d.as<uint32_t>();
+    const uint32_t* src_s = map_s.p ? map_s.as<uint32_t>() : src_d;
+    CompactDense nd;
+    CompactSparse nsp;
+    if (dense && kd < h->n_rows) {
+        timed = h->profiling && kd > 0;
+        HR_TRY(compact_dense(h, s, src_d, kd, &nd, timed ? ev.e : nullptr));
+    }
+    if (sparse && ks < h->n_sparse) HR_TRY(compact_sparse(h, s, src_s, ks, &nsp));
+    unsigned int norm_bits = 0, stats[2] = {0u, 0u};
+    if (nd.max_norm.p) HIP_TRY(h, hipMemcpyAsync(&norm_bits, nd.max_norm.p, 4, hipMemcpyDeviceToHost, s));
+    if (nsp.stats.p) HIP_TRY(h, hipMemcpyAsync(stats, nsp.stats.p, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+
+    auto wall_ms = [](clk::time_point a) { return std::chrono::duration<float, std::milli>(clk::now() - a).count(); };
+    h->compact_ms[0] = h->compact_ms[2] = 0.f;
+    if (timed) (void)hipEventElapsedTime(&h->compact_ms[0], ev.e[0], ev.e[1]);
+
+    // ---- commit: nothing below can fail before the posting rebuild ----
+    if (dense && kd < h->n_rows) {
+        h->tiles = std::move(nd.tiles);
+        h->scale = std::move(nd.scale);
+        h->norm2 = std::move(nd.norm2);
+        h->max_norm = std::move(nd.max_norm);
+        h->cap_rows = nd.cap_rows;
+        h->n_rows = h->n_normed = kd;
+        std::memcpy(&h->max_row_norm, &norm_bits, 4);
+    }
+    if (kept_dense) *kept_dense = h->n_rows;
+    if (sparse && ks < h->n_sparse) {
+        h->s_indptr = std::move(nsp.indptr);
+        h->s_idx = std::move(nsp.idx);
+        h->s_val = std::move(nsp.val);
+        h->n_sparse = h->n_csr = ks;
+        h->nnz_csr = nsp.nnz;
+        std::memcpy(&h->max_sparse_abs, &stats[0], 4);
+        h->sparse_signed = stats[1] != 0;
+        // the postings are rebuilt from range 0: until that has happened the handle is what a failed hr_finalize leaves
+        h->rt_off.release();
+        h->range_base.release();
+        h->post.release();
+        std::vector<int64_t>{0}.swap(h->h_range_base);
+        std::vector<unsigned>().swap(h->h_range_dense);
+        h->n_sparse_built = 0;
+        h->n_ranges = 0;
+        h->n_dense_runs = 0;
+        h->finalized = false;
+        if (kept_sparse) *kept_sparse = ks;
+        const clk::time_point t_build = clk::now();
+        HR_TRY(build_sparse(h));
+        h->compact_ms[2] = wall_ms(t_build);
+        h->finalized = true;
+    }
+    h->compact_ms[1] = wall_ms(t_call);
     return HR_OK;
 }
 
@@ -2322,6 +2543,13 @@ HR_API int hr_debug_gemm_stamps(unsigned long long* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(hbmrag::hr_gemm_stamps), 16 * sizeof(unsigned long long)) == hipSuccess ? 0 : 1;
 }
 #endif
+int hr_last_compact_ms(hr_index* h, float* out_ms, int n) {
+    if (!h || !out_ms || n < 3) return fail(h, HR_EINVAL, "need a handle and room for 3 values");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    for (int i = 0; i < 3; ++i) out_ms[i] = h->compact_ms[i];
+    return HR_OK;
+}
+
 int hr_last_kernel_ms(hr_index* h, float* out_ms, int n) {
     if (!h || !out_ms || n < 2 * PH_COUNT) return fail(h, HR_EINVAL, "need room for %d floats", 2 * PH_COUNT);
     DeviceGuard dg(h->device);

@@ -131,6 +131,33 @@ HR_API int hr_add_sparse(hr_index* h, const int64_t* indptr, const int32_t* indi
  * search workspaces.  May be called again after further adds. */
 HR_API int hr_finalize(hr_index* h);
 
+/* Remove rows for good (Milvus compacts its segments after Collection.delete, reference indexing.py:692-696, and
+ * offers Collection.compact()).  keep: 1 bit per LOCAL row (bit r%8 of byte r/8, the rowmask convention), 1 = the row stays.
+ * on_device = 0: host buffer of ceil(n/8) bytes; 1: device buffer of 8*ceil(n/64) bytes (what hr_filter_eval_dev
+ * writes), n = max(hr_num_rows, hr_num_sparse_rows).  Surviving rows keep their order; new local row = number of
+ * kept rows before it.  The dense and the sparse collection of the handle are compacted with the same mask (each
+ * over the rows it has).  *kept_dense / *kept_sparse (may be NULL) receive the new row counts.
+ *   Result: afterwards the handle cannot be told apart from one built from the surviving rows alone — the same create
+ *     arguments and hr_set_row_offset, hr_add_dense_raw / hr_add_sparse of the survivors in order, hr_finalize: identical
+ *     search results and exactness flags through every entry point and a byte-identical hr_save file (tiles, the per-row
+ *     fp32 array, norm2, the CSR, and the header's max_row_norm, max_sparse_abs, n_rows, n_sparse, nnz); the "some weight
+ *     is negative" state and the postings' dense-run bookkeeping are recomputed from the survivors.  Stored bits are
+ *     gathered; no row is re-quantised.
+ *   Capacity: the dense store gets what hr_reserve gives an empty handle for that many rows, the CSR buffers hold
+ *     exactly the surviving rows, the postings are rebuilt from the first range; hr_device_bytes drops accordingly and
+ *     later appends grow by the usual rule.
+ *   All-or-nothing: the operation is OUT OF PLACE — every new buffer is allocated and filled beside the old store, so
+ *     the old and the new store are in HBM at once — and only then moved into the handle.  A failure before that
+ *     (HR_ENOMEM when the new store does not fit beside the old one) leaves the handle exactly as it was.  If only the
+ *     posting rebuild fails after that, the handle is in the state a failed hr_finalize leaves (CSR complete, not
+ *     finalized) and the next hr_finalize completes it.
+ *   Exclusive like hr_finalize, and it waits for the device first: `*_dev` searches enqueued earlier finish on the old
+ *     store.  The caller issues no search while it runs and forgets every row number and row mask it holds.
+ *   HR_ESTATE on a handle that is not finalized (pending rows must be flushed first); HR_EINVAL for a NULL handle or
+ *     mask.  A mask that keeps every row returns HR_OK and changes nothing, capacity included.  A mask that keeps no row
+ *     leaves a finalized empty handle that answers searches with padded lists and accepts appends. */
+HR_API int hr_compact(hr_index* h, const uint8_t* keep, int on_device, int64_t* kept_dense, int64_t* kept_sparse);
+
 /* Shard snapshot (checkpoint / resume; the reference relies on Milvus'
  * persistence, indexing.py:185-188, :430-431).  One file: header (with the file's
  * total size), dense tiles + norms exactly as they sit in HBM, and the sparse CSR
@@ -490,6 +517,10 @@ HR_API int hr_debug_option(hr_index* h, int key, int value);
 #define HR_N_PHASES 10
 HR_API int hr_set_profiling(hr_index* h, int enabled);
 HR_API int hr_last_kernel_ms(hr_index* h, float* out_ms, int n);
+/* The last hr_compact that changed the handle: out_ms[0] = compact_tiles_kernel between two HIP events (0 unless
+ * hr_set_profiling was on and dense rows survived), out_ms[1] = the whole call, out_ms[2] = the posting rebuild inside
+ * it (host wall time, ms).  n must be >= 3. */
+HR_API int hr_last_compact_ms(hr_index* h, float* out_ms, int n);
 /* Algorithmic bytes one dense scan launch reads (rows*dim*sizeof(elem) + 4*rows: the rows and one float per row —
  * the scale of a COSINE / IP shard, the row term |x|^2 / 2 of an L2 shard, which takes the scale's place). */
 HR_API int64_t hr_dense_scan_bytes(const hr_index* h);
