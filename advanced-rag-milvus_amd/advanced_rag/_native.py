@@ -111,6 +111,9 @@ _SIGNATURES = {
                                         _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_mmr_select_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                      _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_group_select_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
+                                       _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_mask_drop_groups_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "hr_add_layernorm_f16_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                             _c.c_int, _c.c_float, _c.c_void_p]),
     "hr_embed_layernorm_f16_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -462,6 +465,26 @@ def mmr_select_dev(d_ids: int, d_scores: int, d_n: int, B: int, k_in: int, d_tok
                              tok_rows, first_row, _vp(d_lambda) if d_lambda else None, k_out,
                              _vp(d_out_pos) if d_out_pos else None, _vp(d_out_n) if d_out_n else None,
                              _vp(stream) if stream else None)
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+def group_select_dev(d_ids: int, d_n: int, B: int, k_in: int, d_keys: int, key_rows: int, first_row: int, k_out: int,
+                     d_out_pos: int, d_out_keys: int, d_out_n: int, d_flags: int, stream: int = 0):
+    """hr_group_select_dev: the first entry of every group of a batch of ranked lists (device pointers; 0 = NULL)."""
+    L = load_library()
+    p = lambda x: _vp(x) if x else None
+    rc = L.hr_group_select_dev(p(d_ids), p(d_n), B, k_in, p(d_keys), key_rows, first_row, k_out, p(d_out_pos), p(d_out_keys),
+                               p(d_out_n), p(d_flags), p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+def mask_drop_groups_dev(d_mask_in: int, d_mask_out: int, n_rows: int, d_keys: int, d_drop: int, n_drop: int, stream: int = 0):
+    """hr_mask_drop_groups_dev: mask_out = mask_in (0 = all rows) without the rows whose group key is among the n_drop keys."""
+    L = load_library()
+    p = lambda x: _vp(x) if x else None
+    rc = L.hr_mask_drop_groups_dev(p(d_mask_in), p(d_mask_out), n_rows, p(d_keys), p(d_drop), n_drop, p(stream))
     if rc != 0:
         _raise_global(L, rc)
 

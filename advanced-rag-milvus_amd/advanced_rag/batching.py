@@ -10,6 +10,11 @@ round of scans is in flight — or within a short window of the first call of a 
 synchronisation per round, and the per-query lists are handed back to the awaiting coroutines.  Lists the device form
 could not prove exact are redone through the host form, which widens the candidate set by itself.
 
+Grouping searches (search(..., group_by_field=F)) coalesce the same way; the field is part of the request key, so grouped and
+ungrouped requests never share a launch.  Their batch searches the window K' (MilvusIndexManager.group_window) and runs ONE
+`hr_group_select_dev` for all of its queries behind the search on the same stream; a query whose window ended before its
+top_k-th group is redone through the manager's blocking loop, which continues the ranking exactly.
+
 A caller that has BOTH embeddings of a request in hand (HybridRetriever._retrieve_inner via
 MilvusIndexManager.hybrid_search) submits one "hybrid" request instead of two searches and a fusion: the batch runs as
 one `hr_search_hybrid_dev` (both scans, the fused finishing kernel) + one `hr_post_lists_dev` (RRF) — the engine's own
@@ -127,7 +132,7 @@ class SearchCoalescer:
             self.window_s = max(self.window_s, 250e-6)
         self.stats = {"rounds": 0, "requests": 0, "dense_launches": 0, "sparse_launches": 0, "fuse_launches": 0,
                       "hybrid_launches": 0, "mmr_launches": 0, "encode_launches": 0, "encoded_texts": 0, "max_batch_seen": 0, "redone_unproven": 0,
-                      "busy_s": 0.0}
+                      "group_launches": 0, "redone_grouped": 0, "busy_s": 0.0}
         self._engines: Dict[Tuple, Any] = {}   # hybrid engines per (top_k, rrf_k, mmr)
         self._inflight: List[_Request] = []    # the requests of the round in progress (failed as a whole if the worker dies)
         self._outbox: Dict[Any, list] = {}     # event loop -> [(asyncio future, ok, value)] of the round in progress
@@ -299,10 +304,11 @@ class SearchCoalescer:
                 if r.kind == "fuse":
                     _answer(r.future, self.mgr._fuse_rows_blocking, r.payload, r.key)
                     continue
-                coll_name, top_k, expr, params_key = r.key
-                if self.mgr.collections[coll_name].handle is not cs:
-                    # a collection that is NOT spread over the ranks (the local domain shard): its searches have nothing
-                    # to do with the shard set's rounds — the blocking single-shard path answers them
+                coll_name, top_k, expr, params_key, group_field = r.key
+                if group_field is not None or self.mgr.collections[coll_name].handle is not cs:
+                    # two cases for the manager's blocking path.  A grouping search: its loop searches window after window,
+                    # each a round of the shard set.  Or a collection that is NOT spread over the ranks (the local domain
+                    # shard): its searches have nothing to do with the shard set's rounds
                     _answer(r.future, self._lists_blocking, r, r.key)
                     continue
                 drop = float(dict(params_key).get("drop_ratio_search", 0.0)) if r.kind == "sparse" else None
@@ -348,8 +354,8 @@ class SearchCoalescer:
 
     def _lists_blocking(self, r: _Request, key: Tuple):
         """The lists of one dense or sparse request through the manager's blocking single-query path."""
-        coll_name, top_k, expr, params_key = key
-        return self.mgr._search_lists_blocking(r.payload, coll_name, top_k, expr, dict(params_key))
+        coll_name, top_k, expr, params_key, group_field = key
+        return self.mgr._search_lists_blocking(r.payload, coll_name, top_k, expr, dict(params_key), group_field)
 
     def _one_by_one(self, kind: str, key: Tuple, chunk: List[_Request]):
         """Fallback when a batched launch was refused: each request through the blocking single-query path, so that
@@ -366,42 +372,74 @@ class SearchCoalescer:
 
     # ------------------------------------------------------------------ dense
     def _enqueue_dense(self, torch, dev, stream, key, chunk):
-        coll_name, top_k, expr, _ = key
+        coll_name, top_k, expr, _, group_field = key
         handle = self.mgr.collections[coll_name].handle.first
         B = len(chunk)
+        k = self.mgr.group_window(top_k) if group_field is not None else top_k
         q = dense_rows_device([r.payload for r in chunk], dev, handle.dim)
-        ids, sc, fl = list_buffers(B, top_k, dev)
+        ids, sc, fl = list_buffers(B, k, dev)
         mask = self.mgr._device_row_mask(expr, "dense")
-        handle.search_dense_dev(q.data_ptr(), B, top_k, ids.data_ptr(), sc.data_ptr(), fl.data_ptr(),
+        handle.search_dense_dev(q.data_ptr(), B, k, ids.data_ptr(), sc.data_ptr(), fl.data_ptr(),
                                 mask.data_ptr() if mask is not None else 0, stream.cuda_stream)
         self.stats["dense_launches"] += 1
-        return {"ids": ids, "sc": sc, "fl": fl, "keep": (q, mask)}
+        st = {"ids": ids, "sc": sc, "fl": fl, "keep": (q, mask)}
+        if group_field is not None:
+            self._group_select(torch, dev, stream, top_k, group_field, st)
+        return st
+
+    def _group_select(self, torch, dev, stream, top_k, group_field, st):
+        """The first top_k groups of every window of the batch (hr_group_select_dev, same stream, behind the search) -> st["group"]
+        = (positions [B, top_k], groups selected [B], flags [B])."""
+        from . import _native as nat
+        ids = st["ids"]
+        B, window = int(ids.shape[0]), int(ids.shape[1])
+        n = self.mgr.num_rows
+        keys = self.mgr._group_keys_on_device().tensor(group_field, n)
+        pos = torch.empty((B, top_k), dtype=torch.int32, device=dev)
+        n_sel = torch.empty((B,), dtype=torch.int32, device=dev)
+        gfl = torch.empty((B,), dtype=torch.int32, device=dev)
+        nat.group_select_dev(ids.data_ptr(), 0, B, window, keys.data_ptr(), n, 0, top_k, pos.data_ptr(), 0, n_sel.data_ptr(),
+                             gfl.data_ptr(), stream.cuda_stream)
+        self.stats["group_launches"] += 1
+        st["group"] = (pos, n_sel, gfl)
+        st["keep"] = st["keep"] + (keys,)
 
     # ------------------------------------------------------------------ sparse
     def _enqueue_sparse(self, torch, dev, stream, key, chunk):
-        coll_name, top_k, expr, params_key = key
+        coll_name, top_k, expr, params_key, group_field = key
         handle = self.mgr.collections[coll_name].handle.first
         drop = float(dict(params_key).get("drop_ratio_search", 0.0))
         B = len(chunk)
+        k = self.mgr.group_window(top_k) if group_field is not None else top_k
         d_ptr, d_idx, d_val, max_nnz = upload_sparse(
             pack_sparse_queries([r.payload for r in chunk], drop, handle.sparse_dim), dev)
         nnz = int(d_idx.shape[0])
-        ids, sc, fl = list_buffers(B, top_k, dev)
+        ids, sc, fl = list_buffers(B, k, dev)
         mask = self.mgr._device_row_mask(expr, "sparse")
         handle.search_sparse_dev(d_ptr.data_ptr(), d_idx.data_ptr() if nnz else 0, d_val.data_ptr() if nnz else 0, B,
-                                 nnz, int(max_nnz), top_k, ids.data_ptr(), sc.data_ptr(), fl.data_ptr(),
+                                 nnz, int(max_nnz), k, ids.data_ptr(), sc.data_ptr(), fl.data_ptr(),
                                  mask.data_ptr() if mask is not None else 0, stream.cuda_stream)
         self.stats["sparse_launches"] += 1
-        return {"ids": ids, "sc": sc, "fl": fl, "keep": (d_ptr, d_idx, d_val, mask)}
+        st = {"ids": ids, "sc": sc, "fl": fl, "keep": (d_ptr, d_idx, d_val, mask)}
+        if group_field is not None:
+            self._group_select(torch, dev, stream, top_k, group_field, st)
+        return st
 
     def _scatter_lists(self, key, chunk, st):
         ids, sc, fl = st["ids"].cpu().numpy(), st["sc"].cpu().numpy(), st["fl"].cpu().numpy()
+        group = [t.cpu().numpy() for t in st["group"]] if "group" in st else None
         for i, r in enumerate(chunk):
             if fl[i] != 1:  # ties at the candidate cut: the host form widens the candidate set until the proof holds
                 self.stats["redone_unproven"] += 1
                 _answer(r.future, self._lists_blocking, r, key)
-            else:
+            elif group is None:
                 _deliver(r.future, (ids[i], sc[i]))
+            elif group[2][i] != 1:  # the window ended before the top_k-th group: the blocking loop continues the ranking
+                self.stats["redone_grouped"] += 1
+                _answer(r.future, self._lists_blocking, r, key)
+            else:
+                at = group[0][i, :int(group[1][i])]
+                _deliver(r.future, (ids[i][at], sc[i][at]))
 
     _scatter_dense = _scatter_sparse = _scatter_lists     # what _run looks up as "_scatter_" + kind
 

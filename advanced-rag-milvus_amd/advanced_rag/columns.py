@@ -16,9 +16,15 @@ on the prefix need the full strings.  Keys are built lazily, per column, on firs
 For MMR diversification on the device (csrc/mmr.h) the `content` column can hand out its rows' TOKEN SETS
 (`TokenSetColumn`): the reference compares `set(content.lower().split())` of two hits; here every distinct token of the
 collection gets an int32 id and a row keeps its ids, sorted — built lazily as well, and never part of a snapshot.
+
+For grouping search (csrc/group.h) every groupable field hands out an int64 GROUP KEY per row (`GroupKeyColumn`): an
+integer field is its own key; the value of a string field gets its ordinal in a collection-wide dictionary, in first-seen
+order — equal keys mean equal values.  Built lazily, extended by later appends, gathered (never renumbered) by compact(),
+and never part of a snapshot: the TokenSetColumn pattern.
 """
 from __future__ import annotations
 
+import threading
 from typing import Any, Dict, Iterable, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -27,6 +33,18 @@ STRING_COLUMNS = ("id", "doc_id", "content", "timestamp", "metadata_json")
 INT_COLUMNS = ("chunk_index", "token_count")
 FLOAT_COLUMNS = ("entropy", "redundancy", "domain_density")
 KEY_BYTES = 16
+GROUP_STRING_FIELDS = {"doc_id": "doc_id", "id": "id", "chunk_id": "id", "timestamp": "timestamp"}   # field -> column
+
+
+def check_group_field(field) -> str:
+    """The field of a grouping search, or ValueError: float fields cannot be grouped on (Milvus refuses them too), and a
+    field the schema does not have, or whose values are free text (content, metadata_json), is unknown."""
+    if field in FLOAT_COLUMNS:
+        raise ValueError(f"group_by_field {field!r} is a float field: grouping needs an integer or a string field")
+    if field not in INT_COLUMNS and field not in GROUP_STRING_FIELDS:
+        raise ValueError(f"unknown group_by_field: {field!r} (expected one of "
+                         f"{', '.join(sorted(set(INT_COLUMNS) | set(GROUP_STRING_FIELDS)))})")
+    return field
 
 
 def _keep_mask(keep, n: int) -> np.ndarray:
@@ -286,6 +304,49 @@ class TokenSetColumn:
         return self._indptr.nbytes + self._tok.nbytes
 
 
+class GroupKeyColumn:
+    """Append-only int64 group key per global row of one string column: the ordinal of the row's value in one dictionary
+    per collection and field, value -> ordinal in first-seen order.  Rows are keyed once; an ordinal, once given, never
+    changes (compact() gathers the keys and keeps the dictionary), so equal keys stay equal and distinct ones distinct."""
+
+    def __init__(self):
+        self.ordinals: Dict[str, int] = {}
+        self._keys = np.empty(0, dtype=np.int64)
+        self._n = 0
+
+    def __len__(self) -> int:
+        return self._n
+
+    def extend(self, values: Iterable[str]) -> None:
+        ordinals = self.ordinals
+        new = [ordinals.setdefault(v, len(ordinals)) for v in values]
+        if not new:
+            return
+        self._keys = _grown(self._keys, self._n + len(new))
+        self._keys[self._n: self._n + len(new)] = new
+        self._n += len(new)
+
+    def compact(self, keep: np.ndarray) -> None:
+        """Drop the rows whose entry of the boolean `keep` is False.  The dictionary stays: an ordinal never changes."""
+        self._keys = self._keys[: self._n][_keep_mask(keep, self._n)]
+        self._n = self._keys.shape[0]
+
+    def sync(self, column: "StringColumn") -> "GroupKeyColumn":
+        """Key the rows of `column` this column does not hold yet."""
+        step = 1 << 16       # bounded temporaries
+        for a in range(self._n, len(column), step):
+            self.extend(column[a: min(len(column), a + step)])
+        return self
+
+    def array(self) -> np.ndarray:
+        """int64 [rows] view (no copy)."""
+        return self._keys[: self._n]
+
+    @property
+    def nbytes(self) -> int:
+        return self._keys.nbytes
+
+
 class PayloadColumns:
     """dict-like: columns["id"][row], columns["entropy"].array(), len(columns["id"])."""
 
@@ -294,6 +355,10 @@ class PayloadColumns:
         self._c.update({k: NumericColumn(np.int64) for k in INT_COLUMNS})
         self._c.update({k: NumericColumn(np.float32) for k in FLOAT_COLUMNS})
         self._token_sets: Optional[TokenSetColumn] = None    # derived from "content" on first use; not a payload field
+        self._group_keys: Dict[str, GroupKeyColumn] = {}     # string column -> its rows' group keys, on first use
+        # the lazy build and the extension of a group-key column are read-modify-write: the searches of one request run in
+        # different threads (a sharded manager has no front) and ask for the same field at once
+        self._group_lock = threading.Lock()
 
     def __getitem__(self, name: str):
         return self._c["id" if name == "chunk_id" else name]
@@ -327,15 +392,32 @@ class PayloadColumns:
             self._token_sets = TokenSetColumn()
         return self._token_sets.sync(self._c["content"])
 
+    def group_keys(self, field: str) -> np.ndarray:
+        """int64 group key of every row for a grouping search on `field` (a view, no copy): the column itself for an
+        integer field, dictionary ordinals (GroupKeyColumn) for a string field — built on first use, extended by what
+        later appends added.  ValueError for a float or an unknown field."""
+        check_group_field(field)
+        if field in INT_COLUMNS:
+            return self._c[field].array()
+        name = GROUP_STRING_FIELDS[field]
+        with self._group_lock:
+            col = self._group_keys.get(name)
+            if col is None:
+                col = self._group_keys[name] = GroupKeyColumn()
+            return col.sync(self._c[name]).array()
+
     def compact(self, keep: np.ndarray) -> None:
         """Drop the rows whose entry of the boolean `keep` (one per row) is False from every column, one column at a
-        time (the peak extra memory is one column), and from the token sets as far as they are built."""
+        time (the peak extra memory is one column), and from the token sets and the group keys as far as they are built."""
         keep = _keep_mask(keep, self.n_rows)
         for col in self._c.values():
             col.compact(keep)
         if self._token_sets is not None:
             n = len(self._token_sets)
             self._token_sets.compact(keep[:n])
+        with self._group_lock:
+            for col in self._group_keys.values():
+                col.compact(keep[:len(col)])
 
     def filter_columns(self) -> Dict[str, np.ndarray]:
         """What filters.evaluate takes: numpy arrays per field (string fields as unicode arrays — fine for small

@@ -22,6 +22,14 @@ class RetrievalConstants:
     DEFAULT_MMR_LAMBDA = 0.7
 
 
+class GroupingConstants:
+    # window of a grouping search (search(..., group_by_field=F)): the ranking is read K' = min(HR_MAX_TOPK,
+    # GROUP_WINDOW_FACTOR * top_k) rows at a time.  An unmeasured starting value: the answer is exact for any factor >= 1
+    # (a window that ends before the top_k-th group is continued without the groups it showed); the factor only trades the
+    # cost of a wider window against the chance of a continuation round.
+    GROUP_WINDOW_FACTOR = 4
+
+
 class PerformanceConstants:
     TARGET_LATENCY_MS = 80.0
     DEFAULT_MAX_CONCURRENCY = 64
@@ -67,3 +75,6 @@ class IndexingConstants:
 class APIConstants:
     MAX_DOCUMENT_TEXT_LENGTH = 1_000_000
     MAX_QUERY_LENGTH = 10_000
+
+
+GROUP_WINDOW_FACTOR = GroupingConstants.GROUP_WINDOW_FACTOR

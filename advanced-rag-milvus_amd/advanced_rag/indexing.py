@@ -35,8 +35,8 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 
 from . import filters as _filters
-from .columns import FLOAT_COLUMNS, PayloadColumns
-from .constants import IndexingConstants
+from .columns import FLOAT_COLUMNS, PayloadColumns, check_group_field
+from .constants import GROUP_WINDOW_FACTOR, IndexingConstants
 from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache, get_semantic_cache
 from ._native import HR_MAX_TOPK   # importing the binding module does not load the library
 from .shards import PartialAppend, ShardSet
@@ -150,6 +150,11 @@ class MilvusIndexManager:
         self._cols = PayloadColumns()
         self._dev_filters = None
         self._dev_tokens = None    # device_tokens.DeviceTokenSets: the token sets of "content" in HBM, on first use
+        self._dev_groups = None    # device_groups.DeviceGroupKeys: the group keys of the fields grouped on, on first use
+        # grouping searches answered by the blocking loop: searches, windows searched, windows that ended before the
+        # top_k-th group and were continued without the groups they showed
+        self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0}
+        self._stats_lock = threading.Lock()    # the loop runs in worker threads and in the front's thread at once
         self._deleted: Optional[np.ndarray] = None
         self._mask_cache: Dict[Any, Optional[np.ndarray]] = {}   # (expr, rows, delete epoch) -> boolean row filter
         self._delete_epoch = 0
@@ -209,14 +214,15 @@ class MilvusIndexManager:
 
     def _forget_masks(self, rebuild_filters: bool):
         """Drop every cached row mask, host and HBM: the rows changed.  After an APPEND (_append_payload, add_rows) the device
-        filter columns and the token sets stay: they grow in place, every row is uploaded once.  After the row space was REPLACED
-        (attach_shards, add_rows_synthetic, load_snapshot) they go too (rebuild_filters) and are rebuilt on first use.  close() drops
-        HBM masks only."""
+        filter columns, the token sets and the group keys stay: they grow in place, every row is uploaded once.  After the row
+        space was REPLACED (attach_shards, add_rows_synthetic, load_snapshot, compact) they go too (rebuild_filters) and are
+        rebuilt on first use.  close() drops HBM masks only."""
         self._mask_cache.clear()
         self._dev_masks.clear()
         if rebuild_filters:
             self._dev_filters = None
             self._dev_tokens = None
+            self._dev_groups = None
 
     def _initialize_collections(self):
         self._main = ShardSet([self._shard_handle("main", d) for d in self.devices])
@@ -304,6 +310,40 @@ class MilvusIndexManager:
             from .device_tokens import DeviceTokenSets
             self._dev_tokens = DeviceTokenSets(None if self._synthetic_rows else self._cols, self._main.first.device)
         return self._dev_tokens
+
+    def _group_keys_on_device(self):
+        """The HBM mirror of the rows' group keys (what hr_group_select_dev / hr_mask_drop_groups_dev read), on the main
+        shard's device."""
+        with self._mask_lock:
+            if self._dev_groups is None:
+                from .device_groups import DeviceGroupKeys
+                self._dev_groups = DeviceGroupKeys(None if self._synthetic_rows else self._cols, self._main.first.device)
+            return self._dev_groups
+
+    def _host_group_keys(self, field: str) -> np.ndarray:
+        """int64 group key per global row on the host (collections whose masks are host arrays: several shards, the
+        torchrun form, CPU tests)."""
+        if self._synthetic_rows:
+            from .device_groups import synthetic_group_keys
+            return synthetic_group_keys(field, self._synthetic_rows)
+        return self._cols.group_keys(field)
+
+    def _count(self, name: str) -> None:
+        with self._stats_lock:
+            self.stats[name] += 1
+
+    def _check_group_request(self, group_by_field, group_size) -> None:
+        """ValueError for what a grouping search does not serve, before anything is searched."""
+        if group_size != 1:
+            raise ValueError(f"group_size={group_size!r} is not supported: only group_size=1 (the best row of every group) is "
+                             "built — a window of the ranking cannot prove a group's later members exact")
+        if group_by_field is not None:
+            if not isinstance(group_by_field, str):
+                raise ValueError(f"unknown group_by_field: {group_by_field!r}")
+            check_group_field(group_by_field)
+            if self._synthetic_rows:
+                from .device_groups import check_synthetic_group_field
+                check_synthetic_group_field(group_by_field)
 
     def _global_device_mask(self, expr: Optional[str]):
         """Packed mask over GLOBAL rows of `expr` + tombstones as a CUDA tensor (None = all rows), evaluated on the
@@ -805,10 +845,14 @@ class MilvusIndexManager:
             raise ValueError(f"metric_type {metric} does not match collection {coll.name} ({coll.metric})")
         return params
 
-    def _search_lists_blocking(self, query, collection_name: str, top_k: int, filters: Optional[str], params: Dict):
-        """(row ids [k], scores [k]) of ONE query through the host forms (which escalate until the list is proven)."""
+    def _search_lists_blocking(self, query, collection_name: str, top_k: int, filters: Optional[str], params: Dict,
+                               group_by_field: Optional[str] = None):
+        """(row ids [k], scores [k]) of ONE query through the host forms (which escalate until the list is proven).  With
+        group_by_field: the exact grouped ranking (_grouped_lists_blocking), as many entries as there are groups, at most k."""
         coll = self.collections[collection_name]
         drop = float((params.get("params") or params).get("drop_ratio_search", 0.0))
+        if group_by_field is not None:
+            return self._grouped_lists_blocking(query, coll, int(top_k), filters, drop, group_by_field)
         if getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and self._filters_on_device() is not None:
             # one local GPU shard: the mask never leaves the device
             h = coll.handle.first
@@ -828,12 +872,107 @@ class MilvusIndexManager:
             ids, sc = coll.handle.search_dense(dense_rows_host([query]), top_k, mask)
         return ids[0], sc[0]
 
+    @staticmethod
+    def group_window(top_k: int) -> int:
+        """Rows of the ranking a grouping search reads at a time: K' = min(HR_MAX_TOPK, GROUP_WINDOW_FACTOR * top_k)."""
+        if not 1 <= top_k <= HR_MAX_TOPK:
+            raise ValueError(f"a grouping search takes 1 <= top_k <= HR_MAX_TOPK = {HR_MAX_TOPK}, got {top_k}")
+        return min(HR_MAX_TOPK, GROUP_WINDOW_FACTOR * top_k)
+
+    def _grouped_lists_blocking(self, query, coll, top_k: int, filters: Optional[str], drop: float, field: str):
+        """The exact grouped ranking of ONE query: the first top_k rows of the collection's ranking (filter expression and
+        tombstones applied) whose group key differs from the key of every row before them -> (rows, scores), as many as
+        there are groups, at most top_k.
+
+        The ranking is read a window of K' rows at a time through the host forms, which are exact.  A window that holds
+        top_k new groups, or fewer than K' rows (the search ran out of qualifying rows), ends the loop.  Otherwise the
+        first row of every group of the window has been taken, so no other row of those groups can ever be selected:
+        they leave the working mask and the next window is searched without them.  The remaining ranking is the old one
+        minus rows that could not be selected, so the concatenation is the grouped ranking; every continuation removes at
+        least one whole group, so the loop ends."""
+        window = self.group_window(top_k)
+        n = self.num_rows
+        sparse = coll.kind == "sparse"
+        on_device = getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and \
+            self._filters_on_device() is not None
+        q_host = None if sparse else dense_rows_host([query])
+        rows_out: List[np.ndarray] = []
+        scores_out: List[np.ndarray] = []
+        got = 0
+        self._count("group_searches")
+        if on_device:
+            import torch
+            from .device_filters import mask_bytes
+            h = coll.handle.first
+            dev = torch.device("cuda", h.device)
+            nat = self._native
+            with torch.cuda.device(dev):
+                keys = self._group_keys_on_device().tensor(field, n)
+                base = self._device_row_mask(filters, coll.kind)     # cached and shared: never written here
+                work = None                                          # this query's mask once a group has been dropped
+                pos = torch.empty(window, dtype=torch.int32, device=dev)
+                sel_keys = torch.empty(window, dtype=torch.int64, device=dev)
+                counts = torch.empty(2, dtype=torch.int32, device=dev)    # [0] groups selected, [1] the flag
+                stream = torch.cuda.current_stream(dev)
+                while True:
+                    mask = work if work is not None else base
+                    ptr = mask.data_ptr() if mask is not None else 0
+                    if sparse:
+                        ids, sc = h.search_sparse([query], window, drop, None, ptr)
+                    else:
+                        ids, sc = h.search_dense(q_host, window, None, ptr)
+                    self._count("group_rounds")
+                    want = top_k - got
+                    d_ids = torch.from_numpy(ids).to(dev)
+                    nat.group_select_dev(d_ids.data_ptr(), 0, 1, window, keys.data_ptr(), n, 0, want, pos.data_ptr(),
+                                         sel_keys.data_ptr(), counts.data_ptr(), counts.data_ptr() + 4, stream.cuda_stream)
+                    n_sel, flag = (int(x) for x in counts.cpu().tolist())     # synchronises the stream
+                    at = pos[:n_sel].cpu().numpy()
+                    rows_out.append(ids[0][at])
+                    scores_out.append(sc[0][at])
+                    got += n_sel
+                    if flag == 1:
+                        break
+                    if work is None:
+                        work = torch.empty(mask_bytes(n), dtype=torch.uint8, device=dev)
+                    nat.mask_drop_groups_dev(ptr, work.data_ptr(), n, keys.data_ptr(), sel_keys.data_ptr(), n_sel,
+                                             stream.cuda_stream)
+                    stream.synchronize()      # the search reads the mask on a stream of its own
+                    self._count("group_continuations")
+        else:
+            keys = self._host_group_keys(field)
+            keep = self._row_mask(filters)                           # cached and shared: never written here
+            while True:
+                if sparse:
+                    ids, sc = coll.handle.search_sparse([query], window, drop, keep)
+                else:
+                    ids, sc = coll.handle.search_dense(q_host, window, keep)
+                self._count("group_rounds")
+                want = top_k - got
+                ids, sc = ids[0], sc[0]
+                n_valid = int(np.argmax(ids < 0)) if (ids < 0).any() else ids.shape[0]
+                seen, at = set(), []
+                for i, k in enumerate(keys[ids[:n_valid]].tolist()):
+                    if k not in seen:
+                        seen.add(k)
+                        if len(at) < want:
+                            at.append(i)
+                rows_out.append(ids[at])
+                scores_out.append(sc[at])
+                got += len(at)
+                if len(at) == want or n_valid < window:
+                    break
+                gone = np.isin(keys[:n], np.fromiter(seen, dtype=np.int64, count=len(seen)))
+                keep = ~gone if keep is None else (keep[:n] & ~gone)
+                self._count("group_continuations")
+        return np.concatenate(rows_out), np.concatenate(scores_out)
+
     def _search_blocking(self, query_embedding, collection_name: str, top_k: int, filters: Optional[str],
-                         search_params: Optional[Dict]) -> List[Dict[str, Any]]:
+                         search_params: Optional[Dict], group_by_field: Optional[str] = None) -> List[Dict[str, Any]]:
         coll = self.collections[collection_name]
         params = self._search_params(coll, search_params)
         query = self._as_sparse_payload(query_embedding) if coll.kind == "sparse" else query_embedding
-        return self._format_hits(*self._search_lists_blocking(query, collection_name, top_k, filters, params))
+        return self._format_hits(*self._search_lists_blocking(query, collection_name, top_k, filters, params, group_by_field))
 
     @staticmethod
     def _search_dense_device(handle, q_dev, top_k: int):
@@ -880,7 +1019,14 @@ class MilvusIndexManager:
         return tuple(sorted((k, v) for k, v in (params.get("params") or {}).items() if isinstance(v, (int, float, str, bool))))
 
     async def search(self, query_embedding, collection_name: str, top_k: int = 20, filters: Optional[str] = None,
-                     search_params: Optional[Dict] = None) -> List[Dict[str, Any]]:
+                     search_params: Optional[Dict] = None, *, group_by_field: Optional[str] = None,
+                     group_size: int = 1) -> List[Dict[str, Any]]:
+        """Collection.search (reference indexing.py:503-525).  group_by_field=F (pymilvus' grouping search): the best row
+        of each of the top_k best groups of field F, in ranking order — exact at any depth; fewer groups than top_k give a
+        shorter list.  F is an integer or a string field of the schema (chunk_index, token_count, doc_id, id / chunk_id,
+        timestamp); only group_size=1 is built."""
+        if group_by_field is not None or group_size != 1:
+            self._check_group_request(group_by_field, group_size)
         if collection_name not in self.collections:
             raise ValueError(f"Collection {collection_name} not found")
         coll = self.collections[collection_name]
@@ -890,12 +1036,12 @@ class MilvusIndexManager:
                 params = self._search_params(coll, search_params)
                 query = self._as_sparse_payload(query_embedding) if coll.kind == "sparse" else query_embedding
                 fut = front.submit_async("sparse" if coll.kind == "sparse" else "dense",
-                                         (collection_name, int(top_k), filters, self._params_key(params)), query)
+                                         (collection_name, int(top_k), filters, self._params_key(params), group_by_field), query)
                 ids, sc = await asyncio.wait_for(fut, timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
                 return self._format_hits(ids, sc)
             return await asyncio.wait_for(
                 asyncio.to_thread(self._search_blocking, query_embedding, collection_name, top_k, filters,
-                                  search_params),
+                                  search_params, group_by_field),
                 timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
         except asyncio.TimeoutError:
             logging.error("shard search timeout for collection %s", collection_name)

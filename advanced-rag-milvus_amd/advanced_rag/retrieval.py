@@ -32,6 +32,7 @@ logger = logging.getLogger(__name__)
 _TROUBLE_WORDS = ("error", "exception", "stack trace", "failed", "failure", "bug")
 _SUMMARY_WORDS = ("summarize", "summary", "tl;dr", "overview")
 _METHOD_ORDER = ("semantic", "sparse", "domain")
+FUSED_GROUP_FIELDS = ("doc_id", "chunk_index", "timestamp", "id", "chunk_id")   # what a hit dict shows of the groupable fields
 _METHODS_OF_MASK = tuple(tuple(m for b, m in enumerate(_METHOD_ORDER) if (mask >> b) & 1) for mask in range(8))
 
 
@@ -72,8 +73,20 @@ class RetrievalConfig:
     enable_learned_ranker: bool = False
     semantic_search_params: Optional[Dict] = None
     sparse_search_params: Optional[Dict] = None
+    # grouping search (pymilvus' group_by_field): every modality ranks the best chunk of each group (2 x top_k documents
+    # instead of 2 x top_k chunks) and the fused list keeps the first hit of every group.  None = chunks, as the reference.
+    group_by_field: Optional[str] = None
 
     def __post_init__(self):
+        if self.group_by_field is not None:
+            # refused here, once: inside retrieve() a modality whose search raises degrades to "no hits".  token_count can be
+            # grouped on by search(), but a hit does not show it, so the fused list could not be deduplicated on it
+            from .columns import check_group_field
+            if not isinstance(self.group_by_field, str):
+                raise ValueError(f"unknown group_by_field: {self.group_by_field!r}")
+            if check_group_field(self.group_by_field) not in FUSED_GROUP_FIELDS:
+                raise ValueError(f"group_by_field {self.group_by_field!r} is not shown by a hit: retrieve() groups on one of "
+                                 f"{', '.join(FUSED_GROUP_FIELDS)}")
         if self.semantic_search_params is None:
             self.semantic_search_params = {"metric_type": "COSINE", "params": {"ef": 64}}
         if self.sparse_search_params is None:
@@ -133,7 +146,7 @@ class HybridRetriever:
             return RetrievalConfig(hybrid_alpha=base.hybrid_alpha, top_k=clamp_k(top_k),
                                    rerank_top_k=clamp_rerank(rerank_k), enable_reranking=rerank,
                                    dense_weight=base.dense_weight, sparse_weight=base.sparse_weight,
-                                   enable_mmr=mmr, mmr_lambda=lam)
+                                   enable_mmr=mmr, mmr_lambda=lam, group_by_field=base.group_by_field)
 
         return {
             "default": base,
@@ -219,6 +232,8 @@ class HybridRetriever:
         (a manager without the entry point; a request it declined; MMR, which needs the whole fused list, unless the
         manager diversifies on the device: `mmr_on_device`)."""
         one_round = getattr(self.index_manager, "hybrid_search", None)
+        if self.config.group_by_field is not None:
+            return None        # the one-round path does not group: the general path serves the request
         if one_round is None or (self.config.enable_mmr and not getattr(self.index_manager, "mmr_on_device", False)):
             return None
         known = getattr(self.index_manager, "collections", None)
@@ -259,9 +274,10 @@ class HybridRetriever:
         return fused
 
     async def _tagged_search(self, method: str, embedding, collection: str, top_k: int, filters, params):
+        group = {"group_by_field": self.config.group_by_field} if self.config.group_by_field is not None else {}
         try:
             hits = await self.index_manager.search(query_embedding=embedding, collection_name=collection,
-                                                   top_k=top_k, filters=filters, search_params=params)
+                                                   top_k=top_k, filters=filters, search_params=params, **group)
         except Exception:
             return []  # a failing modality degrades to "no hits" (reference :355-358, :387-389, :411-413)
         for h in hits:
@@ -334,9 +350,26 @@ class HybridRetriever:
 
         now = datetime.utcnow()
         fused = [self._finish_fused_hit(payload[doc_id], score, seen_in, now) for doc_id, score, seen_in in ranked]
+        if self.config.group_by_field is not None:
+            fused = self._first_per_group(fused, self.config.group_by_field)
         if self.config.enable_mmr and fused:
             return self._mmr_diversify(fused, self.config.top_k, self.config.mmr_lambda)
         return fused
+
+    @staticmethod
+    def _first_per_group(fused: List[Dict[str, Any]], field: str) -> List[Dict[str, Any]]:
+        """The first hit of every group, in fused order.  The modality lists are grouped already, but the fusion goes by
+        chunk id: two chunks of one document can arrive from different modalities.  Before MMR and before the cut."""
+        seen: Set[Any] = set()
+        out = []
+        for hit in fused:
+            key = hit["id"] if field in ("id", "chunk_id") else (hit.get("metadata") or {}).get(field)
+            if key is None:            # another manager's hit without the field: a group of its own
+                out.append(hit)
+            elif key not in seen:
+                seen.add(key)
+                out.append(hit)
+        return out
 
     @staticmethod
     def _finish_fused_hit(hit: Dict[str, Any], score: float, seen_in, now) -> Dict[str, Any]:

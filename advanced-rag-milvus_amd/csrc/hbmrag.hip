@@ -33,6 +33,7 @@
 #include "filter.h"
 #include "finish.h"
 #include "fuse.h"
+#include "group.h"
 #include "mmr.h"
 #include "text.h"
 #include "select.h"
@@ -1304,7 +1305,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 10700; }  // 1.7.0: hr_compact
+int hr_version(void) { return 10800; }  // 1.8.0: hr_group_select_dev, hr_mask_drop_groups_dev
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2185,6 +2186,37 @@ int hr_mmr_select_dev(const int64_t* d_ids, const double* d_scores, const int32_
                        d_tok, tok_rows, first_row, d_lambda, k_out, d_out_pos, d_out_n);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "mmr_select_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+int hr_group_select_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_in, const int64_t* d_keys, int64_t key_rows,
+                        int64_t first_row, int k_out, int32_t* d_out_pos, int64_t* d_out_keys, int32_t* d_out_n, int32_t* d_flags,
+                        void* stream) {
+    if (B < 0 || k_in <= 0 || k_out <= 0 || k_out > k_in || key_rows < 0 || first_row < 0) return fail(nullptr, HR_EINVAL, "bad group sizes");
+    if (k_in > kFuseMax) return fail(nullptr, HR_ELIMIT, "k_in exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+    if (B == 0) return HR_OK;
+    if (!d_ids || !d_out_pos || !d_out_n) return fail(nullptr, HR_EINVAL, "null buffer");
+    if (key_rows > 0 && !d_keys) return fail(nullptr, HR_EINVAL, "key_rows > 0 needs the key column");
+    hipLaunchKernelGGL(group_select_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, d_ids, d_n, k_in, d_keys, key_rows, first_row,
+                       k_out, d_out_pos, d_out_keys, d_out_n, d_flags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "group_select_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+int hr_mask_drop_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out, int64_t n_rows, const int64_t* d_keys,
+                            const int64_t* d_drop, int n_drop, void* stream) {
+    if (n_rows < 0 || n_drop < 0) return fail(nullptr, HR_EINVAL, "bad group mask sizes");
+    if (n_drop > kFuseMax) return fail(nullptr, HR_ELIMIT, "n_drop exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+    if (n_rows == 0) return HR_OK;
+    if (!d_mask_out || !d_keys || (n_drop > 0 && !d_drop)) return fail(nullptr, HR_EINVAL, "null buffer");
+    if (((uintptr_t)d_mask_in | (uintptr_t)d_mask_out) & 7) return fail(nullptr, HR_EINVAL, "mask buffers must be 8-byte aligned");
+    const int64_t n_words = (n_rows + 63) / 64;
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_words + 3) / 4, 1024));
+    hipLaunchKernelGGL(mask_drop_groups_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_mask_in,
+                       (unsigned long long*)d_mask_out, n_rows, d_keys, d_drop, n_drop);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "mask_drop_groups_kernel: %s", hipGetErrorString(e));
     return HR_OK;
 }
 

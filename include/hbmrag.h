@@ -305,6 +305,38 @@ HR_API int hr_mmr_select_dev(const int64_t* d_ids, const double* d_scores, const
                       const int64_t* d_tok_indptr, const int32_t* d_tok, int64_t tok_rows, int64_t first_row,
                       const double* d_lambda, int k_out, int32_t* d_out_pos, int32_t* d_out_n, void* stream);
 
+/* ---- grouping search: Collection.search(..., group_by_field=F) ---------------------------------------------------
+ * Milvus' grouping search returns the best entity of each of the k best groups.  A group key is an int64 per row
+ * (d_keys[r - first_row], key_rows entries): an integer field as it is, or the ordinal of a string field's value in a
+ * collection-wide dictionary (advanced_rag/columns.py).  Neither entry point reads a score, so descending, ascending
+ * (HR_METRIC_L2) and fp64 fused lists are served alike.
+ *
+ * hr_group_select_dev: the first entry of every group of B ranked lists, in list order (one block per query).
+ *   d_ids [B][k_in]; the valid prefix of list q is d_n[q] entries (clamped into [0, k_in]), or with d_n == NULL the
+ *   entries before the first id < 0.  k_out <= k_in <= 3 * HR_MAX_TOPK (HR_ELIMIT beyond: fused lists fit, as in
+ *   hr_mmr_select_dev).  An id outside [first_row, first_row + key_rows) has no key and is a group of its own (two
+ *   equal such ids are two groups).  d_keys may be NULL when key_rows == 0 (it is not read then).
+ *   Out: d_out_pos [B][k_out] positions into the query's list, ascending, -1 padded; d_out_keys (may be NULL)
+ *   [B][k_out] the keys of the selected entries (the id itself for an entry without a key; 0 padded) — such an id is
+ *   NOT a key: a caller whose lists can hold ids outside the key column must not hand d_out_keys on to
+ *   hr_mask_drop_groups_dev as they are, or every row whose key equals that id is dropped; d_out_n[B];
+ *   d_flags[B] (may be NULL) = 1 iff d_out_n[q] == k_out or the list held fewer than k_in valid entries (the search
+ *   behind it ran out of qualifying rows), else 0: the window ended before the k_out-th group, and every distinct key
+ *   of the window is among the selected.  The result is a function of the inputs alone (positions decide, no race).
+ * hr_mask_drop_groups_dev: bit r of d_mask_out = bit r of d_mask_in AND "d_keys[r] is not among the n_drop keys at
+ *   d_drop" for the n_rows rows of a packed row mask (bit r%8 of byte r/8; both buffers hold 8 * ceil(n_rows / 64)
+ *   bytes, 8-byte aligned; bits at and beyond n_rows are written 0).  d_mask_in == NULL = all rows pass; the two
+ *   buffers may be the same.  d_drop is a DEVICE pointer: any order, duplicates allowed, 0 <= n_drop <=
+ *   3 * HR_MAX_TOPK (HR_ELIMIT beyond).
+ * Together they continue a grouping search exactly: while a window of the ranking ends before the k-th group, the
+ * groups it showed are dropped from the mask and the search is repeated — the dropped rows could never be selected
+ * again.  Bad arguments: HR_EINVAL.  B == 0 / n_rows == 0: HR_OK, nothing is launched.  Asynchronous on `stream`. */
+HR_API int hr_group_select_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_in,
+                        const int64_t* d_keys, int64_t key_rows, int64_t first_row, int k_out,
+                        int32_t* d_out_pos, int64_t* d_out_keys, int32_t* d_out_n, int32_t* d_flags, void* stream);
+HR_API int hr_mask_drop_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out, int64_t n_rows,
+                            const int64_t* d_keys, const int64_t* d_drop, int n_drop, void* stream);
+
 /* Everything after the per-shard lists of a query batch in ONE launch (one block per query): [hr_merge_topk_dev of
  * every modality's exchanged lists] -> hr_fuse_rrf_dev -> [hr_rerank_linear_dev]; results are bit-identical to the
  * separate calls (reference retrieval.py:421-491 fusion, :518-563 rerank, after the server-side shard merge of
