@@ -70,6 +70,8 @@ _SIGNATURES = {
                                          _c.c_void_p]),
     "hr_search_sparse_dmask": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
                                           _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_filter_eval_expr_dev": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                           _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_filter_eval_dev": (_c.c_int, [_c.c_void_p, _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                       _c.c_void_p, _c.c_void_p]),
     "hr_bm25_encode_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_int,
@@ -515,6 +517,29 @@ def filter_eval_dev(terms: Sequence["FilterTerm"], n_rows: int, d_deleted: int, 
     arr = (FilterTerm * max(len(terms), 1))(*terms)
     rc = L.hr_filter_eval_dev(ctypes.byref(arr), len(terms), n_rows, _vp(d_deleted) if d_deleted else None, _vp(d_mask),
                               _vp(d_undecided), _vp(d_counts), _vp(stream) if stream else None)
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+class FilterLeaf(ctypes.Structure):
+    """hr_filter_leaf of include/hbmrag.h."""
+    _fields_ = [("term", FilterTerm), ("set", _c.c_void_p), ("n_set", _c.c_int32), ("reserved", _c.c_int32)]
+
+
+HR_OP_IN = 6
+HR_FILTER_AND, HR_FILTER_OR, HR_FILTER_NOT = -1, -2, -3
+HR_MAX_FILTER_TERMS, HR_MAX_FILTER_PROGRAM, HR_MAX_FILTER_SET_BYTES = 16, 64, 65536
+
+
+def filter_eval_expr_dev(leaves: Sequence["FilterLeaf"], program: Sequence[int], n_rows: int, d_deleted: int, d_mask: int,
+                         d_undecided: int, d_counts: int, stream: int = 0):
+    """hr_filter_eval_expr_dev: leaves + postfix program -> packed row mask (include/hbmrag.h)."""
+    L = load_library()
+    arr = (FilterLeaf * max(len(leaves), 1))(*leaves)
+    prog = (_c.c_int32 * max(len(program), 1))(*program)
+    rc = L.hr_filter_eval_expr_dev(ctypes.byref(arr), len(leaves), ctypes.byref(prog), len(program), n_rows,
+                                   _vp(d_deleted) if d_deleted else None, _vp(d_mask), _vp(d_undecided), _vp(d_counts),
+                                   _vp(stream) if stream else None)
     if rc != 0:
         _raise_global(L, rc)
 

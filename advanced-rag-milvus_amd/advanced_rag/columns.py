@@ -233,6 +233,14 @@ class StringColumn:
         return out
 
 
+    def member_rows(self, rows: np.ndarray, values: Sequence[str]) -> np.ndarray:
+        """Exact `row in values` for the given rows: compare_rows' counterpart for a membership list."""
+        members = {v.encode("utf-8") for v in values}
+        whole = self._buf
+        return np.fromiter((whole[self._off[r]: self._off[r + 1]].tobytes() in members
+                            for r in np.asarray(rows, dtype=np.int64).tolist()), dtype=bool, count=len(rows))
+
+
 class TokenSetColumn:
     """Append-only CSR over global rows: row r holds the sorted, unique int32 ids of `set(content.lower().split())`
     (Python's own lower / split: Unicode case mapping and whitespace are the reference's, retrieval.py:495).  Ids come

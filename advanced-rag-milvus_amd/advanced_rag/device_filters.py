@@ -3,7 +3,8 @@
 The reference hands `expr` to Milvus (indexing.py:503-525) which evaluates it server-side over the scalar fields of
 the schema (indexing.py:191-225).  Here the payload columns live on the host (columns.py) and a COPY of the
 filterable ones lives in HBM — uploaded the first time a field is filtered on, extended by what later appends
-added — so that an expression becomes one `hr_filter_eval_dev` launch that writes the packed row mask the search
+added — so that an expression becomes one `hr_filter_eval_dev` launch (a conjunction of comparisons) or one
+`hr_filter_eval_expr_dev` launch (`in` lists, or, not, parentheses: leaves, sorted sets and a postfix program) that writes the packed row mask the search
 kernels take (no row-sized transfer in either direction; the first filtered request at 10M rows took 44 ms on the
 host, the mask was re-uploaded with every search).
 
@@ -45,12 +46,21 @@ def pack_mask(keep, n_rows: int):
     return (padded.view(-1, 8).to(torch.int32) * weights[None, :]).sum(dim=1).to(torch.uint8)
 
 
+class _Program:
+    """What an expression beyond the flat conjunction carries besides its leaves: the postfix codes over them, the tree
+    (undecided rows are settled on it) and the device tensors of the leaves' sets (alive until the stream has passed)."""
+
+    def __init__(self, codes: List[int], tree, sets: list):
+        self.codes, self.tree, self.sets = codes, tree, sets
+
+
 class DeviceFilters:
     def __init__(self, columns, device: int):
         self.columns = columns                  # PayloadColumns, or None for a payload-free (synthetic) collection
         self.device = int(device)
         self._dev: Dict[str, Tuple[Any, int]] = {}   # column -> (device tensor with spare capacity, rows uploaded)
-        self.stats = {"evaluations": 0, "undecided_rows": 0, "uploaded_bytes": 0}
+        # expr_evaluations: the evaluations among them that took hr_filter_eval_expr_dev (anything but a flat conjunction)
+        self.stats = {"evaluations": 0, "expr_evaluations": 0, "undecided_rows": 0, "uploaded_bytes": 0}
         # one evaluation at a time: the column tensors are owned by `_dev` alone, so a second thread that re-uploads a
         # column (the dense and the sparse search of an uncoalesced retrieve() evaluate a new expression concurrently)
         # would free the tensor the first thread's kernel is about to read
@@ -93,43 +103,123 @@ class DeviceFilters:
         return self._tensor(field, lambda a, b: col.array()[a:b], n)
 
     # ------------------------------------------------------------------ expression -> terms
-    def _terms(self, expr: str, n: int) -> Tuple[List["nat.FilterTerm"], List[Tuple[str, str, str]]]:
+    def _term(self, field: str, op: str, value) -> Tuple["nat.FilterTerm", Optional[Tuple[str, str, str]]]:
+        """One comparison as the kernel takes it (no column pointer yet) and, for a string field, what settles its ties."""
+        if self.columns is None and field != "chunk_index":
+            raise ValueError("this shard was bulk-ingested without payload columns: only chunk_index (= row % 10) "
+                             f"can be filtered on, not {[field]}")
+        t = nat.FilterTerm()
+        t.op = nat.FILTER_OPS[op]
+        if field in INT_COLUMNS:
+            if isinstance(value, str):
+                raise ValueError(f"field {field} is numeric; got string {value!r}")
+            value = _filters.numeric_literal(field, op, value, "i")   # ctypes would wrap an int beyond int64 silently
+            if isinstance(value, float):
+                t.kind, t.dval = nat.HR_COL_I64_VS_F64, value
+            else:
+                t.kind, t.ival = nat.HR_COL_I64, value
+        elif field in FLOAT_COLUMNS:
+            if isinstance(value, str):
+                raise ValueError(f"field {field} is numeric; got string {value!r}")
+            t.kind, t.fval = nat.HR_COL_F32, float(_filters.numeric_literal(field, op, value, "f"))
+        elif field in _STRING_FIELDS:
+            if not isinstance(value, str):
+                raise ValueError(f"field {field} is a string column; got {value!r}")
+            t.kind = nat.HR_COL_STR16
+            t.key[0], t.key[1] = StringColumn.key_of(value)
+            return t, (_STRING_FIELDS[field], op, value)
+        else:
+            raise ValueError(f"unknown filter field: {field}")
+        return t, None
+
+    def _terms(self, expr: str, n: int):
+        """-> (terms, string_terms) for a flat conjunction of comparisons (hr_filter_eval_dev, as ever), or
+        (leaves, _Program) for every other expression (hr_filter_eval_expr_dev)."""
         # every term is checked and built before the first column is touched: an expression that is refused (a literal
         # that would wrap in its field, a type mismatch, an unknown field, too many terms) uploads nothing
-        terms, string_terms, fields = [], [], []
-        for field, op, value in _filters.parse(expr):
-            if self.columns is None and field != "chunk_index":
-                raise ValueError("this shard was bulk-ingested without payload columns: only chunk_index (= row % 10) "
-                                 f"can be filtered on, not {[field]}")
-            t = nat.FilterTerm()
-            t.op = nat.FILTER_OPS[op]
-            if field in INT_COLUMNS:
-                if isinstance(value, str):
-                    raise ValueError(f"field {field} is numeric; got string {value!r}")
-                value = _filters.numeric_literal(field, op, value, "i")   # ctypes would wrap an int beyond int64 silently
-                if isinstance(value, float):
-                    t.kind, t.dval = nat.HR_COL_I64_VS_F64, value
-                else:
-                    t.kind, t.ival = nat.HR_COL_I64, value
-            elif field in FLOAT_COLUMNS:
-                if isinstance(value, str):
-                    raise ValueError(f"field {field} is numeric; got string {value!r}")
-                t.kind, t.fval = nat.HR_COL_F32, float(_filters.numeric_literal(field, op, value, "f"))
-            elif field in _STRING_FIELDS:
-                if not isinstance(value, str):
-                    raise ValueError(f"field {field} is a string column; got {value!r}")
-                t.kind = nat.HR_COL_STR16
-                t.key[0], t.key[1] = StringColumn.key_of(value)
-                string_terms.append((_STRING_FIELDS[field], op, value))
+        flat, tree = _filters.lower(expr)
+        if tree is None:
+            terms, string_terms, fields = [], [], []
+            for field, op, value in flat:
+                t, settle = self._term(field, op, value)
+                if settle is not None:
+                    string_terms.append(settle)
+                terms.append(t)
+                fields.append(field)
+            if len(terms) > 16:
+                raise ValueError("a filter expression may hold up to 16 terms")
+            for t, field in zip(terms, fields):
+                t.col = self._column(field, n).data_ptr()
+            return terms, string_terms
+        leaves, fields, sets, program = [], [], [], []
+
+        def emit(node):
+            if node[0] in ("and", "or"):
+                emit(node[1])
+                emit(node[2])
+                program.append(nat.HR_FILTER_AND if node[0] == "and" else nat.HR_FILTER_OR)
+            elif node[0] == "not":
+                emit(node[1])
+                program.append(nat.HR_FILTER_NOT)
             else:
-                raise ValueError(f"unknown filter field: {field}")
-            terms.append(t)
-            fields.append(field)
-        if len(terms) > 16:
-            raise ValueError("a filter expression may hold up to 16 terms")
-        for t, field in zip(terms, fields):
-            t.col = self._column(field, n).data_ptr()
-        return terms, string_terms
+                program.append(len(leaves))
+                leaf, members = nat.FilterLeaf(), None
+                if node[0] == "cmp":
+                    leaf.term = self._term(node[1], node[2], node[3])[0]
+                else:
+                    leaf.term.op, members = nat.HR_OP_IN, self._members(node[1], node[2])
+                    leaf.term.kind = {np.int64: nat.HR_COL_I64, np.float32: nat.HR_COL_F32, np.uint64: nat.HR_COL_STR16}[members.dtype.type]
+                    leaf.n_set = members.shape[0]
+                leaves.append(leaf)
+                fields.append(node[1])
+                sets.append(members)
+
+        emit(tree)
+        set_bytes = sum((m.nbytes + 15) // 16 * 16 for m in sets if m is not None)
+        if len(leaves) > nat.HR_MAX_FILTER_TERMS:
+            raise ValueError(f"a filter expression may hold up to {nat.HR_MAX_FILTER_TERMS} terms (an `in` list is one term)")
+        if len(program) > nat.HR_MAX_FILTER_PROGRAM:
+            raise ValueError(f"a filter expression may hold up to {nat.HR_MAX_FILTER_PROGRAM} terms and operators together")
+        if set_bytes > nat.HR_MAX_FILTER_SET_BYTES:
+            raise ValueError("the `in` lists of one filter expression may hold up to 4096 strings or 8192 integers together "
+                             f"({nat.HR_MAX_FILTER_SET_BYTES} bytes of members; this one has {set_bytes})")
+        import torch
+        dev = torch.device("cuda", self.device)
+        for i, (leaf, field) in enumerate(zip(leaves, fields)):
+            leaf.term.col = self._column(field, n).data_ptr()
+            if sets[i] is not None and sets[i].shape[0]:
+                m = sets[i]
+                sets[i] = torch.from_numpy(m.view(np.int64) if m.dtype == np.uint64 else m).to(dev)   # lives until the stream is synchronised
+                leaf.set = sets[i].data_ptr()
+        return leaves, _Program(program, tree, sets)
+
+    def _members(self, field: str, values) -> np.ndarray:
+        """The set of `field in values` as the kernel searches it: sorted, without duplicates; int64, float32 (no NaN,
+        -0.0 folded into 0.0) or [n, 2] uint64 prefix keys in lexicographic order (literals that share their first 16
+        bytes are one key: such a row is undecided either way)."""
+        if self.columns is None and field != "chunk_index":
+            raise ValueError("this shard was bulk-ingested without payload columns: only chunk_index (= row % 10) "
+                             f"can be filtered on, not {[field]}")
+        if field in INT_COLUMNS:
+            return np.unique(np.asarray(_filters.list_members(field, values, "i"), dtype=np.int64))
+        if field in FLOAT_COLUMNS:
+            m = np.asarray(_filters.list_members(field, values, "f"), dtype=np.float32)
+            return np.unique(m[m == m] + np.float32(0.0))       # x + 0.0: -0.0 becomes 0.0, everything else stays
+        if field in _STRING_FIELDS:
+            keys = sorted({StringColumn.key_of(v) for v in _filters.list_members(field, values, "s")})
+            return np.asarray(keys, dtype=np.uint64).reshape(-1, 2)
+        raise ValueError(f"unknown filter field: {field}")
+
+    def _settle(self, tree, rows: np.ndarray) -> np.ndarray:
+        """The whole tree on the given rows, string leaves on the full strings: which undecided rows pass."""
+        def leaf(node):
+            field = node[1]
+            if field in _STRING_FIELDS:
+                col = self.columns[_STRING_FIELDS[field]]
+                return col.member_rows(rows, node[2]) if node[0] == "in" else col.compare_rows(rows, node[2], node[3])
+            values = rows % 10 if self.columns is None else self.columns[field].array()[rows]
+            return _filters._leaf_mask(node, {field: values})
+        return _filters.evaluate_tree(tree, leaf)
 
     # ------------------------------------------------------------------ evaluation
     def evaluate(self, expr: Optional[str], n_rows: int, deleted: Optional[np.ndarray] = None, stream=None):
@@ -140,7 +230,8 @@ class DeviceFilters:
     def _evaluate_locked(self, expr, n_rows, deleted, stream):
         import torch
         dev = torch.device("cuda", self.device)
-        terms, string_terms = self._terms(expr, n_rows) if expr else ([], [])
+        terms, settle = self._terms(expr, n_rows) if expr else ([], [])
+        program = settle if isinstance(settle, _Program) else None
         mask = torch.empty(mask_bytes(n_rows), dtype=torch.uint8, device=dev)
         und = torch.empty(mask_bytes(n_rows), dtype=torch.uint8, device=dev)
         counts = torch.zeros(2, dtype=torch.int32, device=dev)
@@ -152,18 +243,27 @@ class DeviceFilters:
             d_del = torch.from_numpy(bits).to(dev)
         st = stream if stream is not None else torch.cuda.current_stream(dev)
         with torch.cuda.stream(st):   # the read-backs and the fix-ups below are ordered behind the kernel on ITS stream
-            nat.filter_eval_dev(terms, n_rows, d_del.data_ptr() if d_del is not None else 0, mask.data_ptr(), und.data_ptr(),
-                                counts.data_ptr(), st.cuda_stream)
-            kept, undecided = (int(x) for x in counts.cpu().tolist())   # synchronises the stream
+            if program is None:
+                nat.filter_eval_dev(terms, n_rows, d_del.data_ptr() if d_del is not None else 0, mask.data_ptr(), und.data_ptr(),
+                                    counts.data_ptr(), st.cuda_stream)
+            else:
+                nat.filter_eval_expr_dev(terms, program.codes, n_rows, d_del.data_ptr() if d_del is not None else 0, mask.data_ptr(),
+                                         und.data_ptr(), counts.data_ptr(), st.cuda_stream)
+                self.stats["expr_evaluations"] += 1
+            kept, undecided = (int(x) for x in counts.cpu().tolist())   # synchronises the stream (the sets may go after it)
             self.stats["evaluations"] += 1
             if undecided:
-                # rows that tie with a literal on the first 16 bytes: every other term has already passed them; settle the
-                # string terms on the full strings (host) and switch the survivors on
+                # rows that tie with a literal on the first 16 bytes.  A conjunction: every other term has already passed
+                # them; settle the string terms on the full strings (host) and switch the survivors on.  Any other tree
+                # is evaluated whole on those rows.
                 self.stats["undecided_rows"] += undecided
                 rows = np.nonzero(np.unpackbits(und.cpu().numpy(), bitorder="little")[:n_rows])[0]
-                ok = np.ones(rows.shape[0], dtype=bool)
-                for col_name, op, value in string_terms:
-                    ok &= self.columns[col_name].compare_rows(rows, op, value)
+                if program is None:
+                    ok = np.ones(rows.shape[0], dtype=bool)
+                    for col_name, op, value in settle:
+                        ok &= self.columns[col_name].compare_rows(rows, op, value)
+                else:
+                    ok = self._settle(program.tree, rows)
                 rows = rows[ok]
                 kept += int(rows.shape[0])
                 for b in range(8):   # rows with the same bit position touch distinct bytes: plain indexed updates

@@ -8,11 +8,18 @@ double-quoted strings with \\ and \" escapes, over the scalar fields of the
 collection schema (indexing.py:191-225).  Milvus evaluates them server-side;
 here they become a per-row predicate over host-side columns and are handed to
 the kernels as a packed bitmask (bit r%8 of byte r/8).
+
+A pymilvus caller writes more than conjunctions, so `parse_tree` also takes
+    field in [literal, ...]   field not in [...]   or / ||   not / !   ( ... )
+with Milvus' precedence (not > and > or).  `parse` keeps to the flat
+conjunction; `evaluate` and `fields` take either form.  The rest of Milvus'
+language (like, arithmetic, a < f < b, field-to-field comparisons, JSON and
+array functions) is refused.
 """
 from __future__ import annotations
 
 import re
-from typing import Any, Dict, List, Tuple
+from typing import Any, Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -62,6 +69,19 @@ def _unquote(tok: str) -> str:
     return "".join(out)
 
 
+def _string_end(text: str, i: int) -> int:
+    """Index just behind the double-quoted string that starts at text[i], or -1 when it does not end."""
+    i += 1
+    while i < len(text):
+        if text[i] == "\\" and i + 1 < len(text):
+            i += 2
+        elif text[i] == '"':
+            return i + 1
+        else:
+            i += 1
+    return -1
+
+
 _TERM = re.compile(r"^\s*([A-Za-z_]\w*)\s*(>=|<=|==|!=|>|<)\s*(.+?)\s*$", re.S)
 
 
@@ -75,6 +95,8 @@ def parse(expr: str) -> List[Tuple[str, str, Any]]:
             raise ValueError(f"cannot parse filter term: {term!r}")
         field, op, raw = m.group(1), m.group(2), m.group(3)
         if raw.startswith('"') and raw.endswith('"') and len(raw) >= 2:
+            if _string_end(raw, 0) != len(raw):   # `"a" or doc_id == "b"` is no literal (it used to be read as one string)
+                raise ValueError(f"bad literal in filter term: {term!r}")
             value: Any = _unquote(raw)
         elif raw in ("True", "true"):
             value = True
@@ -130,25 +152,292 @@ def _compare(col: np.ndarray, op: str, value: Any) -> np.ndarray:
     return col < value
 
 
+def _leaf_mask(node, columns: Dict[str, np.ndarray]) -> np.ndarray:
+    """Row predicate of one leaf: ("cmp", field, op, value) or ("in", field, values)."""
+    field = node[1]
+    if field not in columns:
+        raise ValueError(f"unknown filter field: {field}")
+    col = columns[field]
+    if node[0] == "in":
+        members = list_members(field, node[2], "s" if col.dtype.kind in "US" else "i" if col.dtype.kind in "iu" else "f")
+        if not members:
+            return np.zeros(col.shape[0], dtype=bool)
+        if col.dtype.kind == "f" and col.dtype != np.float32:
+            members = [float(v) for v in node[2]]
+        return np.isin(col, np.asarray(members, dtype=col.dtype if col.dtype.kind not in "US" else None))
+    op, value = node[2], node[3]
+    if col.dtype.kind in "US":
+        if not isinstance(value, str):
+            raise ValueError(f"field {field} is a string column; got {value!r}")
+    elif isinstance(value, str):
+        raise ValueError(f"field {field} is numeric; got string {value!r}")
+    elif col.dtype.kind in "iu":
+        value = numeric_literal(field, op, value, "i")
+    elif col.dtype.kind == "f":
+        rounded = numeric_literal(field, op, value, "f")
+        value = rounded if col.dtype == np.float32 else float(value)
+    return _compare(col, op, value)
+
+
+def evaluate_tree(tree, leaf) -> np.ndarray:
+    """The tree of parse_tree over boolean arrays: `leaf(node)` gives a leaf's rows, and / or / not are & / | / ~."""
+    kind = tree[0]
+    if kind == "and":
+        return evaluate_tree(tree[1], leaf) & evaluate_tree(tree[2], leaf)
+    if kind == "or":
+        return evaluate_tree(tree[1], leaf) | evaluate_tree(tree[2], leaf)
+    if kind == "not":
+        return ~evaluate_tree(tree[1], leaf)
+    return leaf(tree)
+
+
 def evaluate(expr: str, columns: Dict[str, np.ndarray], n_rows: int) -> np.ndarray:
-    """Boolean row predicate (length n_rows) of a conjunctive expression."""
+    """Boolean row predicate (length n_rows) of an expression: a conjunction term by term, any other tree with numpy."""
+    terms, tree = lower(expr)
+    if tree is not None:
+        return evaluate_tree(tree, lambda node: _leaf_mask(node, columns))
     keep = np.ones(n_rows, dtype=bool)
-    for field, op, value in parse(expr):
-        if field not in columns:
-            raise ValueError(f"unknown filter field: {field}")
-        col = columns[field]
-        if col.dtype.kind in "US":
-            if not isinstance(value, str):
-                raise ValueError(f"field {field} is a string column; got {value!r}")
-        elif isinstance(value, str):
-            raise ValueError(f"field {field} is numeric; got string {value!r}")
-        elif col.dtype.kind in "iu":
-            value = numeric_literal(field, op, value, "i")
-        elif col.dtype.kind == "f":
-            rounded = numeric_literal(field, op, value, "f")
-            value = rounded if col.dtype == np.float32 else float(value)
-        keep &= _compare(col, op, value)
+    for field, op, value in terms:
+        keep &= _leaf_mask(("cmp", field, op, value), columns)
     return keep
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the full grammar
+#   expr  := or
+#   or    := and ( ("or" | "OR" | "||") and )*
+#   and   := unary ( ("and" | "AND" | "&&") unary )*
+#   unary := ("not" | "NOT" | "!") unary | "(" expr ")" | leaf
+#   leaf  := field CMP literal | field ["not"] "in" "[" [ literal ("," literal)* ] "]"
+# Trees: ("cmp", field, op, value) | ("in", field, [values]) | ("not", t) | ("and", a, b) | ("or", a, b), and / or
+# left-associative; `field not in [..]` is ("not", ("in", ..)).
+
+_KEYWORDS = {"and": "and", "AND": "and", "&&": "and", "or": "or", "OR": "or", "||": "or", "not": "not", "NOT": "not",
+             "!": "not", "in": "in", "IN": "in"}
+_IDENT = re.compile(r"[A-Za-z_]\w*$")
+_WORD = re.compile(r"[\w.+\-]+")       # identifiers, keywords and numeric literals (1e-3, -inf, 1_000)
+_PUNCT = ("&&", "||", ">=", "<=", "==", "!=", ">", "<", "!", "(", ")", "[", "]", ",")
+
+
+def _tokens(expr: str) -> List[Tuple[str, str, int, int]]:
+    """-> [(kind, text, start, end)], kind one of "str" (text = the quoted source), "word", "cmp", or the keyword /
+    punctuation itself.  What stands inside a quoted string is part of the string."""
+    out, i = [], 0
+    while i < len(expr):
+        ch = expr[i]
+        if ch.isspace():
+            i += 1
+        elif ch == '"':
+            end = _string_end(expr, i)
+            if end < 0:
+                raise ValueError(f"unterminated string in filter expression: {expr!r}")
+            out.append(("str", expr[i:end], i, end))
+            i = end
+        else:
+            m = _WORD.match(expr, i)
+            if m is not None:
+                text = m.group(0)
+                out.append((_KEYWORDS.get(text, "word"), text, i, m.end()))
+                i = m.end()
+                continue
+            for p in _PUNCT:
+                if expr.startswith(p, i):
+                    out.append(("cmp" if p in _OPS else _KEYWORDS.get(p, p), p, i, i + len(p)))
+                    i += len(p)
+                    break
+            else:
+                raise ValueError(f"cannot parse filter expression at {expr[i:i + 12]!r}: {expr!r}")
+    return out
+
+
+def _literal(tok, term: str) -> Any:
+    kind, text = tok[0], tok[1]
+    if kind == "str":
+        return _unquote(text)
+    if kind == "word":
+        if text in ("True", "true"):
+            return True
+        if text in ("False", "false"):
+            return False
+        try:
+            return int(text)
+        except ValueError:
+            try:
+                return float(text)
+            except ValueError:
+                pass
+    raise ValueError(f"bad literal in filter term: {term!r}")
+
+
+def list_members(field: str, values: List[Any], kind: str) -> List[Any]:
+    """The members of `field in [values]` as a column of `kind` ("s" string, "i" INT64, "f" FLOAT) compares them, or
+    ValueError naming the term: strings for a string field; integers within int64 for an INT64 field (a float literal is
+    refused: no row equals 2.5, and Milvus refuses the list); numbers rounded to float32 for a FLOAT field."""
+    term = f"{field} in {_show_list(values)}"
+    strings = [isinstance(v, str) for v in values]
+    if any(strings) and not all(strings):
+        raise ValueError(f"list mixes strings and numbers in filter term: {term}")
+    if kind == "s":
+        if values and not all(strings):
+            raise ValueError(f"field {field} is a string column; got a number in filter term: {term}")
+        return list(values)
+    if any(strings):
+        raise ValueError(f"field {field} is numeric; got a string in filter term: {term}")
+    if kind == "i":
+        if any(isinstance(v, float) for v in values):
+            raise ValueError(f"field {field} is an INT64 field; got a float literal in filter term: {term}")
+        return [numeric_literal(field, "in", v, "i") for v in values]
+    return [numeric_literal(field, "in", v, "f") for v in values]
+
+
+def _show_list(values) -> str:
+    return "[" + ", ".join('"' + v.replace("\\", "\\\\").replace('"', '\\"') + '"' if isinstance(v, str) else str(v)
+                           for v in values) + "]"
+
+
+class _Parser:
+    def __init__(self, expr: str):
+        self.expr, self.toks, self.i = expr, _tokens(expr), 0
+
+    def peek(self) -> str:
+        return self.toks[self.i][0] if self.i < len(self.toks) else "end"
+
+    def text_from(self, first: int, last: Optional[int] = None) -> str:
+        """The source from token `first` up to and including token `last` (default: the one just read)."""
+        last = min(self.i - 1 if last is None else last, len(self.toks) - 1)
+        return self.expr[self.toks[first][2]: self.toks[last][3]] if first <= last else self.expr
+
+    def parse(self):
+        if not self.toks:
+            raise ValueError(f"empty filter expression: {self.expr!r}")
+        tree = self.or_()
+        if self.peek() == ")":
+            raise ValueError(f"unbalanced parentheses in filter expression: {self.expr!r}")
+        if self.peek() != "end":
+            raise ValueError(f"cannot parse filter term: {self.text_from(self.start, len(self.toks) - 1)!r}")
+        return tree
+
+    def or_(self):
+        tree = self.and_()
+        while self.peek() == "or":
+            self.i += 1
+            tree = ("or", tree, self.and_())
+        return tree
+
+    def and_(self):
+        tree = self.unary()
+        while self.peek() == "and":
+            self.i += 1
+            tree = ("and", tree, self.unary())
+        return tree
+
+    def unary(self):
+        kind = self.peek()
+        if kind == "not":
+            self.i += 1
+            return ("not", self.unary())
+        if kind == "(":
+            self.i += 1
+            tree = self.or_()
+            if self.peek() != ")":
+                raise ValueError(f"unbalanced parentheses in filter expression: {self.expr!r}")
+            self.i += 1
+            return tree
+        return self.leaf()
+
+    def leaf(self):
+        self.start = start = self.i
+        if self.peek() == "end":
+            raise ValueError(f"filter expression ends where a term is expected: {self.expr!r}")
+        tok = self.toks[self.i]
+        self.i += 1
+        if tok[0] != "word" or not _IDENT.match(tok[1]) or tok[1] in ("True", "true", "False", "false"):
+            raise ValueError(f"cannot parse filter term: {self.text_from(start, min(start + 2, len(self.toks) - 1))!r}")
+        field, kind = tok[1], self.peek()
+        if kind == "cmp":
+            op = self.toks[self.i][1]
+            self.i += 1
+            if self.peek() == "end":
+                raise ValueError(f"bad literal in filter term: {self.text_from(start)!r}")
+            self.i += 1
+            return ("cmp", field, op, _literal(self.toks[self.i - 1], self.text_from(start)))
+        negate = kind == "not"
+        if negate:
+            self.i += 1
+        if self.peek() != "in":
+            raise ValueError(f"cannot parse filter term: {self.text_from(start, min(self.i, len(self.toks) - 1))!r} "
+                             "(expected a comparison or [not] in [...])")
+        self.i += 1
+        if self.peek() != "[":
+            raise ValueError(f"cannot parse filter term: {self.text_from(start, min(self.i, len(self.toks) - 1))!r} "
+                             "(expected a [list] after in)")
+        self.i += 1
+        close = next((j for j in range(self.i, len(self.toks)) if self.toks[j][0] == "]"), len(self.toks) - 1)
+        term = self.text_from(start, close)
+        values: List[Any] = []
+        if self.peek() == "]":
+            self.i += 1
+        else:
+            while True:
+                if self.peek() == "]" and values:
+                    raise ValueError(f"trailing comma in filter term: {term!r}")
+                if self.peek() not in ("str", "word"):
+                    raise ValueError(f"bad list in filter term: {term!r}")
+                self.i += 1
+                values.append(_literal(self.toks[self.i - 1], term))
+                sep = self.peek()
+                self.i += 1
+                if sep == "]":
+                    break
+                if sep != ",":
+                    raise ValueError(f"bad list in filter term: {term!r}")
+        # what the field's type refuses is refused here, before any evaluator sees the tree
+        if field in NUMERIC_FIELDS or field in STRING_FIELDS:
+            list_members(field, values, "s" if field in STRING_FIELDS else "i" if NUMERIC_FIELDS[field] is np.int64 else "f")
+        else:
+            list_members(field, values, "s" if values and isinstance(values[0], str) else "f")
+        node = ("in", field, values)
+        return ("not", node) if negate else node
+
+
+def parse_tree(expr: str):
+    """The expression as a tree (see the grammar above), or ValueError naming the offending term."""
+    return _Parser(expr).parse()
+
+
+def conjunction_terms(tree) -> Optional[List[Tuple[str, str, Any]]]:
+    """[(field, op, value)] when the tree is a flat conjunction of comparisons (what `parse` returns), else None."""
+    if tree[0] == "cmp":
+        return [tree[1:]]
+    if tree[0] == "and":
+        left, right = conjunction_terms(tree[1]), conjunction_terms(tree[2])
+        if left is not None and right is not None:
+            return left + right
+    return None
+
+
+def lower(expr: str):
+    """-> (terms, None) for a flat conjunction of comparisons (however it is spelled: `and`, `AND`, `&&`, parentheses),
+    (None, tree) for every other expression."""
+    try:
+        return parse(expr), None
+    except ValueError:
+        pass
+    tree = parse_tree(expr)
+    terms = conjunction_terms(tree)
+    return (terms, None) if terms is not None else (None, tree)
+
+
+def leaves(tree) -> List[tuple]:
+    if tree[0] in ("cmp", "in"):
+        return [tree]
+    return [leaf for child in tree[1:] for leaf in leaves(child)]
+
+
+def fields(expr: str) -> set:
+    """The field names an expression of either form mentions."""
+    terms, tree = lower(expr)
+    return {t[0] for t in terms} if tree is None else {leaf[1] for leaf in leaves(tree)}
 
 
 def pack(keep: np.ndarray) -> np.ndarray:

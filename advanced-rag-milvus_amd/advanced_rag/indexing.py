@@ -394,7 +394,7 @@ class MilvusIndexManager:
         if self._synthetic_rows:
             # bulk-ingested rows carry no payload columns; what their synthetic id encodes can still be filtered on:
             # chunk_index = row % 10 (synthetic_id), derived on the fly
-            fields = {f for f, _, _ in _filters.parse(expr)}
+            fields = _filters.fields(expr)
             if fields - {"chunk_index"}:
                 raise ValueError("this shard was bulk-ingested without payload columns: only chunk_index (= row % 10) "
                                  f"can be filtered on, not {sorted(fields - {'chunk_index'})}")

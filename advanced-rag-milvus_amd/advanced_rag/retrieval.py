@@ -76,6 +76,9 @@ class RetrievalConfig:
     # grouping search (pymilvus' group_by_field): every modality ranks the best chunk of each group (2 x top_k documents
     # instead of 2 x top_k chunks) and the fused list keeps the first hit of every group.  None = chunks, as the reference.
     group_by_field: Optional[str] = None
+    # the dict form of a filter also takes {"field": {"$in": [...]}} and {"$nin": [...]} (-> `field in [..]` / `field not in
+    # [..]`).  False = they are refused, as the reference refuses them.
+    extended_filter_operators: bool = False
 
     def __post_init__(self):
         if self.group_by_field is not None:
@@ -114,6 +117,7 @@ class HybridRetriever:
                                        "chunk_index", "token_count"}
     ALLOWED_OPERATORS: Set[str] = {"$gte", "$lte", "$gt", "$lt", "$eq", "$ne"}
     _OP_TEXT = {"$gte": ">=", "$lte": "<=", "$gt": ">", "$lt": "<", "$eq": "==", "$ne": "!="}
+    _LIST_OP_TEXT = {"$in": "in", "$nin": "not in"}      # only with RetrievalConfig(extended_filter_operators=True)
     DOMAIN_WEIGHT = 0.2
     RRF_K = 60
 
@@ -146,7 +150,8 @@ class HybridRetriever:
             return RetrievalConfig(hybrid_alpha=base.hybrid_alpha, top_k=clamp_k(top_k),
                                    rerank_top_k=clamp_rerank(rerank_k), enable_reranking=rerank,
                                    dense_weight=base.dense_weight, sparse_weight=base.sparse_weight,
-                                   enable_mmr=mmr, mmr_lambda=lam, group_by_field=base.group_by_field)
+                                   enable_mmr=mmr, mmr_lambda=lam, group_by_field=base.group_by_field,
+                                   extended_filter_operators=base.extended_filter_operators)
 
         return {
             "default": base,
@@ -430,6 +435,16 @@ class HybridRetriever:
     def _quote(value: str) -> str:
         return '"' + value.replace("\\", "\\\\").replace('"', '\\"') + '"'
 
+    @classmethod
+    def _quote_list(cls, field: str, operand: Any) -> str:
+        """["a", "b"] -> '["a", "b"]': a list of str, or of int / float / bool."""
+        if not isinstance(operand, (list, tuple)):
+            raise ValueError(f"Invalid value type for {field}: {type(operand)} (a list is expected)")
+        if not (all(isinstance(v, str) for v in operand) or
+                all(isinstance(v, (int, float, bool)) and not isinstance(v, str) for v in operand)):
+            raise ValueError(f"Invalid list for {field}: its members must be all strings or all numbers")
+        return "[" + ", ".join(cls._quote(v) if isinstance(v, str) else f"{v}" for v in operand) + "]"
+
     def _build_filter_expression(self, filters: Dict[str, Any]) -> Optional[str]:
         """{"doc_id": "d1", "entropy": {"$gte": 0.2}} -> 'doc_id == "d1" and entropy >= 0.2'."""
         terms: List[str] = []
@@ -441,6 +456,9 @@ class HybridRetriever:
                 raise ValueError(f"Invalid field name format: {field}")
             if isinstance(cond, dict):
                 for op, operand in cond.items():
+                    if op in self._LIST_OP_TEXT and self.config.extended_filter_operators:
+                        terms.append(f"{field} {self._LIST_OP_TEXT[op]} {self._quote_list(field, operand)}")
+                        continue
                     if op not in self.ALLOWED_OPERATORS:
                         logger.warning("Invalid operator attempted: %s", op)
                         raise ValueError(f"Invalid operator: {op}")

@@ -91,4 +91,135 @@ __global__ __launch_bounds__(256) void filter_eval_kernel(FilterArgs a) {
     }
 }
 
+// ---- expressions beyond the conjunction: `in` lists, or, not, parentheses (hr_filter_eval_expr_dev) ------------------
+// The expression arrives as leaves (a comparison as above, or a membership test against a sorted set) and a postfix
+// program over them.  A string leaf cannot always decide a row, so a leaf's value is true, false or unknown and the
+// operators are Kleene's; the value is held as a pair of bounds (lo = "certainly true", hi = "possibly true"), and the
+// evaluation stack as two 32-bit fields of such bits, top of stack in bit 0: a push is a shift, and / or combine bits 0
+// and 1 of both fields, not swaps and inverts bit 0 of the two.  No indexed array, so no scratch memory.
+//
+// The sets are staged in LDS once per block (each at a 16-byte aligned offset) and searched per lane by a binary search
+// whose trip count depends on the set's size alone: the wave stays converged, only the LDS addresses differ.
+constexpr int kFilterMaxProgram = 64;
+constexpr int kFilterMaxDepth = 32;
+constexpr int kFilterMaxSetBytes = 65536;
+
+struct FilterExprArgs {
+    hr_filter_term t[kFilterMaxTerms];
+    const void* set[kFilterMaxTerms];     // device arrays, ascending; staged at set_off
+    int32_t set_off[kFilterMaxTerms];     // byte offset inside the block's LDS
+    int32_t n_set[kFilterMaxTerms];
+    int8_t program[kFilterMaxProgram];    // >= 0: push that leaf; HR_FILTER_AND / _OR / _NOT
+    int n_leaves, n_program;
+    int64_t n_rows;
+    const uint8_t* deleted;
+    unsigned long long* mask;
+    unsigned long long* undecided;
+    int32_t* counts;
+};
+
+// Index of the last member <= v among n >= 1 ascending members (0 when there is none): the member to compare with.
+template <typename T>
+__device__ inline bool filter_set_has(const T* set, int n, T v) {
+    int base = 0;
+    for (int len = n; len > 1;) {
+        const int half = len >> 1;
+        if (set[base + half] <= v) base += half;
+        len -= half;
+    }
+    return set[base] == v;
+}
+
+struct FilterKey {
+    unsigned long long w0, w1;
+    __device__ bool operator<=(const FilterKey& o) const { return w0 < o.w0 || (w0 == o.w0 && w1 <= o.w1); }
+    __device__ bool operator==(const FilterKey& o) const { return w0 == o.w0 && w1 == o.w1; }
+};
+
+__global__ __launch_bounds__(256) void filter_expr_kernel(FilterExprArgs a) {
+    extern __shared__ __align__(16) unsigned char filter_sets[];
+    for (int i = 0; i < a.n_leaves; ++i) {
+        if (a.t[i].op != HR_OP_IN) continue;
+        const int words = a.n_set[i] * (a.t[i].kind == HR_COL_F32 ? 1 : a.t[i].kind == HR_COL_I64 ? 2 : 4);
+        const uint32_t* src = (const uint32_t*)a.set[i];
+        uint32_t* dst = (uint32_t*)(filter_sets + a.set_off[i]);
+        for (int j = threadIdx.x; j < words; j += 256) dst[j] = src[j];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
+    const int64_t n_words = (a.n_rows + 63) / 64;
+    int kept = 0, und = 0;
+    for (int64_t w = wave; w < n_words; w += n_waves) {
+        const int64_t row = w * 64 + lane;
+        const bool in = row < a.n_rows;
+        bool dead = !in;
+        if (in && a.deleted) dead = (a.deleted[row >> 3] >> (row & 7)) & 1;
+        uint32_t lo = 0, hi = 0;
+        for (int pc = 0; pc < a.n_program; ++pc) {
+            const int code = a.program[pc];
+            if (code == HR_FILTER_AND) {
+                lo = (lo >> 1) & (lo | ~1u);
+                hi = (hi >> 1) & (hi | ~1u);
+            } else if (code == HR_FILTER_OR) {
+                lo = (lo >> 1) | (lo & 1u);
+                hi = (hi >> 1) | (hi & 1u);
+            } else if (code == HR_FILTER_NOT) {
+                const uint32_t was = lo;
+                lo = (lo & ~1u) | (~hi & 1u);
+                hi = (hi & ~1u) | (~was & 1u);
+            } else {
+                const hr_filter_term& t = a.t[code];
+                bool pass = false, tie = false;
+                if (t.op == HR_OP_IN) {
+                    const int n = a.n_set[code];
+                    const unsigned char* set = filter_sets + a.set_off[code];
+                    if (n > 0) {   // a row beyond n_rows searches for 0: every read stays inside the set
+                        if (t.kind == HR_COL_I64) {
+                            pass = filter_set_has<int64_t>((const int64_t*)set, n, in ? ((const int64_t*)t.col)[row] : 0);
+                        } else if (t.kind == HR_COL_F32) {
+                            pass = filter_set_has<float>((const float*)set, n, in ? ((const float*)t.col)[row] : 0.0f);
+                        } else {
+                            FilterKey k{0, 0};
+                            if (in) k = FilterKey{((const unsigned long long*)t.col)[2 * row], ((const unsigned long long*)t.col)[2 * row + 1]};
+                            tie = filter_set_has<FilterKey>((const FilterKey*)set, n, k);   // equal prefix: the host decides
+                        }
+                    }
+                } else if (in) {
+                    switch (t.kind) {
+                        case HR_COL_I64: pass = filter_cmp<int64_t>(((const int64_t*)t.col)[row], t.ival, t.op); break;
+                        case HR_COL_I64_VS_F64: pass = filter_cmp<double>((double)((const int64_t*)t.col)[row], t.dval, t.op); break;
+                        case HR_COL_F32: pass = filter_cmp<float>(((const float*)t.col)[row], t.fval, t.op); break;
+                        default: {  // HR_COL_STR16
+                            const unsigned long long k0 = ((const unsigned long long*)t.col)[2 * row];
+                            const unsigned long long k1 = ((const unsigned long long*)t.col)[2 * row + 1];
+                            if (k0 == t.key[0] && k1 == t.key[1]) {
+                                tie = true;
+                            } else {
+                                const bool less = k0 < t.key[0] || (k0 == t.key[0] && k1 < t.key[1]);
+                                pass = t.op == HR_OP_EQ ? false : t.op == HR_OP_NE ? true
+                                     : (t.op == HR_OP_LT || t.op == HR_OP_LE) ? less : !less;
+                            }
+                        }
+                    }
+                }
+                lo = (lo << 1) | (uint32_t)(pass && !tie);
+                hi = (hi << 1) | (uint32_t)(pass || tie);
+            }
+        }
+        const bool keep = !dead && (lo & 1u), undecided = !dead && (hi & 1u) && !(lo & 1u);
+        const unsigned long long km = __ballot(keep), um = __ballot(undecided);
+        if (lane == 0) {
+            a.mask[w] = km;
+            a.undecided[w] = um;
+            kept += __popcll(km);
+            und += __popcll(um);
+        }
+    }
+    if (lane == 0 && (kept | und)) {
+        if (kept) atomicAdd(&a.counts[0], kept);
+        if (und) atomicAdd(&a.counts[1], und);
+    }
+}
+
 }  // namespace hbmrag

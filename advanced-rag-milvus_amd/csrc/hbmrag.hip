@@ -1305,7 +1305,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 10800; }  // 1.8.0: hr_group_select_dev, hr_mask_drop_groups_dev
+int hr_version(void) { return 10900; }  // 1.9.0: hr_filter_eval_expr_dev
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2051,6 +2051,79 @@ int hr_filter_eval_dev(const hr_filter_term* terms, int n_terms, int64_t n_rows,
     hipLaunchKernelGGL(filter_eval_kernel, dim3(blocks), dim3(256), 0, s, a);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "filter_eval_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+int hr_filter_eval_expr_dev(const hr_filter_leaf* leaves, int n_leaves, const int32_t* program, int n_program, int64_t n_rows,
+                            const uint8_t* d_deleted, uint8_t* d_mask, uint8_t* d_undecided, int32_t* d_counts, void* stream) {
+    if (n_leaves < 0 || n_leaves > kFilterMaxTerms) return fail(nullptr, HR_ELIMIT, "a filter expression may hold up to %d terms", kFilterMaxTerms);
+    if (n_program < 0 || n_program > kFilterMaxProgram)
+        return fail(nullptr, HR_ELIMIT, "a filter program may hold up to %d codes", kFilterMaxProgram);
+    if (n_rows < 0 || n_leaves == 0 || n_program == 0 || !leaves || !program || !d_mask || !d_undecided || !d_counts)
+        return fail(nullptr, HR_EINVAL, "bad filter arguments");
+    if (((uintptr_t)d_mask | (uintptr_t)d_undecided) & 7) return fail(nullptr, HR_EINVAL, "mask buffers must be 8-byte aligned");
+    FilterExprArgs a{};
+    size_t set_bytes = 0;
+    for (int i = 0; i < n_leaves; ++i) {
+        const hr_filter_term& t = leaves[i].term;
+        if (t.kind < HR_COL_I64 || t.kind > HR_COL_STR16 || t.op < HR_OP_EQ || t.op > HR_OP_IN || !t.col)
+            return fail(nullptr, HR_EINVAL, "bad filter term %d", i);
+        a.t[i] = t;
+        if (t.op != HR_OP_IN) continue;
+        const size_t member = t.kind == HR_COL_F32 ? 4 : t.kind == HR_COL_I64 ? 8 : 16, align = member == 4 ? 4 : 8;
+        if (t.kind == HR_COL_I64_VS_F64 || leaves[i].n_set < 0 || (leaves[i].set == nullptr) != (leaves[i].n_set == 0) ||
+            ((uintptr_t)leaves[i].set & (align - 1)))
+            return fail(nullptr, HR_EINVAL, "bad filter term %d (membership: kind, set pointer or set size)", i);
+        if ((size_t)leaves[i].n_set > kFilterMaxSetBytes / member) return fail(nullptr, HR_ELIMIT, "the sets of a filter expression may hold up to %d bytes", kFilterMaxSetBytes);
+        a.set[i] = leaves[i].set;
+        a.n_set[i] = leaves[i].n_set;
+        a.set_off[i] = (int32_t)set_bytes;
+        set_bytes += ((size_t)leaves[i].n_set * member + 15) & ~(size_t)15;
+        if (set_bytes > (size_t)kFilterMaxSetBytes)
+            return fail(nullptr, HR_ELIMIT, "the sets of a filter expression may hold up to %d bytes", kFilterMaxSetBytes);
+    }
+    int depth = 0;
+    for (int pc = 0; pc < n_program; ++pc) {
+        const int32_t code = program[pc];
+        if (code >= 0) {
+            if (code >= n_leaves) return fail(nullptr, HR_EINVAL, "filter program: code %d names leaf %d of %d", pc, code, n_leaves);
+            if (++depth > kFilterMaxDepth) return fail(nullptr, HR_EINVAL, "filter program: deeper than %d at code %d", kFilterMaxDepth, pc);
+        } else if (code == HR_FILTER_AND || code == HR_FILTER_OR) {
+            if (depth < 2) return fail(nullptr, HR_EINVAL, "filter program: code %d pops from an empty stack", pc);
+            --depth;
+        } else if (code == HR_FILTER_NOT) {
+            if (depth < 1) return fail(nullptr, HR_EINVAL, "filter program: code %d pops from an empty stack", pc);
+        } else {
+            return fail(nullptr, HR_EINVAL, "filter program: unknown code %d at %d", code, pc);
+        }
+        a.program[pc] = (int8_t)code;
+    }
+    if (depth != 1) return fail(nullptr, HR_EINVAL, "filter program: %d values left at the end, not 1", depth);
+    a.n_leaves = n_leaves;
+    a.n_program = n_program;
+    a.n_rows = n_rows;
+    a.deleted = d_deleted;
+    a.mask = (unsigned long long*)d_mask;
+    a.undecided = (unsigned long long*)d_undecided;
+    a.counts = d_counts;
+    hipStream_t s = (hipStream_t)stream;
+    static bool attr_set = false;  // benign race: the attribute is idempotent
+    if (!attr_set) {
+        hipError_t e0 = hipFuncSetAttribute((const void*)filter_expr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kFilterMaxSetBytes);
+        if (e0 != hipSuccess) return fail(nullptr, HR_EHIP, "hipFuncSetAttribute: %s", hipGetErrorString(e0));
+        attr_set = true;
+    }
+    hipError_t e = hipMemsetAsync(d_counts, 0, 8, s);
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (n_rows == 0) return HR_OK;
+    const int64_t n_words = (n_rows + 63) / 64;
+    // every block stages the sets before its first row: past a few KiB of them, fewer blocks with more trips each (two
+    // blocks of 64 KiB fit a CU: 1024 blocks are two rounds of the device) stage less than the column read costs
+    const int64_t cap = set_bytes > 4096 ? 1024 : 4096;
+    const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_words + 3) / 4, cap));
+    hipLaunchKernelGGL(filter_expr_kernel, dim3(blocks), dim3(256), set_bytes, s, a);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "filter_expr_kernel: %s", hipGetErrorString(e));
     return HR_OK;
 }
 

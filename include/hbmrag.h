@@ -412,6 +412,45 @@ typedef struct hr_filter_term {
 HR_API int hr_filter_eval_dev(const hr_filter_term* terms, int n_terms, int64_t n_rows, const uint8_t* d_deleted,
                        uint8_t* d_mask, uint8_t* d_undecided, int32_t* d_counts, void* stream);
 
+/* The same mask for the rest of the filter language: `field in [..]`, `or`, `not`, parentheses (advanced_rag/filters.py
+ * has the grammar).  The expression is a set of LEAVES and a postfix PROGRAM over them, both HOST arrays copied into
+ * the launch: at most HR_MAX_FILTER_TERMS leaves and HR_MAX_FILTER_PROGRAM codes.  A code >= 0 pushes the value of that
+ * leaf; HR_FILTER_AND / HR_FILTER_OR pop two values and push one, HR_FILTER_NOT replaces the top.  The program is checked
+ * before anything is enqueued: every leaf index in range, no pop from an empty stack, depth never above 32 and exactly 1
+ * at the end (HR_EINVAL otherwise; HR_ELIMIT for too many leaves, codes or set bytes).  A refused call launches nothing
+ * and leaves the outputs alone.
+ *
+ * A leaf is a comparison (term as in hr_filter_eval_dev) or, with term.op == HR_OP_IN, a membership test of the column
+ * (term.kind HR_COL_I64, HR_COL_F32 or HR_COL_STR16; never HR_COL_I64_VS_F64) against `set`: a DEVICE array of n_set
+ * members, strictly ascending (int64; float32 without NaN, membership is float32 ==, so -0.0 and 0.0 are one member
+ * and a NaN row is a member of nothing; two-word prefix keys in unsigned lexicographic order), naturally aligned, NULL
+ * iff n_set == 0 (no row is a member).  All sets of one call, each rounded up to 16 bytes, hold at most
+ * HR_MAX_FILTER_SET_BYTES: 8192 int64, 16384 float32 or 4096 keys.  They are read while the kernel runs: keep them
+ * alive until `stream` has passed the call.
+ *
+ * Values are three-valued, because a string leaf cannot always decide: a string comparison is unknown for a row whose
+ * key equals the literal's (today's tie), a string membership leaf is unknown iff the row's key equals a member key and
+ * false otherwise (literals that share their first 16 bytes are ONE member key), a numeric leaf is never unknown.  The
+ * operators are Kleene's: `and` is false if a side is false, else unknown if a side is unknown; `or` mirrors it;
+ * not unknown = unknown.  d_mask bit = row not deleted and the expression true; d_undecided bit = row not deleted and
+ * the expression unknown — for the caller to settle by evaluating the WHOLE expression on the full strings of those
+ * rows.  A decided bit is right whatever the full strings say; an undecided row may turn out either way (also where
+ * Kleene cannot see that it is decided, `a or not a`).  For a conjunction of comparison leaves all four outputs equal
+ * hr_filter_eval_dev's.  d_mask, d_undecided, d_counts, their alignment, the bits at and beyond n_rows, n_rows == 0 and
+ * d_deleted are as in hr_filter_eval_dev. */
+enum { HR_OP_IN = 6 };                          /* membership leaf; valid only in hr_filter_eval_expr_dev */
+enum { HR_FILTER_AND = -1, HR_FILTER_OR = -2, HR_FILTER_NOT = -3 };   /* program codes; code >= 0 pushes leaf `code` */
+#define HR_MAX_FILTER_PROGRAM 64
+#define HR_MAX_FILTER_SET_BYTES 65536           /* all sets of one expression together: 8192 int64, 16384 float32, or 4096 string keys */
+typedef struct hr_filter_leaf {
+    hr_filter_term term;     /* comparison leaf: as in hr_filter_eval_dev.  op == HR_OP_IN: kind HR_COL_I64 / HR_COL_F32 / HR_COL_STR16 and col as there, literal fields unused */
+    const void* set;         /* HR_OP_IN: DEVICE array of n_set members, strictly ascending (int64; float32 without NaN; two-word keys in unsigned lexicographic order); NULL iff n_set == 0 */
+    int32_t n_set, reserved;
+} hr_filter_leaf;
+HR_API int hr_filter_eval_expr_dev(const hr_filter_leaf* leaves, int n_leaves, const int32_t* program, int n_program,
+                                   int64_t n_rows, const uint8_t* d_deleted, uint8_t* d_mask, uint8_t* d_undecided,
+                                   int32_t* d_counts, void* stream);
+
 /* ---- BM25 document payloads (ingest) ----------------------------------------------------------------------------
  * The `encode_sparse` hook of the ingest path (reference indexing.py:629-654, called per chunk from index_chunks
  * :379-404) for the BM25 encoder of this build (advanced_rag/bm25.py), a batch at a time on the device: d_text = the
