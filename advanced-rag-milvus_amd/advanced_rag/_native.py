@@ -24,6 +24,7 @@ PHASE_NAMES = ("prep", "dense_scan", "group_select", "refine", "topk",
                "sparse_scan", "sparse_select", "sparse_refine", "sparse_topk", "finish_fused")
 HR_DEBUG_FINISH_MODE, HR_DEBUG_FAIL_NEXT_BUILD, HR_DEBUG_DENSE_KERNELS, HR_DEBUG_SPARSE_RPB, HR_DEBUG_GROUP_ROWS = 1, 2, 3, 4, 5
 HR_DEBUG_NO_TRIM = 6
+HR_DEBUG_NO_RANGE_CLAMP = 7
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libhbmrag.so")
@@ -64,6 +65,8 @@ _SIGNATURES = {
     "hr_dense_scan_bytes": (_c.c_int64, [_c.c_void_p]),
     "hr_search_dense": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                    _c.c_void_p]),
+    "hr_search_dense_range": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_search_sparse": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
                                     _c.c_float, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_search_dense_dmask": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
@@ -83,6 +86,8 @@ _SIGNATURES = {
                                _c.c_void_p, _c.c_void_p]),
     "hr_search_dense_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_search_dense_range_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                             _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_search_sparse_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int64,
                                         _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                         _c.c_void_p]),
@@ -337,6 +342,33 @@ class ShardHandle:
         self._check(self._lib.hr_search_dense(self._h, _vp(q), B, k, _vp(m), _vp(ids), _vp(sc)))
         return ids, sc
 
+    @staticmethod
+    def _bounds(b, B: int, name: str):
+        """One side of a range search's bounds: None (unbounded), a number for every query, or B numbers."""
+        if b is None:
+            return None
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(b, dtype=np.float64), (B,)))
+        if np.isnan(a).any():
+            raise ValueError(f"{name} of query {int(np.flatnonzero(np.isnan(a))[0])} is NaN")
+        return a
+
+    def search_dense_range(self, q: np.ndarray, k: int, radius=None, range_filter=None,
+                           rowmask: Optional[np.ndarray] = None, d_rowmask: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """Range search (hr_search_dense_range): the best k rows among those whose canonical score lies in the range
+        (COSINE, IP: radius < score <= range_filter; L2: range_filter <= distance < radius).  radius / range_filter:
+        None = unbounded, one number, or one per query.  An empty interval raises ValueError (HR_EINVAL)."""
+        q = np.ascontiguousarray(np.atleast_2d(q), dtype=np.float32)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != shard dim {self.dim}")
+        B = q.shape[0]
+        r, f = self._bounds(radius, B, "radius"), self._bounds(range_filter, B, "range_filter")
+        ids = np.empty((B, k), dtype=np.int64)
+        sc = np.empty((B, k), dtype=np.float32)
+        m = d_rowmask if d_rowmask else self._mask(rowmask, self.num_rows)
+        self._check(self._lib.hr_search_dense_range(self._h, _vp(q), B, k, _vp(m),
+                                                    1 if d_rowmask else 0, _vp(r), _vp(f), _vp(ids), _vp(sc)))
+        return ids, sc
+
     def search_sparse(self, queries: Sequence[Tuple[Sequence[int], Sequence[float]]], k: int,
                       drop_ratio: float = 0.0, rowmask: Optional[np.ndarray] = None,
                       d_rowmask: int = 0) -> Tuple[np.ndarray, np.ndarray]:
@@ -373,6 +405,14 @@ class ShardHandle:
         self._check(self._lib.hr_search_dense_dev(self._h, _vp(d_q), B, k, _vp(d_rowmask) if d_rowmask else None,
                                                   _vp(d_ids), _vp(d_scores), _vp(d_flags) if d_flags else None,
                                                   _vp(stream) if stream else None))
+
+    def search_dense_range_dev(self, d_q: int, B: int, k: int, d_radius: int, d_range_filter: int, d_ids: int,
+                               d_scores: int, d_flags: int = 0, d_rowmask: int = 0, stream: int = 0):
+        """d_radius / d_range_filter: device pointers of B float64 each, 0 = that side unbounded for every query."""
+        self._check(self._lib.hr_search_dense_range_dev(
+            self._h, _vp(d_q), B, k, _vp(d_rowmask) if d_rowmask else None, _vp(d_radius) if d_radius else None,
+            _vp(d_range_filter) if d_range_filter else None, _vp(d_ids), _vp(d_scores),
+            _vp(d_flags) if d_flags else None, _vp(stream) if stream else None))
 
     def search_sparse_dev(self, d_indptr: int, d_idx: int, d_val: int, B: int, nnz_total: int, max_q_nnz: int, k: int,
                           d_ids: int, d_scores: int, d_flags: int = 0, d_rowmask: int = 0, stream: int = 0):

@@ -10,6 +10,11 @@ round of scans is in flight — or within a short window of the first call of a 
 synchronisation per round, and the per-query lists are handed back to the awaiting coroutines.  Lists the device form
 could not prove exact are redone through the host form, which widens the candidate set by itself.
 
+Range searches (search_params {"params": {"radius": r, "range_filter": f}} on a dense collection) coalesce too: the two
+numbers are per-query operands of `hr_search_dense_range_dev` (the request carries them beside its query, RangedQuery),
+the request key only says "ranged" — ranged requests with different bounds share a launch, and never one with unranged
+requests.
+
 Grouping searches (search(..., group_by_field=F)) coalesce the same way; the field is part of the request key, so grouped and
 ungrouped requests never share a launch.  Their batch searches the window K' (MilvusIndexManager.group_window) and runs ONE
 `hr_group_select_dev` for all of its queries behind the search on the same stream; a query whose window ended before its
@@ -102,6 +107,13 @@ class _LoopFuture:
 
 
 @dataclass
+class RangedQuery:
+    """The payload of a dense range-search request: the query and its (radius, range_filter)."""
+    query: Any
+    bounds: Tuple[float, float]
+
+
+@dataclass
 class _Request:
     kind: str                 # "dense" | "sparse" | "fuse"
     key: Tuple                # requests with equal (kind, key) share a launch
@@ -132,7 +144,7 @@ class SearchCoalescer:
             self.window_s = max(self.window_s, 250e-6)
         self.stats = {"rounds": 0, "requests": 0, "dense_launches": 0, "sparse_launches": 0, "fuse_launches": 0,
                       "hybrid_launches": 0, "mmr_launches": 0, "encode_launches": 0, "encoded_texts": 0, "max_batch_seen": 0, "redone_unproven": 0,
-                      "group_launches": 0, "redone_grouped": 0, "busy_s": 0.0}
+                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "busy_s": 0.0}
         self._engines: Dict[Tuple, Any] = {}   # hybrid engines per (top_k, rrf_k, mmr)
         self._inflight: List[_Request] = []    # the requests of the round in progress (failed as a whole if the worker dies)
         self._outbox: Dict[Any, list] = {}     # event loop -> [(asyncio future, ok, value)] of the round in progress
@@ -355,6 +367,9 @@ class SearchCoalescer:
     def _lists_blocking(self, r: _Request, key: Tuple):
         """The lists of one dense or sparse request through the manager's blocking single-query path."""
         coll_name, top_k, expr, params_key, group_field = key
+        if isinstance(r.payload, RangedQuery):
+            return self.mgr._search_lists_blocking(r.payload.query, coll_name, top_k, expr, dict(params_key), group_field,
+                                                   r.payload.bounds)
         return self.mgr._search_lists_blocking(r.payload, coll_name, top_k, expr, dict(params_key), group_field)
 
     def _one_by_one(self, kind: str, key: Tuple, chunk: List[_Request]):
@@ -375,6 +390,8 @@ class SearchCoalescer:
         coll_name, top_k, expr, _, group_field = key
         handle = self.mgr.collections[coll_name].handle.first
         B = len(chunk)
+        if isinstance(chunk[0].payload, RangedQuery):   # the key's "ranged" marker: every request of the chunk is one
+            return self._enqueue_dense_range(torch, dev, stream, handle, top_k, expr, chunk)
         k = self.mgr.group_window(top_k) if group_field is not None else top_k
         q = dense_rows_device([r.payload for r in chunk], dev, handle.dim)
         ids, sc, fl = list_buffers(B, k, dev)
@@ -386,6 +403,20 @@ class SearchCoalescer:
         if group_field is not None:
             self._group_select(torch, dev, stream, top_k, group_field, st)
         return st
+
+    def _enqueue_dense_range(self, torch, dev, stream, handle, top_k, expr, chunk):
+        """The ranged requests of a round in ONE hr_search_dense_range_dev: the bounds are a [2, B] float64 operand."""
+        B = len(chunk)
+        q = dense_rows_device([r.payload.query for r in chunk], dev, handle.dim)
+        rb = torch.from_numpy(np.array([r.payload.bounds for r in chunk], dtype=np.float64).T.copy()).to(dev)
+        ids, sc, fl = list_buffers(B, top_k, dev)
+        mask = self.mgr._device_row_mask(expr, "dense")
+        handle.search_dense_range_dev(q.data_ptr(), B, top_k, rb[0].data_ptr(), rb[1].data_ptr(), ids.data_ptr(),
+                                      sc.data_ptr(), fl.data_ptr(), mask.data_ptr() if mask is not None else 0,
+                                      stream.cuda_stream)
+        self.stats["dense_launches"] += 1
+        self.stats["range_launches"] += 1
+        return {"ids": ids, "sc": sc, "fl": fl, "keep": (q, rb, mask)}
 
     def _group_select(self, torch, dev, stream, top_k, group_field, st):
         """The first top_k groups of every window of the batch (hr_group_select_dev, same stream, behind the search) -> st["group"]

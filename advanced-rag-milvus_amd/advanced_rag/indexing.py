@@ -30,7 +30,7 @@ import os
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from enum import Enum
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -81,6 +81,41 @@ def metric_code(name: str) -> int:
 def metric_name(code) -> str:
     """The label of a shard handle's metric code; handles that carry none (stubs) are COSINE collections."""
     return {0: "IP", 1: "COSINE", 2: "L2"}.get(code, "COSINE")
+
+
+RANGE_KEYS = ("radius", "range_filter")
+
+
+def range_bounds(params: Optional[Dict], metric: str) -> Optional[Tuple[float, float]]:
+    """Milvus' range search: (radius, range_filter) of search_params["params"], or None when neither is given.
+
+    Kept are the rows with radius < score <= range_filter (COSINE, IP) or range_filter <= distance < radius (L2); an
+    absent side is unbounded: radius = -inf and range_filter = +inf for COSINE and IP, the opposite for L2.  ValueError
+    for a bound that is not a number or is NaN, and for an empty interval (radius >= range_filter; L2: range_filter >=
+    radius)."""
+    metric_code(metric)
+    inner = (params or {}).get("params") or {}
+    if not any(k in inner and inner[k] is not None for k in RANGE_KEYS):
+        return None
+    l2 = metric == "L2"
+    fill = {"radius": float("inf") if l2 else float("-inf"), "range_filter": float("-inf") if l2 else float("inf")}
+    out = []
+    for k in RANGE_KEYS:
+        v = inner.get(k)
+        if v is None:
+            out.append(fill[k])
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError(f"{k} must be a number, got {v!r}")
+        v = float(v)
+        if v != v:
+            raise ValueError(f"{k} is NaN")
+        out.append(v)
+    radius, range_filter = out
+    if (range_filter >= radius) if l2 else (radius >= range_filter):
+        raise ValueError(f"empty range for {metric}: radius={radius}, range_filter={range_filter} "
+                         + ("(kept are range_filter <= distance < radius)" if l2 else "(kept are radius < score <= range_filter)"))
+    return radius, range_filter
 
 
 class ShardCollection:
@@ -845,14 +880,32 @@ class MilvusIndexManager:
             raise ValueError(f"metric_type {metric} does not match collection {coll.name} ({coll.metric})")
         return params
 
+    def _range_request(self, coll, params: Dict, group_by_field: Optional[str]) -> Optional[Tuple[float, float]]:
+        """The (radius, range_filter) of a request's search params, or None; refuses what range search is not built for."""
+        bounds = range_bounds(params, coll.metric if coll.kind != "sparse" else "IP")
+        if bounds is None:
+            return None
+        if coll.kind == "sparse":
+            raise ValueError(f"range search (radius / range_filter) is not built for the sparse collection {coll.name}: "
+                             "the sparse scan has no range clamp")
+        if group_by_field is not None:
+            raise ValueError("range search (radius / range_filter) cannot be combined with group_by_field")
+        if hasattr(coll.handle, "round"):
+            raise NotImplementedError("range search (radius / range_filter) is not built for the torchrun form "
+                                      "(CollectiveShardSet)")
+        return bounds
+
     def _search_lists_blocking(self, query, collection_name: str, top_k: int, filters: Optional[str], params: Dict,
-                               group_by_field: Optional[str] = None):
+                               group_by_field: Optional[str] = None, bounds: Optional[Tuple[float, float]] = None):
         """(row ids [k], scores [k]) of ONE query through the host forms (which escalate until the list is proven).  With
-        group_by_field: the exact grouped ranking (_grouped_lists_blocking), as many entries as there are groups, at most k."""
+        group_by_field: the exact grouped ranking (_grouped_lists_blocking), as many entries as there are groups, at most k.
+        bounds = (radius, range_filter) of a range search on a dense collection: the range forms of the same paths."""
         coll = self.collections[collection_name]
         drop = float((params.get("params") or params).get("drop_ratio_search", 0.0))
         if group_by_field is not None:
             return self._grouped_lists_blocking(query, coll, int(top_k), filters, drop, group_by_field)
+        if bounds is not None:
+            return self._range_lists_blocking(query, coll, int(top_k), filters, bounds)
         if getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and self._filters_on_device() is not None:
             # one local GPU shard: the mask never leaves the device
             h = coll.handle.first
@@ -871,6 +924,38 @@ class MilvusIndexManager:
         else:
             ids, sc = coll.handle.search_dense(dense_rows_host([query]), top_k, mask)
         return ids[0], sc[0]
+
+    def _range_lists_blocking(self, query, coll, top_k: int, filters: Optional[str], bounds: Tuple[float, float]):
+        """_search_lists_blocking for a range search on a dense collection: the same three paths (mask in HBM, query in
+        HBM, host mask over every shard) through hr_search_dense_range / hr_search_dense_range_dev."""
+        radius, range_filter = bounds
+        if getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and self._filters_on_device() is not None:
+            h = coll.handle.first
+            d_mask = self._device_row_mask(filters, coll.kind)
+            if hasattr(query, "is_cuda") and query.is_cuda and d_mask is None:
+                ids, sc = self._search_dense_range_device(h, query, top_k, bounds)
+            else:
+                ids, sc = h.search_dense_range(dense_rows_host([query]), top_k, radius, range_filter, None,
+                                               d_mask.data_ptr() if d_mask is not None else 0)
+            return ids[0], sc[0]
+        ids, sc = coll.handle.search_dense(dense_rows_host([query]), top_k, self._row_mask(filters), bounds=bounds)
+        return ids[0], sc[0]
+
+    @staticmethod
+    def _search_dense_range_device(handle, q_dev, top_k: int, bounds: Tuple[float, float]):
+        """_search_dense_device for a range search: an unproven list (rows within the scan's error of a bound, ties at the
+        candidate cut) is redone through the host form."""
+        import torch
+        q = dense_rows_device([q_dev], q_dev.device, handle.dim)
+        ids, sc, flag = list_buffers(1, top_k, q.device)
+        rb = torch.tensor(bounds, dtype=torch.float64, device=q.device)
+        stream = torch.cuda.current_stream(q.device)
+        handle.search_dense_range_dev(q.data_ptr(), 1, top_k, rb.data_ptr(), rb.data_ptr() + 8, ids.data_ptr(), sc.data_ptr(),
+                                      flag.data_ptr(), 0, stream.cuda_stream)
+        stream.synchronize()
+        if int(flag.item()) != 1:
+            return handle.search_dense_range(q.cpu().numpy(), top_k, bounds[0], bounds[1])
+        return ids.cpu().numpy(), sc.cpu().numpy()
 
     @staticmethod
     def group_window(top_k: int) -> int:
@@ -971,8 +1056,10 @@ class MilvusIndexManager:
                          search_params: Optional[Dict], group_by_field: Optional[str] = None) -> List[Dict[str, Any]]:
         coll = self.collections[collection_name]
         params = self._search_params(coll, search_params)
+        bounds = self._range_request(coll, params, group_by_field)
         query = self._as_sparse_payload(query_embedding) if coll.kind == "sparse" else query_embedding
-        return self._format_hits(*self._search_lists_blocking(query, collection_name, top_k, filters, params, group_by_field))
+        return self._format_hits(*self._search_lists_blocking(query, collection_name, top_k, filters, params, group_by_field,
+                                                              bounds))
 
     @staticmethod
     def _search_dense_device(handle, q_dev, top_k: int):
@@ -1016,7 +1103,14 @@ class MilvusIndexManager:
 
     @staticmethod
     def _params_key(params: Dict) -> tuple:
-        return tuple(sorted((k, v) for k, v in (params.get("params") or {}).items() if isinstance(v, (int, float, str, bool))))
+        """What of a request's search params decides which requests may share a launch.  The two numbers of a range search
+        are operands of the launch, not part of the key: one marker says "ranged", so that ranged requests with different
+        bounds share a launch and never share one with unranged requests."""
+        inner = params.get("params") or {}
+        key = tuple(sorted((k, v) for k, v in inner.items() if isinstance(v, (int, float, str, bool)) and k not in RANGE_KEYS))
+        if any(inner.get(k) is not None for k in RANGE_KEYS):
+            key += (("ranged", True),)
+        return key
 
     async def search(self, query_embedding, collection_name: str, top_k: int = 20, filters: Optional[str] = None,
                      search_params: Optional[Dict] = None, *, group_by_field: Optional[str] = None,
@@ -1034,7 +1128,11 @@ class MilvusIndexManager:
         try:
             if front is not None:
                 params = self._search_params(coll, search_params)
+                bounds = self._range_request(coll, params, group_by_field)
                 query = self._as_sparse_payload(query_embedding) if coll.kind == "sparse" else query_embedding
+                if bounds is not None:
+                    from .batching import RangedQuery
+                    query = RangedQuery(query, bounds)
                 fut = front.submit_async("sparse" if coll.kind == "sparse" else "dense",
                                          (collection_name, int(top_k), filters, self._params_key(params), group_by_field), query)
                 ids, sc = await asyncio.wait_for(fut, timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
@@ -1072,8 +1170,11 @@ class MilvusIndexManager:
         if mmr_lambda is not None and front.collective:
             return None
         try:
-            self._search_params(sem, semantic_params)
+            if range_bounds(self._search_params(sem, semantic_params), sem.metric) is not None:
+                return None        # a range on the semantic list: the one-round path has no range form
             sp = self._search_params(spa, sparse_params)
+            if range_bounds(sp, "IP") is not None:
+                return None        # the general path refuses a range on sparse_index: it owns the error
             drop = float((sp.get("params") or sp).get("drop_ratio_search", 0.0))
             payload = self._as_sparse_payload(sparse_embedding)
         except Exception:

@@ -263,11 +263,15 @@ class ShardSet:
         ids = [to_global(li, self.rows_of[s]) for s, (li, _) in enumerate(parts)]
         return merge_lists(ids, [sc for _, sc in parts], k, ascending)
 
-    def search_dense(self, q: np.ndarray, k: int, keep: Optional[np.ndarray] = None):
-        """q [B, dim] float32; keep = boolean filter over GLOBAL rows (or None) -> (ids [B,k] global rows, scores)."""
+    def search_dense(self, q: np.ndarray, k: int, keep: Optional[np.ndarray] = None, bounds=None):
+        """q [B, dim] float32; keep = boolean filter over GLOBAL rows (or None) -> (ids [B,k] global rows, scores).
+        bounds = (radius, range_filter) of a range search, numbers or one per query: every shard's range form gets them, and
+        the merge is the usual one (the per-shard lists are in range already)."""
         def one(s):
             if self.handles[s].num_rows == 0:
                 return empty_lists(np.atleast_2d(q).shape[0], k)
+            if bounds is not None:
+                return self.handles[s].search_dense_range(q, k, bounds[0], bounds[1], *self._local_mask(s, keep))
             return self.handles[s].search_dense(q, k, *self._local_mask(s, keep))
         return self._gather(self._fan_out(one), k, self.dense_ascending)
 
@@ -631,7 +635,9 @@ class CollectiveShardSet:
             body = wire.pack(wire.OP_ROUND, {**fields, **wire.mask_fields(mask_id, mask_new, mask_bytes)}, sections, self.PACKET_BYTES)
             return self._dispatch(body, mask_bytes=mask_bytes)
 
-    def search_dense(self, q: np.ndarray, k: int, keep: Optional[np.ndarray] = None):
+    def search_dense(self, q: np.ndarray, k: int, keep: Optional[np.ndarray] = None, bounds=None):
+        if bounds is not None:
+            raise NotImplementedError("range search is not built for the torchrun form: a round's packet carries no bounds")
         return self.round(q, None, k, 0.0, keep)[0]
 
     def search_sparse(self, queries, k: int, drop_ratio: float = 0.0, keep: Optional[np.ndarray] = None):

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "range_bounds.h"
 
 namespace hbmrag {
 
@@ -88,10 +89,32 @@ __global__ void row_norms_kernel(const chunk_t* __restrict__ tiles, int KT, int6
 // L2 shards (qcoef != nullptr) also get, per slot, the coefficient of the row term, 1 / |q| (1 for a zero query, whose
 // fragments are zero: the scan then ranks by -|x|^2 / 2), and the per-query part of the scan's error bound,
 // rt_eps / |q| (infinite when it leaves the fp32 range: such a list is never proven); padding slots get 0.
+//
+// Range search (rp.hi_a != nullptr; hr_search_dense_range*): per slot the two bounds of the query IN THE SCAN'S DOMAIN,
+// where the scan's value a of a row lies within eps(q) of the exact t (COSINE: the cosine; IP: S / |q|; L2:
+// (|q|^2 - D) / (2 |q|), decreasing in D), and per query the two canonical bounds the refine tests (rp.bounds).
+//   hi_a >= t + eps(q) for every row whose canonical fp32 score passes the BETTER bound (range_filter): the scan may turn
+//           a > hi_a into -inf, such a row is certainly out of range;
+//   lo_a <  t - eps(q) for every row whose canonical score passes the WORSE bound (radius): a_cut <= lo_a proves that no
+//           row outside the candidate groups is in range.
+// The slack between a bound on the canonical fp32 score and a bound on the exact value is derived in DESIGN.md
+// section 3.1 ("Range search") and restated in numpy by tests/test_range_host.py.
+struct RangePrep {
+    const double* radius;        // [B] or null = unbounded
+    const double* range_filter;  // [B] or null = unbounded
+    double* bounds;              // [B][2] out: radius, range_filter with the absent sides filled in
+    float* hi_a;                 // [slots] out (padding slots: +inf)
+    float* lo_a;                 // [slots] out (padding slots: -inf)
+    float eps_abs;               // the scan's error bound that does not depend on the query (dense_eps)
+    float max_norm;              // largest row norm of the shard
+    int metric;
+    int no_clamp;                // HR_DEBUG_NO_RANGE_CLAMP: every ceiling is +inf
+};
+
 template <typename STORE>
 __global__ void prep_queries_kernel(const float* __restrict__ q, int B, int dim, int KT,
                                     chunk_t* __restrict__ qfrag, double* __restrict__ qn2,
-                                    float* __restrict__ qcoef, float* __restrict__ qeps, float rt_eps) {
+                                    float* __restrict__ qcoef, float* __restrict__ qeps, float rt_eps, RangePrep rp) {
     constexpr int EPC = kChunkBytes / (int)sizeof(STORE);
     const int slot = blockIdx.x;
     const int g = slot >> 4, col = slot & 15;
@@ -112,12 +135,28 @@ __global__ void prep_queries_kernel(const float* __restrict__ q, int B, int dim,
             qn2[slot] = s;
         }
         s_inv = (s > 0.0) ? (float)(1.0 / sqrt(s)) : 0.0f;
+        float e_q = 0.f;
         if (qcoef) {
             const float c = slot < B ? ((s > 0.0) ? (float)(1.0 / sqrt(s)) : 1.0f) : 0.0f;
             float e = rt_eps * c * 1.000001f;
             if (!(e < 3.0e38f)) e = __builtin_inff();
             qcoef[slot] = c;
             qeps[slot] = e;
+            e_q = e;
+        }
+        if (rp.hi_a) {
+            const bool l2 = rp.metric == HR_METRIC_L2;
+            const double INF = (double)__builtin_inff();
+            float hi = __builtin_inff(), lo = -__builtin_inff();
+            if (slot < B) {
+                const double r = rp.radius ? rp.radius[slot] : (l2 ? INF : -INF);
+                const double f = rp.range_filter ? rp.range_filter[slot] : (l2 ? -INF : INF);
+                rp.bounds[2 * slot] = r;
+                rp.bounds[2 * slot + 1] = f;
+                range_scan_bounds(rp.metric, s, r, f, (double)rp.eps_abs + (double)e_q, (double)rp.max_norm, &hi, &lo);
+            }
+            rp.hi_a[slot] = rp.no_clamp ? __builtin_inff() : hi;
+            rp.lo_a[slot] = lo;
         }
     }
     __syncthreads();
@@ -187,11 +226,13 @@ __device__ __forceinline__ void store_group_max(float v, float* gmax, int64_t gm
 // L2 = the squared-Euclidean form (compile time: the COSINE / IP instantiations are what they were): `scale` then holds
 // the row terms |x|^2 / 2, qcoef[16 g + c] the coefficient 1 / |q| of query slot 16 g + c, and the epilogue is
 // acc - term * coef = (2 x.q - |x|^2) / (2 |q|): larger = nearer, so everything downstream of the maxima is unchanged.
-template <typename STORE, int G, int RS, int PF, int NRB, bool L2 = false>
+// RANGE = range search (compile time as well): qhi[16 g + c] is the ceiling hi_a of query slot 16 g + c
+// (prep_queries_kernel), and a value above it becomes -inf before the group maximum, exactly what a masked row gets.
+template <typename STORE, int G, int RS, int PF, int NRB, bool L2 = false, bool RANGE = false>
 __global__ __launch_bounds__(512) void dense_scan_kernel(
     const chunk_t* __restrict__ tiles, const chunk_t* __restrict__ qfrag, const float* __restrict__ scale,
     const uint8_t* __restrict__ rowmask, float* __restrict__ gmax, int nq, int KT, int64_t n_rows,
-    int64_t n_super, const float* __restrict__ qcoef) {
+    int64_t n_super, const float* __restrict__ qcoef, const float* __restrict__ qhi) {
     // NRB = row blocks per candidate group: 4 (64-row groups) or 1 (16-row groups).
     // `group` below walks SUPER-groups of 4 row blocks either way; gmax is [nq][n_super*4/NRB].
     static_assert(NRB == 1 || NRB == kRowBlocksPerSuper, "group = one row block or one super-group");
@@ -212,6 +253,9 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
     float cf[G];  // L2: this lane's query coefficients (the buffer holds every slot of the pass, padding included)
 #pragma unroll
     for (int g = 0; g < G; ++g) cf[g] = L2 ? qcoef[16 * g + (lane & 15)] : 0.f;
+    float hi[G];  // RANGE: this lane's query ceilings
+#pragma unroll
+    for (int g = 0; g < G; ++g) hi[g] = RANGE ? qhi[16 * g + (lane & 15)] : 0.f;
 
     // Prefetch cursor: walks (group, pair, kt) exactly PF steps ahead of the
     // consumer, across pair and group boundaries, so the wave's HBM stream
@@ -290,6 +334,7 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float v = L2 ? acc[s][g][r] - sc[r] * cf[g] : acc[s][g][r] * sc[r];
+                        if (RANGE) v = v > hi[g] ? NEG_INF : v;
                         v = (ok[r] != 0.f) ? v : NEG_INF;
                         mr = fmaxf(mr, v);
                     }
@@ -324,12 +369,12 @@ __global__ __launch_bounds__(512) void dense_scan_kernel(
 // L2: L2 : HBM traffic = 1 : 1.  MFMA work per corpus KiB is GQ x 16 cycles per
 // SIMD (GQ = 16: 64 cycles per KiB per CU against ~100 cycles per KiB of HBM
 // supply), so the pass stays HBM-bound.
-// L2, epilogue and output: those of dense_scan_kernel.
-template <typename STORE, int GQ, int NRB, bool L2 = false>
+// L2, RANGE, epilogue and output: those of dense_scan_kernel.
+template <typename STORE, int GQ, int NRB, bool L2 = false, bool RANGE = false>
 __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
     const chunk_t* __restrict__ tiles, const chunk_t* __restrict__ qfrag, const float* __restrict__ scale,
     const uint8_t* __restrict__ rowmask, float* __restrict__ gmax, int nq, int KT, int64_t n_rows,
-    int64_t n_super, const float* __restrict__ qcoef) {
+    int64_t n_super, const float* __restrict__ qcoef, const float* __restrict__ qhi) {
     constexpr int RS = 2, BKT = 2, PF = 4;  // query chunk = 2 k-steps (16 staging registers), corpus ring = 4 k-steps
     constexpr int kPairs = kRowBlocksPerSuper / RS;
     constexpr int kFrags = GQ * BKT;           // 1 KiB query fragments per k-chunk
@@ -348,6 +393,9 @@ __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
     float cf[GQ];  // L2: this lane's query coefficients
 #pragma unroll
     for (int g = 0; g < GQ; ++g) cf[g] = L2 ? qcoef[16 * g + (lane & 15)] : 0.f;
+    float hi[GQ];  // RANGE: this lane's query ceilings
+#pragma unroll
+    for (int g = 0; g < GQ; ++g) hi[g] = RANGE ? qhi[16 * g + (lane & 15)] : 0.f;
     const int64_t n_rounds = (n_super + total_waves - 1) / total_waves;  // the same for every wave: lockstep
 
     // corpus prefetch cursor (the walk of dense_scan_kernel's); past the end, and for idle waves (every wave walks
@@ -454,6 +502,7 @@ __global__ __launch_bounds__(512) void dense_scan_bigq_kernel(
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             float v = L2 ? acc[s][g][r] - sc[r] * cf[g] : acc[s][g][r] * sc[r];
+                            if (RANGE) v = v > hi[g] ? NEG_INF : v;
                             v = (ok[r] != 0.f) ? v : NEG_INF;
                             mr = fmaxf(mr, v);
                         }
@@ -1187,6 +1236,17 @@ __global__ __launch_bounds__(512) void dense_scan_gemm_kernel(
 // L2 (compile time; metric = HR_METRIC_L2): D = the k-ordered fp64 sum of d * d, d = x[k] - q[k], every operation
 // rounded on its own; the slot's score is -(float) D, so that (score desc, row asc) is (distance asc, row asc) and the
 // selection kernels stay as they are (select_topk_block negates back on the way out).
+// Range search: the test of the result semantics on the fp32 score a slot carries (L2: the slot's score is -D32), widened
+// to double.  range_q = the query's two bounds, radius then range_filter.  A row that fails is invalid exactly like a row
+// outside the mask.  Invariant: the test is applied by the CALLERS of refine_dense_slot (refine_dense_kernel, the dense
+// block of finish_kernel), to the slot's result, right behind the call; refine_dense_slot itself is what it was
+// (profiles/range_refine_inline_form.txt records what hipcc made of a form inside the slot function).
+template <bool L2>
+__device__ __forceinline__ bool dense_score_in_range(float score, const double* __restrict__ range_q) {
+    const double v = L2 ? -(double)score : (double)score, radius = range_q[0], range_filter = range_q[1];
+    return L2 ? (range_filter <= v && v < radius) : (radius < v && v <= range_filter);
+}
+
 // One candidate row slot of query qi: returns false (invalid) or the canonical score and the row.
 template <typename STORE, bool L2 = false>
 __device__ inline bool refine_dense_slot(const chunk_t* __restrict__ tiles, int KT, int dim, const float* __restrict__ qq,
@@ -1262,7 +1322,8 @@ __global__ __launch_bounds__(64) void refine_dense_kernel(
     const chunk_t* __restrict__ tiles, int KT, int dim, const float* __restrict__ q,
     const double* __restrict__ qn2, const double* __restrict__ norm2,
     const uint8_t* __restrict__ rowmask, const int32_t* __restrict__ cand, int C, int group_rows,
-    int64_t n_rows, int metric, float* __restrict__ out_score, int32_t* __restrict__ out_row) {
+    int64_t n_rows, int metric, float* __restrict__ out_score, int32_t* __restrict__ out_row,
+    const double* __restrict__ range_bounds) {
     const int qi = blockIdx.y, lane = threadIdx.x;
     const int slot = blockIdx.x * 64 + lane;          // candidate row slot of this query
     const int n_slots = C * group_rows;
@@ -1270,13 +1331,11 @@ __global__ __launch_bounds__(64) void refine_dense_kernel(
     const int64_t o = (int64_t)qi * n_slots + slot;
     float sc = -__builtin_inff();
     int32_t row = -1;
-    if (!refine_dense_slot<STORE, L2>(tiles, KT, dim, q + (int64_t)qi * dim, qn2[qi], norm2, rowmask, cand + (int64_t)qi * C,
-                                      group_rows, n_rows, metric, slot, &sc, &row)) {
-        sc = -__builtin_inff();
-        row = -1;
-    }
-    out_score[o] = sc;
-    out_row[o] = row;
+    bool ok = refine_dense_slot<STORE, L2>(tiles, KT, dim, q + (int64_t)qi * dim, qn2[qi], norm2, rowmask,
+                                           cand + (int64_t)qi * C, group_rows, n_rows, metric, slot, &sc, &row);
+    if (ok && range_bounds) ok = dense_score_in_range<L2>(sc, range_bounds + 2 * qi);
+    out_score[o] = ok ? sc : -__builtin_inff();
+    out_row[o] = ok ? row : -1;
 }
 
 }  // namespace hbmrag

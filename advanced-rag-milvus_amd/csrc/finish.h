@@ -33,6 +33,7 @@ struct FinishMod {
     const float* q;
     const double* qn2;
     const double* norm2;
+    const double* range_bounds;  // range search: [B][2] radius, range_filter (null otherwise)
     // sparse
     const int64_t* indptr;
     const int32_t* idx;
@@ -143,6 +144,7 @@ __global__ __launch_bounds__(kFinishThreads) void finish_kernel(FinishPair p) {
         for (int k = tid; k < a.dim; k += kFinishThreads) qq[k] = a.q[(int64_t)q * a.dim + k];
         __syncthreads();
         const double qn2 = a.qn2[q];
+        const double* rq = a.range_bounds ? a.range_bounds + 2 * q : nullptr;
         for (int slot = tid; slot < n_live_slots; slot += kFinishThreads) {
 #ifdef HR_STAMP
             if (blockIdx.x == 0) atomicAdd(&hr_finish_stamps[blockIdx.y][6], 1ull);   // rows that take the canonical chain
@@ -162,6 +164,7 @@ __global__ __launch_bounds__(kFinishThreads) void finish_kernel(FinishPair p) {
                                                        a.group_rows, a.n_rows, a.metric, slot, &sc, &row)
                          : refine_dense_slot<float>(a.tiles, a.KT, a.dim, qq, qn2, a.norm2, a.rowmask, s_cand,
                                                     a.group_rows, a.n_rows, a.metric, slot, &sc, &row);
+            if (ok && rq) ok = a.metric == HR_METRIC_L2 ? dense_score_in_range<true>(sc, rq) : dense_score_in_range<false>(sc, rq);
             s_key[slot] = ok ? rank_key(sc, (uint32_t)row) : 0ull;
         }
     } else {

@@ -117,6 +117,8 @@ struct Workspace : WorkspaceQueues {
     struct Workspace* sparse_ws = nullptr;  // private buffers of the sparse chain when it runs concurrently
     DevBuf qfrag, qn2, gmax, bmax, cand, acut, cscore, crow, flags, qscale, qeps, qfloor, pq_n, pq_idx, pq_w;
     DevBuf qcoef, dqeps;   // L2 shards: per query slot, the row term's coefficient 1 / |q| and the per-query error term
+    DevBuf rbounds, rhi, rlo;   // range search: per query the two canonical bounds, per query slot the scan's ceiling and floor
+    DevBuf d_radius, d_rfilter;                   // range search, host form: the callers' bounds
     DevBuf d_q, d_ids, d_scores, d_mask;          // host-form staging
     DevBuf d_qptr, d_qidx, d_qval;                // sparse query staging
     DevBuf f_ids, f_out_ids, f_out_scores, f_out_meth, f_n;  // hr_fuse_rrf staging
@@ -361,12 +363,13 @@ struct ScanArgs {
     int nq;
     int64_t n_super;
     const float* qcoef;  // L2 passes: the coefficients of this pass's query slots
+    const float* qhi;    // range passes: the ceilings of this pass's query slots
 };
 
-template <typename STORE, int G, int NRB, bool L2>
+template <typename STORE, int G, int NRB, bool L2, bool RANGE>
 hipError_t launch_scan_lds(const ScanArgs& a) {
     constexpr int RS = 2, PF = 4;
-    auto kern = dense_scan_kernel<STORE, G, RS, PF, NRB, L2>;
+    auto kern = dense_scan_kernel<STORE, G, RS, PF, NRB, L2, RANGE>;
     const hr_index* h = a.h;
     const size_t lds = (size_t)G * h->KT * 1024;
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -386,14 +389,14 @@ hipError_t launch_scan_lds(const ScanArgs& a) {
                                        (int64_t)scan_cus(h) * per_cu);
     blocks = std::max<int64_t>(blocks, 1);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), lds, a.s, h->tiles.as<chunk_t>(), a.qfrag,
-                       h->scale.as<float>(), a.mask, a.gmax, a.nq, h->KT, h->n_rows, a.n_super, a.qcoef);
+                       h->scale.as<float>(), a.mask, a.gmax, a.nq, h->KT, h->n_rows, a.n_super, a.qcoef, a.qhi);
     return hipGetLastError();
 }
 
 // Large-batch pass (dense_scan_bigq_kernel): GQ query groups streamed through LDS in k-chunks.
-template <typename STORE, int GQ, int NRB, bool L2>
+template <typename STORE, int GQ, int NRB, bool L2, bool RANGE>
 hipError_t launch_scan_bigq(const ScanArgs& a) {
-    auto kern = dense_scan_bigq_kernel<STORE, GQ, NRB, L2>;
+    auto kern = dense_scan_bigq_kernel<STORE, GQ, NRB, L2, RANGE>;
     const hr_index* h = a.h;
     const size_t lds = (size_t)2 * GQ * 2 * 1024;  // 2 buffers x GQ groups x BKT(2) fragments of 1 KiB
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -401,7 +404,7 @@ hipError_t launch_scan_bigq(const ScanArgs& a) {
     int64_t blocks = std::min<int64_t>((a.n_super + 7) / 8, (int64_t)scan_cus(h));
     blocks = std::max<int64_t>(blocks, 1);
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), lds, a.s, h->tiles.as<chunk_t>(), a.qfrag,
-                       h->scale.as<float>(), a.mask, a.gmax, a.nq, h->KT, h->n_rows, a.n_super, a.qcoef);
+                       h->scale.as<float>(), a.mask, a.gmax, a.nq, h->KT, h->n_rows, a.n_super, a.qcoef, a.qhi);
     return hipGetLastError();
 }
 
@@ -460,13 +463,13 @@ auto with_store(int dtype, F f) {
     return f(float{});
 }
 
-// The two generic kernels: STORE x L2 here, NRB x G below.
-template <typename STORE, bool L2>
+// The two generic kernels: STORE x L2 x RANGE here, NRB x G below.
+template <typename STORE, bool L2, bool RANGE>
 hipError_t launch_scan_generic(const ScanPlan& p, const ScanArgs& a) {
     return with_constant<1, 4>(p.NRB, [&](auto nrb) {
-        if (p.kind == SCAN_BIGQ) return launch_scan_bigq<STORE, 8, decltype(nrb)::value, L2>(a);
+        if (p.kind == SCAN_BIGQ) return launch_scan_bigq<STORE, 8, decltype(nrb)::value, L2, RANGE>(a);
         return with_constant<1, 2, 3, 4>(
-            p.G, [&](auto g) { return launch_scan_lds<STORE, decltype(g)::value, decltype(nrb)::value, L2>(a); });
+            p.G, [&](auto g) { return launch_scan_lds<STORE, decltype(g)::value, decltype(nrb)::value, L2, RANGE>(a); });
     });
 }
 
@@ -479,16 +482,24 @@ hipError_t launch_scan(const ScanPlan& p, const ScanArgs& a) {
         case SCAN_BIGQ:
             return with_store(a.h->dtype, [&](auto store) {
                 using STORE = decltype(store);
-                return p.l2 ? launch_scan_generic<STORE, true>(p, a) : launch_scan_generic<STORE, false>(p, a);
+                if (p.range) return p.l2 ? launch_scan_generic<STORE, true, true>(p, a) : launch_scan_generic<STORE, false, true>(p, a);
+                return p.l2 ? launch_scan_generic<STORE, true, false>(p, a) : launch_scan_generic<STORE, false, false>(p, a);
             });
         default: return hipErrorInvalidValue;
     }
 }
 
+// A range search's bounds as the device sees them: [B] doubles each, null = that side unbounded for every query.
+struct DenseRange {
+    const double* d_radius;
+    const double* d_range_filter;
+};
+
 int g_dense_kernels = 0;  // HR_DEBUG_DENSE_KERNELS: bit mask that takes scan kernels out of the selection (scan_plan.h)
 int g_sparse_rpb = 0;     // HR_DEBUG_SPARSE_RPB: doc ranges per sparse-scan block (0 = by shard size)
 int g_no_trim = 0;        // HR_DEBUG_NO_TRIM: 1 = refine all C candidate groups (A/B of the data-dependent candidate set)
 int g_group_rows = 0;     // HR_DEBUG_GROUP_ROWS: candidate-group size of handles created from now on (0 = by shard size)
+int g_no_range_clamp = 0; // HR_DEBUG_NO_RANGE_CLAMP: 1 = the range scans get +inf ceilings (what the clamp proves, A/B)
 
 // Two-level candidate selection: per-bucket maxima, then one block per query — for one modality or for both
 // modalities of a hybrid search in one pair of launches (select.h: GroupSelPair).
@@ -572,6 +583,7 @@ struct FinishSide {
     const uint8_t* mask;
     TopkArgs topk;
     const float* d_q;  // dense refine
+    const double* range_bounds;  // dense refine of a range search: [B][2] radius, range_filter
     const int64_t* q_ptr;  // sparse refine: the query CSR and the fixed stride of the scan's query layout
     const int32_t* q_idx;
     const float* q_val;
@@ -610,8 +622,10 @@ int side_common(hr_index* h, Workspace* ws, int B, int k, int C, int GR, int64_t
     return HR_OK;
 }
 inline int64_t dense_super_groups(const hr_index* h) { return (h->n_rows + kSuperRows - 1) / kSuperRows; }
+// ranged: the finish of a range search: the refine tests ws->rbounds and the proof takes the per-query floors ws->rlo
+// (both written by the range search's query prep).
 int dense_side(hr_index* h, Workspace* ws, const float* d_q, int B, int k, int C, const uint8_t* d_mask, const OutLists& out,
-               FinishSide* f) {
+               FinishSide* f, bool ranged = false) {
     const int GR = group_rows_for(h, h->n_rows);
     HR_TRY(side_common(h, ws, B, k, C, GR, dense_super_groups(h) * (kSuperRows / GR), d_mask, out, f));
     f->d_q = d_q;
@@ -621,6 +635,10 @@ int dense_side(hr_index* h, Workspace* ws, const float* d_q, int B, int k, int C
     t.cut_floor = -INFINITY;
     t.eps_abs_q = t.norm_mode == 2 ? ws->dqeps.as<float>() : nullptr;   // L2: the row term's share, 1 / |q| times a constant
     t.qn2 = ws->qn2.as<double>();
+    if (ranged) {
+        f->range_bounds = ws->rbounds.as<double>();
+        t.cut_floor_q = ws->rlo.as<float>();   // a_cut <= lo_a: no row outside the candidates is in range
+    }
     return HR_OK;
 }
 int sparse_side(hr_index* h, Workspace* ws, const int64_t* d_qptr, const int32_t* d_qidx, const float* d_qval, int B,
@@ -684,6 +702,7 @@ FinishMod finish_mod(const hr_index* h, const FinishSide& f) {
         m.q = f.d_q;
         m.qn2 = f.ws->qn2.as<double>();
         m.norm2 = h->norm2.as<double>();
+        m.range_bounds = f.range_bounds;
         m.n_rows = h->n_rows;
     }
     return m;
@@ -696,7 +715,7 @@ int launch_refine(hr_index* h, hipStream_t s, int B, const FinishSide& f) {
                         : (l2 ? refine_dense_kernel<float, true> : refine_dense_kernel<float, false>);
         hipLaunchKernelGGL(kern, dim3((f.C * f.GR + 63) / 64, B), dim3(64), 0, s, h->tiles.as<chunk_t>(), h->KT, (int)h->dim,
                            f.d_q, ws->qn2.as<double>(), h->norm2.as<double>(), f.mask, ws->cand.as<int32_t>(), f.C, f.GR,
-                           h->n_rows, h->metric, ws->cscore.as<float>(), ws->crow.as<int32_t>());
+                           h->n_rows, h->metric, ws->cscore.as<float>(), ws->crow.as<int32_t>(), f.range_bounds);
     } else {
         // 64 docs per wave: shorter chains finish this kernel sooner (0.60 -> 0.55 ms at 10M docs, 0.168 -> 0.136 ms at 1.25M
         // with 16) but the step does not gain — the kernel runs beside the scans, and what it takes from the HBM sooner they
@@ -778,10 +797,11 @@ int finish_enqueue(hr_index* h, hipStream_t s, int B, const FinishSide* f, int n
 // shard scan (leaves the group maxima in ws), PHASE_FINISH = candidate select + refine + top-k from those maxima.
 int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float* d_q, int B, int k,
                          const uint8_t* d_mask, const OutLists& out, int C, hipEvent_t scan_done = nullptr,
-                         int phases = PHASE_ALL) {
+                         int phases = PHASE_ALL, const DenseRange* rng = nullptr) {
     // one plan per pass (scan_plan.h); the full-batch plan gives the queries per pass
+    const bool ranged = rng != nullptr;
     auto plan_for = [&](int nq) {
-        return scan_plan(h->KT, h->dtype, h->metric, h->n_rows, h->group_rows_override, g_dense_kernels, B, nq);
+        return scan_plan(h->KT, h->dtype, h->metric, h->n_rows, h->group_rows_override, g_dense_kernels, B, nq, ranged);
     };
     const ScanPlan first = plan_for(B);
     if (first.kind == SCAN_NONE)
@@ -800,8 +820,24 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
     float* const d_coef = l2 ? ws->qcoef.as<float>() : nullptr;
     float* const d_qeps = l2 ? ws->dqeps.as<float>() : nullptr;
     const float rt_eps = l2 ? dense_l2_rt_eps(h) : 0.f;
+    RangePrep rp{};
+    if (ranged) {  // ceilings and floors per query SLOT, as the coefficients
+        HIP_TRY(h, ws->rbounds.ensure((size_t)B * 2 * sizeof(double)));
+        HIP_TRY(h, ws->rhi.ensure((size_t)n_chunks * chunk_q * sizeof(float)));
+        HIP_TRY(h, ws->rlo.ensure((size_t)n_chunks * chunk_q * sizeof(float)));
+        int norm_mode;
+        dense_eps(h, &rp.eps_abs, &norm_mode);
+        rp.radius = rng->d_radius;
+        rp.range_filter = rng->d_range_filter;
+        rp.bounds = ws->rbounds.as<double>();
+        rp.hi_a = ws->rhi.as<float>();
+        rp.lo_a = ws->rlo.as<float>();
+        rp.max_norm = h->max_row_norm;
+        rp.metric = h->metric;
+        rp.no_clamp = g_no_range_clamp;
+    }
     FinishSide f;
-    HR_TRY(dense_side(h, ws, d_q, B, k, C, d_mask, out, &f));
+    HR_TRY(dense_side(h, ws, d_q, B, k, C, d_mask, out, &f, ranged));
 
     if (phases & PHASE_PREP) {
         // every pass's queries in one launch: pass c owns fragment groups [c * Gmax, ...) of qfrag (slot = query number)
@@ -809,14 +845,15 @@ int dense_search_enqueue(hr_index* h, Workspace* ws, hipStream_t s, const float*
         const int G_total = (n_chunks - 1) * Gmax + plan_for(B - (n_chunks - 1) * chunk_q).G;
         hipLaunchKernelGGL(h->dtype == HR_F16 ? prep_queries_kernel<_Float16> : prep_queries_kernel<float>, dim3(16 * G_total),
                            dim3(256), 0, s, d_q, B, (int)h->dim, h->KT, ws->qfrag.as<chunk_t>(), ws->qn2.as<double>(), d_coef,
-                           d_qeps, rt_eps);
+                           d_qeps, rt_eps, rp);
         HIP_TRY(h, hipGetLastError());
     }
     for (int c0 = 0; (phases & PHASE_SCAN) && c0 < B; c0 += chunk_q) {
         const int nq = std::min(chunk_q, B - c0);
         Span sp(h, s, PH_SCAN);
         const ScanArgs a{h, s, ws->qfrag.as<chunk_t>() + (size_t)(c0 / chunk_q) * chunk_frag, d_mask,
-                         ws->gmax.as<float>() + (int64_t)c0 * f.n_groups, nq, dense_super_groups(h), l2 ? d_coef + c0 : nullptr};
+                         ws->gmax.as<float>() + (int64_t)c0 * f.n_groups, nq, dense_super_groups(h), l2 ? d_coef + c0 : nullptr,
+                         ranged ? ws->rhi.as<float>() + c0 : nullptr};
         HIP_TRY(h, launch_scan(plan_for(nq), a));
     }
     if (scan_done) HIP_TRY(h, hipEventRecord(scan_done, s));
@@ -1305,7 +1342,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 10900; }  // 1.9.0: hr_filter_eval_expr_dev
+int hr_version(void) { return 11000; }  // 1.10.0: hr_search_dense_range, hr_search_dense_range_dev
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -1796,6 +1833,23 @@ int hr_search_dense_dev(hr_index* h, const float* d_q, int B, int k, const uint8
     return dense_search_enqueue(h, ws, s, d_q, B, k, d_rowmask, {d_ids, d_scores, d_flags}, candidate_groups_for_k(k));
 }
 
+int hr_search_dense_range_dev(hr_index* h, const float* d_q, int B, int k, const uint8_t* d_rowmask, const double* d_radius,
+                              const double* d_range_filter, int64_t* d_ids, float* d_scores, int32_t* d_flags,
+                              void* stream) {
+    HR_TRY(check_search_args(h, B, k, true));
+    if (!d_q || !d_ids || !d_scores) return fail(h, HR_EINVAL, "null buffer");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    DeviceGuard dg(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (h->n_rows == 0) return fill_empty(h, s, B, k, d_ids, d_scores, d_flags);
+    StreamWs ws_held;
+    Workspace* ws = ws_for_stream(h, stream, ws_held);
+    if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
+    const DenseRange rng{d_radius, d_range_filter};
+    return dense_search_enqueue(h, ws, s, d_q, B, k, d_rowmask, {d_ids, d_scores, d_flags}, candidate_groups_for_k(k), nullptr,
+                                PHASE_ALL, &rng);
+}
+
 int hr_search_sparse_dev(hr_index* h, const int64_t* d_q_indptr, const int32_t* d_q_idx, const float* d_q_val, int B,
                          int64_t q_nnz_total, int max_q_nnz, int k, const uint8_t* d_rowmask, int64_t* d_ids,
                          float* d_scores, int32_t* d_flags, void* stream) {
@@ -2223,6 +2277,9 @@ int hr_debug_option(hr_index* h, int key, int value) {
         case HR_DEBUG_NO_TRIM:
             g_no_trim = value != 0;
             return HR_OK;
+        case HR_DEBUG_NO_RANGE_CLAMP:
+            g_no_range_clamp = value != 0;
+            return HR_OK;
         case HR_DEBUG_FAIL_NEXT_BUILD:
             if (!h) return fail(nullptr, HR_EINVAL, "null handle");
             h->fault_inject = value ? 1 : 0;
@@ -2494,22 +2551,50 @@ int hr_encoder_tail_f16_dev(const void* d_attn_fr, const void* d_x, int x_fr, vo
 }
 
 // ---- host-buffer, synchronous forms -------------------------------------------------
+// ranged: a range search with host arrays radius / range_filter ([B] each, null = unbounded).
 static int search_dense_host(hr_index* h, const float* q, int B, int k, const uint8_t* rowmask, bool mask_on_device,
-                             int64_t* out_ids, float* out_scores) {
+                             int64_t* out_ids, float* out_scores, bool ranged = false, const double* radius = nullptr,
+                             const double* range_filter = nullptr) {
     HR_TRY(check_search_args(h, B, k, true));
     if (!q || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
     for (int64_t i = 0; i < (int64_t)B * h->dim; ++i)   // the scan's bound (and the ranking) assume finite queries
         if (!std::isfinite(q[i])) return fail(h, HR_EINVAL, "non-finite value in query %lld", (long long)(i / h->dim));
+    for (int b = 0; ranged && b < B; ++b) {  // refused before anything is launched or written
+        const bool l2 = h->metric == HR_METRIC_L2;
+        const double r = radius ? radius[b] : (l2 ? INFINITY : -INFINITY);
+        const double f = range_filter ? range_filter[b] : (l2 ? -INFINITY : INFINITY);
+        if (std::isnan(r) || std::isnan(f)) return fail(h, HR_EINVAL, "NaN range bound in query %d", b);
+        if (l2 ? f >= r : r >= f)
+            return fail(h, HR_EINVAL, "empty range in query %d: radius %g, range_filter %g (%s)", b, r, f,
+                        l2 ? "L2 keeps range_filter <= distance < radius" : "kept are radius < score <= range_filter");
+    }
+    DenseRange rng{nullptr, nullptr};
     return search_host(
         h, B, k, &hr_index::n_rows, rowmask, mask_on_device, out_ids, out_scores,
         [&](Workspace* ws, hipStream_t s) {
             HIP_TRY(h, ws->d_q.ensure((size_t)B * h->dim * 4));
             HIP_TRY(h, hipMemcpyAsync(ws->d_q.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, s));
+            if (radius) {
+                HIP_TRY(h, ws->d_radius.ensure((size_t)B * sizeof(double)));
+                HIP_TRY(h, hipMemcpyAsync(ws->d_radius.p, radius, (size_t)B * sizeof(double), hipMemcpyHostToDevice, s));
+                rng.d_radius = ws->d_radius.as<double>();
+            }
+            if (range_filter) {
+                HIP_TRY(h, ws->d_rfilter.ensure((size_t)B * sizeof(double)));
+                HIP_TRY(h, hipMemcpyAsync(ws->d_rfilter.p, range_filter, (size_t)B * sizeof(double), hipMemcpyHostToDevice, s));
+                rng.d_range_filter = ws->d_rfilter.as<double>();
+            }
             return (int)HR_OK;
         },
         [&](Workspace* ws, hipStream_t s, const uint8_t* d_mask, const OutLists& out, int C) {
-            return dense_search_enqueue(h, ws, s, ws->d_q.as<float>(), B, k, d_mask, out, C);
+            return dense_search_enqueue(h, ws, s, ws->d_q.as<float>(), B, k, d_mask, out, C, nullptr, PHASE_ALL,
+                                        ranged ? &rng : nullptr);
         });
+}
+
+int hr_search_dense_range(hr_index* h, const float* q, int B, int k, const uint8_t* rowmask, int mask_on_device,
+                          const double* radius, const double* range_filter, int64_t* out_ids, float* out_scores) {
+    return search_dense_host(h, q, B, k, rowmask, mask_on_device != 0, out_ids, out_scores, true, radius, range_filter);
 }
 
 int hr_search_dense(hr_index* h, const float* q, int B, int k, const uint8_t* rowmask, int64_t* out_ids,

@@ -23,6 +23,7 @@ struct ScanPlan {
     int chunk_q;  // queries per full pass of the search (16 x the groups a pass owns in the fragment buffer)
     int NRB;      // row blocks per candidate group: 1 (16-row groups) or 4 (64-row groups)
     bool l2;      // the squared-Euclidean epilogue
+    bool range;   // the range-search epilogue (per-query ceilings)
 };
 
 // HR_DEBUG_DENSE_KERNELS bit mask (tests drive every scan kernel at every shape): 1 = no register-resident 256-query
@@ -43,10 +44,13 @@ inline int scan_group_rows(int64_t n_rows, int group_rows_override) {
 
 // The pass that scans a chunk of nq queries of a batch of B (nq = min(chunk_q, what is left of B); the first pass of
 // a batch: nq = min(B, its own chunk_q), so scan_plan(..., B, B) yields chunk_q).  KT = 1 KiB tiles per row.
+// range = a pass of a range search: the two generic kernels only (the inline-asm forms have no ceiling), so 256 ranged
+// queries are two 128-query passes, as for L2.
 inline ScanPlan scan_plan(int KT, int dtype, int metric, int64_t n_rows, int group_rows_override, int mask, int B,
-                          int nq) {
+                          int nq, bool range = false) {
     ScanPlan p{};
     p.l2 = metric == HR_METRIC_L2;
+    p.range = range;
     p.NRB = scan_group_rows(n_rows, group_rows_override) == 16 ? 1 : 4;
     const int g_fit = kScanTileKiB / (KT > 1 ? KT : 1);
     const int g_small = g_fit < 1 ? 1 : g_fit > 4 ? 4 : g_fit;  // groups of the LDS-resident tile
@@ -61,11 +65,12 @@ inline ScanPlan scan_plan(int KT, int dtype, int metric, int64_t n_rows, int gro
         p.chunk_q = 16 * g_small;
         return p;
     }
-    // 256 queries per pass: fp16 COSINE / IP only (the inline-asm forms have no L2 epilogue); which form
+    // 256 queries per pass: fp16 COSINE / IP without a range only (the inline-asm forms have no L2 and no range epilogue);
+    // which form
     const bool f16 = dtype == HR_F16;
     const bool gemm = f16 && KT >= 8 && !(mask & SCAN_NO_GEMM);
     const bool qreg = f16 && KT == 24 && !(mask & SCAN_NO_QREG) && !((mask & SCAN_PREFER_GEMM) && gemm);
-    const int kind256 = (B <= 128 || p.l2) ? SCAN_NONE
+    const int kind256 = (B <= 128 || p.l2 || range) ? SCAN_NONE
                         : qreg             ? ((mask & SCAN_Q64_FORM) ? SCAN_Q64 : SCAN_QREG)
                         : gemm             ? SCAN_GEMM
                                            : SCAN_NONE;

@@ -46,6 +46,19 @@
  *            is a valid hit at distance exactly +0.  A zero query is legal
  *            (D = |x|^2).  Row norms must stay inside the fp32 range squared
  *            (|x|^2 / 2 is kept per row as a float).
+ *   dense, range search (hr_search_dense_range*): the best k rows among the rows whose
+ *            canonical score lies in the range; ranking, padding and scores are those of
+ *            the plain search.  The test is made on the fp32 score the list carries,
+ *            widened to double and compared with the bounds as doubles (Milvus' rules):
+ *              COSINE, IP : radius < (double)score32 <= range_filter
+ *              L2         : range_filter <= (double)D32 < radius
+ *            so a row equal to the query is a hit at range_filter = 0.  Either bound may
+ *            be absent: an absent radius is -inf (COSINE, IP) / +inf (L2), an absent
+ *            range_filter the opposite.  Both absent: the plain search bit for bit, ids,
+ *            scores and flags.  Fewer than k rows in range: the list is shorter and padded
+ *            as usual.  No row in range: all padding, and proven.  Bounds are per query.
+ *            A NaN bound and an empty interval (radius >= range_filter; L2: range_filter
+ *            >= radius) are refused with HR_EINVAL naming the query, nothing is launched.
  *   sparse : score32 = (float) sum over the row's stored entries, in stored
  *            (index) order, of value*query_value in fp64; only rows with
  *            score32 > 0 qualify; same ranking rule.
@@ -185,6 +198,13 @@ HR_API int64_t hr_device_bytes(const hr_index* h);    /* HBM held by the shard *
  *   out_ids  [B*k] int64, out_scores [B*k] fp32, best first. */
 HR_API int hr_search_dense(hr_index* h, const float* q, int B, int k, const uint8_t* rowmask,
                     int64_t* out_ids, float* out_scores);
+/* Range search (Collection.search with params {"radius": r, "range_filter": f}; semantics above).  radius and
+ * range_filter are HOST arrays of B doubles, NULL = that side unbounded for every query (+-inf in an entry = unbounded
+ * for that query).  rowmask as in hr_search_dense, or with mask_on_device != 0 a device pointer as in
+ * hr_search_dense_dmask.  Escalates by itself like hr_search_dense: the lists are exact whatever the bounds.  A refused
+ * call (NaN, empty interval) launches nothing and leaves the output buffers untouched. */
+HR_API int hr_search_dense_range(hr_index* h, const float* q, int B, int k, const uint8_t* rowmask, int mask_on_device,
+                                 const double* radius, const double* range_filter, int64_t* out_ids, float* out_scores);
 /* Sparse queries as CSR (q_indptr[B+1]); drop_ratio = Milvus
  * drop_ratio_search (reference retrieval.py:97-101): the
  * floor(drop_ratio*nnz) smallest-|value| entries of each query are ignored. */
@@ -226,6 +246,12 @@ HR_API int hr_search_sparse_dev(hr_index* h, const int64_t* d_q_indptr, const in
                          const float* d_q_val, int B, int64_t q_nnz_total, int max_q_nnz, int k,
                          const uint8_t* d_rowmask, int64_t* d_ids, float* d_scores,
                          int32_t* d_flags, void* stream);
+/* Range search, device form: d_radius / d_range_filter are DEVICE arrays of B doubles (NULL = unbounded for every
+ * query).  The bound values are not looked at on the host: NaN and empty intervals are the caller's to check, like
+ * query values.  d_flags[q] = 0 where the proof fails: always possible for rows within the scan's error of a bound. */
+HR_API int hr_search_dense_range_dev(hr_index* h, const float* d_q, int B, int k, const uint8_t* d_rowmask,
+                                     const double* d_radius, const double* d_range_filter,
+                                     int64_t* d_ids, float* d_scores, int32_t* d_flags, void* stream);
 /* Both modalities of one query batch in ONE call: the dense scan runs alone on
  * `stream`; the sparse chain then runs on a library-owned side stream so that
  * it overlaps the dense path's latency-bound tail (candidate select, refine,
@@ -571,9 +597,12 @@ HR_API int hr_set_scan_cus(hr_index* h, int n_cus);
  *   afterwards.
  * HR_DEBUG_NO_TRIM (process-wide): 1 = refine every one of the C candidate groups of a query (round 3's behaviour) instead
  *   of only those whose maximum is within twice the scan's error bound of the k-th largest group maximum (A/B, tests).
+ * HR_DEBUG_NO_RANGE_CLAMP (process-wide): 1 = the scans of a range search get +inf ceilings, i.e. they do not drop the
+ *   rows above range_filter.  Results through the host form do not change (exactness never rests on the clamp); the
+ *   device form's flags show what the clamp proves (tests, tests/probes/range_probe.py).
  * The library reads no environment variables. */
 enum { HR_DEBUG_FINISH_MODE = 1, HR_DEBUG_FAIL_NEXT_BUILD = 2, HR_DEBUG_DENSE_KERNELS = 3, HR_DEBUG_SPARSE_RPB = 4,
-       HR_DEBUG_GROUP_ROWS = 5, HR_DEBUG_NO_TRIM = 6 };
+       HR_DEBUG_GROUP_ROWS = 5, HR_DEBUG_NO_TRIM = 6, HR_DEBUG_NO_RANGE_CLAMP = 7 };
 HR_API int hr_debug_option(hr_index* h, int key, int value);
 
 /* ---- measurement hooks -------------------------------------------------------
