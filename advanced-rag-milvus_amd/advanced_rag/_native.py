@@ -137,6 +137,12 @@ _SIGNATURES = {
                                            _c.c_float, _c.c_void_p]),
     "hr_encoder_tail_f16_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p,
                                            _c.c_int64, _c.c_int, _c.c_int, _c.c_float, _c.c_int, _c.c_void_p]),
+    "hr_mask_rows_scratch_bytes": (_c.c_size_t, [_c.c_int64]),
+    "hr_mask_rows_dev": (_c.c_int, [_c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_void_p,
+                                    _c.c_void_p, _c.c_void_p]),
+    "hr_get_dense_rows_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_void_p,
+                                         _c.c_void_p]),
+    "hr_get_dense_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
     "hr_set_profiling": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "hr_last_kernel_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
     "hr_last_compact_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
@@ -249,8 +255,11 @@ class ShardHandle:
         return cls(dim, dtype, metric, sparse_dim, device, _adopt=h.value)
 
     # -- ingest
+    row_offset = 0    # global id of local row 0 as set through this object (a loaded snapshot carries its own)
+
     def set_row_offset(self, first_row: int):
         self._check(self._lib.hr_set_row_offset(self._h, first_row))
+        self.row_offset = int(first_row)
 
     def reserve(self, n_rows: int):
         self._check(self._lib.hr_reserve(self._h, n_rows))
@@ -314,6 +323,24 @@ class ShardHandle:
     @property
     def dense_scan_bytes(self) -> int:
         return int(self._lib.hr_dense_scan_bytes(self._h))
+
+    # -- read path
+    def get_dense_rows(self, rows) -> np.ndarray:
+        """hr_get_dense_rows: the stored vectors of the rows with the given GLOBAL ids (local row + row offset; any
+        order, repeats allowed) as float32 [n, dim], fp16 shards widened exactly.  An id outside the shard: ValueError."""
+        ids = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        out = np.empty((ids.shape[0], self.dim), dtype=np.float32)
+        self._check(self._lib.hr_get_dense_rows(self._h, _vp(ids), ids.shape[0], _vp(out)))
+        return out
+
+    def get_dense_rows_dev(self, d_rows: int, n: int, out_dtype: int, d_out: int, out_stride: int = 0, d_missing: int = 0,
+                           stream: int = 0):
+        """hr_get_dense_rows_dev (device pointers, asynchronous on `stream`): row i of d_out = the stored row d_rows[i] as
+        out_dtype (HR_F32, or HR_F16 on an fp16 shard); out_stride in elements (0 = dim); an id outside the shard gives a
+        row of zeros and is counted in the int32 at d_missing (0 = not wanted)."""
+        self._check(self._lib.hr_get_dense_rows_dev(self._h, _vp(d_rows) if d_rows else None, n, out_dtype,
+                                                    _vp(d_out) if d_out else None, out_stride or self.dim,
+                                                    _vp(d_missing) if d_missing else None, _vp(stream) if stream else None))
 
     # -- search, host buffers
     @staticmethod
@@ -518,6 +545,22 @@ def group_select_dev(d_ids: int, d_n: int, B: int, k_in: int, d_keys: int, key_r
     p = lambda x: _vp(x) if x else None
     rc = L.hr_group_select_dev(p(d_ids), p(d_n), B, k_in, p(d_keys), key_rows, first_row, k_out, p(d_out_pos), p(d_out_keys),
                                p(d_out_n), p(d_flags), p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+def mask_rows_scratch_bytes(n_rows: int) -> int:
+    """hr_mask_rows_scratch_bytes: device scratch hr_mask_rows_dev needs for a mask of n_rows rows."""
+    return int(load_library().hr_mask_rows_scratch_bytes(n_rows))
+
+
+def mask_rows_dev(d_mask: int, n_rows: int, first_row: int, offset: int, limit: int, d_rows: int, d_counts: int,
+                  d_scratch: int, stream: int = 0):
+    """hr_mask_rows_dev: packed row mask (0 = every row) -> d_counts[0] = set bits below n_rows, d_counts[1] = ids written,
+    d_rows[i] = first_row + the (offset + i)-th set bit (int64 device buffers; asynchronous on `stream`)."""
+    L = load_library()
+    p = lambda x: _vp(x) if x else None
+    rc = L.hr_mask_rows_dev(p(d_mask), n_rows, first_row, offset, limit, p(d_rows), p(d_counts), p(d_scratch), p(stream))
     if rc != 0:
         _raise_global(L, rc)
 

@@ -78,3 +78,6 @@ class APIConstants:
 
 
 GROUP_WINDOW_FACTOR = GroupingConstants.GROUP_WINDOW_FACTOR
+
+# Collection.query: offset + limit of one call may not exceed this (Milvus' own cap on a query's window)
+QUERY_MAX_WINDOW = 16384

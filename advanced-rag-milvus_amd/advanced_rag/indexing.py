@@ -36,7 +36,7 @@ import numpy as np
 
 from . import filters as _filters
 from .columns import FLOAT_COLUMNS, PayloadColumns, check_group_field
-from .constants import GROUP_WINDOW_FACTOR, IndexingConstants
+from .constants import GROUP_WINDOW_FACTOR, QUERY_MAX_WINDOW, IndexingConstants
 from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache, get_semantic_cache
 from ._native import HR_MAX_TOPK   # importing the binding module does not load the library
 from .shards import PartialAppend, ShardSet
@@ -156,6 +156,11 @@ class ShardCollection:
         the collections of a manager share their rows, so all of them are compacted)."""
         return self.manager.compact()
 
+    def query(self, expr: Optional[str] = None, output_fields: Optional[Sequence[str]] = None, limit: Optional[int] = None,
+              offset: int = 0) -> List[Dict[str, Any]]:
+        """pymilvus' Collection.query(expr, output_fields, limit, offset), synchronous (MilvusIndexManager.query)."""
+        return self.manager._query_blocking(self.name, expr, output_fields, limit, offset)
+
 
 class MilvusIndexManager:
     def __init__(self, host: str = "localhost", port: int = 19530, enable_sharding: bool = True, num_shards: int = 4,
@@ -188,7 +193,8 @@ class MilvusIndexManager:
         self._dev_groups = None    # device_groups.DeviceGroupKeys: the group keys of the fields grouped on, on first use
         # grouping searches answered by the blocking loop: searches, windows searched, windows that ended before the
         # top_k-th group and were continued without the groups they showed
-        self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0}
+        # queries: query() calls answered; query_device: those whose page came from hr_mask_rows_dev (mask never left HBM)
+        self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "queries": 0, "query_device": 0}
         self._stats_lock = threading.Lock()    # the loop runs in worker threads and in the front's thread at once
         self._deleted: Optional[np.ndarray] = None
         self._mask_cache: Dict[Any, Optional[np.ndarray]] = {}   # (expr, rows, delete epoch) -> boolean row filter
@@ -1361,6 +1367,124 @@ class MilvusIndexManager:
             return await asyncio.get_event_loop().run_in_executor(self.embedding_executor,
                                                                   lambda: gen.encode_domain(text, domain))
         return np.random.randn(self.domain_dim).astype(np.float32)
+
+    # ------------------------------------------------------------------ query (rows by expression, no query vector)
+    COUNT_FIELD = "count(*)"
+    QUERY_FIELDS = ("id", "chunk_id", "doc_id", "content", "chunk_index", "token_count", "entropy", "redundancy",
+                    "domain_density", "metadata_json", "timestamp", "embedding")
+    # what a payload-free (synthetic) collection can derive from the row number: the fields _format_hits shows for it
+    SYNTHETIC_QUERY_FIELDS = {"id": lambda r: MilvusIndexManager.synthetic_id(r), "chunk_id": lambda r: MilvusIndexManager.synthetic_id(r),
+                              "doc_id": lambda r: f"doc{r // 10}", "content": lambda r: "", "chunk_index": lambda r: r % 10,
+                              "entropy": lambda r: 0.0, "redundancy": lambda r: 0.0, "domain_density": lambda r: 0.0,
+                              "timestamp": lambda r: ""}
+
+    def _query_request(self, collection_name: str, output_fields, limit, offset):
+        """Check a query's arguments before anything is evaluated -> (collection, fields without duplicates, count?, limit, offset)."""
+        if collection_name not in self.collections:
+            raise ValueError(f"Collection {collection_name} not found")
+        coll = self.collections[collection_name]
+        if output_fields is None:
+            output_fields = []
+        if isinstance(output_fields, str) or not all(isinstance(f, str) for f in output_fields):
+            raise ValueError(f"output_fields must be a list of field names, got {output_fields!r}")
+        fields = list(dict.fromkeys(output_fields))
+        count = self.COUNT_FIELD in fields
+        if count and len(fields) != 1:
+            raise ValueError(f"{self.COUNT_FIELD} cannot be combined with other output fields: {fields}")
+        for f in fields:
+            if not count and f not in self.QUERY_FIELDS:
+                raise ValueError(f"unknown output field: {f!r} (known: {', '.join(self.QUERY_FIELDS)}, {self.COUNT_FIELD})")
+            if not count and self._synthetic_rows and f != "embedding" and f not in self.SYNTHETIC_QUERY_FIELDS:
+                raise ValueError(f"this shard was bulk-ingested without payload columns: it has no {f}")
+        for name, v in (("offset", offset), ("limit", limit)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, np.integer))):
+                raise ValueError(f"{name} must be an integer, got {v!r}")
+        if offset is None or offset < 0:
+            raise ValueError(f"offset must be >= 0, got {offset!r}")
+        if limit is not None and (limit < 0 or not 1 <= offset + limit <= QUERY_MAX_WINDOW):
+            raise ValueError(f"a query takes 1 <= offset + limit <= {QUERY_MAX_WINDOW} and limit >= 0, got offset={offset}, limit={limit}")
+        if "embedding" in fields:
+            if coll.kind == "sparse":
+                raise ValueError(f"reading sparse vectors back (embedding of {coll.name}) is not built")
+            if not hasattr(coll.handle, "handles"):
+                raise NotImplementedError("reading stored vectors back (embedding) is not built for the torchrun form "
+                                          "(CollectiveShardSet)")
+        return coll, fields, count, (None if limit is None else int(limit)), int(offset)
+
+    def _query_rows_device(self, expr: Optional[str], limit: Optional[int], offset: int) -> Tuple[int, np.ndarray]:
+        """(rows that pass, the page's global rows) of one GPU shard: the cached packed mask of `expr` + tombstones stays in
+        HBM and hr_mask_rows_dev turns it into the page; two counts and the page's ids come back, nothing row-sized moves.
+        limit None: count first, then fetch everything after `offset`."""
+        import torch
+        nat = self._native
+        n = self.num_rows
+        dev = torch.device("cuda", self._main.first.device)
+        with torch.cuda.device(dev):
+            mask = self._global_device_mask(expr)          # None: every row passes (no expression, no tombstone)
+            ptr = mask.data_ptr() if mask is not None else 0
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+            scratch = torch.empty(max(nat.mask_rows_scratch_bytes(n), 8), dtype=torch.uint8, device=dev) if ptr else None
+            stream = torch.cuda.current_stream(dev)
+
+            def page(lim: int):
+                rows = torch.empty(max(lim, 1), dtype=torch.int64, device=dev)
+                nat.mask_rows_dev(ptr, n, 0, offset, lim, rows.data_ptr(), counts.data_ptr(),
+                                  scratch.data_ptr() if scratch is not None else 0, stream.cuda_stream)
+                total, written = (int(x) for x in counts.cpu().tolist())     # synchronises the stream
+                return total, rows[:written].cpu().numpy()
+
+            if limit is None:
+                total, _ = page(0)
+                if total <= offset:
+                    return total, np.zeros(0, np.int64)
+                limit = total - offset
+            return page(limit)
+
+    def _query_rows_host(self, expr: Optional[str], limit: Optional[int], offset: int) -> Tuple[int, np.ndarray]:
+        """The same contract over the host view of the mask (several shards, the torchrun form on rank 0, CPU stand-ins)."""
+        keep = self._row_mask(expr)
+        rows = np.arange(self.num_rows, dtype=np.int64) if keep is None else np.flatnonzero(keep).astype(np.int64)
+        return int(rows.shape[0]), rows[offset:] if limit is None else rows[offset:offset + limit]
+
+    def _query_blocking(self, collection_name: str, expr: Optional[str], output_fields, limit: Optional[int],
+                        offset: int) -> List[Dict[str, Any]]:
+        coll, fields, count, limit, offset = self._query_request(collection_name, output_fields, limit, offset)
+        expr = expr if (expr is not None and str(expr).strip()) else None
+        if expr is None and limit is None and not count:
+            raise ValueError("a query without an expression needs a limit")
+        on_device = getattr(self._main, "n_shards", 1) == 1 and hasattr(self._main, "handles") and \
+            self._filters_on_device() is not None
+        if count:
+            limit, offset = 0, 0
+        total, rows = (self._query_rows_device if on_device else self._query_rows_host)(expr, limit, offset)
+        self._count("queries")
+        if on_device:
+            self._count("query_device")
+        if count:
+            return [{self.COUNT_FIELD: total}]
+        vectors = coll.handle.get_dense_rows(rows) if "embedding" in fields and len(rows) else None
+        if self._synthetic_rows:
+            getters = {f: self.SYNTHETIC_QUERY_FIELDS[f] for f in ["id"] + fields if f != "embedding"}
+        else:
+            c = self._cols
+            getters = {f: c["id" if f == "chunk_id" else f].__getitem__ for f in ["id"] + fields if f != "embedding"}
+        out = []
+        for i, row in enumerate(rows.tolist()):
+            ent = {f: get(row) for f, get in getters.items()}
+            if "embedding" in fields:
+                ent["embedding"] = vectors[i]
+            out.append(ent)
+        return out
+
+    async def query(self, collection_name: str, expr: Optional[str] = None, output_fields: Optional[Sequence[str]] = None,
+                    limit: Optional[int] = None, offset: int = 0) -> List[Dict[str, Any]]:
+        """pymilvus' Collection.query: the rows that pass `expr` (the filter language of filters.py; "" or None = every
+        row, then `limit` is required) and are not deleted, in ASCENDING GLOBAL ROW order — Milvus promises none; this one
+        is promised, so pages concatenate — without the first `offset`, at most `limit` of them (limit=None with an
+        expression: all of them).  1 <= offset + limit <= QUERY_MAX_WINDOW.  -> flat dicts: the primary key "id" always,
+        the requested fields besides (QUERY_FIELDS); "embedding" is the stored vector of the named collection as float32
+        [dim] (fp16 shards widened exactly).  output_fields=["count(*)"] -> [{"count(*)": n}].  Refusals are ValueError."""
+        return await asyncio.to_thread(self._query_blocking, collection_name, expr, output_fields, limit, offset)
 
     # ------------------------------------------------------------------ misc
     def get_collection_stats(self, collection_name: str) -> Dict[str, Any]:

@@ -282,6 +282,36 @@ class ShardSet:
             return self.handles[s].search_sparse(queries, k, drop_ratio, *self._local_mask(s, keep))
         return self._gather(self._fan_out(one), k)
 
+    # ------------------------------------------------------------------ read path
+    def get_dense_rows(self, global_rows) -> np.ndarray:
+        """The stored vectors of the given GLOBAL rows (any order, repeats allowed) as float32 [n, dim], in request order:
+        `rows_of` inverted gives shard and local row, every shard gathers its part (hr_get_dense_rows, in parallel through
+        the pool) and the parts are scattered back.  A row no shard holds: ValueError."""
+        g = np.ascontiguousarray(global_rows, dtype=np.int64).reshape(-1)
+        parts, found = [], np.zeros(g.shape[0], dtype=bool)
+        for s, rows in enumerate(self.rows_of):      # ascending per shard: a binary search inverts it
+            at = np.searchsorted(rows, g)
+            hit = at < len(rows)
+            hit[hit] = rows[at[hit]] == g[hit]
+            parts.append((np.flatnonzero(hit), at[hit]))
+            found |= hit
+        if not found.all():
+            raise ValueError(f"row {int(g[np.flatnonzero(~found)[0]])} is not in this collection ({self._n} rows)")
+
+        def one(s):
+            where, local = parts[s]
+            if not len(where):
+                return None
+            h = self.handles[s]
+            return h.get_dense_rows(local + int(getattr(h, "row_offset", 0)))
+        got = self._fan_out(one)
+        dim = next((v.shape[1] for v in got if v is not None), int(getattr(self.handles[0], "dim", 0)))
+        out = np.empty((g.shape[0], dim), dtype=np.float32)
+        for (where, _), v in zip(parts, got):
+            if v is not None:
+                out[where] = v
+        return out
+
     # ------------------------------------------------------------------ snapshot
     def save(self, path_of_shard) -> None:
         """path_of_shard(s) -> file for shard s."""
@@ -438,6 +468,10 @@ class CollectiveShardSet:
     def compact(self, keep_global, d_keep: int = 0):
         """Not in the torchrun form: every rank would have to compact its shard and renumber in step."""
         raise NotImplementedError("compaction of a torchrun collection (CollectiveShardSet) is not implemented")
+
+    def get_dense_rows(self, global_rows):
+        """Not in the torchrun form: the rows would have to travel from the ranks that hold them."""
+        raise NotImplementedError("reading stored vectors back from a torchrun collection (CollectiveShardSet) is not implemented")
 
     def _global_rows(self) -> np.ndarray:
         """Global row of every local row of this rank."""

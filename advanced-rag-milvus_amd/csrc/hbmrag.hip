@@ -35,6 +35,7 @@
 #include "fuse.h"
 #include "group.h"
 #include "mmr.h"
+#include "query.h"
 #include "text.h"
 #include "select.h"
 #include "sparse.h"
@@ -1342,7 +1343,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11000; }  // 1.10.0: hr_search_dense_range, hr_search_dense_range_dev
+int hr_version(void) { return 11100; }  // 1.11.0: hr_mask_rows_dev, hr_get_dense_rows, hr_get_dense_rows_dev
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2348,6 +2349,121 @@ int hr_mask_drop_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out, int64
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "mask_drop_groups_kernel: %s", hipGetErrorString(e));
     return HR_OK;
+}
+
+// ---- read path (query.h) -----------------------------------------------------------------------------------------------
+size_t hr_mask_rows_scratch_bytes(int64_t n_rows) {
+    if (n_rows < 0) return 0;
+    const int64_t n_words = (n_rows + 63) / 64;
+    const int64_t nb = (n_words + kCompactBlock - 1) / kCompactBlock;
+    return (size_t)(std::max<int64_t>(nb, 1) + 1) * 8;  // the blocks' prefix, then the total
+}
+
+int hr_mask_rows_dev(const uint8_t* d_mask, int64_t n_rows, int64_t first_row, int64_t offset, int64_t limit, int64_t* d_rows,
+                     int64_t* d_counts, void* d_scratch, void* stream) {
+    constexpr int64_t kMax = 1ll << 62;
+    if (n_rows < 0 || offset < 0 || limit < 0) return fail(nullptr, HR_EINVAL, "n_rows, offset and limit must be >= 0");
+    if (n_rows >= kMax || offset >= kMax || limit >= kMax) return fail(nullptr, HR_EINVAL, "n_rows, offset and limit must be below 2^62");
+    if (!d_counts || (!d_rows && limit > 0)) return fail(nullptr, HR_EINVAL, "null buffer");
+    if ((uintptr_t)d_mask & 7) return fail(nullptr, HR_EINVAL, "the mask must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (!d_mask || n_rows == 0) {
+        const int64_t n_out = n_rows > offset ? std::min(n_rows - offset, limit) : 0;
+        const int64_t blocks = std::max<int64_t>(1, (n_out + 255) / 256);
+        if (blocks > 0x7fffffffll) return fail(nullptr, HR_ELIMIT, "page too large");
+        hipLaunchKernelGGL(mask_rows_all_kernel, dim3((unsigned)blocks), dim3(256), 0, s, n_rows, first_row, offset, limit, d_rows, d_counts);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(nullptr, HR_EHIP, "mask_rows_all_kernel: %s", hipGetErrorString(e));
+        return HR_OK;
+    }
+    if (!d_scratch || ((uintptr_t)d_scratch & 7)) return fail(nullptr, HR_EINVAL, "scratch of hr_mask_rows_scratch_bytes bytes, 8-byte aligned, is required");
+    const int64_t n_words = (n_rows + 63) / 64;
+    const int64_t nb = (n_words + kCompactBlock - 1) / kCompactBlock;
+    if (nb > 0x7fffffffll) return fail(nullptr, HR_ELIMIT, "too many rows");
+    unsigned long long* block_off = (unsigned long long*)d_scratch;
+    unsigned long long* total = block_off + nb;
+    const unsigned long long* mask = (const unsigned long long*)d_mask;
+    hipLaunchKernelGGL((compact_block_sums_kernel<KeepCount>), dim3((unsigned)nb), dim3(kCompactBlock), 0, s, KeepCount{mask, n_rows},
+                       n_words, block_off);
+    hipLaunchKernelGGL(compact_scan_sums_kernel, dim3(1), dim3(kCompactBlock), 0, s, block_off, nb, total);
+    hipLaunchKernelGGL(mask_rows_window_kernel, dim3((unsigned)nb), dim3(kCompactBlock), 0, s, mask, n_rows, n_words, block_off, total,
+                       first_row, offset, limit, d_rows, d_counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "mask_rows_window_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+namespace {
+// Caller holds h->rw (shared) and has h's device current.
+int get_rows_enqueue(hr_index* h, hipStream_t s, const int64_t* d_rows, int64_t n, int out_dtype, void* d_out, int64_t out_stride,
+                     int32_t* d_missing) {
+    if (d_missing) HIP_TRY(h, hipMemsetAsync(d_missing, 0, sizeof(int32_t), s));
+    if (n == 0) return HR_OK;
+    const int64_t blocks = ((n + kRowsPerBlock - 1) / kRowsPerBlock + kGetRowsWaves - 1) / kGetRowsWaves;
+    if (blocks > 0x7fffffffll) return fail(h, HR_ELIMIT, "too many rows");
+    const size_t out_elem = out_dtype == HR_F16 ? 2 : 4;
+    const bool vec = ((uintptr_t)d_out & 15) == 0 && (out_stride * out_elem) % 16 == 0;
+    const dim3 grid((unsigned)blocks), block(kGetRowsWaves * 64);
+#define HR_GET_ROWS(SRC, OUT, VEC)                                                                                              \
+    hipLaunchKernelGGL((get_rows_kernel<SRC, OUT, VEC>), grid, block, 0, s, h->tiles.as<chunk_t>(), h->n_rows, h->row_offset, h->KT, \
+                       h->dim, d_rows, n, d_out, out_stride, d_missing)
+    if (h->dtype == HR_F16 && out_dtype == HR_F16) { if (vec) HR_GET_ROWS(true, true, true); else HR_GET_ROWS(true, true, false); }
+    else if (h->dtype == HR_F16) { if (vec) HR_GET_ROWS(true, false, true); else HR_GET_ROWS(true, false, false); }
+    else { if (vec) HR_GET_ROWS(false, false, true); else HR_GET_ROWS(false, false, false); }
+#undef HR_GET_ROWS
+    HIP_TRY(h, hipGetLastError());
+    return HR_OK;
+}
+
+int check_get_rows(hr_index* h, int64_t n) {
+    if (!h) return fail(nullptr, HR_EINVAL, "null handle");
+    if (h->dim == 0) return fail(h, HR_ESTATE, "handle has no dense collection");
+    if (!h->finalized) return fail(h, HR_ESTATE, "rows are read after hr_finalize");
+    if (n < 0) return fail(h, HR_EINVAL, "n must be >= 0 (got %lld)", (long long)n);
+    return HR_OK;
+}
+}  // namespace
+
+int hr_get_dense_rows_dev(hr_index* h, const int64_t* d_rows, int64_t n, int out_dtype, void* d_out, int64_t out_stride,
+                          int32_t* d_missing, void* stream) {
+    HR_TRY(check_get_rows(h, n));
+    if (out_dtype != HR_F32 && out_dtype != HR_F16) return fail(h, HR_EINVAL, "unknown out_dtype %d", out_dtype);
+    if (out_dtype == HR_F16 && h->dtype != HR_F16) return fail(h, HR_EINVAL, "HR_F16 output needs an fp16 shard (this one stores fp32)");
+    if (out_stride < h->dim) return fail(h, HR_EINVAL, "out_stride %lld is below dim %lld", (long long)out_stride, (long long)h->dim);
+    if (n > 0 && (!d_rows || !d_out)) return fail(h, HR_EINVAL, "null buffer");
+    if ((uintptr_t)d_out & (out_dtype == HR_F16 ? 1 : 3)) return fail(h, HR_EINVAL, "d_out is not aligned to its element type");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    DeviceGuard dg(h->device);
+    return get_rows_enqueue(h, (hipStream_t)stream, d_rows, n, out_dtype, d_out, out_stride, d_missing);
+}
+
+int hr_get_dense_rows(hr_index* h, const int64_t* rows, int64_t n, float* out) {
+    HR_TRY(check_get_rows(h, n));
+    if (n == 0) return HR_OK;
+    if (!rows || !out) return fail(h, HR_EINVAL, "null buffer");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    for (int64_t i = 0; i < n; ++i)   // refused before anything is read or written
+        if (rows[i] < h->row_offset || rows[i] - h->row_offset >= h->n_rows)
+            return fail(h, HR_EINVAL, "row id %lld (entry %lld) is outside this shard's rows [%lld, %lld)", (long long)rows[i],
+                        (long long)i, (long long)h->row_offset, (long long)(h->row_offset + h->n_rows));
+    DeviceGuard dg(h->device);
+    Workspace* ws = take_ws(h);
+    if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
+    int rc = [&]() -> int {
+        hipStream_t s = ws->stream;
+        const size_t out_bytes = (size_t)n * h->dim * sizeof(float);
+        if (ws->d_ids.ensure((size_t)n * 8) != hipSuccess || ws->d_q.ensure(out_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, HR_ENOMEM, "cannot stage %lld rows", (long long)n);
+        }
+        HIP_TRY(h, hipMemcpyAsync(ws->d_ids.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HR_TRY(get_rows_enqueue(h, s, ws->d_ids.as<int64_t>(), n, HR_F32, ws->d_q.p, h->dim, nullptr));
+        HIP_TRY(h, hipMemcpyAsync(out, ws->d_q.p, out_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        return HR_OK;
+    }();
+    give_ws(h, ws);
+    return rc;
 }
 
 int hr_add_layernorm_f16_dev(const void* d_x, const void* d_residual, const void* d_gamma, const void* d_beta, void* d_out,

@@ -477,6 +477,40 @@ HR_API int hr_filter_eval_expr_dev(const hr_filter_leaf* leaves, int n_leaves, c
                                    int64_t n_rows, const uint8_t* d_deleted, uint8_t* d_mask, uint8_t* d_undecided,
                                    int32_t* d_counts, void* stream);
 
+/* ---- read path: Collection.query(expr, output_fields, limit, offset) ---------------------------------------------------
+ * pymilvus reads rows back without a query vector: the rows that pass an expression, paged, with their fields and
+ * vectors.  The expression becomes a packed row mask (hr_filter_eval_dev / hr_filter_eval_expr_dev); these entry points
+ * turn the mask into a page of row ids and fetch stored rows out of the tiles.
+ *
+ * hr_mask_rows_dev: d_mask is the packed row mask every search entry point takes (bit r%8 of byte r/8, 8 * ceil(n_rows /
+ *   64) bytes, 8-byte aligned); bits at and beyond n_rows may hold anything and are ignored; NULL = every row passes.
+ *   d_counts[0] = the number of set bits below n_rows, whatever the page ("count(*)"); d_counts[1] = the number of ids
+ *   written, max(0, min(limit, d_counts[0] - offset)); d_rows[i] = first_row + the (offset + i)-th set bit in ascending
+ *   row order for i < d_counts[1] — entries at and beyond d_counts[1] are not written.  n_rows == 0 and limit == 0 still
+ *   write the counts (d_rows may be NULL when limit == 0).  d_scratch: hr_mask_rows_scratch_bytes(n_rows) bytes of
+ *   device memory, 8-byte aligned, not read or written when d_mask is NULL.  HR_EINVAL: a negative n_rows, offset or
+ *   limit (or one of 2^62 and more), NULL outputs.  Asynchronous on `stream`; allocates nothing and never waits for the
+ *   device.  The result is a function of the inputs alone: a three-phase ordered prefix (the scan of hr_compact) decides
+ *   every position, no atomic does.
+ *
+ * hr_get_dense_rows_dev: output row i = the stored elements 0 .. dim-1 of the row with GLOBAL id d_rows[i] (local row +
+ *   hr_set_row_offset), as they sit in HBM: nothing is re-quantised and the padding of the last tile is never shown.  Ids
+ *   may come in any order and may repeat.  out_dtype = HR_F32: every element widened exactly (fp16 shards too); HR_F16:
+ *   the raw bits, valid only on an fp16 shard (HR_EINVAL on an fp32 one).  out_stride, in elements, >= dim; elements
+ *   between dim and the stride are left alone, and nothing is written after element dim-1 of the last row.  An id
+ *   outside [row_offset, row_offset + hr_num_rows) reads nothing: its output row is zeros, and *d_missing (may be NULL),
+ *   which the call zeroes, counts such ids.  HR_ESTATE before hr_finalize and on a handle without a dense collection.
+ *   The call takes the shared lock while it enqueues, like the `*_dev` searches; the caller keeps appends and
+ *   compaction away until `stream` has passed (hr_compact waits for the device by itself).
+ * hr_get_dense_rows: the host form, fp32, out [n][dim], synchronous.  It refuses an id outside the shard with HR_EINVAL,
+ *   naming the first one, and writes nothing. */
+HR_API size_t hr_mask_rows_scratch_bytes(int64_t n_rows);
+HR_API int hr_mask_rows_dev(const uint8_t* d_mask, int64_t n_rows, int64_t first_row, int64_t offset, int64_t limit,
+                     int64_t* d_rows, int64_t* d_counts, void* d_scratch, void* stream);
+HR_API int hr_get_dense_rows_dev(hr_index* h, const int64_t* d_rows, int64_t n, int out_dtype, void* d_out,
+                          int64_t out_stride, int32_t* d_missing, void* stream);
+HR_API int hr_get_dense_rows(hr_index* h, const int64_t* rows, int64_t n, float* out);
+
 /* ---- BM25 document payloads (ingest) ----------------------------------------------------------------------------
  * The `encode_sparse` hook of the ingest path (reference indexing.py:629-654, called per chunk from index_chunks
  * :379-404) for the BM25 encoder of this build (advanced_rag/bm25.py), a batch at a time on the device: d_text = the
