@@ -121,6 +121,9 @@ _SIGNATURES = {
     "hr_group_select_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_mask_drop_groups_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
+    "hr_group_select_n_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
+                                         _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_mask_keep_groups_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "hr_add_layernorm_f16_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                             _c.c_int, _c.c_float, _c.c_void_p]),
     "hr_embed_layernorm_f16_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -561,6 +564,28 @@ def mask_rows_dev(d_mask: int, n_rows: int, first_row: int, offset: int, limit: 
     L = load_library()
     p = lambda x: _vp(x) if x else None
     rc = L.hr_mask_rows_dev(p(d_mask), n_rows, first_row, offset, limit, p(d_rows), p(d_counts), p(d_scratch), p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+def group_select_n_dev(d_ids: int, d_n: int, B: int, k_in: int, d_keys: int, key_rows: int, first_row: int, k_out: int,
+                       group_size: int, d_out_pos: int, d_out_keys: int, d_out_cnt: int, d_out_n: int, d_flags: int, stream: int = 0):
+    """hr_group_select_n_dev: the first group_size entries of every group of a batch of ranked lists (device pointers; 0 =
+    NULL) -> positions [B][k_out * group_size], keys [B][k_out], members [B][k_out], groups [B], flags [B] (bit 0: the
+    groups are final, bit 1: so are their members)."""
+    L = load_library()
+    p = lambda x: _vp(x) if x else None
+    rc = L.hr_group_select_n_dev(p(d_ids), p(d_n), B, k_in, p(d_keys), key_rows, first_row, k_out, group_size, p(d_out_pos),
+                                 p(d_out_keys), p(d_out_cnt), p(d_out_n), p(d_flags), p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+def mask_keep_groups_dev(d_mask_in: int, d_mask_out: int, n_rows: int, d_keys: int, d_keep: int, n_keep: int, stream: int = 0):
+    """hr_mask_keep_groups_dev: mask_out = mask_in (0 = all rows) restricted to the rows whose group key is among the n_keep keys."""
+    L = load_library()
+    p = lambda x: _vp(x) if x else None
+    rc = L.hr_mask_keep_groups_dev(p(d_mask_in), p(d_mask_out), n_rows, p(d_keys), p(d_keep), n_keep, p(stream))
     if rc != 0:
         _raise_global(L, rc)
 

@@ -18,7 +18,9 @@ requests.
 Grouping searches (search(..., group_by_field=F)) coalesce the same way; the field is part of the request key, so grouped and
 ungrouped requests never share a launch.  Their batch searches the window K' (MilvusIndexManager.group_window) and runs ONE
 `hr_group_select_dev` for all of its queries behind the search on the same stream; a query whose window ended before its
-top_k-th group is redone through the manager's blocking loop, which continues the ranking exactly.
+top_k-th group is redone through the manager's blocking loop, which continues the ranking exactly.  The group size is part of
+the key too: a batch with group_size > 1 runs ONE `hr_group_select_n_dev`, and a query is answered from it only when both of its
+flag bits are set (the groups are final and so are their members); any other is redone through the blocking loop's two phases.
 
 A caller that has BOTH embeddings of a request in hand (HybridRetriever._retrieve_inner via
 MilvusIndexManager.hybrid_search) submits one "hybrid" request instead of two searches and a fusion: the batch runs as
@@ -316,7 +318,7 @@ class SearchCoalescer:
                 if r.kind == "fuse":
                     _answer(r.future, self.mgr._fuse_rows_blocking, r.payload, r.key)
                     continue
-                coll_name, top_k, expr, params_key, group_field = r.key
+                coll_name, top_k, expr, params_key, group_field, _ = r.key
                 if group_field is not None or self.mgr.collections[coll_name].handle is not cs:
                     # two cases for the manager's blocking path.  A grouping search: its loop searches window after window,
                     # each a round of the shard set.  Or a collection that is NOT spread over the ranks (the local domain
@@ -366,11 +368,12 @@ class SearchCoalescer:
 
     def _lists_blocking(self, r: _Request, key: Tuple):
         """The lists of one dense or sparse request through the manager's blocking single-query path."""
-        coll_name, top_k, expr, params_key, group_field = key
+        coll_name, top_k, expr, params_key, group_field, group_size = key
         if isinstance(r.payload, RangedQuery):
             return self.mgr._search_lists_blocking(r.payload.query, coll_name, top_k, expr, dict(params_key), group_field,
                                                    r.payload.bounds)
-        return self.mgr._search_lists_blocking(r.payload, coll_name, top_k, expr, dict(params_key), group_field)
+        return self.mgr._search_lists_blocking(r.payload, coll_name, top_k, expr, dict(params_key), group_field,
+                                               group_size=group_size)
 
     def _one_by_one(self, kind: str, key: Tuple, chunk: List[_Request]):
         """Fallback when a batched launch was refused: each request through the blocking single-query path, so that
@@ -387,12 +390,12 @@ class SearchCoalescer:
 
     # ------------------------------------------------------------------ dense
     def _enqueue_dense(self, torch, dev, stream, key, chunk):
-        coll_name, top_k, expr, _, group_field = key
+        coll_name, top_k, expr, _, group_field, group_size = key
         handle = self.mgr.collections[coll_name].handle.first
         B = len(chunk)
         if isinstance(chunk[0].payload, RangedQuery):   # the key's "ranged" marker: every request of the chunk is one
             return self._enqueue_dense_range(torch, dev, stream, handle, top_k, expr, chunk)
-        k = self.mgr.group_window(top_k) if group_field is not None else top_k
+        k = self.mgr.group_window(top_k, group_size) if group_field is not None else top_k
         q = dense_rows_device([r.payload for r in chunk], dev, handle.dim)
         ids, sc, fl = list_buffers(B, k, dev)
         mask = self.mgr._device_row_mask(expr, "dense")
@@ -401,7 +404,7 @@ class SearchCoalescer:
         self.stats["dense_launches"] += 1
         st = {"ids": ids, "sc": sc, "fl": fl, "keep": (q, mask)}
         if group_field is not None:
-            self._group_select(torch, dev, stream, top_k, group_field, st)
+            self._group_select(torch, dev, stream, top_k, group_field, group_size, st)
         return st
 
     def _enqueue_dense_range(self, torch, dev, stream, handle, top_k, expr, chunk):
@@ -418,30 +421,37 @@ class SearchCoalescer:
         self.stats["range_launches"] += 1
         return {"ids": ids, "sc": sc, "fl": fl, "keep": (q, rb, mask)}
 
-    def _group_select(self, torch, dev, stream, top_k, group_field, st):
+    def _group_select(self, torch, dev, stream, top_k, group_field, group_size, st):
         """The first top_k groups of every window of the batch (hr_group_select_dev, same stream, behind the search) -> st["group"]
-        = (positions [B, top_k], groups selected [B], flags [B])."""
+        = (positions [B, top_k], groups selected [B], flags [B]).  With group_size > 1: hr_group_select_n_dev, positions
+        [B, top_k * group_size] (-1 where a group has fewer members), flags 3 = groups and members are final."""
         from . import _native as nat
         ids = st["ids"]
         B, window = int(ids.shape[0]), int(ids.shape[1])
         n = self.mgr.num_rows
         keys = self.mgr._group_keys_on_device().tensor(group_field, n)
-        pos = torch.empty((B, top_k), dtype=torch.int32, device=dev)
+        pos = torch.empty((B, top_k * group_size), dtype=torch.int32, device=dev)
         n_sel = torch.empty((B,), dtype=torch.int32, device=dev)
         gfl = torch.empty((B,), dtype=torch.int32, device=dev)
-        nat.group_select_dev(ids.data_ptr(), 0, B, window, keys.data_ptr(), n, 0, top_k, pos.data_ptr(), 0, n_sel.data_ptr(),
-                             gfl.data_ptr(), stream.cuda_stream)
+        if group_size > 1:
+            cnt = torch.empty((B, top_k), dtype=torch.int32, device=dev)
+            nat.group_select_n_dev(ids.data_ptr(), 0, B, window, keys.data_ptr(), n, 0, top_k, group_size, pos.data_ptr(), 0,
+                                   cnt.data_ptr(), n_sel.data_ptr(), gfl.data_ptr(), stream.cuda_stream)
+            st["keep"] = st["keep"] + (cnt,)
+        else:
+            nat.group_select_dev(ids.data_ptr(), 0, B, window, keys.data_ptr(), n, 0, top_k, pos.data_ptr(), 0, n_sel.data_ptr(),
+                                 gfl.data_ptr(), stream.cuda_stream)
         self.stats["group_launches"] += 1
         st["group"] = (pos, n_sel, gfl)
         st["keep"] = st["keep"] + (keys,)
 
     # ------------------------------------------------------------------ sparse
     def _enqueue_sparse(self, torch, dev, stream, key, chunk):
-        coll_name, top_k, expr, params_key, group_field = key
+        coll_name, top_k, expr, params_key, group_field, group_size = key
         handle = self.mgr.collections[coll_name].handle.first
         drop = float(dict(params_key).get("drop_ratio_search", 0.0))
         B = len(chunk)
-        k = self.mgr.group_window(top_k) if group_field is not None else top_k
+        k = self.mgr.group_window(top_k, group_size) if group_field is not None else top_k
         d_ptr, d_idx, d_val, max_nnz = upload_sparse(
             pack_sparse_queries([r.payload for r in chunk], drop, handle.sparse_dim), dev)
         nnz = int(d_idx.shape[0])
@@ -453,21 +463,27 @@ class SearchCoalescer:
         self.stats["sparse_launches"] += 1
         st = {"ids": ids, "sc": sc, "fl": fl, "keep": (d_ptr, d_idx, d_val, mask)}
         if group_field is not None:
-            self._group_select(torch, dev, stream, top_k, group_field, st)
+            self._group_select(torch, dev, stream, top_k, group_field, group_size, st)
         return st
 
     def _scatter_lists(self, key, chunk, st):
         ids, sc, fl = st["ids"].cpu().numpy(), st["sc"].cpu().numpy(), st["fl"].cpu().numpy()
         group = [t.cpu().numpy() for t in st["group"]] if "group" in st else None
+        members = key[5] > 1 if group is not None else False      # group_size > 1: both flag bits must be set
         for i, r in enumerate(chunk):
             if fl[i] != 1:  # ties at the candidate cut: the host form widens the candidate set until the proof holds
                 self.stats["redone_unproven"] += 1
                 _answer(r.future, self._lists_blocking, r, key)
             elif group is None:
                 _deliver(r.future, (ids[i], sc[i]))
-            elif group[2][i] != 1:  # the window ended before the top_k-th group: the blocking loop continues the ranking
+            elif group[2][i] != (3 if members else 1):
+                # the window ended before the top_k-th group (or, with group_size > 1, before a group's last member was
+                # proven): the blocking loop continues the ranking
                 self.stats["redone_grouped"] += 1
                 _answer(r.future, self._lists_blocking, r, key)
+            elif members:
+                at = group[0][i][group[0][i] >= 0]          # slot order = group order, members in list order
+                _deliver(r.future, (ids[i][at], sc[i][at]))
             else:
                 at = group[0][i, :int(group[1][i])]
                 _deliver(r.future, (ids[i][at], sc[i][at]))

@@ -1,4 +1,5 @@
-"""The rows' group keys in HBM: what `hr_group_select_dev` and `hr_mask_drop_groups_dev` (csrc/group.h) read.
+"""The rows' group keys in HBM: what `hr_group_select_dev`, `hr_group_select_n_dev` and the two group-mask kernels
+(csrc/group.h) read.
 
 Milvus groups a search on a scalar field server-side (`Collection.search(..., group_by_field=F)`).  Here the group keys of
 a field (columns.PayloadColumns.group_keys: one int64 per row — an integer field as it is, the dictionary ordinal of a
@@ -33,6 +34,23 @@ def synthetic_group_keys(field: str, n: int) -> np.ndarray:
     """Host restatement of the generated keys of a payload-free collection."""
     rows = np.arange(n, dtype=np.int64)
     return rows // 10 if check_synthetic_group_field(field) == "doc_id" else rows % 10
+
+
+def group_select_n_host(ids: np.ndarray, keys: np.ndarray, k_out: int, group_size: int):
+    """numpy restatement of hr_group_select_n_dev for one list whose ids all lie in the key column: the valid prefix ends
+    at the first id < 0.  -> (positions: one int array per selected group, the groups' keys, entries in the valid prefix)."""
+    neg = np.flatnonzero(ids < 0)
+    n = int(neg[0]) if neg.size else int(ids.shape[0])
+    members: Dict[int, list] = {}          # insertion order = order of first appearance
+    for i, k in enumerate(keys[ids[:n]].tolist()):
+        at = members.get(k)
+        if at is None:
+            if len(members) == k_out:      # a group beyond the k_out-th: not selected, its members not counted
+                continue
+            at = members[k] = []
+        if len(at) < group_size:
+            at.append(i)
+    return [np.asarray(at, dtype=np.int64) for at in members.values()], list(members), n
 
 
 class DeviceGroupKeys:

@@ -167,8 +167,12 @@ class MilvusIndexManager:
                  semantic_dim: int = 1536, sparse_dim: int = 10000, domain_dim: int = 768, connect: bool = True,
                  *, dtype: str = "float16", device: int = 0, devices: Optional[Sequence[int]] = None,
                  enable_domain: bool = True, device_embedding_cache: int = 0, coalesce: bool = True,
-                 semantic_metric: str = "COSINE", domain_metric: str = "COSINE", mmr_on_device: bool = False):
+                 semantic_metric: str = "COSINE", domain_metric: str = "COSINE", mmr_on_device: bool = False,
+                 group_members: bool = False):
         self.host, self.port = host, port
+        # grouping searches with group_size > 1 (the best group_size rows of each of the top_k best groups): off = such a
+        # request is refused, as before the second phase of _grouped_members_blocking existed
+        self.group_members = bool(group_members)
         # MMR profiles (troubleshooting, analysis) through the one-round path: the rows' token sets are mirrored into HBM
         # and hr_mmr_select_dev diversifies the fused lists there (hybrid_search(mmr_lambda=...)); off = the general path
         self.mmr_on_device = bool(mmr_on_device)
@@ -193,8 +197,11 @@ class MilvusIndexManager:
         self._dev_groups = None    # device_groups.DeviceGroupKeys: the group keys of the fields grouped on, on first use
         # grouping searches answered by the blocking loop: searches, windows searched, windows that ended before the
         # top_k-th group and were continued without the groups they showed
+        # group_fill_searches: grouping searches with group_size > 1 that needed the fill phase (a group's members were
+        # not proven by the window that showed it); group_fill_rounds: the windows that phase searched
         # queries: query() calls answered; query_device: those whose page came from hr_mask_rows_dev (mask never left HBM)
-        self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "queries": 0, "query_device": 0}
+        self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
+                      "group_fill_rounds": 0, "queries": 0, "query_device": 0}
         self._stats_lock = threading.Lock()    # the loop runs in worker threads and in the front's thread at once
         self._deleted: Optional[np.ndarray] = None
         self._mask_cache: Dict[Any, Optional[np.ndarray]] = {}   # (expr, rows, delete epoch) -> boolean row filter
@@ -373,11 +380,22 @@ class MilvusIndexManager:
         with self._stats_lock:
             self.stats[name] += 1
 
-    def _check_group_request(self, group_by_field, group_size) -> None:
+    def _check_group_request(self, group_by_field, group_size, top_k=None, strict_group_size=None) -> None:
         """ValueError for what a grouping search does not serve, before anything is searched."""
-        if group_size != 1:
-            raise ValueError(f"group_size={group_size!r} is not supported: only group_size=1 (the best row of every group) is "
-                             "built — a window of the ranking cannot prove a group's later members exact")
+        if not self.group_members:
+            if group_size != 1:
+                raise ValueError(f"group_size={group_size!r} is not supported: only group_size=1 (the best row of every group) is "
+                                 "built — a window of the ranking cannot prove a group's later members exact")
+        else:
+            if isinstance(group_size, (bool, np.bool_)) or not isinstance(group_size, (int, np.integer)) or group_size < 1:
+                raise ValueError(f"group_size must be an integer >= 1, got {group_size!r}")
+            if strict_group_size is not None and not isinstance(strict_group_size, (bool, np.bool_)):
+                raise ValueError(f"strict_group_size must be True, False or absent, got {strict_group_size!r}")
+            if group_size > 1 and group_by_field is None:
+                raise ValueError(f"group_size={group_size} needs group_by_field")
+            if group_size > 1 and int(top_k) * int(group_size) > HR_MAX_TOPK:
+                raise ValueError(f"a grouping search returns at most top_k * group_size <= HR_MAX_TOPK = {HR_MAX_TOPK} rows, "
+                                 f"got {top_k} * {group_size}")
         if group_by_field is not None:
             if not isinstance(group_by_field, str):
                 raise ValueError(f"unknown group_by_field: {group_by_field!r}")
@@ -902,12 +920,16 @@ class MilvusIndexManager:
         return bounds
 
     def _search_lists_blocking(self, query, collection_name: str, top_k: int, filters: Optional[str], params: Dict,
-                               group_by_field: Optional[str] = None, bounds: Optional[Tuple[float, float]] = None):
+                               group_by_field: Optional[str] = None, bounds: Optional[Tuple[float, float]] = None,
+                               group_size: int = 1):
         """(row ids [k], scores [k]) of ONE query through the host forms (which escalate until the list is proven).  With
-        group_by_field: the exact grouped ranking (_grouped_lists_blocking), as many entries as there are groups, at most k.
+        group_by_field: the exact grouped ranking (_grouped_lists_blocking), as many entries as there are groups, at most k —
+        with group_size > 1 up to group_size entries per group, a group's entries adjacent (_grouped_members_blocking).
         bounds = (radius, range_filter) of a range search on a dense collection: the range forms of the same paths."""
         coll = self.collections[collection_name]
         drop = float((params.get("params") or params).get("drop_ratio_search", 0.0))
+        if group_by_field is not None and group_size > 1:
+            return self._grouped_members_blocking(query, coll, int(top_k), filters, drop, group_by_field, int(group_size))
         if group_by_field is not None:
             return self._grouped_lists_blocking(query, coll, int(top_k), filters, drop, group_by_field)
         if bounds is not None:
@@ -964,11 +986,12 @@ class MilvusIndexManager:
         return ids.cpu().numpy(), sc.cpu().numpy()
 
     @staticmethod
-    def group_window(top_k: int) -> int:
-        """Rows of the ranking a grouping search reads at a time: K' = min(HR_MAX_TOPK, GROUP_WINDOW_FACTOR * top_k)."""
+    def group_window(top_k: int, group_size: int = 1) -> int:
+        """Rows of the ranking a grouping search reads at a time: K' = min(HR_MAX_TOPK, GROUP_WINDOW_FACTOR * top_k *
+        group_size)."""
         if not 1 <= top_k <= HR_MAX_TOPK:
             raise ValueError(f"a grouping search takes 1 <= top_k <= HR_MAX_TOPK = {HR_MAX_TOPK}, got {top_k}")
-        return min(HR_MAX_TOPK, GROUP_WINDOW_FACTOR * top_k)
+        return min(HR_MAX_TOPK, GROUP_WINDOW_FACTOR * top_k * group_size)
 
     def _grouped_lists_blocking(self, query, coll, top_k: int, filters: Optional[str], drop: float, field: str):
         """The exact grouped ranking of ONE query: the first top_k rows of the collection's ranking (filter expression and
@@ -1058,14 +1081,158 @@ class MilvusIndexManager:
                 self._count("group_continuations")
         return np.concatenate(rows_out), np.concatenate(scores_out)
 
+    def _grouped_members_blocking(self, query, coll, top_k: int, filters: Optional[str], drop: float, field: str,
+                                  group_size: int):
+        """The exact grouped ranking of ONE query with group_size > 1 members per group: for the first top_k groups of the
+        collection's ranking R (groups ordered by their first row in R), the first min(group_size, members in R) rows of
+        each -> (rows, scores), groups in group order, a group's rows adjacent and in R order.
+
+        Phase 1 is _grouped_lists_blocking's loop — windows of K' rows, the groups already shown dropped from the mask
+        between windows — with a select that emits up to group_size members per group from the window in which the
+        group first appears.  A window is a prefix of the masked ranking, so a group with group_size members in it is
+        closed (they are its best), and so is every group of a window that was not full (the ranking ran out).
+
+        Phase 2 fills the open groups O: the base mask AND "key in O", one search of K2 = min(HR_MAX_TOPK, max(|O| *
+        group_size, K')) rows.  Restricting R to some groups keeps its order, so a group's first rows in that list are
+        its first rows in R.  A list that is not full closes every group; a full one spreads >= |O| * group_size rows over
+        at most |O| groups, so one of them holds group_size and closes: at most |O| rounds (top_k * group_size <=
+        HR_MAX_TOPK keeps K2 >= |O| * group_size)."""
+        g = group_size
+        window = self.group_window(top_k, g)
+        be = self._group_backend(query, coll, filters, drop, field)
+        groups: List[list] = []            # [key, rows, scores, closed] in group order
+        self._count("group_searches")
+        mask = be.base
+        while True:
+            ids, sc = be.search(mask, window)
+            self._count("group_rounds")
+            at, keys, n_valid = be.select(ids, top_k - len(groups), g)
+            for a, k in zip(at, keys):
+                groups.append([k, ids[a], sc[a], len(a) == g or n_valid < window])
+            if len(groups) == top_k or n_valid < window:
+                break
+            mask = be.drop(mask, keys)     # every group of the window was selected: none of their rows can be selected again
+            self._count("group_continuations")
+        open_ = [grp for grp in groups if not grp[3]]
+        if open_:
+            self._count("group_fill_searches")
+        while open_:
+            k2 = min(HR_MAX_TOPK, max(len(open_) * g, window))
+            ids, sc = be.search(be.keep([grp[0] for grp in open_]), k2)
+            self._count("group_fill_rounds")
+            at, keys, n_valid = be.select(ids, len(open_), g)
+            found = dict(zip(keys, at))
+            for grp in open_:
+                a = found.get(grp[0])
+                if a is not None and len(a) >= len(grp[1]):      # (both are prefixes of the group's rows in R)
+                    grp[1], grp[2] = ids[a], sc[a]
+                grp[3] = n_valid < k2 or len(grp[1]) == g
+            still = [grp for grp in open_ if not grp[3]]
+            if len(still) == len(open_):
+                raise RuntimeError("grouping search: a full fill window closed no group")      # the pigeonhole step failed
+            open_ = still
+        if not groups:
+            return np.zeros(0, np.int64), np.zeros(0, np.float32)
+        return np.concatenate([grp[1] for grp in groups]), np.concatenate([grp[2] for grp in groups])
+
+    def _group_backend(self, query, coll, filters: Optional[str], drop: float, field: str):
+        """What _grouped_members_blocking's two phases run on: the device form (one local GPU shard: hr_group_select_n_dev,
+        hr_mask_drop_groups_dev, hr_mask_keep_groups_dev, masks in HBM) or the host form (several shards, the torchrun
+        form, stand-in managers: numpy restatements of the kernels over boolean row masks).  Both offer
+        base / search(mask, k) -> (ids [k], scores [k]) / select(ids, k_out, g) -> (positions per group, keys, valid
+        entries) / drop(mask, keys) -> mask / keep(keys) -> base restricted to the keys."""
+        n = self.num_rows
+        sparse = coll.kind == "sparse"
+        q_host = None if sparse else dense_rows_host([query])
+        mgr = self
+        if getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and self._filters_on_device() is not None:
+            import torch
+            from .device_filters import mask_bytes
+            h = coll.handle.first
+            dev = torch.device("cuda", h.device)
+            nat = self._native
+
+            class Device:
+                def __init__(self):
+                    with torch.cuda.device(dev):
+                        self.keys = mgr._group_keys_on_device().tensor(field, n)
+                        self.base = mgr._device_row_mask(filters, coll.kind)     # cached and shared: never written here
+                        self.work = [None, None]                                 # this query's drop mask and keep mask
+                        self.pos = torch.empty(HR_MAX_TOPK, dtype=torch.int32, device=dev)
+                        self.sel_keys = torch.empty(HR_MAX_TOPK, dtype=torch.int64, device=dev)
+                        self.cnt = torch.empty(HR_MAX_TOPK + 1, dtype=torch.int32, device=dev)   # members per group, then the groups
+
+                def search(self, mask, k):
+                    ptr = mask.data_ptr() if mask is not None else 0
+                    ids, sc = h.search_sparse([query], k, drop, None, ptr) if sparse else h.search_dense(q_host, k, None, ptr)
+                    return ids[0], sc[0]
+
+                def select(self, ids, k_out, g):
+                    with torch.cuda.device(dev):
+                        stream = torch.cuda.current_stream(dev)
+                        d_ids = torch.from_numpy(ids).to(dev)
+                        nat.group_select_n_dev(d_ids.data_ptr(), 0, 1, len(ids), self.keys.data_ptr(), n, 0, k_out, g,
+                                               self.pos.data_ptr(), self.sel_keys.data_ptr(), self.cnt.data_ptr(),
+                                               self.cnt.data_ptr() + 4 * HR_MAX_TOPK, 0, stream.cuda_stream)
+                        cnt = self.cnt.cpu().numpy()                             # synchronises the stream
+                        n_sel = int(cnt[HR_MAX_TOPK])
+                        pos = self.pos[:k_out * g].cpu().numpy().astype(np.int64)
+                        keys = self.sel_keys[:n_sel].cpu().tolist()
+                    neg = np.flatnonzero(ids < 0)
+                    return ([pos[o * g:o * g + int(cnt[o])] for o in range(n_sel)], keys,
+                            int(neg[0]) if neg.size else len(ids))
+
+                def _mask_op(self, op, slot, mask, keys):
+                    with torch.cuda.device(dev):
+                        stream = torch.cuda.current_stream(dev)
+                        if self.work[slot] is None:
+                            self.work[slot] = torch.empty(mask_bytes(n), dtype=torch.uint8, device=dev)
+                        d_set = torch.tensor(keys, dtype=torch.int64, device=dev)
+                        op(mask.data_ptr() if mask is not None else 0, self.work[slot].data_ptr(), n, self.keys.data_ptr(),
+                           d_set.data_ptr(), len(keys), stream.cuda_stream)
+                        stream.synchronize()      # the search reads the mask on a stream of its own
+                    return self.work[slot]
+
+                def drop(self, mask, keys):
+                    return self._mask_op(nat.mask_drop_groups_dev, 0, mask, keys)
+
+                def keep(self, keys):
+                    return self._mask_op(nat.mask_keep_groups_dev, 1, self.base, keys)
+
+            return Device()
+
+        from .device_groups import group_select_n_host
+        host_keys = self._host_group_keys(field)
+
+        class Host:
+            base = mgr._row_mask(filters)                                        # cached and shared: never written here
+
+            def search(self, mask, k):
+                ids, sc = coll.handle.search_sparse([query], k, drop, mask) if sparse else coll.handle.search_dense(q_host, k, mask)
+                return ids[0], sc[0]
+
+            def select(self, ids, k_out, g):
+                return group_select_n_host(ids, host_keys, k_out, g)
+
+            def drop(self, mask, keys):
+                gone = np.isin(host_keys[:n], np.asarray(keys, dtype=np.int64))
+                return ~gone if mask is None else (mask[:n] & ~gone)
+
+            def keep(self, keys):
+                kept = np.isin(host_keys[:n], np.asarray(keys, dtype=np.int64))
+                return kept if self.base is None else (self.base[:n] & kept)
+
+        return Host()
+
     def _search_blocking(self, query_embedding, collection_name: str, top_k: int, filters: Optional[str],
-                         search_params: Optional[Dict], group_by_field: Optional[str] = None) -> List[Dict[str, Any]]:
+                         search_params: Optional[Dict], group_by_field: Optional[str] = None,
+                         group_size: int = 1) -> List[Dict[str, Any]]:
         coll = self.collections[collection_name]
         params = self._search_params(coll, search_params)
         bounds = self._range_request(coll, params, group_by_field)
         query = self._as_sparse_payload(query_embedding) if coll.kind == "sparse" else query_embedding
         return self._format_hits(*self._search_lists_blocking(query, collection_name, top_k, filters, params, group_by_field,
-                                                              bounds))
+                                                              bounds, group_size))
 
     @staticmethod
     def _search_dense_device(handle, q_dev, top_k: int):
@@ -1120,13 +1287,16 @@ class MilvusIndexManager:
 
     async def search(self, query_embedding, collection_name: str, top_k: int = 20, filters: Optional[str] = None,
                      search_params: Optional[Dict] = None, *, group_by_field: Optional[str] = None,
-                     group_size: int = 1) -> List[Dict[str, Any]]:
+                     group_size: int = 1, strict_group_size: Optional[bool] = None) -> List[Dict[str, Any]]:
         """Collection.search (reference indexing.py:503-525).  group_by_field=F (pymilvus' grouping search): the best row
         of each of the top_k best groups of field F, in ranking order — exact at any depth; fewer groups than top_k give a
         shorter list.  F is an integer or a string field of the schema (chunk_index, token_count, doc_id, id / chunk_id,
-        timestamp); only group_size=1 is built."""
-        if group_by_field is not None or group_size != 1:
-            self._check_group_request(group_by_field, group_size)
+        timestamp).  group_size=g > 1 is served by a manager created with group_members=True: up to g rows of each of the
+        top_k best groups as one flat list, groups in ranking order, a group's rows adjacent and in ranking order; top_k * g
+        <= HR_MAX_TOPK.  The answer is exact (pymilvus' strict_group_size=True), so strict_group_size changes nothing."""
+        if group_by_field is not None or group_size != 1 or strict_group_size is not None:
+            self._check_group_request(group_by_field, group_size, top_k, strict_group_size)
+        group_size = int(group_size)
         if collection_name not in self.collections:
             raise ValueError(f"Collection {collection_name} not found")
         coll = self.collections[collection_name]
@@ -1140,12 +1310,13 @@ class MilvusIndexManager:
                     from .batching import RangedQuery
                     query = RangedQuery(query, bounds)
                 fut = front.submit_async("sparse" if coll.kind == "sparse" else "dense",
-                                         (collection_name, int(top_k), filters, self._params_key(params), group_by_field), query)
+                                         (collection_name, int(top_k), filters, self._params_key(params), group_by_field,
+                                          group_size), query)
                 ids, sc = await asyncio.wait_for(fut, timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
                 return self._format_hits(ids, sc)
             return await asyncio.wait_for(
                 asyncio.to_thread(self._search_blocking, query_embedding, collection_name, top_k, filters,
-                                  search_params, group_by_field),
+                                  search_params, group_by_field, group_size),
                 timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
         except asyncio.TimeoutError:
             logging.error("shard search timeout for collection %s", collection_name)

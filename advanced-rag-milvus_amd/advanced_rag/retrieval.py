@@ -24,6 +24,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
 
+from ._native import HR_MAX_TOPK   # importing the binding module does not load the library
 from .constants import RetrievalConstants
 from .ranker import LearnedRanker
 
@@ -76,6 +77,9 @@ class RetrievalConfig:
     # grouping search (pymilvus' group_by_field): every modality ranks the best chunk of each group (2 x top_k documents
     # instead of 2 x top_k chunks) and the fused list keeps the first hit of every group.  None = chunks, as the reference.
     group_by_field: Optional[str] = None
+    # with group_by_field: up to group_size chunks of every group in every modality list and in the fused list (pymilvus'
+    # group_size; needs an index manager created with group_members=True, and 2 * top_k * group_size <= 256)
+    group_size: int = 1
     # the dict form of a filter also takes {"field": {"$in": [...]}} and {"$nin": [...]} (-> `field in [..]` / `field not in
     # [..]`).  False = they are refused, as the reference refuses them.
     extended_filter_operators: bool = False
@@ -90,6 +94,10 @@ class RetrievalConfig:
             if check_group_field(self.group_by_field) not in FUSED_GROUP_FIELDS:
                 raise ValueError(f"group_by_field {self.group_by_field!r} is not shown by a hit: retrieve() groups on one of "
                                  f"{', '.join(FUSED_GROUP_FIELDS)}")
+        if isinstance(self.group_size, bool) or not isinstance(self.group_size, int) or self.group_size < 1:
+            raise ValueError(f"group_size must be an integer >= 1, got {self.group_size!r}")
+        if self.group_size > 1 and self.group_by_field is None:
+            raise ValueError(f"group_size={self.group_size} needs group_by_field")
         if self.semantic_search_params is None:
             self.semantic_search_params = {"metric_type": "COSINE", "params": {"ef": 64}}
         if self.sparse_search_params is None:
@@ -151,6 +159,7 @@ class HybridRetriever:
                                    rerank_top_k=clamp_rerank(rerank_k), enable_reranking=rerank,
                                    dense_weight=base.dense_weight, sparse_weight=base.sparse_weight,
                                    enable_mmr=mmr, mmr_lambda=lam, group_by_field=base.group_by_field,
+                                   group_size=base.group_size,
                                    extended_filter_operators=base.extended_filter_operators)
 
         return {
@@ -190,6 +199,10 @@ class HybridRetriever:
         # The active profile becomes self.config for this request (and stays so
         # afterwards) exactly as reference retrieval.py:281-284 does.
         self.config = self.profiles.get(profile, self.config)
+        if self.config.group_size > 1 and 2 * self.config.top_k * self.config.group_size > HR_MAX_TOPK:
+            # refused here: inside the searches a modality that raises degrades to "no hits"
+            raise ValueError(f"retrieve() with group_size={self.config.group_size} searches 2 * top_k groups per modality: "
+                             f"2 * top_k * group_size <= {HR_MAX_TOPK}, got 2 * {self.config.top_k} * {self.config.group_size}")
 
         dense_q = await self._get_semantic_embedding(query)
         sparse_q = await self._get_sparse_embedding(query)
@@ -280,9 +293,15 @@ class HybridRetriever:
 
     async def _tagged_search(self, method: str, embedding, collection: str, top_k: int, filters, params):
         group = {"group_by_field": self.config.group_by_field} if self.config.group_by_field is not None else {}
+        if self.config.group_size > 1:
+            group["group_size"] = self.config.group_size
         try:
             hits = await self.index_manager.search(query_embedding=embedding, collection_name=collection,
                                                    top_k=top_k, filters=filters, search_params=params, **group)
+        except ValueError:
+            if self.config.group_size > 1:
+                raise      # a manager without group_members=True refuses the request: that is the caller's to see
+            return []
         except Exception:
             return []  # a failing modality degrades to "no hits" (reference :355-358, :387-389, :411-413)
         for h in hits:
@@ -356,23 +375,23 @@ class HybridRetriever:
         now = datetime.utcnow()
         fused = [self._finish_fused_hit(payload[doc_id], score, seen_in, now) for doc_id, score, seen_in in ranked]
         if self.config.group_by_field is not None:
-            fused = self._first_per_group(fused, self.config.group_by_field)
+            fused = self._first_per_group(fused, self.config.group_by_field, self.config.group_size)
         if self.config.enable_mmr and fused:
             return self._mmr_diversify(fused, self.config.top_k, self.config.mmr_lambda)
         return fused
 
     @staticmethod
-    def _first_per_group(fused: List[Dict[str, Any]], field: str) -> List[Dict[str, Any]]:
-        """The first hit of every group, in fused order.  The modality lists are grouped already, but the fusion goes by
-        chunk id: two chunks of one document can arrive from different modalities.  Before MMR and before the cut."""
-        seen: Set[Any] = set()
+    def _first_per_group(fused: List[Dict[str, Any]], field: str, group_size: int = 1) -> List[Dict[str, Any]]:
+        """The first group_size hits of every group, in fused order.  The modality lists are grouped already, but the fusion
+        goes by chunk id: more chunks of one document can arrive from different modalities.  Before MMR and before the cut."""
+        seen: Dict[Any, int] = {}
         out = []
         for hit in fused:
             key = hit["id"] if field in ("id", "chunk_id") else (hit.get("metadata") or {}).get(field)
             if key is None:            # another manager's hit without the field: a group of its own
                 out.append(hit)
-            elif key not in seen:
-                seen.add(key)
+            elif seen.get(key, 0) < group_size:
+                seen[key] = seen.get(key, 0) + 1
                 out.append(hit)
         return out
 

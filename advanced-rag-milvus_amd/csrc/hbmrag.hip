@@ -2335,20 +2335,49 @@ int hr_group_select_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_i
     return HR_OK;
 }
 
-int hr_mask_drop_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out, int64_t n_rows, const int64_t* d_keys,
-                            const int64_t* d_drop, int n_drop, void* stream) {
-    if (n_rows < 0 || n_drop < 0) return fail(nullptr, HR_EINVAL, "bad group mask sizes");
-    if (n_drop > kFuseMax) return fail(nullptr, HR_ELIMIT, "n_drop exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+int hr_group_select_n_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_in, const int64_t* d_keys, int64_t key_rows,
+                          int64_t first_row, int k_out, int group_size, int32_t* d_out_pos, int64_t* d_out_keys, int32_t* d_out_cnt,
+                          int32_t* d_out_n, int32_t* d_flags, void* stream) {
+    if (B < 0 || k_in <= 0 || k_out <= 0 || k_out > k_in || group_size <= 0 || key_rows < 0 || first_row < 0)
+        return fail(nullptr, HR_EINVAL, "bad group sizes");
+    if (k_in > kFuseMax) return fail(nullptr, HR_ELIMIT, "k_in exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+    if ((int64_t)k_out * group_size > kFuseMax) return fail(nullptr, HR_ELIMIT, "k_out * group_size exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+    if (B == 0) return HR_OK;
+    if (!d_ids || !d_out_pos || !d_out_cnt || !d_out_n) return fail(nullptr, HR_EINVAL, "null buffer");
+    if (key_rows > 0 && !d_keys) return fail(nullptr, HR_EINVAL, "key_rows > 0 needs the key column");
+    hipLaunchKernelGGL(group_select_n_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, d_ids, d_n, k_in, d_keys, key_rows,
+                       first_row, k_out, group_size, d_out_pos, d_out_keys, d_out_cnt, d_out_n, d_flags);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "group_select_n_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+// hr_mask_drop_groups_dev (keep = false) and hr_mask_keep_groups_dev (keep = true): one kernel, the sense compiled in.
+static int mask_groups(bool keep, const uint8_t* d_mask_in, uint8_t* d_mask_out, int64_t n_rows, const int64_t* d_keys,
+                       const int64_t* d_set, int n_set, void* stream) {
+    const char* what = keep ? "n_keep" : "n_drop";
+    if (n_rows < 0 || n_set < 0) return fail(nullptr, HR_EINVAL, "bad group mask sizes");
+    if (n_set > kFuseMax) return fail(nullptr, HR_ELIMIT, "%s exceeds 3 * HR_MAX_TOPK = %d", what, kFuseMax);
     if (n_rows == 0) return HR_OK;
-    if (!d_mask_out || !d_keys || (n_drop > 0 && !d_drop)) return fail(nullptr, HR_EINVAL, "null buffer");
+    if (!d_mask_out || !d_keys || (n_set > 0 && !d_set)) return fail(nullptr, HR_EINVAL, "null buffer");
     if (((uintptr_t)d_mask_in | (uintptr_t)d_mask_out) & 7) return fail(nullptr, HR_EINVAL, "mask buffers must be 8-byte aligned");
     const int64_t n_words = (n_rows + 63) / 64;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_words + 3) / 4, 1024));
-    hipLaunchKernelGGL(mask_drop_groups_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)d_mask_in,
-                       (unsigned long long*)d_mask_out, n_rows, d_keys, d_drop, n_drop);
+    hipLaunchKernelGGL(keep ? mask_groups_kernel<true> : mask_groups_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const unsigned long long*)d_mask_in, (unsigned long long*)d_mask_out, n_rows, d_keys, d_set, n_set);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "mask_drop_groups_kernel: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "mask_groups_kernel: %s", hipGetErrorString(e));
     return HR_OK;
+}
+
+int hr_mask_drop_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out, int64_t n_rows, const int64_t* d_keys,
+                            const int64_t* d_drop, int n_drop, void* stream) {
+    return mask_groups(false, d_mask_in, d_mask_out, n_rows, d_keys, d_drop, n_drop, stream);
+}
+
+int hr_mask_keep_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out, int64_t n_rows, const int64_t* d_keys,
+                            const int64_t* d_keep, int n_keep, void* stream) {
+    return mask_groups(true, d_mask_in, d_mask_out, n_rows, d_keys, d_keep, n_keep, stream);
 }
 
 // ---- read path (query.h) -----------------------------------------------------------------------------------------------

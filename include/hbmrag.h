@@ -356,12 +356,40 @@ HR_API int hr_mmr_select_dev(const int64_t* d_ids, const double* d_scores, const
  *   3 * HR_MAX_TOPK (HR_ELIMIT beyond).
  * Together they continue a grouping search exactly: while a window of the ranking ends before the k-th group, the
  * groups it showed are dropped from the mask and the search is repeated — the dropped rows could never be selected
- * again.  Bad arguments: HR_EINVAL.  B == 0 / n_rows == 0: HR_OK, nothing is launched.  Asynchronous on `stream`. */
+ * again.  Bad arguments: HR_EINVAL.  B == 0 / n_rows == 0: HR_OK, nothing is launched.  Asynchronous on `stream`.
+ *
+ * group_size > 1 (the best group_size entities of each of the k best groups):
+ * hr_group_select_n_dev: hr_group_select_dev with up to group_size members per group.  Inputs and conventions are
+ *   the same (valid prefix by d_n or the first id < 0; an id outside the key column is a group of its own with one
+ *   member; d_keys may be NULL when key_rows == 0).  1 <= group_size, k_out <= k_in <= 3 * HR_MAX_TOPK and
+ *   k_out * group_size <= 3 * HR_MAX_TOPK (HR_ELIMIT beyond).
+ *   Out: d_out_pos [B][k_out * group_size]: slot o * group_size + m = the list position of the m-th member, in list
+ *   order, of the o-th group, in order of first appearance; -1 padded.  d_out_keys [B][k_out] (may be NULL) the keys
+ *   of the selected groups, 0 padded; d_out_cnt [B][k_out] the members written per group, 0 padded; d_out_n [B] the
+ *   groups selected; d_flags [B] (may be NULL): bit 0 = hr_group_select_dev's flag (d_out_n[q] == k_out, or fewer than
+ *   k_in valid entries), bit 1 = every selected group has group_size members, or the list held fewer than k_in valid
+ *   entries.  An entry's rank in its group is the number of earlier entries with its key, a group's ordinal the number
+ *   of group leaders before its leader: positions decide, no atomic or thread order does.  With group_size == 1,
+ *   d_out_pos, d_out_keys, d_out_n and bit 0 of d_flags equal hr_group_select_dev's outputs.
+ * hr_mask_keep_groups_dev: the complement sense of hr_mask_drop_groups_dev — bit r of d_mask_out = bit r of d_mask_in
+ *   AND "d_keys[r] IS among the n_keep keys at d_keep" — with the same buffer rules (8 * ceil(n_rows / 64) bytes, bits
+ *   at and beyond n_rows written 0, NULL input = all rows, the buffers may be the same, d_keep a device array in any
+ *   order with duplicates, 0 <= n_keep <= 3 * HR_MAX_TOPK).  n_keep == 0 writes an all-zero mask.
+ * Together they make the members exact: a group whose window showed group_size members, or whose window was not full,
+ * is closed — a window is a prefix of the masked ranking.  The open groups are filled by searching under "base mask AND
+ * key among the open groups": restricting a ranking to some groups keeps its order, and a full list of at least
+ * |open| * group_size rows closes at least one group. */
 HR_API int hr_group_select_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_in,
                         const int64_t* d_keys, int64_t key_rows, int64_t first_row, int k_out,
                         int32_t* d_out_pos, int64_t* d_out_keys, int32_t* d_out_n, int32_t* d_flags, void* stream);
 HR_API int hr_mask_drop_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out, int64_t n_rows,
                             const int64_t* d_keys, const int64_t* d_drop, int n_drop, void* stream);
+HR_API int hr_group_select_n_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_in,
+                          const int64_t* d_keys, int64_t key_rows, int64_t first_row, int k_out, int group_size,
+                          int32_t* d_out_pos, int64_t* d_out_keys, int32_t* d_out_cnt, int32_t* d_out_n,
+                          int32_t* d_flags, void* stream);
+HR_API int hr_mask_keep_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out, int64_t n_rows,
+                            const int64_t* d_keys, const int64_t* d_keep, int n_keep, void* stream);
 
 /* Everything after the per-shard lists of a query batch in ONE launch (one block per query): [hr_merge_topk_dev of
  * every modality's exchanged lists] -> hr_fuse_rrf_dev -> [hr_rerank_linear_dev]; results are bit-identical to the
