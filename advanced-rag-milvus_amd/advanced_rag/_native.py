@@ -146,6 +146,11 @@ _SIGNATURES = {
     "hr_get_dense_rows_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_void_p,
                                          _c.c_void_p]),
     "hr_get_dense_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p]),
+    "hr_get_sparse_rows_scratch_bytes": (_c.c_size_t, [_c.c_int64]),
+    "hr_get_sparse_rows_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
+                                          _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_get_sparse_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
+                                      _c.c_void_p]),
     "hr_set_profiling": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "hr_last_kernel_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
     "hr_last_compact_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
@@ -344,6 +349,34 @@ class ShardHandle:
         self._check(self._lib.hr_get_dense_rows_dev(self._h, _vp(d_rows) if d_rows else None, n, out_dtype,
                                                     _vp(d_out) if d_out else None, out_stride or self.dim,
                                                     _vp(d_missing) if d_missing else None, _vp(stream) if stream else None))
+
+    def get_sparse_rows(self, rows) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """hr_get_sparse_rows: the stored sparse rows with the given GLOBAL ids (any order, repeats allowed) as one CSR
+        (indptr int64 [n + 1], indices int32 [nnz], values float32 [nnz]): the sizing call, then the fetch.  An id outside
+        the shard: ValueError."""
+        ids = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1)
+        n = ids.shape[0]
+        indptr = np.zeros(n + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        self._check(self._lib.hr_get_sparse_rows(self._h, _vp(ids), n, _vp(indptr), None, None, 0, ctypes.byref(total)))
+        nnz = int(total.value)
+        indices, values = np.empty(nnz, dtype=np.int32), np.empty(nnz, dtype=np.float32)
+        if nnz:
+            self._check(self._lib.hr_get_sparse_rows(self._h, _vp(ids), n, _vp(indptr), _vp(indices), _vp(values), nnz,
+                                                     ctypes.byref(total)))
+            if int(total.value) != nnz:  # an append or a compaction between the two calls
+                raise HbmRagError(2, "the sparse rows changed between the sizing call and the fetch")
+        return indptr, indices, values
+
+    def get_sparse_rows_dev(self, d_rows: int, n: int, d_out_indptr: int, d_out_idx: int, d_out_val: int, cap: int, d_counts: int,
+                            d_scratch: int, stream: int = 0):
+        """hr_get_sparse_rows_dev (device pointers, asynchronous on `stream`): the stored rows d_rows[0 .. n) as a CSR in
+        d_out_indptr [n + 1] / d_out_idx / d_out_val (capacity `cap` entries; 0 with null entry buffers = sizes only);
+        d_counts[0] = all entries, d_counts[1] = ids outside the shard (empty rows); d_scratch =
+        get_sparse_rows_scratch_bytes(n) bytes."""
+        p = lambda x: _vp(x) if x else None  # noqa: E731
+        self._check(self._lib.hr_get_sparse_rows_dev(self._h, p(d_rows), n, p(d_out_indptr), p(d_out_idx), p(d_out_val), cap,
+                                                     p(d_counts), p(d_scratch), p(stream)))
 
     # -- search, host buffers
     @staticmethod
@@ -555,6 +588,11 @@ def group_select_dev(d_ids: int, d_n: int, B: int, k_in: int, d_keys: int, key_r
 def mask_rows_scratch_bytes(n_rows: int) -> int:
     """hr_mask_rows_scratch_bytes: device scratch hr_mask_rows_dev needs for a mask of n_rows rows."""
     return int(load_library().hr_mask_rows_scratch_bytes(n_rows))
+
+
+def get_sparse_rows_scratch_bytes(n: int) -> int:
+    """hr_get_sparse_rows_scratch_bytes: device scratch hr_get_sparse_rows_dev needs for n requested rows."""
+    return int(load_library().hr_get_sparse_rows_scratch_bytes(n))
 
 
 def mask_rows_dev(d_mask: int, n_rows: int, first_row: int, offset: int, limit: int, d_rows: int, d_counts: int,

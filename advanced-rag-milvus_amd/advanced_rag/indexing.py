@@ -39,7 +39,7 @@ from .columns import FLOAT_COLUMNS, PayloadColumns, check_group_field
 from .constants import GROUP_WINDOW_FACTOR, QUERY_MAX_WINDOW, IndexingConstants
 from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache, get_semantic_cache
 from ._native import HR_MAX_TOPK   # importing the binding module does not load the library
-from .shards import PartialAppend, ShardSet
+from .shards import PartialAppend, ShardSet, is_native_handle
 from .staging import dense_rows_device, dense_rows_host, list_buffers
 
 logger = logging.getLogger(__name__)
@@ -161,6 +161,13 @@ class ShardCollection:
         """pymilvus' Collection.query(expr, output_fields, limit, offset), synchronous (MilvusIndexManager.query)."""
         return self.manager._query_blocking(self.name, expr, output_fields, limit, offset)
 
+    def search_by_ids(self, ids, top_k: int = 20, filters: Optional[str] = None, search_params: Optional[Dict] = None, *,
+                      group_by_field: Optional[str] = None, group_size: int = 1,
+                      strict_group_size: Optional[bool] = None) -> List[List[Dict[str, Any]]]:
+        """Search with the stored vectors of the entities `ids`, synchronous (MilvusIndexManager.search_by_ids)."""
+        return self.manager._search_by_ids_blocking(ids, self.name, top_k, filters, search_params, group_by_field, group_size,
+                                                    strict_group_size)
+
 
 class MilvusIndexManager:
     def __init__(self, host: str = "localhost", port: int = 19530, enable_sharding: bool = True, num_shards: int = 4,
@@ -200,8 +207,9 @@ class MilvusIndexManager:
         # group_fill_searches: grouping searches with group_size > 1 that needed the fill phase (a group's members were
         # not proven by the window that showed it); group_fill_rounds: the windows that phase searched
         # queries: query() calls answered; query_device: those whose page came from hr_mask_rows_dev (mask never left HBM)
+        # search_by_ids: search_by_ids() calls whose ids were resolved and whose stored vectors were fetched
         self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
-                      "group_fill_rounds": 0, "queries": 0, "query_device": 0}
+                      "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0}
         self._stats_lock = threading.Lock()    # the loop runs in worker threads and in the front's thread at once
         self._deleted: Optional[np.ndarray] = None
         self._mask_cache: Dict[Any, Optional[np.ndarray]] = {}   # (expr, rows, delete epoch) -> boolean row filter
@@ -1574,13 +1582,17 @@ class MilvusIndexManager:
             raise ValueError(f"offset must be >= 0, got {offset!r}")
         if limit is not None and (limit < 0 or not 1 <= offset + limit <= QUERY_MAX_WINDOW):
             raise ValueError(f"a query takes 1 <= offset + limit <= {QUERY_MAX_WINDOW} and limit >= 0, got offset={offset}, limit={limit}")
-        if "embedding" in fields:
-            if coll.kind == "sparse":
-                raise ValueError(f"reading sparse vectors back (embedding of {coll.name}) is not built")
-            if not hasattr(coll.handle, "handles"):
-                raise NotImplementedError("reading stored vectors back (embedding) is not built for the torchrun form "
-                                          "(CollectiveShardSet)")
+        if "embedding" in fields and not hasattr(coll.handle, "handles"):
+            raise NotImplementedError("reading stored vectors back (embedding) is not built for the torchrun form "
+                                      "(CollectiveShardSet)")
         return coll, fields, count, (None if limit is None else int(limit)), int(offset)
+
+    def _query_rows(self, expr: Optional[str], limit: Optional[int], offset: int) -> Tuple[int, np.ndarray, bool]:
+        """(rows that pass, the page's global rows, whether the page came from the device mask)."""
+        on_device = getattr(self._main, "n_shards", 1) == 1 and hasattr(self._main, "handles") and \
+            self._filters_on_device() is not None
+        total, rows = (self._query_rows_device if on_device else self._query_rows_host)(expr, limit, offset)
+        return total, rows, on_device
 
     def _query_rows_device(self, expr: Optional[str], limit: Optional[int], offset: int) -> Tuple[int, np.ndarray]:
         """(rows that pass, the page's global rows) of one GPU shard: the cached packed mask of `expr` + tombstones stays in
@@ -1623,17 +1635,17 @@ class MilvusIndexManager:
         expr = expr if (expr is not None and str(expr).strip()) else None
         if expr is None and limit is None and not count:
             raise ValueError("a query without an expression needs a limit")
-        on_device = getattr(self._main, "n_shards", 1) == 1 and hasattr(self._main, "handles") and \
-            self._filters_on_device() is not None
         if count:
             limit, offset = 0, 0
-        total, rows = (self._query_rows_device if on_device else self._query_rows_host)(expr, limit, offset)
+        total, rows, on_device = self._query_rows(expr, limit, offset)
         self._count("queries")
         if on_device:
             self._count("query_device")
         if count:
             return [{self.COUNT_FIELD: total}]
-        vectors = coll.handle.get_dense_rows(rows) if "embedding" in fields and len(rows) else None
+        vectors = None
+        if "embedding" in fields and len(rows):
+            vectors = self._sparse_payloads(coll, rows) if coll.kind == "sparse" else coll.handle.get_dense_rows(rows)
         if self._synthetic_rows:
             getters = {f: self.SYNTHETIC_QUERY_FIELDS[f] for f in ["id"] + fields if f != "embedding"}
         else:
@@ -1654,8 +1666,114 @@ class MilvusIndexManager:
         is promised, so pages concatenate — without the first `offset`, at most `limit` of them (limit=None with an
         expression: all of them).  1 <= offset + limit <= QUERY_MAX_WINDOW.  -> flat dicts: the primary key "id" always,
         the requested fields besides (QUERY_FIELDS); "embedding" is the stored vector of the named collection as float32
-        [dim] (fp16 shards widened exactly).  output_fields=["count(*)"] -> [{"count(*)": n}].  Refusals are ValueError."""
+        [dim] (fp16 shards widened exactly); on sparse_index it is the stored payload {"indices": int32 [nnz], "values":
+        float32 [nnz]} — the shape of an ingested payload, which search() takes as it is (_sparse_payloads has the rule for
+        rows without entries).  output_fields=["count(*)"] -> [{"count(*)": n}].  Refusals are ValueError."""
         return await asyncio.to_thread(self._query_blocking, collection_name, expr, output_fields, limit, offset)
+
+    # ------------------------------------------------------------------ stored vectors as queries
+    def _sparse_rows_device(self, h, rows: np.ndarray):
+        """The CSR of the stored sparse rows `rows` of one GPU shard whose local rows are the global rows, through
+        hr_get_sparse_rows_dev: the count pass sizes the entry buffers, the second call fills them.  A row the shard has no
+        sparse row for is empty (the device form's rule for an id outside the shard)."""
+        import torch
+        nat = self._native
+        n = int(rows.shape[0])
+        dev = torch.device("cuda", h.device)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            d_rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64) + int(getattr(h, "row_offset", 0))).to(dev)
+            indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            counts = torch.empty(2, dtype=torch.int64, device=dev)
+            scratch = torch.empty(nat.get_sparse_rows_scratch_bytes(n), dtype=torch.uint8, device=dev)
+
+            def call(idx, val, cap):
+                h.get_sparse_rows_dev(d_rows.data_ptr(), n, indptr.data_ptr(), idx.data_ptr() if cap else 0,
+                                      val.data_ptr() if cap else 0, cap, counts.data_ptr(), scratch.data_ptr(), stream.cuda_stream)
+                return int(counts.cpu()[0])      # synchronises the stream
+
+            total = call(None, None, 0)
+            idx = torch.empty(total, dtype=torch.int32, device=dev)
+            val = torch.empty(total, dtype=torch.float32, device=dev)
+            if total and call(idx, val, total) != total:
+                raise RuntimeError("the sparse rows changed while they were read")
+            return indptr.cpu().numpy(), idx.cpu().numpy(), val.cpu().numpy()
+
+    def _sparse_payloads(self, coll, rows: np.ndarray) -> List[Dict[str, np.ndarray]]:
+        """The stored sparse payloads of the global rows `rows`, in that order, each {"indices": int32 [nnz], "values":
+        float32 [nnz]} — indices ascending, the stored bits.  index_chunks and the bulk ingests give every row of a batch
+        that carries sparse payloads a sparse row (an EMPTY one where a chunk's encoding failed or a shard refused the
+        batch), so sparse row r belongs to entity r and a failed encoding reads back as two empty arrays.  Only rows
+        appended without any sparse payload after the last batch with one (sparse encoding switched off, add_rows without
+        a CSR) have no sparse row at all; they lie beyond num_sparse_rows and read back as two empty arrays too — on one
+        GPU shard by the device form's rule for an id outside the shard, elsewhere by ShardSet.get_sparse_rows."""
+        s = coll.handle
+        # rows_of ascends without repeats: it is the identity exactly when its last entry is its length - 1
+        one_gpu = s.n_shards == 1 and is_native_handle(s.first) and len(s.rows_of[0]) and \
+            int(s.rows_of[0][-1]) == len(s.rows_of[0]) - 1
+        ptr, idx, val = self._sparse_rows_device(s.first, rows) if one_gpu else s.get_sparse_rows(rows)
+        return [{"indices": idx[ptr[i]:ptr[i + 1]].copy(), "values": val[ptr[i]:ptr[i + 1]].copy()} for i in range(len(rows))]
+
+    def _rows_of_ids(self, ids) -> np.ndarray:
+        """The global row of every primary key of `ids`, in request order: `id in [...]` through the filter language (on
+        one GPU shard the device mask; keys that share their first 16 bytes through its undecided-rows host path), the mask
+        as a page of ascending rows, the rows matched to the request by the host id column.  Of several live rows with one
+        id the lowest is taken.  ValueError for an id no live row carries."""
+        if not isinstance(ids, (list, tuple)) or not len(ids):
+            raise ValueError(f"ids must be a non-empty list of primary keys, got {ids!r}")
+        for i in ids:
+            if not isinstance(i, str):
+                raise ValueError(f"a primary key is a string, got {i!r}")
+        wanted = list(dict.fromkeys(ids))
+        _, rows, _ = self._query_rows("id in " + _filters._show_list(wanted), None, 0)
+        id_of = self.synthetic_id if self._synthetic_rows else self._cols["id"].__getitem__
+        row_of: Dict[str, int] = {}
+        for r in rows.tolist():
+            row_of.setdefault(id_of(r), r)         # ascending rows: the lowest row of an id stays
+        for i in wanted:
+            if i not in row_of:
+                raise ValueError(f"no entity with id {i!r} in this collection (deleted entities are not found)")
+        return np.asarray([row_of[i] for i in ids], dtype=np.int64)
+
+    def _stored_queries_blocking(self, ids, collection_name: str) -> list:
+        """What search() takes as the query for each entity of `ids`: its stored vector of the named collection."""
+        if collection_name not in self.collections:
+            raise ValueError(f"Collection {collection_name} not found")
+        coll = self.collections[collection_name]
+        if not hasattr(coll.handle, "handles"):
+            raise NotImplementedError("search by primary key is not built for the torchrun form (CollectiveShardSet)")
+        rows = self._rows_of_ids(ids)
+        self._count("search_by_ids")
+        if coll.kind == "sparse":
+            return self._sparse_payloads(coll, rows)
+        return list(coll.handle.get_dense_rows(rows))
+
+    async def search_by_ids(self, ids, collection_name: str, top_k: int = 20, filters: Optional[str] = None,
+                            search_params: Optional[Dict] = None, *, group_by_field: Optional[str] = None,
+                            group_size: int = 1, strict_group_size: Optional[bool] = None) -> List[List[Dict[str, Any]]]:
+        """pymilvus' search by primary key ("more like this entity"): one hit list per id of `ids`, in request order, each
+        exactly what search() returns for that entity's STORED vector of the named collection with the same arguments —
+        the fp32-widened stored row of a dense collection, the stored payload of sparse_index; filters, range params and
+        grouping pass through untouched.  The entity itself is NOT excluded (it is its own best hit wherever the metric
+        makes it so): a `range_filter` or the filter `id not in [...]` drops it.  A duplicate id gives two equal lists; of
+        several live rows with one id (a re-ingest without a delete) the lowest row is used.  The vectors are fetched once
+        for all ids and make one hop through the host; the searches are search() calls, so concurrent ones share the
+        batching front's launches.  ValueError: `ids` empty or not a list, an id that is not a string, an id no live row
+        carries (a deleted entity is not found), and whatever the filter language (its list cap) and search() (a sparse
+        row of more than HR_MAX_QUERY_NNZ entries) refuse.  NotImplementedError in the torchrun form."""
+        queries = await asyncio.to_thread(self._stored_queries_blocking, ids, collection_name)
+        return list(await asyncio.gather(*(self.search(q, collection_name, top_k, filters, search_params,
+                                                       group_by_field=group_by_field, group_size=group_size,
+                                                       strict_group_size=strict_group_size) for q in queries)))
+
+    def _search_by_ids_blocking(self, ids, collection_name: str, top_k: int, filters: Optional[str],
+                                search_params: Optional[Dict], group_by_field: Optional[str], group_size: int,
+                                strict_group_size: Optional[bool]) -> List[List[Dict[str, Any]]]:
+        """search_by_ids for a synchronous caller: the same lists, every search through the blocking path."""
+        if group_by_field is not None or group_size != 1 or strict_group_size is not None:
+            self._check_group_request(group_by_field, group_size, top_k, strict_group_size)
+        return [self._search_blocking(q, collection_name, top_k, filters, search_params, group_by_field, int(group_size))
+                for q in self._stored_queries_blocking(ids, collection_name)]
 
     # ------------------------------------------------------------------ misc
     def get_collection_stats(self, collection_name: str) -> Dict[str, Any]:

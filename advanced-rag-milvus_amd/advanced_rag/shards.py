@@ -283,10 +283,9 @@ class ShardSet:
         return self._gather(self._fan_out(one), k)
 
     # ------------------------------------------------------------------ read path
-    def get_dense_rows(self, global_rows) -> np.ndarray:
-        """The stored vectors of the given GLOBAL rows (any order, repeats allowed) as float32 [n, dim], in request order:
-        `rows_of` inverted gives shard and local row, every shard gathers its part (hr_get_dense_rows, in parallel through
-        the pool) and the parts are scattered back.  A row no shard holds: ValueError."""
+    def _locate(self, global_rows):
+        """`rows_of` inverted: -> (the rows as int64 [n], per shard (positions in the request, local rows)).  A row no
+        shard holds: ValueError."""
         g = np.ascontiguousarray(global_rows, dtype=np.int64).reshape(-1)
         parts, found = [], np.zeros(g.shape[0], dtype=bool)
         for s, rows in enumerate(self.rows_of):      # ascending per shard: a binary search inverts it
@@ -297,6 +296,13 @@ class ShardSet:
             found |= hit
         if not found.all():
             raise ValueError(f"row {int(g[np.flatnonzero(~found)[0]])} is not in this collection ({self._n} rows)")
+        return g, parts
+
+    def get_dense_rows(self, global_rows) -> np.ndarray:
+        """The stored vectors of the given GLOBAL rows (any order, repeats allowed) as float32 [n, dim], in request order:
+        `rows_of` inverted gives shard and local row, every shard gathers its part (hr_get_dense_rows, in parallel through
+        the pool) and the parts are scattered back.  A row no shard holds: ValueError."""
+        g, parts = self._locate(global_rows)
 
         def one(s):
             where, local = parts[s]
@@ -311,6 +317,39 @@ class ShardSet:
             if v is not None:
                 out[where] = v
         return out
+
+    def get_sparse_rows(self, global_rows) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The stored sparse rows of the given GLOBAL rows (any order, repeats allowed) as one CSR in request order
+        (indptr int64 [n + 1], indices int32, values float32): the inversion and the fan-out of get_dense_rows, every
+        shard's ragged part (hr_get_sparse_rows) stitched in.  A row no shard holds: ValueError.  A row whose shard has
+        fewer sparse rows than dense ones (appended without a sparse payload: local row >= num_sparse_rows) is empty."""
+        g, parts = self._locate(global_rows)
+
+        def one(s):
+            where, local = parts[s]
+            if not len(where):
+                return None
+            h = self.handles[s]
+            stored = local < int(h.num_sparse_rows)
+            ptr, idx, val = h.get_sparse_rows(local[stored] + int(getattr(h, "row_offset", 0)))
+            lens = np.zeros(len(where), dtype=np.int64)
+            lens[stored] = np.diff(ptr)
+            return lens, idx, val
+        got = self._fan_out(one)
+        lens = np.zeros(g.shape[0], dtype=np.int64)
+        for (where, _), v in zip(parts, got):
+            if v is not None:
+                lens[where] = v[0]
+        indptr = np.zeros(g.shape[0] + 1, dtype=np.int64)
+        np.cumsum(lens, out=indptr[1:])
+        indices, values = np.empty(int(indptr[-1]), dtype=np.int32), np.empty(int(indptr[-1]), dtype=np.float32)
+        for (where, _), v in zip(parts, got):
+            if v is None or not len(v[1]):
+                continue
+            n_of = v[0]          # the part's entries lie back to back in the order of `where`: entry -> its place in the whole
+            dst = np.repeat(indptr[where] - (np.cumsum(n_of) - n_of), n_of) + np.arange(len(v[1]), dtype=np.int64)
+            indices[dst], values[dst] = v[1], v[2]
+        return indptr, indices, values
 
     # ------------------------------------------------------------------ snapshot
     def save(self, path_of_shard) -> None:
@@ -472,6 +511,10 @@ class CollectiveShardSet:
     def get_dense_rows(self, global_rows):
         """Not in the torchrun form: the rows would have to travel from the ranks that hold them."""
         raise NotImplementedError("reading stored vectors back from a torchrun collection (CollectiveShardSet) is not implemented")
+
+    def get_sparse_rows(self, global_rows):
+        """Not in the torchrun form, as for the dense vectors."""
+        raise NotImplementedError("reading stored sparse vectors back from a torchrun collection (CollectiveShardSet) is not implemented")
 
     def _global_rows(self) -> np.ndarray:
         """Global row of every local row of this rank."""

@@ -1343,7 +1343,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11100; }  // 1.11.0: hr_mask_rows_dev, hr_get_dense_rows, hr_get_dense_rows_dev
+int hr_version(void) { return 11200; }  // 1.12.0: hr_get_sparse_rows, hr_get_sparse_rows_dev
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2488,6 +2488,118 @@ int hr_get_dense_rows(hr_index* h, const int64_t* rows, int64_t n, float* out) {
         HIP_TRY(h, hipMemcpyAsync(ws->d_ids.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, s));
         HR_TRY(get_rows_enqueue(h, s, ws->d_ids.as<int64_t>(), n, HR_F32, ws->d_q.p, h->dim, nullptr));
         HIP_TRY(h, hipMemcpyAsync(out, ws->d_q.p, out_bytes, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        return HR_OK;
+    }();
+    give_ws(h, ws);
+    return rc;
+}
+
+size_t hr_get_sparse_rows_scratch_bytes(int64_t n) {
+    if (n < 0) return 0;
+    const int64_t nb = (n + kCompactBlock - 1) / kCompactBlock;
+    return (size_t)(std::max<int64_t>(nb, 1) + 1) * 8;  // the blocks' prefix, then the total
+}
+
+namespace {
+int check_get_sparse_rows(hr_index* h, int64_t n) {
+    if (!h) return fail(nullptr, HR_EINVAL, "null handle");
+    if (h->sparse_dim == 0) return fail(h, HR_ESTATE, "handle has no sparse collection");
+    if (!h->finalized) return fail(h, HR_ESTATE, "sparse rows are read after hr_finalize (rows added since are staged on the host)");
+    if (n < 0) return fail(h, HR_EINVAL, "n must be >= 0 (got %lld)", (long long)n);
+    return HR_OK;
+}
+
+// Caller holds h->rw (shared), has h's device current and has checked the arguments.  cap == 0: sizes only.
+int get_sparse_rows_enqueue(hr_index* h, hipStream_t s, const int64_t* d_rows, int64_t n, int64_t* d_out_indptr, int32_t* d_out_idx,
+                            float* d_out_val, int64_t cap, int64_t* d_counts, void* d_scratch) {
+    const int64_t nb = (n + kCompactBlock - 1) / kCompactBlock;
+    const int64_t gather_blocks = (n + kGetSparseWaves - 1) / kGetSparseWaves;
+    if (nb > 0x7fffffffll || gather_blocks > 0x7fffffffll) return fail(h, HR_ELIMIT, "too many rows (%lld)", (long long)n);
+    if (n == 0) {
+        hipLaunchKernelGGL(get_sparse_empty_kernel, dim3(1), dim3(64), 0, s, d_out_indptr, d_counts);
+        HIP_TRY(h, hipGetLastError());
+        return HR_OK;
+    }
+    unsigned long long* block_off = (unsigned long long*)d_scratch;
+    unsigned long long* total = block_off + nb;
+    const RequestedLength len{h->s_indptr.as<int64_t>(), d_rows, h->n_sparse, h->row_offset};
+    HIP_TRY(h, hipMemsetAsync(d_counts + 1, 0, 8, s));
+    hipLaunchKernelGGL((compact_block_sums_kernel<RequestedLength>), dim3((unsigned)nb), dim3(kCompactBlock), 0, s, len, n, block_off);
+    hipLaunchKernelGGL(compact_scan_sums_kernel, dim3(1), dim3(kCompactBlock), 0, s, block_off, nb, total);
+    hipLaunchKernelGGL(get_sparse_indptr_kernel, dim3((unsigned)nb), dim3(kCompactBlock), 0, s, len, n, block_off, total, d_out_indptr,
+                       d_counts);
+    if (cap > 0 && h->n_sparse > 0)
+        hipLaunchKernelGGL(get_sparse_rows_kernel, dim3((unsigned)gather_blocks), dim3(kGetSparseWaves * 64), 0, s, h->s_indptr.as<int64_t>(),
+                           h->s_idx.as<int32_t>(), h->s_val.as<float>(), h->n_sparse, h->row_offset, d_rows, n, d_out_indptr, d_out_idx,
+                           d_out_val, cap);
+    HIP_TRY(h, hipGetLastError());
+    return HR_OK;
+}
+}  // namespace
+
+int hr_get_sparse_rows_dev(hr_index* h, const int64_t* d_rows, int64_t n, int64_t* d_out_indptr, int32_t* d_out_idx, float* d_out_val,
+                           int64_t cap, int64_t* d_counts, void* d_scratch, void* stream) {
+    if (!h) return fail(nullptr, HR_EINVAL, "null handle");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    HR_TRY(check_get_sparse_rows(h, n));
+    if (cap < 0) return fail(h, HR_EINVAL, "cap must be >= 0 (got %lld)", (long long)cap);
+    if (!d_out_indptr || !d_counts || !d_scratch || (n > 0 && !d_rows)) return fail(h, HR_EINVAL, "null buffer");
+    if (cap > 0 && (!d_out_idx || !d_out_val)) return fail(h, HR_EINVAL, "null entry buffers with cap %lld", (long long)cap);
+    if (((uintptr_t)d_rows | (uintptr_t)d_out_indptr | (uintptr_t)d_counts | (uintptr_t)d_scratch) & 7)
+        return fail(h, HR_EINVAL, "d_rows, d_out_indptr, d_counts and d_scratch must be 8-byte aligned");
+    if (((uintptr_t)d_out_idx | (uintptr_t)d_out_val) & 3) return fail(h, HR_EINVAL, "the entry buffers must be 4-byte aligned");
+    DeviceGuard dg(h->device);
+    return get_sparse_rows_enqueue(h, (hipStream_t)stream, d_rows, n, d_out_indptr, d_out_idx, d_out_val, cap, d_counts, d_scratch);
+}
+
+int hr_get_sparse_rows(hr_index* h, const int64_t* rows, int64_t n, int64_t* out_indptr, int32_t* out_idx, float* out_val, int64_t cap,
+                       int64_t* nnz_total) {
+    if (!h) return fail(nullptr, HR_EINVAL, "null handle");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    HR_TRY(check_get_sparse_rows(h, n));
+    if (cap < 0) return fail(h, HR_EINVAL, "cap must be >= 0 (got %lld)", (long long)cap);
+    if (!out_indptr || !nnz_total || (n > 0 && !rows)) return fail(h, HR_EINVAL, "null buffer");
+    if (cap > 0 && (!out_idx || !out_val)) return fail(h, HR_EINVAL, "null entry buffers with cap %lld", (long long)cap);
+    for (int64_t i = 0; i < n; ++i)   // refused before anything is read or written
+        if (rows[i] < h->row_offset || rows[i] - h->row_offset >= h->n_sparse)
+            return fail(h, HR_EINVAL, "row id %lld (entry %lld) is outside this shard's sparse rows [%lld, %lld)", (long long)rows[i],
+                        (long long)i, (long long)h->row_offset, (long long)(h->row_offset + h->n_sparse));
+    if (n == 0) {
+        out_indptr[0] = 0;
+        *nnz_total = 0;
+        return HR_OK;
+    }
+    DeviceGuard dg(h->device);
+    Workspace* ws = take_ws(h);
+    if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
+    int rc = [&]() -> int {
+        hipStream_t s = ws->stream;
+        // d_q: the output indptr [n + 1], the two counts, then the scan's scratch
+        const size_t scratch_at = (size_t)(n + 3) * 8;
+        if (ws->d_ids.ensure((size_t)n * 8) != hipSuccess || ws->d_q.ensure(scratch_at + hr_get_sparse_rows_scratch_bytes(n)) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, HR_ENOMEM, "cannot stage %lld rows", (long long)n);
+        }
+        int64_t* d_indptr = ws->d_q.as<int64_t>();
+        int64_t* d_counts = d_indptr + n + 1;
+        void* d_scratch = (char*)ws->d_q.p + scratch_at;
+        HIP_TRY(h, hipMemcpyAsync(ws->d_ids.p, rows, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        HR_TRY(get_sparse_rows_enqueue(h, s, ws->d_ids.as<int64_t>(), n, d_indptr, nullptr, nullptr, 0, d_counts, d_scratch));
+        int64_t total = 0;
+        HIP_TRY(h, hipMemcpyAsync(&total, d_counts, 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_indptr, d_indptr, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));  // the entry buffers are sized by it
+        *nnz_total = total;
+        if (total == 0 || total > cap) return HR_OK;  // the caller sizes its buffers from *nnz_total and calls again
+        if (ws->d_qidx.ensure((size_t)total * 4) != hipSuccess || ws->d_qval.ensure((size_t)total * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(h, HR_ENOMEM, "cannot stage %lld entries", (long long)total);
+        }
+        HR_TRY(get_sparse_rows_enqueue(h, s, ws->d_ids.as<int64_t>(), n, d_indptr, ws->d_qidx.as<int32_t>(), ws->d_qval.as<float>(), total,
+                                       d_counts, d_scratch));
+        HIP_TRY(h, hipMemcpyAsync(out_idx, ws->d_qidx.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipMemcpyAsync(out_val, ws->d_qval.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(h, hipStreamSynchronize(s));
         return HR_OK;
     }();

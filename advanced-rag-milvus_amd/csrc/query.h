@@ -1,7 +1,7 @@
 // Read path (Collection.query): a row mask becomes a page of row ids, and stored rows come back out of the tiles.
 //
 // Replaces Collection.query(expr, output_fields, limit, offset) of the Milvus server (pymilvus; the reference reads rows
-// back only through search hits, indexing.py:527-547).  Two kernels:
+// back only through search hits, indexing.py:527-547).  Two kernels, and the sparse rows' gather at the end of the file:
 //   mask_rows_window_kernel  the third phase of compact.h's scan with a window: of the set bits of a packed row mask, in
 //                            ascending row order, the ones numbered [offset, offset + limit) are written as 64-bit row ids.
 //                            Phases 1 and 2 are compact.h's own (compact_block_sums_kernel<KeepCount>,
@@ -123,6 +123,79 @@ __global__ void __launch_bounds__(kGetRowsWaves * 64) get_rows_kernel(const chun
                     if (e0 + j < dim) op[e0 + j] = (out_t)x[j];
             }
         }
+    }
+}
+
+// ---- stored sparse rows out of the CSR (hr_get_sparse_rows_dev) ----
+// compact.h's CSR gather with an id list in place of the row map.  The lengths of the requested rows are summed by the
+// three-phase scan (compact_block_sums_kernel<RequestedLength>, compact_scan_sums_kernel, get_sparse_indptr_kernel), so
+// every output position is an ordered prefix over the request.  An id outside the shard has length 0.
+struct RequestedLength {
+    const int64_t* indptr;
+    const int64_t* ids;
+    int64_t n_rows, row_offset;
+    // n_rows > 0 whenever indptr is read; the subtraction cannot wrap for any id the test below lets through
+    __device__ bool holds(int64_t id) const { return id >= row_offset && id - row_offset < n_rows; }
+    __device__ unsigned operator()(int64_t i) const {
+        const int64_t id = ids[i];
+        if (!holds(id)) return 0u;
+        const int64_t s = id - row_offset;
+        return (unsigned)(indptr[s + 1] - indptr[s]);
+    }
+};
+
+// n == 0: the indptr's one entry and both counts.
+__global__ void get_sparse_empty_kernel(int64_t* __restrict__ out_indptr, int64_t* __restrict__ counts) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        out_indptr[0] = 0;
+        counts[0] = 0;
+        counts[1] = 0;
+    }
+}
+
+// Phase 3: out_indptr[i] = entries of the requested rows before i, out_indptr[n] = counts[0] = all of them (*total, phase
+// 2).  counts[1], zeroed by the caller, counts the ids outside the shard: one order-independent atomic per wave.
+__global__ void __launch_bounds__(kCompactBlock) get_sparse_indptr_kernel(RequestedLength len, int64_t n,
+                                                                         const unsigned long long* __restrict__ block_off,
+                                                                         const unsigned long long* __restrict__ total,
+                                                                         int64_t* __restrict__ out_indptr, int64_t* __restrict__ counts) {
+    __shared__ unsigned long long wave_tot[kCompactBlock / 64];
+    const int64_t i = (int64_t)blockIdx.x * kCompactBlock + threadIdx.x;
+    const bool wanted = i < n;
+    const bool live = wanted && len.holds(len.ids[i]);
+    const unsigned v = live ? len(i) : 0u;
+    unsigned long long block_total;
+    const unsigned long long before = block_off[blockIdx.x] + compact_block_scan(v, wave_tot, &block_total);
+    if (wanted) out_indptr[i] = (int64_t)before;
+    if (i == 0) {
+        out_indptr[n] = (int64_t)*total;
+        counts[0] = (int64_t)*total;
+    }
+    const int n_miss = __popcll(__ballot(wanted && !live));
+    if ((threadIdx.x & 63) == 0 && n_miss) atomicAdd((unsigned long long*)&counts[1], (unsigned long long)n_miss);
+}
+
+// The entries: a wave per requested row, lanes over its entries (compact_csr_kernel's walk).  Entry e of output row i
+// goes to out_indptr[i] + e, and only when that is below cap: nothing at or past cap is touched.
+constexpr int kGetSparseWaves = 4;  // waves (requested rows) per block
+__global__ void __launch_bounds__(kGetSparseWaves * 64) get_sparse_rows_kernel(const int64_t* __restrict__ indptr, const int32_t* __restrict__ idx,
+                                                                              const float* __restrict__ val, int64_t n_rows, int64_t row_offset,
+                                                                              const int64_t* __restrict__ ids, int64_t n,
+                                                                              const int64_t* __restrict__ out_indptr, int32_t* __restrict__ out_idx,
+                                                                              float* __restrict__ out_val, int64_t cap) {
+    const int lane = threadIdx.x & 63;
+    const int64_t i = (int64_t)blockIdx.x * kGetSparseWaves + (threadIdx.x >> 6);
+    if (i >= n) return;  // wave-uniform
+    const int64_t id = ids[i];
+    if (id < row_offset || id - row_offset >= n_rows) return;  // wave-uniform: an empty row
+    const int64_t s = id - row_offset;
+    const int64_t e0 = indptr[s], d0 = out_indptr[i];
+    int64_t len = indptr[s + 1] - e0;
+    if (d0 >= cap) return;
+    if (cap - d0 < len) len = cap - d0;  // the row that cap cuts
+    for (int64_t e = lane; e < len; e += 64) {
+        out_idx[d0 + e] = idx[e0 + e];
+        out_val[d0 + e] = val[e0 + e];
     }
 }
 

@@ -531,13 +531,41 @@ HR_API int hr_filter_eval_expr_dev(const hr_filter_leaf* leaves, int n_leaves, c
  *   The call takes the shared lock while it enqueues, like the `*_dev` searches; the caller keeps appends and
  *   compaction away until `stream` has passed (hr_compact waits for the device by itself).
  * hr_get_dense_rows: the host form, fp32, out [n][dim], synchronous.  It refuses an id outside the shard with HR_EINVAL,
- *   naming the first one, and writes nothing. */
+ *   naming the first one, and writes nothing.
+ *
+ * hr_get_sparse_rows_dev: the stored sparse rows with GLOBAL ids d_rows[0 .. n) (local row + hr_set_row_offset; any
+ *   order, repeats allowed), as one CSR: d_out_indptr[0] = 0, d_out_indptr[i+1] - d_out_indptr[i] = the stored length of
+ *   row d_rows[i], its entries at d_out_idx / d_out_val [d_out_indptr[i], d_out_indptr[i+1]) — the indices ascending as
+ *   hr_add_sparse stored them, the values the stored bits.  An id outside [row_offset, row_offset + hr_num_sparse_rows)
+ *   is an empty row and is counted in d_counts[1].  d_counts[0] = the entries of all requested rows = d_out_indptr[n] =
+ *   what `cap` must be for nothing to be cut.  `cap` is the capacity of the two entry buffers, in entries: an entry whose
+ *   output position is at or beyond cap is not written and nothing past cap is touched, while d_out_indptr and d_counts
+ *   are always complete — the caller compares d_counts[0] with cap and calls again if it was too small.  cap == 0 (the
+ *   entry buffers may then be NULL) is the count pass: sizes only.  n == 0 writes d_out_indptr[0] = 0 and both counts and
+ *   launches nothing that reads the store (d_rows may be NULL).  d_scratch: hr_get_sparse_rows_scratch_bytes(n) bytes of
+ *   device memory, 8-byte aligned.  The result is a function of the inputs alone: the three-phase ordered prefix of
+ *   hr_compact over the request's row lengths decides every position, no atomic does (the missing count is an
+ *   order-independent sum).  Asynchronous on `stream`; allocates nothing and never waits for the device.  The call takes
+ *   the shared lock while it enqueues, like the `*_dev` searches; the caller keeps appends and compaction away until
+ *   `stream` has passed.  HR_ESTATE before hr_finalize (rows added since are staged on the host) and on a handle without
+ *   a sparse collection; HR_EINVAL: a NULL handle, a negative n or cap, NULL d_out_indptr / d_counts / d_scratch (or
+ *   d_rows with n > 0), NULL entry buffers with cap > 0, d_rows / d_out_indptr / d_counts / d_scratch not 8-byte or an
+ *   entry buffer not 4-byte aligned; HR_ELIMIT: n too large for one grid.  A refused call launches nothing.
+ * hr_get_sparse_rows: the host form, synchronous: out_indptr [n+1] and *nnz_total (= out_indptr[n]) are always written;
+ *   the entries only when *nnz_total <= cap — otherwise the call still returns HR_OK, and the caller sizes its buffers from
+ *   *nnz_total and calls again (cap == 0 with NULL entry buffers is the sizing call).  It refuses an id outside the shard
+ *   with HR_EINVAL, naming the first one, and writes nothing. */
 HR_API size_t hr_mask_rows_scratch_bytes(int64_t n_rows);
 HR_API int hr_mask_rows_dev(const uint8_t* d_mask, int64_t n_rows, int64_t first_row, int64_t offset, int64_t limit,
                      int64_t* d_rows, int64_t* d_counts, void* d_scratch, void* stream);
 HR_API int hr_get_dense_rows_dev(hr_index* h, const int64_t* d_rows, int64_t n, int out_dtype, void* d_out,
                           int64_t out_stride, int32_t* d_missing, void* stream);
 HR_API int hr_get_dense_rows(hr_index* h, const int64_t* rows, int64_t n, float* out);
+HR_API size_t hr_get_sparse_rows_scratch_bytes(int64_t n);
+HR_API int hr_get_sparse_rows_dev(hr_index* h, const int64_t* d_rows, int64_t n, int64_t* d_out_indptr, int32_t* d_out_idx,
+                           float* d_out_val, int64_t cap, int64_t* d_counts, void* d_scratch, void* stream);
+HR_API int hr_get_sparse_rows(hr_index* h, const int64_t* rows, int64_t n, int64_t* out_indptr, int32_t* out_idx,
+                       float* out_val, int64_t cap, int64_t* nnz_total);
 
 /* ---- BM25 document payloads (ingest) ----------------------------------------------------------------------------
  * The `encode_sparse` hook of the ingest path (reference indexing.py:629-654, called per chunk from index_chunks
