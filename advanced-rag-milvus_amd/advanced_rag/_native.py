@@ -19,6 +19,7 @@ HR_F32, HR_F16 = 0, 1
 HR_METRIC_IP, HR_METRIC_COSINE, HR_METRIC_L2 = 0, 1, 2
 HR_METHOD_SEMANTIC, HR_METHOD_SPARSE, HR_METHOD_DOMAIN = 1, 2, 4
 HR_MAX_TOPK = 256
+HR_MAX_DEEP_K = 16384   # hr_search_*_deep, hr_deep_topk_dev: offset + k
 HR_N_PHASES = 10
 PHASE_NAMES = ("prep", "dense_scan", "group_select", "refine", "topk",
                "sparse_scan", "sparse_select", "sparse_refine", "sparse_topk", "finish_fused")
@@ -151,6 +152,13 @@ _SIGNATURES = {
                                           _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_get_sparse_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int64,
                                       _c.c_void_p]),
+    "hr_search_dense_deep": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                        _c.c_void_p]),
+    "hr_search_sparse_deep": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int,
+                                         _c.c_float, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "hr_deep_topk_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
+    "hr_deep_topk_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64,
+                                    _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_set_profiling": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "hr_last_kernel_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
     "hr_last_compact_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
@@ -448,6 +456,34 @@ class ShardHandle:
                                                _vp(m), _vp(ids), _vp(sc)))
         return ids, sc
 
+    def search_dense_deep(self, q: np.ndarray, k: int, offset: int = 0, rowmask: Optional[np.ndarray] = None,
+                          d_rowmask: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """Deep search (hr_search_dense_deep): entries offset .. offset + k - 1 of the collection's exact ranking,
+        offset + k <= HR_MAX_DEEP_K.  Every row is refined: a call reads the whole shard once per query."""
+        q = np.ascontiguousarray(np.atleast_2d(q), dtype=np.float32)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != shard dim {self.dim}")
+        B = q.shape[0]
+        ids = np.empty((B, max(k, 0)), dtype=np.int64)
+        sc = np.empty((B, max(k, 0)), dtype=np.float32)
+        m = d_rowmask if d_rowmask else self._mask(rowmask, self.num_rows)
+        self._check(self._lib.hr_search_dense_deep(self._h, _vp(q), B, k, offset, _vp(m), 1 if d_rowmask else 0, _vp(ids),
+                                                   _vp(sc)))
+        return ids, sc
+
+    def search_sparse_deep(self, queries: Sequence[Tuple[Sequence[int], Sequence[float]]], k: int, offset: int = 0,
+                           drop_ratio: float = 0.0, rowmask: Optional[np.ndarray] = None,
+                           d_rowmask: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """Deep search of the sparse collection (hr_search_sparse_deep); only rows with a positive score are ranked."""
+        B = len(queries)
+        indptr, idx, val = csr_of_queries(queries)
+        ids = np.empty((B, max(k, 0)), dtype=np.int64)
+        sc = np.empty((B, max(k, 0)), dtype=np.float32)
+        m = d_rowmask if d_rowmask else self._mask(rowmask, self.num_sparse_rows)
+        self._check(self._lib.hr_search_sparse_deep(self._h, _vp(indptr), _vp(idx), _vp(val), B, k, offset, float(drop_ratio),
+                                                    _vp(m), 1 if d_rowmask else 0, _vp(ids), _vp(sc)))
+        return ids, sc
+
     def fuse_rrf(self, ids_a, ids_b, ids_c=(), wa: float = 0.7, wb: float = 0.3, wc: float = 0.2, rrf_k: int = 60):
         a = np.ascontiguousarray(ids_a, dtype=np.int64)
         b = np.ascontiguousarray(ids_b, dtype=np.int64)
@@ -588,6 +624,21 @@ def group_select_dev(d_ids: int, d_n: int, B: int, k_in: int, d_keys: int, key_r
 def mask_rows_scratch_bytes(n_rows: int) -> int:
     """hr_mask_rows_scratch_bytes: device scratch hr_mask_rows_dev needs for a mask of n_rows rows."""
     return int(load_library().hr_mask_rows_scratch_bytes(n_rows))
+
+
+def deep_topk_scratch_bytes(n: int, B: int, window: int) -> int:
+    """hr_deep_topk_scratch_bytes: device scratch hr_deep_topk_dev needs for B queries at offset + k = window."""
+    return int(load_library().hr_deep_topk_scratch_bytes(n, B, window))
+
+
+def deep_topk_dev(d_scores: int, d_rows: int, n: int, B: int, k: int, offset: int, ascending: bool, row_offset: int,
+                  d_out_ids: int, d_out_scores: int, d_scratch: int, stream: int = 0):
+    """hr_deep_topk_dev: entries offset .. offset + k - 1 of [B][n] candidates by (score desc, row asc), on device arrays."""
+    L = load_library()
+    rc = L.hr_deep_topk_dev(_vp(d_scores), _vp(d_rows), n, B, k, offset, 1 if ascending else 0, row_offset, _vp(d_out_ids),
+                            _vp(d_out_scores), _vp(d_scratch), _vp(stream) if stream else None)
+    if rc != 0:
+        _raise_global(L, rc)
 
 
 def get_sparse_rows_scratch_bytes(n: int) -> int:

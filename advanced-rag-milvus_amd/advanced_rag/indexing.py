@@ -118,6 +118,22 @@ def range_bounds(params: Optional[Dict], metric: str) -> Optional[Tuple[float, f
     return radius, range_filter
 
 
+def deep_window(top_k, offset=0) -> int:
+    """W = offset + top_k of a search request, the depth of the ranking it reads.  top_k >= 1 and offset >= 0 are integers
+    (bool and floats are refused, as group_size refuses them) and W <= QUERY_MAX_WINDOW, Milvus' cap on offset + limit.
+    W <= HR_MAX_TOPK is served by the plain search, a deeper window by the deep search."""
+    for name, v in (("top_k", top_k), ("offset", offset)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if top_k < 1:
+        raise ValueError(f"top_k must be >= 1, got {top_k}")
+    if offset < 0:
+        raise ValueError(f"offset must be >= 0, got {offset}")
+    if int(top_k) + int(offset) > QUERY_MAX_WINDOW:
+        raise ValueError(f"a search takes offset + top_k <= {QUERY_MAX_WINDOW}, got offset={offset}, top_k={top_k}")
+    return int(top_k) + int(offset)
+
+
 class ShardCollection:
     """What `manager.collections[name]` holds: a named view of one ShardSet (the
     collection's shard handles, one per device) with the handful of Collection methods the reference calls
@@ -208,8 +224,9 @@ class MilvusIndexManager:
         # not proven by the window that showed it); group_fill_rounds: the windows that phase searched
         # queries: query() calls answered; query_device: those whose page came from hr_mask_rows_dev (mask never left HBM)
         # search_by_ids: search_by_ids() calls whose ids were resolved and whose stored vectors were fetched
+        # deep_searches: searches with offset + top_k > HR_MAX_TOPK, answered by the deep forms (a full refine of the shard)
         self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
-                      "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0}
+                      "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0, "deep_searches": 0}
         self._stats_lock = threading.Lock()    # the loop runs in worker threads and in the front's thread at once
         self._deleted: Optional[np.ndarray] = None
         self._mask_cache: Dict[Any, Optional[np.ndarray]] = {}   # (expr, rows, delete epoch) -> boolean row filter
@@ -1242,6 +1259,49 @@ class MilvusIndexManager:
         return self._format_hits(*self._search_lists_blocking(query, collection_name, top_k, filters, params, group_by_field,
                                                               bounds, group_size))
 
+    def _deep_request(self, coll, top_k, offset, search_params: Optional[Dict], group_by_field: Optional[str],
+                      group_size: int) -> int:
+        """W of a request that names an offset or a top_k beyond HR_MAX_TOPK; refuses what a deep window (W > HR_MAX_TOPK)
+        is not built for.  Nothing is launched for a refused request."""
+        window = deep_window(top_k, offset)
+        if window <= HR_MAX_TOPK:
+            return window
+        if group_by_field is not None or group_size != 1:
+            raise ValueError(f"a deep window (offset + top_k = {window} > HR_MAX_TOPK = {HR_MAX_TOPK}) cannot be combined "
+                             "with group_by_field")
+        if range_bounds(self._search_params(coll, search_params), coll.metric if coll.kind != "sparse" else "IP") is not None:
+            raise ValueError(f"a deep window (offset + top_k = {window} > HR_MAX_TOPK = {HR_MAX_TOPK}) cannot be combined "
+                             "with range search (radius / range_filter)")
+        if hasattr(coll.handle, "round"):
+            raise NotImplementedError("deep search (offset + top_k > HR_MAX_TOPK) is not built for the torchrun form "
+                                      "(CollectiveShardSet)")
+        return window
+
+    def _deep_blocking(self, query_embedding, collection_name: str, top_k: int, offset: int, filters: Optional[str],
+                       search_params: Optional[Dict]) -> List[Dict[str, Any]]:
+        """Entries offset .. offset + top_k - 1 of ONE query's exact ranking through the deep forms (hr_search_*_deep): every
+        row of the collection is refined, so the call costs a read of the whole shard.  Only the top_k hits are formatted."""
+        coll = self.collections[collection_name]
+        params = self._search_params(coll, search_params)
+        drop = float((params.get("params") or params).get("drop_ratio_search", 0.0))
+        query = self._as_sparse_payload(query_embedding) if coll.kind == "sparse" else query_embedding
+        self._count("deep_searches")
+        if getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and self._filters_on_device() is not None:
+            h = coll.handle.first    # one local GPU shard: the mask never leaves the device
+            d_mask = self._device_row_mask(filters, coll.kind)
+            ptr = d_mask.data_ptr() if d_mask is not None else 0
+            if coll.kind == "sparse":
+                ids, sc = h.search_sparse_deep([query], top_k, offset, drop, None, ptr)
+            else:
+                ids, sc = h.search_dense_deep(dense_rows_host([query]), top_k, offset, None, ptr)
+        else:
+            mask = self._row_mask(filters)
+            if coll.kind == "sparse":
+                ids, sc = coll.handle.search_sparse_deep([query], top_k, offset, drop, mask)
+            else:
+                ids, sc = coll.handle.search_dense_deep(dense_rows_host([query]), top_k, offset, mask)
+        return self._format_hits(ids[0], sc[0])
+
     @staticmethod
     def _search_dense_device(handle, q_dev, top_k: int):
         """Query already in HBM (device-resident embedding cache): device form, no upload; an unproven
@@ -1295,8 +1355,11 @@ class MilvusIndexManager:
 
     async def search(self, query_embedding, collection_name: str, top_k: int = 20, filters: Optional[str] = None,
                      search_params: Optional[Dict] = None, *, group_by_field: Optional[str] = None,
-                     group_size: int = 1, strict_group_size: Optional[bool] = None) -> List[Dict[str, Any]]:
-        """Collection.search (reference indexing.py:503-525).  group_by_field=F (pymilvus' grouping search): the best row
+                     group_size: int = 1, strict_group_size: Optional[bool] = None, offset: int = 0) -> List[Dict[str, Any]]:
+        """Collection.search (reference indexing.py:503-525).  offset=o: hits o .. o + top_k - 1 of the ranking, with
+        W = o + top_k <= QUERY_MAX_WINDOW (deep_window).  W <= HR_MAX_TOPK is the plain search at top_k = W with the first o
+        hits cut; a deeper window takes the deep search (exact, a full read of the shard per query; not with
+        group_by_field, range search or the torchrun form).  group_by_field=F (pymilvus' grouping search): the best row
         of each of the top_k best groups of field F, in ranking order — exact at any depth; fewer groups than top_k give a
         shorter list.  F is an integer or a string field of the schema (chunk_index, token_count, doc_id, id / chunk_id,
         timestamp).  group_size=g > 1 is served by a manager created with group_members=True: up to g rows of each of the
@@ -1308,6 +1371,23 @@ class MilvusIndexManager:
         if collection_name not in self.collections:
             raise ValueError(f"Collection {collection_name} not found")
         coll = self.collections[collection_name]
+        paged = isinstance(offset, (bool, np.bool_)) or not isinstance(offset, (int, np.integer)) or offset != 0
+        if paged or (isinstance(top_k, (int, np.integer)) and top_k > HR_MAX_TOPK):
+            window = self._deep_request(coll, top_k, offset, search_params, group_by_field, group_size)
+            if window > HR_MAX_TOPK:
+                try:
+                    return await asyncio.wait_for(
+                        asyncio.to_thread(self._deep_blocking, query_embedding, collection_name, int(top_k), int(offset), filters,
+                                          search_params),
+                        timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
+                except asyncio.TimeoutError:
+                    logging.error("shard search timeout for collection %s", collection_name)
+                    raise Exception(f"Search timeout for collection {collection_name}")
+            if group_by_field is not None:
+                raise ValueError("offset cannot be combined with group_by_field")
+            # the plain search at depth W (through the batching front as any other), the first `offset` hits cut
+            hits = await self.search(query_embedding, collection_name, window, filters, search_params)
+            return hits[int(offset):]
         front = self._coalescer(coll)
         try:
             if front is not None:

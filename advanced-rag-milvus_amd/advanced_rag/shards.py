@@ -69,6 +69,15 @@ def merge_lists(ids: Sequence[np.ndarray], scores: Sequence[np.ndarray], k: int,
     return out_ids, out_sc
 
 
+def merge_deep_lists(ids: Sequence[np.ndarray], scores: Sequence[np.ndarray], top_k: int, offset: int = 0,
+                     ascending: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """Per-shard deep lists (each [B, W] at depth W = offset + top_k with offset 0, global rows, -1 padded) -> entries
+    offset .. offset + top_k - 1 of their merge by (score desc or distance asc, row asc), [B, top_k], -1 / 0 padded.  A row
+    of the collection's first W is among its own shard's first W, so the merge of the shards' lists is the collection's."""
+    m_ids, m_sc = merge_lists(ids, scores, offset + top_k, ascending)
+    return np.ascontiguousarray(m_ids[:, offset:]), np.ascontiguousarray(m_sc[:, offset:])
+
+
 class PartialAppend(RuntimeError):
     """A multi-shard append failed after some pieces had gone in: global rows [base, end) exist in the shards."""
 
@@ -281,6 +290,44 @@ class ShardSet:
                 return empty_lists(len(queries), k)
             return self.handles[s].search_sparse(queries, k, drop_ratio, *self._local_mask(s, keep))
         return self._gather(self._fan_out(one), k)
+
+    @staticmethod
+    def _deep_of(handle, name: str):
+        """A handle's deep form at depth W, offset 0.  A libhbmrag shard has one; a test stand-in that ranks on the host takes
+        any k through its plain form."""
+        deep = getattr(handle, name + "_deep", None)
+        if deep is not None:
+            return lambda x, W, *rest: deep(x, W, 0, *rest)
+        return getattr(handle, name)
+
+    def _deep(self, name: str, rows_attr: str, B: int, k: int, offset: int, ascending: bool, call):
+        """Every shard's list at depth W = offset + k (call(form, s) -> its lists), merged and cut on the host."""
+        W = offset + k
+
+        def one(s):
+            if getattr(self.handles[s], rows_attr) == 0:
+                return empty_lists(B, W)
+            return call(self._deep_of(self.handles[s], name), s)
+        parts = self._fan_out(one)
+        ids = [li if self.n_shards == 1 else to_global(li, self.rows_of[s]) for s, (li, _) in enumerate(parts)]
+        return merge_deep_lists(ids, [sc for _, sc in parts], k, offset, ascending)
+
+    def search_dense_deep(self, q: np.ndarray, k: int, offset: int = 0, keep: Optional[np.ndarray] = None):
+        """Deep search (offset + k <= HR_MAX_DEEP_K): entries offset .. offset + k - 1 of the collection's exact ranking.
+        One libhbmrag shard cuts the window on the device; several shards return their lists at depth offset + k, merged by
+        (score desc or distance asc, global row asc) and cut on the host."""
+        h = self.handles[0]
+        if self.n_shards == 1 and hasattr(h, "search_dense_deep") and h.num_rows:
+            return h.search_dense_deep(q, k, offset, *self._local_mask(0, keep))
+        return self._deep("search_dense", "num_rows", np.atleast_2d(q).shape[0], k, offset, self.dense_ascending,
+                          lambda form, s: form(q, offset + k, *self._local_mask(s, keep)))
+
+    def search_sparse_deep(self, queries, k: int, offset: int = 0, drop_ratio: float = 0.0, keep: Optional[np.ndarray] = None):
+        h = self.handles[0]
+        if self.n_shards == 1 and hasattr(h, "search_sparse_deep") and h.num_sparse_rows:
+            return h.search_sparse_deep(queries, k, offset, drop_ratio, *self._local_mask(0, keep))
+        return self._deep("search_sparse", "num_sparse_rows", len(queries), k, offset, False,
+                          lambda form, s: form(queries, offset + k, drop_ratio, *self._local_mask(s, keep)))
 
     # ------------------------------------------------------------------ read path
     def _locate(self, global_rows):

@@ -26,6 +26,7 @@
 #include "common.h"
 #include "attention.h"
 #include "compact.h"
+#include "deep.h"
 #include "encoder_layer.h"
 #include "scan_plan.h"
 #include "dense.h"
@@ -708,15 +709,22 @@ FinishMod finish_mod(const hr_index* h, const FinishSide& f) {
     }
     return m;
 }
-int launch_refine(hr_index* h, hipStream_t s, int B, const FinishSide& f) {
-    Workspace* ws = f.ws;
+// Where a refine reads its candidate groups and leaves its slots: the workspace's buffers (the finishing chain), or
+// buffers the call owns (deep search).
+struct RefineBufs {
+    const double* qn2;     // dense: [B] squared query norms
+    const int32_t* cand;   // [B][C]
+    float* cscore;         // [B][C * GR]
+    int32_t* crow;
+};
+int launch_refine(hr_index* h, hipStream_t s, int B, const FinishSide& f, const RefineBufs& b) {
     if (!f.sparse) {
         const bool f16 = h->dtype == HR_F16, l2 = h->metric == HR_METRIC_L2;
         auto kern = f16 ? (l2 ? refine_dense_kernel<_Float16, true> : refine_dense_kernel<_Float16, false>)
                         : (l2 ? refine_dense_kernel<float, true> : refine_dense_kernel<float, false>);
         hipLaunchKernelGGL(kern, dim3((f.C * f.GR + 63) / 64, B), dim3(64), 0, s, h->tiles.as<chunk_t>(), h->KT, (int)h->dim,
-                           f.d_q, ws->qn2.as<double>(), h->norm2.as<double>(), f.mask, ws->cand.as<int32_t>(), f.C, f.GR,
-                           h->n_rows, h->metric, ws->cscore.as<float>(), ws->crow.as<int32_t>(), f.range_bounds);
+                           f.d_q, b.qn2, h->norm2.as<double>(), f.mask, b.cand, f.C, f.GR,
+                           h->n_rows, h->metric, b.cscore, b.crow, f.range_bounds);
     } else {
         // 64 docs per wave: shorter chains finish this kernel sooner (0.60 -> 0.55 ms at 10M docs, 0.168 -> 0.136 ms at 1.25M
         // with 16) but the step does not gain — the kernel runs beside the scans, and what it takes from the HBM sooner they
@@ -727,11 +735,14 @@ int launch_refine(hr_index* h, hipStream_t s, int B, const FinishSide& f) {
         hipLaunchKernelGGL(hashed ? refine_sparse_kernel<true> : refine_sparse_kernel<false>,
                            dim3((f.C * f.GR + 4 * dpw - 1) / (4 * dpw), B), dim3(256), lds, s, h->s_indptr.as<int64_t>(),
                            h->s_idx.as<int32_t>(), h->s_val.as<float>(), f.q_ptr, f.q_idx, f.q_val, f.mask,
-                           ws->cand.as<int32_t>(), f.C, f.GR, h->n_sparse, f.stride, dpw, ws->cscore.as<float>(),
-                           ws->crow.as<int32_t>());
+                           b.cand, f.C, f.GR, h->n_sparse, f.stride, dpw, b.cscore, b.crow);
     }
     HIP_TRY(h, hipGetLastError());
     return HR_OK;
+}
+int launch_refine(hr_index* h, hipStream_t s, int B, const FinishSide& f) {
+    Workspace* ws = f.ws;
+    return launch_refine(h, s, B, f, {ws->qn2.as<double>(), ws->cand.as<int32_t>(), ws->cscore.as<float>(), ws->crow.as<int32_t>()});
 }
 
 enum { PHASE_SCAN = 1, PHASE_FINISH = 2, PHASE_PREP = 4, PHASE_ALL = 7 };
@@ -1343,7 +1354,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11200; }  // 1.12.0: hr_get_sparse_rows, hr_get_sparse_rows_dev
+int hr_version(void) { return 11300; }  // 1.13.0: hr_search_dense_deep, hr_search_sparse_deep, hr_deep_topk_dev
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2863,18 +2874,35 @@ int hr_search_dense_dmask(hr_index* h, const float* q, int B, int k, const uint8
     return search_dense_host(h, q, B, k, d_rowmask, true, out_ids, out_scores);
 }
 
-static int search_sparse_host(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B, int k,
-                              float drop_ratio, const uint8_t* rowmask, bool mask_on_device, int64_t* out_ids,
-                              float* out_scores) {
-    HR_TRY(check_search_args(h, B, k, false));
-    if (!q_indptr || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
-    if (!(drop_ratio >= 0.f && drop_ratio < 1.f)) return fail(h, HR_EINVAL, "drop_ratio must be in [0,1)");
-    // Host prep: drop the floor(drop_ratio*nnz) smallest-|value| entries (ties:
-    // the later entry goes first), then order by index.
-    std::vector<int64_t> ptr(B + 1, 0);
+// The sparse host forms' query prep: the checked, dropped and index-ordered queries as one CSR, and how to stage it.
+struct SparseQueries {
+    std::vector<int64_t> ptr;
     std::vector<int32_t> idx;
     std::vector<float> val;
     int max_nnz = 0;
+    int stage(hr_index* h, Workspace* ws, hipStream_t s) const {
+        const size_t B1 = ptr.size(), nnz = idx.size();
+        HIP_TRY(h, ws->d_qptr.ensure(B1 * 8));
+        HIP_TRY(h, ws->d_qidx.ensure(std::max<size_t>(nnz, 1) * 4));
+        HIP_TRY(h, ws->d_qval.ensure(std::max<size_t>(nnz, 1) * 4));
+        HIP_TRY(h, hipMemcpyAsync(ws->d_qptr.p, ptr.data(), B1 * 8, hipMemcpyHostToDevice, s));
+        if (nnz) {
+            HIP_TRY(h, hipMemcpyAsync(ws->d_qidx.p, idx.data(), nnz * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(h, hipMemcpyAsync(ws->d_qval.p, val.data(), nnz * 4, hipMemcpyHostToDevice, s));
+        }
+        return HR_OK;
+    }
+};
+static int prep_sparse_queries(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B,
+                               float drop_ratio, SparseQueries* out) {
+    if (!(drop_ratio >= 0.f && drop_ratio < 1.f)) return fail(h, HR_EINVAL, "drop_ratio must be in [0,1)");
+    // Host prep: drop the floor(drop_ratio*nnz) smallest-|value| entries (ties:
+    // the later entry goes first), then order by index.
+    std::vector<int64_t>& ptr = out->ptr;
+    std::vector<int32_t>& idx = out->idx;
+    std::vector<float>& val = out->val;
+    int& max_nnz = out->max_nnz;
+    ptr.assign(B + 1, 0);
     for (int b = 0; b < B; ++b) {
         const int64_t e0 = q_indptr[b], e1 = q_indptr[b + 1];
         if (e1 < e0) return fail(h, HR_EINVAL, "query indptr not monotone");
@@ -2905,24 +2933,22 @@ static int search_sparse_host(hr_index* h, const int64_t* q_indptr, const int32_
         max_nnz = std::max(max_nnz, (int)keep.size());
     }
     if (max_nnz > HR_MAX_QUERY_NNZ) return fail(h, HR_ELIMIT, "query nnz %d exceeds HR_MAX_QUERY_NNZ", max_nnz);
+    return HR_OK;
+}
 
+static int search_sparse_host(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B, int k,
+                              float drop_ratio, const uint8_t* rowmask, bool mask_on_device, int64_t* out_ids,
+                              float* out_scores) {
+    HR_TRY(check_search_args(h, B, k, false));
+    if (!q_indptr || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
+    SparseQueries sq;
+    HR_TRY(prep_sparse_queries(h, q_indptr, q_idx, q_val, B, drop_ratio, &sq));
     return search_host(
         h, B, k, &hr_index::n_sparse, rowmask, mask_on_device, out_ids, out_scores,
-        [&](Workspace* ws, hipStream_t s) {
-            const size_t nnz = idx.size();
-            HIP_TRY(h, ws->d_qptr.ensure((size_t)(B + 1) * 8));
-            HIP_TRY(h, ws->d_qidx.ensure(std::max<size_t>(nnz, 1) * 4));
-            HIP_TRY(h, ws->d_qval.ensure(std::max<size_t>(nnz, 1) * 4));
-            HIP_TRY(h, hipMemcpyAsync(ws->d_qptr.p, ptr.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, s));
-            if (nnz) {
-                HIP_TRY(h, hipMemcpyAsync(ws->d_qidx.p, idx.data(), nnz * 4, hipMemcpyHostToDevice, s));
-                HIP_TRY(h, hipMemcpyAsync(ws->d_qval.p, val.data(), nnz * 4, hipMemcpyHostToDevice, s));
-            }
-            return (int)HR_OK;
-        },
+        [&](Workspace* ws, hipStream_t s) { return sq.stage(h, ws, s); },
         [&](Workspace* ws, hipStream_t s, const uint8_t* d_mask, const OutLists& out, int C) {
             return sparse_search_enqueue(h, ws, s, ws->d_qptr.as<int64_t>(), ws->d_qidx.as<int32_t>(),
-                                         ws->d_qval.as<float>(), B, max_nnz, k, d_mask, out, C);
+                                         ws->d_qval.as<float>(), B, sq.max_nnz, k, d_mask, out, C);
         });
 }
 
@@ -2933,6 +2959,231 @@ int hr_search_sparse(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx,
 int hr_search_sparse_dmask(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B, int k,
                            float drop_ratio, const uint8_t* d_rowmask, int64_t* out_ids, float* out_scores) {
     return search_sparse_host(h, q_indptr, q_idx, q_val, B, k, drop_ratio, d_rowmask, true, out_ids, out_scores);
+}
+
+// ---- deep search (deep.h) ----------------------------------------------------------------------------------------
+namespace {
+inline size_t deep_align(size_t b) { return (b + 255) / 256 * 256; }
+inline size_t deep_zeroed_bytes(int B) { return deep_align((size_t)B * sizeof(DeepState)) + (size_t)B * kDeepPasses * 256 * sizeof(unsigned); }
+inline int deep_sort_slots(int W) {   // keys the sort holds in LDS: W padded to a power of two, 64 at least
+    int P = 64;
+    while (P < W) P <<= 1;
+    return P;
+}
+int check_deep_window(const hr_index* h, int k, int offset) {
+    if (k < 1) return fail(h, HR_EINVAL, "k must be positive (got %d)", k);
+    if (offset < 0) return fail(h, HR_EINVAL, "offset must not be negative (got %d)", offset);
+    if ((int64_t)k + offset > HR_MAX_DEEP_K)
+        return fail(h, HR_ELIMIT, "k + offset = %lld exceeds HR_MAX_DEEP_K=%d", (long long)k + offset, HR_MAX_DEEP_K);
+    return HR_OK;
+}
+}  // namespace
+
+size_t hr_deep_topk_scratch_bytes(int64_t n, int B, int window) {
+    (void)n;   // the per-query tables do not grow with the candidates
+    if (B < 1 || window < 1) return 0;
+    return deep_zeroed_bytes(B) + (size_t)B * window * sizeof(unsigned long long);
+}
+
+int hr_deep_topk_dev(const float* d_scores, const int32_t* d_rows, int64_t n, int B, int k, int offset, int ascending,
+                     int64_t row_offset, int64_t* d_out_ids, float* d_out_scores, void* d_scratch, void* stream) {
+    HR_TRY(check_deep_window(nullptr, k, offset));
+    if (n < 0) return fail(nullptr, HR_EINVAL, "n must not be negative");
+    if (B < 1) return fail(nullptr, HR_EINVAL, "batch size must be positive (got %d)", B);
+    if (B > 65535) return fail(nullptr, HR_ELIMIT, "batch size %d exceeds one grid (65535)", B);
+    if (n > 0x7fffffffll) return fail(nullptr, HR_ELIMIT, "n exceeds the int32 row range");
+    if (!d_out_ids || !d_out_scores) return fail(nullptr, HR_EINVAL, "null buffer");
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        HIP_TRY(nullptr, hipMemsetAsync(d_out_ids, 0xFF, (size_t)B * k * sizeof(int64_t), s));
+        HIP_TRY(nullptr, hipMemsetAsync(d_out_scores, 0, (size_t)B * k * sizeof(float), s));
+        return HR_OK;
+    }
+    if (!d_scores || !d_rows || !d_scratch) return fail(nullptr, HR_EINVAL, "null buffer");
+    if ((uintptr_t)d_scratch % 8) return fail(nullptr, HR_EINVAL, "scratch buffer not 8-byte aligned");
+    const int W = k + offset;
+    DeepArgs a{};
+    a.score = d_scores;
+    a.row = d_rows;
+    a.n = n;
+    a.W = W;
+    char* base = static_cast<char*>(d_scratch);
+    a.state = reinterpret_cast<DeepState*>(base);
+    a.hist = reinterpret_cast<unsigned*>(base + deep_align((size_t)B * sizeof(DeepState)));
+    a.keys = reinterpret_cast<unsigned long long*>(base + deep_zeroed_bytes(B));
+    HIP_TRY(nullptr, hipMemsetAsync(base, 0, deep_zeroed_bytes(B), s));
+    // blocks per query: 8 keys per thread at least, and no more than a few rounds of the chip
+    const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>((n + kDeepHistThreads * 8 - 1) / (kDeepHistThreads * 8), 1),
+                                                        std::max(1, 4096 / B));
+    for (int pass = 0; pass < kDeepPasses; ++pass) {
+        hipLaunchKernelGGL(deep_hist_kernel, dim3(blocks, B), dim3(kDeepHistThreads), 0, s, a, pass);
+        hipLaunchKernelGGL(deep_pick_kernel, dim3(B), dim3(64), 0, s, a, pass);
+    }
+    hipLaunchKernelGGL(deep_gather_kernel, dim3(blocks, B), dim3(kDeepHistThreads), 0, s, a);
+    HIP_TRY(nullptr, hipGetLastError());
+    const int P = deep_sort_slots(W);
+    if ((size_t)P * sizeof(unsigned long long) > 48 * 1024)   // per device, idempotent: set where the default does not reach
+        HIP_TRY(nullptr, hipFuncSetAttribute((const void*)deep_sort_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             deep_sort_slots(HR_MAX_DEEP_K) * (int)sizeof(unsigned long long)));
+    hipLaunchKernelGGL(deep_sort_kernel, dim3(B), dim3(kDeepSortThreads), (size_t)P * sizeof(unsigned long long), s, a, P, k, offset,
+                       ascending != 0, row_offset, d_out_ids, d_out_scores);
+    HIP_TRY(nullptr, hipGetLastError());
+    return HR_OK;
+}
+
+namespace {
+constexpr size_t kDeepCandidateCap = (size_t)512 << 20;   // transient candidate arrays of one pass of queries
+
+// What the two deep host forms share, after their own argument checks and query prep.  stage(ws, s) uploads the queries
+// and runs their device prep; refine(s, c0, nq, d_mask, C, GR, bufs) refines all C candidate groups for queries
+// c0 .. c0 + nq - 1 into bufs.  Every buffer that grows with the shard is a local of this call.
+extern "C++" template <typename Stage, typename Refine>
+int deep_host(hr_index* h, int B, int k, int offset, int64_t hr_index::*rows, bool ascending, int ph_refine, int ph_topk,
+              const uint8_t* rowmask, bool mask_on_device, int64_t* out_ids, float* out_scores, Stage stage, Refine refine) {
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    DeviceGuard dg(h->device);
+    const int64_t n_rows = h->*rows;
+    if (n_rows == 0) {
+        std::fill(out_ids, out_ids + (size_t)B * k, (int64_t)-1);
+        std::fill(out_scores, out_scores + (size_t)B * k, 0.f);
+        return HR_OK;
+    }
+    const int GR = group_rows_for(h, n_rows);
+    const int64_t n_groups = (n_rows + GR - 1) / GR;
+    const int64_t C64 = round_up(n_groups, 16), n_slots = C64 * GR;   // every group, as the last rung of next_candidate_count
+    if (n_slots > 0x7fffffffll) return fail(h, HR_ELIMIT, "shard too large for a full refine");
+    const int C = (int)C64;
+    const size_t per_query = (size_t)n_slots * 8 + (size_t)C * 4;
+    int Bp = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, kDeepCandidateCap / per_query));
+    DevBuf cscore, crow, cand, acut, scratch, d_ids, d_scores;
+    for (;; Bp = (Bp + 1) / 2) {
+        const bool ok = cscore.alloc_exact((size_t)Bp * n_slots * 4) == hipSuccess &&
+                        crow.alloc_exact((size_t)Bp * n_slots * 4) == hipSuccess &&
+                        cand.alloc_exact((size_t)Bp * C * 4) == hipSuccess;
+        if (ok) break;
+        (void)hipGetLastError();
+        cscore.release(), crow.release(), cand.release();
+        if (Bp == 1)
+            return fail(h, HR_ENOMEM, "deep search: %zu bytes of candidate arrays for one query do not fit", per_query);
+    }
+    if (acut.alloc_exact((size_t)Bp * 4) != hipSuccess || d_ids.alloc_exact((size_t)B * k * 8) != hipSuccess ||
+        d_scores.alloc_exact((size_t)B * k * 4) != hipSuccess ||
+        scratch.alloc_exact(hr_deep_topk_scratch_bytes(n_slots, Bp, k + offset)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, HR_ENOMEM, "deep search: list buffers do not fit");
+    }
+    PooledWs pooled(h);
+    Workspace* ws = pooled.w;
+    if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
+    hipStream_t s = ws->stream;
+    HR_TRY(stage(ws, s));
+    const uint8_t* d_mask = mask_on_device ? rowmask : nullptr;
+    if (rowmask && !mask_on_device) {
+        const size_t mb = (size_t)(n_rows + 7) / 8;
+        HIP_TRY(h, ws->d_mask.ensure(mb));
+        HIP_TRY(h, hipMemcpyAsync(ws->d_mask.p, rowmask, mb, hipMemcpyHostToDevice, s));
+        d_mask = ws->d_mask.as<uint8_t>();
+    }
+    {   // n_groups <= C: select_groups_block writes the identity list (and -1 behind the last group); no maxima are read
+        GroupSelPair p{};
+        p.n = 1;
+        GroupSelArgs& g = p.m[0];
+        g.n_groups = n_groups;
+        g.n_buckets = bucket_count(n_groups);
+        g.C = C;
+        g.cand = cand.as<int32_t>();
+        g.a_cut = acut.as<float>();
+        HR_TRY(launch_group_select_pair(h, s, Bp, p));
+    }
+    int rc = HR_OK;
+    for (int c0 = 0; c0 < B && rc == HR_OK; c0 += Bp) {
+        const int nq = std::min(Bp, B - c0);
+        {
+            Span sp(h, s, ph_refine);
+            rc = refine(s, c0, nq, d_mask, C, GR, RefineBufs{nullptr, cand.as<int32_t>(), cscore.as<float>(), crow.as<int32_t>()});
+        }
+        if (rc != HR_OK) break;
+        Span sp(h, s, ph_topk);
+        rc = hr_deep_topk_dev(cscore.as<float>(), crow.as<int32_t>(), n_slots, nq, k, offset, ascending, h->row_offset,
+                              d_ids.as<int64_t>() + (size_t)c0 * k, d_scores.as<float>() + (size_t)c0 * k, scratch.p, s);
+        if (rc != HR_OK) rc = fail(h, rc, "deep selection: %s", std::string(g_last_error).c_str());
+    }
+    if (rc != HR_OK) {
+        (void)hipStreamSynchronize(s);   // the locals are freed on return
+        return rc;
+    }
+    HIP_TRY(h, hipMemcpyAsync(out_ids, d_ids.p, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out_scores, d_scores.p, (size_t)B * k * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return HR_OK;
+}
+
+int check_deep_args(hr_index* h, int B, int k, int offset, bool dense) {
+    if (!h) return fail(nullptr, HR_EINVAL, "null handle");
+    if (B <= 0) return fail(h, HR_EINVAL, "batch size must be positive (got %d)", B);
+    HR_TRY(check_deep_window(h, k, offset));
+    if (!h->finalized) return fail(h, HR_ESTATE, "search before hr_finalize");
+    if (dense && h->dim == 0) return fail(h, HR_ESTATE, "handle has no dense collection");
+    if (!dense && h->sparse_dim == 0) return fail(h, HR_ESTATE, "handle has no sparse collection");
+    return HR_OK;
+}
+}  // namespace
+
+int hr_search_dense_deep(hr_index* h, const float* q, int B, int k, int offset, const uint8_t* rowmask, int mask_on_device,
+                         int64_t* out_ids, float* out_scores) {
+    HR_TRY(check_deep_args(h, B, k, offset, true));
+    if (!q || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
+    for (int64_t i = 0; i < (int64_t)B * h->dim; ++i)
+        if (!std::isfinite(q[i])) return fail(h, HR_EINVAL, "non-finite value in query %lld", (long long)(i / h->dim));
+    Workspace* held = nullptr;
+    return deep_host(
+        h, B, k, offset, &hr_index::n_rows, h->metric == HR_METRIC_L2, PH_REFINE, PH_TOPK, rowmask, mask_on_device != 0, out_ids,
+        out_scores,
+        [&](Workspace* ws, hipStream_t s) {
+            held = ws;
+            HIP_TRY(h, ws->d_q.ensure((size_t)B * h->dim * 4));
+            HIP_TRY(h, hipMemcpyAsync(ws->d_q.p, q, (size_t)B * h->dim * 4, hipMemcpyHostToDevice, s));
+            // the query prep of a plain search (squared norms for the refine); no scan, no finish
+            return dense_search_enqueue(h, ws, s, ws->d_q.as<float>(), B, 1, nullptr, OutLists{nullptr, nullptr, nullptr},
+                                        candidate_groups_for_k(1), nullptr, PHASE_PREP);
+        },
+        [&](hipStream_t s, int c0, int nq, const uint8_t* d_mask, int C, int GR, RefineBufs b) {
+            FinishSide f{};
+            f.GR = GR;
+            f.C = C;
+            f.mask = d_mask;
+            f.d_q = held->d_q.as<float>() + (size_t)c0 * h->dim;
+            b.qn2 = held->qn2.as<double>() + c0;
+            return launch_refine(h, s, nq, f, b);
+        });
+}
+
+int hr_search_sparse_deep(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B, int k,
+                          int offset, float drop_ratio, const uint8_t* rowmask, int mask_on_device, int64_t* out_ids,
+                          float* out_scores) {
+    HR_TRY(check_deep_args(h, B, k, offset, false));
+    if (!q_indptr || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
+    SparseQueries sq;
+    HR_TRY(prep_sparse_queries(h, q_indptr, q_idx, q_val, B, drop_ratio, &sq));
+    Workspace* held = nullptr;
+    return deep_host(
+        h, B, k, offset, &hr_index::n_sparse, false, PH_SREFINE, PH_STOPK, rowmask, mask_on_device != 0, out_ids, out_scores,
+        [&](Workspace* ws, hipStream_t s) {
+            held = ws;
+            return sq.stage(h, ws, s);
+        },
+        [&](hipStream_t s, int c0, int nq, const uint8_t* d_mask, int C, int GR, RefineBufs b) {
+            FinishSide f{};
+            f.sparse = true;
+            f.GR = GR;
+            f.C = C;
+            f.mask = d_mask;
+            f.q_ptr = held->d_qptr.as<int64_t>() + c0;   // the entries are positions in the whole batch's arrays
+            f.q_idx = held->d_qidx.as<int32_t>();
+            f.q_val = held->d_qval.as<float>();
+            f.stride = (int)round_up(std::max(sq.max_nnz, 1), 64);
+            return launch_refine(h, s, nq, f, b);
+        });
 }
 
 int hr_fuse_rrf(hr_index* h, const int64_t* ids_a, int na, const int64_t* ids_b, int nb, const int64_t* ids_c, int nc,

@@ -220,6 +220,39 @@ HR_API int hr_search_sparse_dmask(hr_index* h, const int64_t* q_indptr, const in
                            int B, int k, float drop_ratio, const uint8_t* d_rowmask,
                            int64_t* out_ids, float* out_scores);
 
+/* ---- deep search: top_k + offset up to HR_MAX_DEEP_K rows per query, exact ---------------------------------------
+ * R = the collection's ranking of one query: the rows that pass the mask (sparse: with a positive score), by canonical
+ * score descending (L2: distance ascending), then row ascending.  The deep list is R[offset : offset + k]: global ids
+ * and canonical fp32 scores, padded with -1 / 0 when R is shorter.  1 <= k, 0 <= offset (HR_EINVAL otherwise),
+ * W = offset + k <= HR_MAX_DEEP_K (HR_ELIMIT beyond).  With offset = 0 the first HR_MAX_TOPK entries are, bit for
+ * bit, the list hr_search_dense / hr_search_sparse return.
+ *   How: no scan and no proof.  Every row of the shard is refined in the canonical fp64 arithmetic (the last rung of
+ *     the host forms' escalation ladder) and a grid-wide radix select + one LDS sort per query take the window, so the
+ *     list is exact by construction and a call costs a full read of the shard per query whatever W is.
+ *   Host arrays in and out, synchronous.  rowmask / mask_on_device as in hr_search_dense_range; the finite-value checks
+ *     (and drop_ratio) are those of hr_search_dense / hr_search_sparse.
+ *   Memory: the candidate arrays (8 bytes per row and query, + 4 bytes per candidate group) belong to the call and are
+ *     freed before it returns; queries run in passes that keep them under 512 MiB.  When one query's arrays cannot be
+ *     allocated the call fails with HR_ENOMEM, writes nothing and leaves the handle as it was.  hr_device_bytes is
+ *     unchanged by a call. */
+#define HR_MAX_DEEP_K 16384  /* Milvus' cap on offset + limit */
+HR_API int hr_search_dense_deep(hr_index* h, const float* q, int B, int k, int offset, const uint8_t* rowmask,
+                                int mask_on_device, int64_t* out_ids, float* out_scores);
+HR_API int hr_search_sparse_deep(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B,
+                                 int k, int offset, float drop_ratio, const uint8_t* rowmask, int mask_on_device,
+                                 int64_t* out_ids, float* out_scores);
+/* The selection of the deep search on the caller's device arrays (no handle): d_scores / d_rows [B][n], a candidate with
+ * row < 0 is invalid, the valid (score, row) pairs of one query are unique.  Writes [B][k] ids (row + row_offset) and
+ * scores: entries offset .. offset + k - 1 of the candidates ordered by (score desc, row asc), then -1 / 0.
+ * ascending != 0: the scores are negated distances and are written out negated (the order is the same).
+ * d_scratch: hr_deep_topk_scratch_bytes(n, B, k + offset) bytes, 8-byte aligned, owned by the call until the stream has
+ * run it.  Asynchronous on `stream`; the result is a function of the inputs alone (integer atomics, then a sort).
+ * HR_EINVAL: k < 1, offset < 0, n < 0, B < 1, a NULL buffer; HR_ELIMIT: k + offset > HR_MAX_DEEP_K, n >= 2^31, B > 65535.
+ * n == 0 writes only padding.  A refused call launches nothing. */
+HR_API size_t hr_deep_topk_scratch_bytes(int64_t n, int B, int window);
+HR_API int hr_deep_topk_dev(const float* d_scores, const int32_t* d_rows, int64_t n, int B, int k, int offset, int ascending,
+                            int64_t row_offset, int64_t* d_out_ids, float* d_out_scores, void* d_scratch, void* stream);
+
 /* Reciprocal-rank fusion of up to three ranked id lists of ONE query
  * (reference HybridRetriever._fuse_results, retrieval.py:421-491), executed
  * by the device kernel.  ids < 0 end a list.  out arrays hold na+nb+nc
