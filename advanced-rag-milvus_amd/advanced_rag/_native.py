@@ -724,6 +724,7 @@ class FilterLeaf(ctypes.Structure):
 
 
 HR_OP_IN = 6
+HR_COL_TOKENS, HR_OP_MATCH = 4, 7     # the keyword leaf (TEXT_MATCH): only together, only in hr_filter_eval_expr_dev
 HR_FILTER_AND, HR_FILTER_OR, HR_FILTER_NOT = -1, -2, -3
 HR_MAX_FILTER_TERMS, HR_MAX_FILTER_PROGRAM, HR_MAX_FILTER_SET_BYTES = 16, 64, 65536
 

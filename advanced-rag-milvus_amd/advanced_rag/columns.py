@@ -248,7 +248,10 @@ class TokenSetColumn:
     Rows are tokenised once; an id, once given, never changes."""
     MAX_TOKENS = (1 << 31) - 1     # ids are int32
 
-    def __init__(self):
+    def __init__(self, tokenizer=None):
+        """tokenizer: text -> iterable of tokens (duplicates allowed); None = the reference's `text.lower().split()`.  The
+        keyword filter's column (PayloadColumns.word_sets) passes filters.analyze."""
+        self._tokenize = tokenizer if tokenizer is not None else (lambda text: text.lower().split())
         self.ids: Dict[str, int] = {}
         self._indptr = np.zeros(1, dtype=np.int64)
         self._tok = np.empty(0, dtype=np.int32)
@@ -258,10 +261,10 @@ class TokenSetColumn:
         return self._n
 
     def extend(self, contents: Iterable[str]) -> None:
-        ids, rows, lens = self.ids, [], []
+        ids, rows, lens, tokenize = self.ids, [], [], self._tokenize
         for text in contents:
             row = []
-            for t in set(text.lower().split()):
+            for t in dict.fromkeys(tokenize(text)):      # distinct tokens in the order of their first occurrence
                 i = ids.get(t)
                 if i is None:
                     if len(ids) >= self.MAX_TOKENS:
@@ -363,6 +366,8 @@ class PayloadColumns:
         self._c.update({k: NumericColumn(np.int64) for k in INT_COLUMNS})
         self._c.update({k: NumericColumn(np.float32) for k in FLOAT_COLUMNS})
         self._token_sets: Optional[TokenSetColumn] = None    # derived from "content" on first use; not a payload field
+        self._word_sets: Optional[TokenSetColumn] = None     # the same under filters.analyze: what TEXT_MATCH reads
+        self._word_lock = threading.Lock()                   # the build and the extension are read-modify-write
         self._group_keys: Dict[str, GroupKeyColumn] = {}     # string column -> its rows' group keys, on first use
         # the lazy build and the extension of a group-key column are read-modify-write: the searches of one request run in
         # different threads (a sharded manager has no front) and ask for the same field at once
@@ -400,6 +405,17 @@ class PayloadColumns:
             self._token_sets = TokenSetColumn()
         return self._token_sets.sync(self._c["content"])
 
+    def word_sets(self) -> TokenSetColumn:
+        """The WORD sets of every row's content, what TEXT_MATCH filters on: a second TokenSetColumn whose tokenizer is
+        filters.analyze (the BM25 words: "timeout," is "timeout"), with a dictionary of its own (`.ids`, word -> id in
+        first-seen order; an id never changes).  Built on first use — the host tokenises every row once —, extended by
+        what later appends added, gathered by compact(), never part of a snapshot."""
+        with self._word_lock:
+            if self._word_sets is None:
+                from .filters import analyze
+                self._word_sets = TokenSetColumn(analyze)
+            return self._word_sets.sync(self._c["content"])
+
     def group_keys(self, field: str) -> np.ndarray:
         """int64 group key of every row for a grouping search on `field` (a view, no copy): the column itself for an
         integer field, dictionary ordinals (GroupKeyColumn) for a string field — built on first use, extended by what
@@ -423,6 +439,9 @@ class PayloadColumns:
         if self._token_sets is not None:
             n = len(self._token_sets)
             self._token_sets.compact(keep[:n])
+        with self._word_lock:
+            if self._word_sets is not None:
+                self._word_sets.compact(keep[:len(self._word_sets)])
         with self._group_lock:
             for col in self._group_keys.values():
                 col.compact(keep[:len(col)])

@@ -8,6 +8,10 @@ added — so that an expression becomes one `hr_filter_eval_dev` launch (a conju
 kernels take (no row-sized transfer in either direction; the first filtered request at 10M rows took 44 ms on the
 host, the mask was re-uploaded with every search).
 
+A keyword leaf, TEXT_MATCH(content, "words"), reads the rows' WORD SETS instead of a scalar column: a CSR of int32 word ids
+(columns.PayloadColumns.word_sets, mirrored by device_tokens.DeviceTokenSets and owned here, so it goes wherever this object
+goes).  The query's words are looked up in the collection's dictionary on the host and travel like an `in` set.
+
 Strings (doc_id, chunk_id, timestamp) are compared through order-preserving 16-byte prefix keys; the rare rows whose
 first 16 bytes equal the literal's come back in an "undecided" mask and are settled here on the full strings.
 `filters.evaluate` (numpy, host) is the restatement the tests hold this against, bit for bit.
@@ -60,7 +64,9 @@ class DeviceFilters:
         self.device = int(device)
         self._dev: Dict[str, Tuple[Any, int]] = {}   # column -> (device tensor with spare capacity, rows uploaded)
         # expr_evaluations: the evaluations among them that took hr_filter_eval_expr_dev (anything but a flat conjunction)
-        self.stats = {"evaluations": 0, "expr_evaluations": 0, "undecided_rows": 0, "uploaded_bytes": 0}
+        # match_leaves: the TEXT_MATCH leaves among the evaluated expressions
+        self.stats = {"evaluations": 0, "expr_evaluations": 0, "undecided_rows": 0, "uploaded_bytes": 0, "match_leaves": 0}
+        self._words = None                      # DeviceTokenSets over columns.word_sets(): built by the first TEXT_MATCH
         # one evaluation at a time: the column tensors are owned by `_dev` alone, so a second thread that re-uploads a
         # column (the dense and the sparse search of an uncoalesced retrieve() evaluate a new expression concurrently)
         # would free the tensor the first thread's kernel is about to read
@@ -102,6 +108,37 @@ class DeviceFilters:
         col = self.columns[field]
         return self._tensor(field, lambda a, b: col.array()[a:b], n)
 
+    def _word_sets(self, stream):
+        """-> (indptr int64 CUDA tensor [rows + 1], word ids int32 CUDA tensor or None, rows) of the word mirror, what
+        later appends added uploaded on `stream`: the kernel that follows on that stream sees every row."""
+        import torch
+        from .device_tokens import DeviceTokenSets
+        if self._words is None:
+            self._words = DeviceTokenSets(self.columns, self.device, source=lambda cols: cols.word_sets())
+        before = self._words.stats["uploaded_bytes"]
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))):
+            indptr, tok, rows = self._words.tensors()
+            if indptr is None:       # a collection without a row: one offset, no word
+                indptr = torch.zeros(1, dtype=torch.int64, device=torch.device("cuda", self.device))
+        self.stats["uploaded_bytes"] += self._words.stats["uploaded_bytes"] - before
+        return indptr, tok, rows
+
+    @property
+    def word_mirror_bytes(self) -> int:
+        """HBM the word mirror holds (0 before the first TEXT_MATCH)."""
+        return self._words.nbytes if self._words is not None else 0
+
+    def _match_ids(self, field: str, text: str) -> np.ndarray:
+        """The query words of TEXT_MATCH(field, text) as the kernel searches them: their ids in the collection's
+        dictionary, ascending, each once; a word no row holds has no id and is dropped (it can match nothing)."""
+        if self.columns is None:
+            raise ValueError("this shard was bulk-ingested without payload columns: only chunk_index (= row % 10) "
+                             f"can be filtered on, not {[field]}")
+        if field not in _filters.TEXT_FIELDS:
+            raise ValueError(f"TEXT_MATCH analyses only the field content, not {field}, in filter term: TEXT_MATCH({field}, ...)")
+        ids = self.columns.word_sets().ids      # the first use tokenises every row on the host, once
+        return np.asarray(sorted({ids[w] for w in set(_filters.analyze(text)) if w in ids}), dtype=np.int32)
+
     # ------------------------------------------------------------------ expression -> terms
     def _term(self, field: str, op: str, value) -> Tuple["nat.FilterTerm", Optional[Tuple[str, str, str]]]:
         """One comparison as the kernel takes it (no column pointer yet) and, for a string field, what settles its ties."""
@@ -132,7 +169,7 @@ class DeviceFilters:
             raise ValueError(f"unknown filter field: {field}")
         return t, None
 
-    def _terms(self, expr: str, n: int):
+    def _terms(self, expr: str, n: int, stream=None):
         """-> (terms, string_terms) for a flat conjunction of comparisons (hr_filter_eval_dev, as ever), or
         (leaves, _Program) for every other expression (hr_filter_eval_expr_dev)."""
         # every term is checked and built before the first column is touched: an expression that is refused (a literal
@@ -166,6 +203,10 @@ class DeviceFilters:
                 leaf, members = nat.FilterLeaf(), None
                 if node[0] == "cmp":
                     leaf.term = self._term(node[1], node[2], node[3])[0]
+                elif node[0] == "match":
+                    members = self._match_ids(node[1], node[2])
+                    leaf.term.kind, leaf.term.op, leaf.term.ival = nat.HR_COL_TOKENS, nat.HR_OP_MATCH, int(node[3])
+                    leaf.n_set = members.shape[0]
                 else:
                     leaf.term.op, members = nat.HR_OP_IN, self._members(node[1], node[2])
                     leaf.term.kind = {np.int64: nat.HR_COL_I64, np.float32: nat.HR_COL_F32, np.uint64: nat.HR_COL_STR16}[members.dtype.type]
@@ -181,12 +222,18 @@ class DeviceFilters:
         if len(program) > nat.HR_MAX_FILTER_PROGRAM:
             raise ValueError(f"a filter expression may hold up to {nat.HR_MAX_FILTER_PROGRAM} terms and operators together")
         if set_bytes > nat.HR_MAX_FILTER_SET_BYTES:
-            raise ValueError("the `in` lists of one filter expression may hold up to 4096 strings or 8192 integers together "
+            raise ValueError("the `in` lists of one filter expression may hold up to 4096 strings or 8192 integers together, "
+                             "the TEXT_MATCH texts 16384 words "
                              f"({nat.HR_MAX_FILTER_SET_BYTES} bytes of members; this one has {set_bytes})")
         import torch
         dev = torch.device("cuda", self.device)
         for i, (leaf, field) in enumerate(zip(leaves, fields)):
-            leaf.term.col = self._column(field, n).data_ptr()
+            if leaf.term.op == nat.HR_OP_MATCH:
+                indptr, tok, rows = self._word_sets(stream)
+                leaf.term.col, leaf.term.key[0], leaf.term.key[1] = indptr.data_ptr(), tok.data_ptr() if tok is not None else 0, rows
+                sets.append(indptr)              # (an own tensor for an empty collection) alive as long as the sets
+            else:
+                leaf.term.col = self._column(field, n).data_ptr()
             if sets[i] is not None and sets[i].shape[0]:
                 m = sets[i]
                 sets[i] = torch.from_numpy(m.view(np.int64) if m.dtype == np.uint64 else m).to(dev)   # lives until the stream is synchronised
@@ -214,6 +261,9 @@ class DeviceFilters:
         """The whole tree on the given rows, string leaves on the full strings: which undecided rows pass."""
         def leaf(node):
             field = node[1]
+            if node[0] == "match":
+                content = self.columns["content"]
+                return _filters.match_rows([content[int(r)] for r in rows], node[2], node[3])
             if field in _STRING_FIELDS:
                 col = self.columns[_STRING_FIELDS[field]]
                 return col.member_rows(rows, node[2]) if node[0] == "in" else col.compare_rows(rows, node[2], node[3])
@@ -230,7 +280,8 @@ class DeviceFilters:
     def _evaluate_locked(self, expr, n_rows, deleted, stream):
         import torch
         dev = torch.device("cuda", self.device)
-        terms, settle = self._terms(expr, n_rows) if expr else ([], [])
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        terms, settle = self._terms(expr, n_rows, st) if expr else ([], [])
         program = settle if isinstance(settle, _Program) else None
         mask = torch.empty(mask_bytes(n_rows), dtype=torch.uint8, device=dev)
         und = torch.empty(mask_bytes(n_rows), dtype=torch.uint8, device=dev)
@@ -241,7 +292,6 @@ class DeviceFilters:
             packed = np.packbits(deleted[:n_rows], bitorder="little")
             bits[: packed.size] = packed
             d_del = torch.from_numpy(bits).to(dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
         with torch.cuda.stream(st):   # the read-backs and the fix-ups below are ordered behind the kernel on ITS stream
             if program is None:
                 nat.filter_eval_dev(terms, n_rows, d_del.data_ptr() if d_del is not None else 0, mask.data_ptr(), und.data_ptr(),
@@ -250,6 +300,7 @@ class DeviceFilters:
                 nat.filter_eval_expr_dev(terms, program.codes, n_rows, d_del.data_ptr() if d_del is not None else 0, mask.data_ptr(),
                                          und.data_ptr(), counts.data_ptr(), st.cuda_stream)
                 self.stats["expr_evaluations"] += 1
+                self.stats["match_leaves"] += sum(1 for leaf in terms if leaf.term.op == nat.HR_OP_MATCH)
             kept, undecided = (int(x) for x in counts.cpu().tolist())   # synchronises the stream (the sets may go after it)
             self.stats["evaluations"] += 1
             if undecided:

@@ -16,8 +16,11 @@ import numpy as np
 
 
 class DeviceTokenSets:
-    def __init__(self, columns, device: int):
+    def __init__(self, columns, device: int, source=None):
+        """source: PayloadColumns -> the host TokenSetColumn to mirror; None = `columns.token_sets()` (MMR's tokens).  The
+        keyword filter (device_filters.py) mirrors `columns.word_sets()` through the same code."""
         self.columns = columns                  # PayloadColumns, or None for a payload-free (synthetic) collection
+        self._source = source if source is not None else (lambda cols: cols.token_sets())
         self.device = int(device)
         self._indptr = None                     # int64 [capacity + 1], valid for rows <= _rows
         self._tok = None                        # int32 [capacity], valid below _used
@@ -45,7 +48,7 @@ class DeviceTokenSets:
         import torch
         with self._lock:
             t0 = time.perf_counter()
-            host = self.columns.token_sets()
+            host = self._source(self.columns)
             self.stats["host_build_s"] += time.perf_counter() - t0
             n = len(host)
             if n == 0:

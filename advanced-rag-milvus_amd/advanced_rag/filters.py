@@ -12,9 +12,13 @@ the kernels as a packed bitmask (bit r%8 of byte r/8).
 A pymilvus caller writes more than conjunctions, so `parse_tree` also takes
     field in [literal, ...]   field not in [...]   or / ||   not / !   ( ... )
 with Milvus' precedence (not > and > or).  `parse` keeps to the flat
-conjunction; `evaluate` and `fields` take either form.  The rest of Milvus'
-language (like, arithmetic, a < f < b, field-to-field comparisons, JSON and
-array functions) is refused.
+conjunction; `evaluate` and `fields` take either form.  `parse_tree` also takes the
+keyword filter of Milvus 2.5,
+    TEXT_MATCH(content, "words"[, minimum_should_match=m])
+over the words of `content` (`analyze`, the BM25 tokenizer): a row passes iff at least
+m (default 1) distinct words of the query are among its words.  The rest of Milvus'
+language (like, PHRASE_MATCH, arithmetic, a < f < b, field-to-field comparisons,
+JSON and array functions) is refused.
 """
 from __future__ import annotations
 
@@ -27,6 +31,23 @@ _OPS = (">=", "<=", "==", "!=", ">", "<")
 NUMERIC_FIELDS = {"chunk_index": np.int64, "token_count": np.int64, "entropy": np.float32,
                   "redundancy": np.float32, "domain_density": np.float32}
 STRING_FIELDS = ("id", "chunk_id", "doc_id", "timestamp")
+TEXT_FIELDS = ("content",)             # what TEXT_MATCH analyses
+MATCH_MAX = 16384                      # minimum_should_match, and the word ids one expression can carry to the device
+_ANALYZER = re.compile(r"\w+")
+
+
+def analyze(text: str) -> List[str]:
+    """The words of a text as TEXT_MATCH sees them, in order: maximal runs of Unicode word characters of the lower-cased
+    text — what the BM25 modality tokenises with (bm25._WORD), so "Timeout," and "timeout" are one word."""
+    return _ANALYZER.findall(text.lower())
+
+
+def match_rows(contents, text: str, m: int) -> np.ndarray:
+    """TEXT_MATCH over a sequence of str: row r passes iff at least m distinct words of `text` are among its words."""
+    words = set(analyze(text))
+    if not words or m > len(words):
+        return np.zeros(len(contents), dtype=bool)
+    return np.fromiter((len(words.intersection(analyze(c))) >= m for c in contents), dtype=bool, count=len(contents))
 
 
 def _split_terms(expr: str) -> List[str]:
@@ -153,11 +174,14 @@ def _compare(col: np.ndarray, op: str, value: Any) -> np.ndarray:
 
 
 def _leaf_mask(node, columns: Dict[str, np.ndarray]) -> np.ndarray:
-    """Row predicate of one leaf: ("cmp", field, op, value) or ("in", field, values)."""
+    """Row predicate of one leaf: ("cmp", field, op, value), ("in", field, values) or ("match", field, text, m) — the last
+    over columns["content"], any sequence of str."""
     field = node[1]
     if field not in columns:
         raise ValueError(f"unknown filter field: {field}")
     col = columns[field]
+    if node[0] == "match":
+        return match_rows(col, node[2], node[3])
     if node[0] == "in":
         members = list_members(field, node[2], "s" if col.dtype.kind in "US" else "i" if col.dtype.kind in "iu" else "f")
         if not members:
@@ -209,14 +233,16 @@ def evaluate(expr: str, columns: Dict[str, np.ndarray], n_rows: int) -> np.ndarr
 #   and   := unary ( ("and" | "AND" | "&&") unary )*
 #   unary := ("not" | "NOT" | "!") unary | "(" expr ")" | leaf
 #   leaf  := field CMP literal | field ["not"] "in" "[" [ literal ("," literal)* ] "]"
-# Trees: ("cmp", field, op, value) | ("in", field, [values]) | ("not", t) | ("and", a, b) | ("or", a, b), and / or
-# left-associative; `field not in [..]` is ("not", ("in", ..)).
+#          | ("TEXT_MATCH" | "text_match") "(" field "," string [ "," "minimum_should_match" "=" integer ] ")"
+# Trees: ("cmp", field, op, value) | ("in", field, [values]) | ("match", field, text, m) | ("not", t) | ("and", a, b) |
+# ("or", a, b), and / or left-associative; `field not in [..]` is ("not", ("in", ..)); m = 1 without the option.
 
 _KEYWORDS = {"and": "and", "AND": "and", "&&": "and", "or": "or", "OR": "or", "||": "or", "not": "not", "NOT": "not",
              "!": "not", "in": "in", "IN": "in"}
 _IDENT = re.compile(r"[A-Za-z_]\w*$")
 _WORD = re.compile(r"[\w.+\-]+")       # identifiers, keywords and numeric literals (1e-3, -inf, 1_000)
-_PUNCT = ("&&", "||", ">=", "<=", "==", "!=", ">", "<", "!", "(", ")", "[", "]", ",")
+_PUNCT = ("&&", "||", ">=", "<=", "==", "!=", ">", "<", "!", "(", ")", "[", "]", ",", "=")   # "=": only inside TEXT_MATCH(...)
+_MATCH_NAMES = ("TEXT_MATCH", "text_match")
 
 
 def _tokens(expr: str) -> List[Tuple[str, str, int, int]]:
@@ -354,6 +380,8 @@ class _Parser:
         if tok[0] != "word" or not _IDENT.match(tok[1]) or tok[1] in ("True", "true", "False", "false"):
             raise ValueError(f"cannot parse filter term: {self.text_from(start, min(start + 2, len(self.toks) - 1))!r}")
         field, kind = tok[1], self.peek()
+        if field in _MATCH_NAMES and kind == "(":
+            return self.match(start)
         if kind == "cmp":
             op = self.toks[self.i][1]
             self.i += 1
@@ -400,6 +428,46 @@ class _Parser:
         return ("not", node) if negate else node
 
 
+    def match(self, start: int):
+        """TEXT_MATCH ( field , "text" [, minimum_should_match = integer] ) with the name already read."""
+        close = next((j for j in range(self.i, len(self.toks)) if self.toks[j][0] == ")"), len(self.toks) - 1)
+        term = self.text_from(start, close)
+
+        def take(kind: str, what: str):
+            if self.peek() != kind:
+                raise ValueError(f"{what} in filter term: {term!r}")
+            self.i += 1
+            return self.toks[self.i - 1]
+
+        take("(", "expected (")
+        field = take("word", "expected a field name after TEXT_MATCH(")[1]
+        if not _IDENT.match(field):
+            raise ValueError(f"expected a field name after TEXT_MATCH( in filter term: {term!r}")
+        if field not in TEXT_FIELDS:
+            raise ValueError(f"TEXT_MATCH analyses only the field content, not {field}, in filter term: {term!r}")
+        if self.peek() != ",":
+            raise ValueError(f"TEXT_MATCH needs a field and a quoted text; the text is missing in filter term: {term!r}")
+        self.i += 1
+        if self.peek() in (")", "end"):
+            raise ValueError(f"TEXT_MATCH needs a field and a quoted text; the text is missing in filter term: {term!r}")
+        text = _unquote(take("str", "the text of TEXT_MATCH must be a double-quoted string")[1])
+        m = 1
+        if self.peek() == ",":
+            self.i += 1
+            option = take("word", "expected minimum_should_match=<integer> after the text")[1]
+            if option != "minimum_should_match":
+                raise ValueError(f"unknown TEXT_MATCH option {option!r} (only minimum_should_match) in filter term: {term!r}")
+            take("=", "expected = after minimum_should_match")
+            raw = take("word", "minimum_should_match needs an integer")[1]
+            if not re.fullmatch(r"[0-9]+", raw) or not 1 <= int(raw) <= MATCH_MAX:
+                raise ValueError(f"minimum_should_match must be an integer from 1 to {MATCH_MAX}, got {raw} in filter term: {term!r}")
+            m = int(raw)
+        if self.peek() != ")":
+            raise ValueError(f"missing ) in filter term: {term!r}")
+        self.i += 1
+        return ("match", field, text, m)
+
+
 def parse_tree(expr: str):
     """The expression as a tree (see the grammar above), or ValueError naming the offending term."""
     return _Parser(expr).parse()
@@ -429,7 +497,7 @@ def lower(expr: str):
 
 
 def leaves(tree) -> List[tuple]:
-    if tree[0] in ("cmp", "in"):
+    if tree[0] in ("cmp", "in", "match"):
         return [tree]
     return [leaf for child in tree[1:] for leaf in leaves(child)]
 

@@ -483,7 +483,10 @@ class MilvusIndexManager:
                 raise ValueError("this shard was bulk-ingested without payload columns: only chunk_index (= row % 10) "
                                  f"can be filtered on, not {sorted(fields - {'chunk_index'})}")
             return _filters.evaluate(expr, {"chunk_index": np.arange(n, dtype=np.int64) % 10}, n)
-        return _filters.evaluate(expr, self._columns(), n)
+        columns = self._columns()
+        if "content" in _filters.fields(expr):    # TEXT_MATCH: the one leaf that reads a text field, any sequence of str
+            columns = dict(columns, content=self._cols["content"])
+        return _filters.evaluate(expr, columns, n)
 
     def _tombstone(self, expr: str):
         n = self.num_rows

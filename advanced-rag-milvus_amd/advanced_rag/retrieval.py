@@ -464,10 +464,31 @@ class HybridRetriever:
             raise ValueError(f"Invalid list for {field}: its members must be all strings or all numbers")
         return "[" + ", ".join(cls._quote(v) if isinstance(v, str) else f"{v}" for v in operand) + "]"
 
+    @classmethod
+    def _text_match_term(cls, operand: Any) -> str:
+        """{"content": {"$text_match": "disk failure"}} or {"$text_match": {"query": "...", "minimum_should_match": 2}}
+        -> 'TEXT_MATCH(content, "disk failure"[, minimum_should_match=2])' (filters.py has the semantics)."""
+        m = None
+        if isinstance(operand, dict):
+            if not set(operand) <= {"query", "minimum_should_match"} or "query" not in operand:
+                raise ValueError(f"$text_match takes a string, or query and minimum_should_match, got {sorted(operand)}")
+            operand, m = operand["query"], operand.get("minimum_should_match")
+        if not isinstance(operand, str):
+            raise ValueError(f"Invalid value type for content: {type(operand)}")
+        if m is None:
+            return f"TEXT_MATCH(content, {cls._quote(operand)})"
+        if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 16384:
+            raise ValueError(f"minimum_should_match must be an integer from 1 to 16384, got {m!r}")
+        return f"TEXT_MATCH(content, {cls._quote(operand)}, minimum_should_match={m})"
+
     def _build_filter_expression(self, filters: Dict[str, Any]) -> Optional[str]:
         """{"doc_id": "d1", "entropy": {"$gte": 0.2}} -> 'doc_id == "d1" and entropy >= 0.2'."""
         terms: List[str] = []
         for field, cond in filters.items():
+            if (field == "content" and self.config.extended_filter_operators and isinstance(cond, dict)
+                    and set(cond) == {"$text_match"}):
+                terms.append(self._text_match_term(cond["$text_match"]))
+                continue
             if field not in self.ALLOWED_FILTER_FIELDS:
                 logger.warning("Invalid filter field attempted: %s", field)
                 raise ValueError(f"Invalid filter field: {field}")

@@ -136,11 +136,67 @@ struct FilterKey {
     __device__ bool operator==(const FilterKey& o) const { return w0 == o.w0 && w1 == o.w1; }
 };
 
+// A TEXT_MATCH leaf (kind HR_COL_TOKENS, op HR_OP_MATCH) reads a row's WORD SET, not one scalar: a CSR of ascending int32
+// word ids per row (term.col = int64 indptr[tok_rows + 1], term.key[0] = the word array, term.key[1] = tok_rows, a row at or
+// beyond tok_rows is empty).  A row passes iff at least term.ival of the leaf's set members are among its words.  A lane
+// that walked its own row would read 4 bytes at a stride of the row length, so the leaf is wave-cooperative instead: the
+// words of the wave's 64 rows are ONE contiguous span of the array, indptr[64w] .. indptr[min(64w + 64, tok_rows)], which
+// the wave streams 64 entries at a time (lane = entry: coalesced).  Every entry is looked up in the LDS-staged set with
+// the fixed-trip search above; a hit belongs to the row whose span holds the entry — the number of row ENDS <= the
+// entry's offset, an upper bound, so that empty rows (equal ends) are stepped over — and bumps that row's counter in LDS
+// (integer atomics: the sum does not depend on their order).  Lane r then reads counter r.  Ends and counters are per
+// wave and rewritten by every leaf of every trip.  Only filter_expr_kernel<true> carries any of this: an expression
+// without such a leaf launches <false>, the kernel it always ran.
+struct FilterMatchScratch {
+    long long end[4][64];   // per wave: offset, from the span's start, where the words of row r end
+    int count[4][64];       // per wave: set members found in row r
+};
+
+__device__ inline bool filter_match(const hr_filter_term& t, const int32_t* set, int n, int64_t w, int lane,
+                                    long long* end, int* count) {
+    const int64_t* indptr = (const int64_t*)t.col;
+    const int32_t* words = (const int32_t*)(uintptr_t)t.key[0];
+    const int64_t tok_rows = (int64_t)t.key[1], r0 = w * 64;
+    const int64_t begin = indptr[r0 < tok_rows ? r0 : tok_rows];
+    const int64_t last = r0 + lane + 1;
+    end[lane] = indptr[last < tok_rows ? last : tok_rows] - begin;   // one coalesced 8-byte load; non-decreasing over the lanes
+    count[lane] = 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int64_t total = end[63];
+    for (int64_t e0 = 0; e0 < total; e0 += 64) {    // wave-uniform trip count
+        const int64_t e = e0 + lane;
+        const bool live = e < total;
+        const int32_t word = live ? words[begin + e] : 0;
+        if (live && filter_set_has<int32_t>(set, n, word)) {
+            int r = 0;                               // the rows whose words end at or before e: at most 63, as end[63] > e
+            for (int step = 32; step; step >>= 1)
+                if (end[r + step - 1] <= e) r += step;
+            atomicAdd(&count[r], 1);
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const bool pass = (int64_t)count[lane] >= t.ival;
+    __builtin_amdgcn_wave_barrier();                 // the next leaf rewrites ends and counters only after every lane has read
+    return pass;
+}
+
+template <bool kHasMatch>
 __global__ __launch_bounds__(256) void filter_expr_kernel(FilterExprArgs a) {
     extern __shared__ __align__(16) unsigned char filter_sets[];
     for (int i = 0; i < a.n_leaves; ++i) {
-        if (a.t[i].op != HR_OP_IN) continue;
-        const int words = a.n_set[i] * (a.t[i].kind == HR_COL_F32 ? 1 : a.t[i].kind == HR_COL_I64 ? 2 : 4);
+        int per_member;
+        if constexpr (kHasMatch) {
+            if (a.t[i].op != HR_OP_IN && a.t[i].op != HR_OP_MATCH) continue;
+            per_member = (a.t[i].kind == HR_COL_F32 || a.t[i].kind == HR_COL_TOKENS) ? 1 : a.t[i].kind == HR_COL_I64 ? 2 : 4;
+        } else {
+            if (a.t[i].op != HR_OP_IN) continue;
+            per_member = a.t[i].kind == HR_COL_F32 ? 1 : a.t[i].kind == HR_COL_I64 ? 2 : 4;
+        }
+        const int words = a.n_set[i] * per_member;
         const uint32_t* src = (const uint32_t*)a.set[i];
         uint32_t* dst = (uint32_t*)(filter_sets + a.set_off[i]);
         for (int j = threadIdx.x; j < words; j += 256) dst[j] = src[j];
@@ -171,7 +227,15 @@ __global__ __launch_bounds__(256) void filter_expr_kernel(FilterExprArgs a) {
             } else {
                 const hr_filter_term& t = a.t[code];
                 bool pass = false, tie = false;
-                if (t.op == HR_OP_IN) {
+                if (kHasMatch && t.op == HR_OP_MATCH) {
+                    if constexpr (kHasMatch) {
+                        __shared__ FilterMatchScratch scratch;
+                        const int n = a.n_set[code], wv = threadIdx.x >> 6;
+                        if (n > 0)   // an empty set: no member is found in any row, and ival >= 1
+                            pass = filter_match(t, (const int32_t*)(filter_sets + a.set_off[code]), n, w, lane, scratch.end[wv],
+                                                scratch.count[wv]);
+                    }
+                } else if (t.op == HR_OP_IN) {
                     const int n = a.n_set[code];
                     const unsigned char* set = filter_sets + a.set_off[code];
                     if (n > 0) {   // a row beyond n_rows searches for 0: every read stays inside the set

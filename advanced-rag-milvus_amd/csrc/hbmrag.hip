@@ -1354,7 +1354,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11300; }  // 1.13.0: hr_search_dense_deep, hr_search_sparse_deep, hr_deep_topk_dev
+int hr_version(void) { return 11400; }  // 1.14.0: HR_COL_TOKENS / HR_OP_MATCH, the keyword leaf of hr_filter_eval_expr_dev
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2130,8 +2130,27 @@ int hr_filter_eval_expr_dev(const hr_filter_leaf* leaves, int n_leaves, const in
     if (((uintptr_t)d_mask | (uintptr_t)d_undecided) & 7) return fail(nullptr, HR_EINVAL, "mask buffers must be 8-byte aligned");
     FilterExprArgs a{};
     size_t set_bytes = 0;
+    bool has_match = false;   // a keyword leaf: the launch takes the kernel variant that carries the wave-cooperative leaf
     for (int i = 0; i < n_leaves; ++i) {
         const hr_filter_term& t = leaves[i].term;
+        if ((t.kind == HR_COL_TOKENS) != (t.op == HR_OP_MATCH))   // the keyword leaf's two constants come together or not at all
+            return fail(nullptr, HR_EINVAL, "bad filter term %d", i);
+        if (t.op == HR_OP_MATCH) {
+            const int64_t tok_rows = (int64_t)t.key[1];
+            if (!t.col || ((uintptr_t)t.col & 7) || tok_rows < 0 || (t.key[0] & 3) || (t.key[0] == 0 && tok_rows > 0) || t.ival < 1 ||
+                leaves[i].n_set < 0 || (leaves[i].set == nullptr) != (leaves[i].n_set == 0) || ((uintptr_t)leaves[i].set & 3))
+                return fail(nullptr, HR_EINVAL, "bad filter term %d (keyword match: word sets, minimum_should_match or set)", i);
+            if ((size_t)leaves[i].n_set > kFilterMaxSetBytes / 4) return fail(nullptr, HR_ELIMIT, "the sets of a filter expression may hold up to %d bytes", kFilterMaxSetBytes);
+            a.t[i] = t;
+            a.set[i] = leaves[i].set;
+            a.n_set[i] = leaves[i].n_set;
+            a.set_off[i] = (int32_t)set_bytes;
+            set_bytes += ((size_t)leaves[i].n_set * 4 + 15) & ~(size_t)15;
+            if (set_bytes > (size_t)kFilterMaxSetBytes)
+                return fail(nullptr, HR_ELIMIT, "the sets of a filter expression may hold up to %d bytes", kFilterMaxSetBytes);
+            has_match = true;
+            continue;
+        }
         if (t.kind < HR_COL_I64 || t.kind > HR_COL_STR16 || t.op < HR_OP_EQ || t.op > HR_OP_IN || !t.col)
             return fail(nullptr, HR_EINVAL, "bad filter term %d", i);
         a.t[i] = t;
@@ -2175,7 +2194,9 @@ int hr_filter_eval_expr_dev(const hr_filter_leaf* leaves, int n_leaves, const in
     hipStream_t s = (hipStream_t)stream;
     static bool attr_set = false;  // benign race: the attribute is idempotent
     if (!attr_set) {
-        hipError_t e0 = hipFuncSetAttribute((const void*)filter_expr_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kFilterMaxSetBytes);
+        hipError_t e0 = hipFuncSetAttribute((const void*)filter_expr_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kFilterMaxSetBytes);
+        if (e0 == hipSuccess)
+            e0 = hipFuncSetAttribute((const void*)filter_expr_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kFilterMaxSetBytes);
         if (e0 != hipSuccess) return fail(nullptr, HR_EHIP, "hipFuncSetAttribute: %s", hipGetErrorString(e0));
         attr_set = true;
     }
@@ -2187,7 +2208,8 @@ int hr_filter_eval_expr_dev(const hr_filter_leaf* leaves, int n_leaves, const in
     // blocks of 64 KiB fit a CU: 1024 blocks are two rounds of the device) stage less than the column read costs
     const int64_t cap = set_bytes > 4096 ? 1024 : 4096;
     const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((n_words + 3) / 4, cap));
-    hipLaunchKernelGGL(filter_expr_kernel, dim3(blocks), dim3(256), set_bytes, s, a);
+    if (has_match) hipLaunchKernelGGL(filter_expr_kernel<true>, dim3(blocks), dim3(256), set_bytes, s, a);
+    else hipLaunchKernelGGL(filter_expr_kernel<false>, dim3(blocks), dim3(256), set_bytes, s, a);
     e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "filter_expr_kernel: %s", hipGetErrorString(e));
     return HR_OK;

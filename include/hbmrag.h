@@ -524,15 +524,34 @@ HR_API int hr_filter_eval_dev(const hr_filter_term* terms, int n_terms, int64_t 
  * rows.  A decided bit is right whatever the full strings say; an undecided row may turn out either way (also where
  * Kleene cannot see that it is decided, `a or not a`).  For a conjunction of comparison leaves all four outputs equal
  * hr_filter_eval_dev's.  d_mask, d_undecided, d_counts, their alignment, the bits at and beyond n_rows, n_rows == 0 and
- * d_deleted are as in hr_filter_eval_dev. */
+ * d_deleted are as in hr_filter_eval_dev.
+ *
+ * A KEYWORD leaf (TEXT_MATCH(content, "words"[, minimum_should_match=m]) of the filter language) has term.kind ==
+ * HR_COL_TOKENS and term.op == HR_OP_MATCH; the two constants are valid only together and only here
+ * (hr_filter_eval_dev refuses kind 4, and (HR_COL_I64, op 7) stays a bad term).  It reads the rows' WORD SETS, a CSR in
+ * device memory, and is true for a row iff at least m of the leaf's set members are among the row's words:
+ *   term.col     device int64 indptr[tok_rows + 1], non-decreasing, 8-byte aligned, never NULL; the words of row r are
+ *                entries indptr[r] .. indptr[r + 1] of the word array
+ *   term.key[0]  device address of the int32 word array, 4-byte aligned; 0 allowed only when tok_rows == 0
+ *   term.key[1]  tok_rows >= 0; a row r >= tok_rows (n_rows may be larger or smaller) has the empty set
+ *   term.ival    m >= 1
+ *   set, n_set   the query's word ids: strictly ascending int32, 4-byte aligned, NULL iff n_set == 0 (no row passes)
+ * Within a row the word ids are ascending and unique; the kernel may rely on that (a repeated id would be counted
+ * twice).  The ids share the HR_MAX_FILTER_SET_BYTES budget with the `in` sets at 4 bytes each, rounded up to 16 per
+ * set: 16384 ids alone.  m > n_set is allowed and matches no row.  The leaf is never unknown: ids are exact, nothing is
+ * hashed or truncated.  HR_EINVAL "bad filter term i": either constant with the wrong partner, m < 1, tok_rows < 0, a
+ * NULL or misaligned indptr, a misaligned word array or a NULL one with tok_rows > 0, a set pointer that disagrees
+ * with n_set or is misaligned; HR_ELIMIT past the set budget; as every refusal, before anything is enqueued or written.
+ * The word CSR is read once per leaf, 4 * entries + 8 * rows bytes, whatever n_set is. */
 enum { HR_OP_IN = 6 };                          /* membership leaf; valid only in hr_filter_eval_expr_dev */
+enum { HR_COL_TOKENS = 4, HR_OP_MATCH = 7 };    /* keyword leaf: only together, only in hr_filter_eval_expr_dev */
 enum { HR_FILTER_AND = -1, HR_FILTER_OR = -2, HR_FILTER_NOT = -3 };   /* program codes; code >= 0 pushes leaf `code` */
 #define HR_MAX_FILTER_PROGRAM 64
 #define HR_MAX_FILTER_SET_BYTES 65536           /* all sets of one expression together: 8192 int64, 16384 float32, or 4096 string keys */
 typedef struct hr_filter_leaf {
     hr_filter_term term;     /* comparison leaf: as in hr_filter_eval_dev.  op == HR_OP_IN: kind HR_COL_I64 / HR_COL_F32 / HR_COL_STR16 and col as there, literal fields unused */
     const void* set;         /* HR_OP_IN: DEVICE array of n_set members, strictly ascending (int64; float32 without NaN; two-word keys in unsigned lexicographic order); NULL iff n_set == 0 */
-    int32_t n_set, reserved;
+    int32_t n_set, reserved; /* HR_OP_MATCH: set = the query's word ids, strictly ascending int32 (see the keyword leaf above) */
 } hr_filter_leaf;
 HR_API int hr_filter_eval_expr_dev(const hr_filter_leaf* leaves, int n_leaves, const int32_t* program, int n_program,
                                    int64_t n_rows, const uint8_t* d_deleted, uint8_t* d_mask, uint8_t* d_undecided,
