@@ -19,6 +19,8 @@ HR_F32, HR_F16 = 0, 1
 HR_METRIC_IP, HR_METRIC_COSINE, HR_METRIC_L2 = 0, 1, 2
 HR_METHOD_SEMANTIC, HR_METHOD_SPARSE, HR_METHOD_DOMAIN = 1, 2, 4
 HR_MAX_TOPK = 256
+# normalisation of one list's scores in the weighted score fusion (hr_fuse_scores_dev; the table is in include/hbmrag.h)
+HR_NORM_COSINE, HR_NORM_ATAN, HR_NORM_ATAN_DIST, HR_NORM_MINMAX, HR_NORM_MINMAX_DIST = 0, 1, 2, 3, 4
 HR_MAX_DEEP_K = 16384   # hr_search_*_deep, hr_deep_topk_dev: offset + k
 HR_N_PHASES = 10
 PHASE_NAMES = ("prep", "dense_scan", "group_select", "refine", "topk",
@@ -85,6 +87,11 @@ _SIGNATURES = {
     "hr_fuse_rrf": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int,
                                _c.c_double, _c.c_double, _c.c_double, _c.c_int, _c.c_void_p, _c.c_void_p,
                                _c.c_void_p, _c.c_void_p]),
+    "hr_fuse_scores": (_c.c_int, [_c.c_void_p] + [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int] * 3 +
+                       [_c.c_double, _c.c_double, _c.c_double, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_fuse_scores_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int] * 3 +
+                           [_c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_void_p, _c.c_int, _c.c_void_p,
+                            _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_search_dense_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_search_dense_range_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
@@ -498,6 +505,28 @@ class ShardHandle:
                                           _vp(os_), _vp(om), ctypes.byref(n)))
         return oi[:n.value].copy(), os_[:n.value].copy(), om[:n.value].copy()
 
+    def fuse_scores(self, lists, norms, weights=(0.7, 0.3, 0.2)):
+        """hr_fuse_scores: weighted score fusion of up to three (ids, fp32 scores) lists of one query; norms = one
+        HR_NORM_* code per list.  -> (ids, float64 fused scores, method bit masks) in fused order."""
+        lists = list(lists) + [((), ())] * (3 - len(lists))
+        norms = list(norms) + [HR_NORM_COSINE] * (3 - len(norms))
+        w = list(weights) + [0.0] * (3 - len(weights))
+        ids = [np.ascontiguousarray(l[0], dtype=np.int64) for l in lists]
+        sc = [np.ascontiguousarray(l[1], dtype=np.float32) for l in lists]
+        if any(len(i) != len(s) for i, s in zip(ids, sc)):
+            raise ValueError("a list's ids and scores differ in length")
+        cap = max(sum(len(i) for i in ids), 1)
+        oi = np.empty(cap, dtype=np.int64)
+        os_ = np.empty(cap, dtype=np.float64)
+        om = np.empty(cap, dtype=np.int32)
+        n = ctypes.c_int32(0)
+        args = []
+        for i, s, code in zip(ids, sc, norms):
+            args += [_vp(i) if len(i) else None, _vp(s) if len(i) else None, len(i), int(code)]
+        self._check(self._lib.hr_fuse_scores(self._h, *args, float(w[0]), float(w[1]), float(w[2]), _vp(oi), _vp(os_),
+                                             _vp(om), ctypes.byref(n)))
+        return oi[:n.value].copy(), os_[:n.value].copy(), om[:n.value].copy()
+
     # -- search, device buffers (raw pointers; asynchronous on `stream`)
     def search_dense_dev(self, d_q: int, B: int, k: int, d_ids: int, d_scores: int, d_flags: int = 0,
                          d_rowmask: int = 0, stream: int = 0):
@@ -595,6 +624,19 @@ def _raise_global(L, rc: int):
     if rc == 1:
         raise ValueError(msg)
     raise HbmRagError(rc, msg)
+
+
+def fuse_scores_dev(d_a: int, d_sa: int, ka: int, norm_a: int, d_b: int, d_sb: int, kb: int, norm_b: int, d_c: int,
+                    d_sc: int, kc: int, norm_c: int, B: int, wa: float, wb: float, wc: float, d_w_query: int, top_k: int,
+                    d_out_ids: int, d_out_scores: int, d_out_methods: int, d_n_out: int, stream: int = 0):
+    """hr_fuse_scores_dev: weighted score fusion of a batch (device pointers; 0 = NULL; norm_* = HR_NORM_* per list)."""
+    L = load_library()
+    p = lambda v: _vp(v) if v else None
+    rc = L.hr_fuse_scores_dev(p(d_a), p(d_sa), ka, norm_a, p(d_b), p(d_sb), kb, norm_b, p(d_c), p(d_sc), kc, norm_c, B,
+                              wa, wb, wc, p(d_w_query), top_k, p(d_out_ids), p(d_out_scores), p(d_out_methods),
+                              p(d_n_out), p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
 
 
 def mmr_select_dev(d_ids: int, d_scores: int, d_n: int, B: int, k_in: int, d_tok_indptr: int, d_tok: int, tok_rows: int,
@@ -774,7 +816,7 @@ class PostArgs(ctypes.Structure):
         ("method_bonus", _c.c_double), ("recency_w", _c.c_double), ("recency", _c.c_void_p), ("k_out", _c.c_int32),
         ("asc_mask", _c.c_int32), ("rr_ids", _c.c_void_p), ("rr_scores", _c.c_void_p), ("rr_orig", _c.c_void_p),
         ("flags", _c.c_void_p), ("flag_stride", _c.c_int64), ("n_flag_rows", _c.c_int32), ("reserved2", _c.c_int32),
-        ("agg_flags", _c.c_void_p), ("w_query", _c.c_void_p),
+        ("agg_flags", _c.c_void_p), ("w_query", _c.c_void_p), ("fusion", _c.c_int32), ("norm", _c.c_int32 * 3),
     ]
 
 

@@ -6,7 +6,8 @@ Milvus server is free to batch with the others (indexing.py:503-506 runs it in a
 scan of the whole shard, so the counterpart of the server's request queue is this front: calls that arrive while a
 round of scans is in flight — or within a short window of the first call of a round — are packed per
 (collection, top_k, filter expression, search params) into ONE `hr_search_dense_dev` / `hr_search_sparse_dev` batch
-(and the rank fusions of the same callers into one `hr_fuse_rrf_dev`), run on the front's own stream with one
+(and the rank fusions of the same callers into one `hr_fuse_rrf_dev`, or — weighted score fusions, a kind of their own —
+into one `hr_fuse_scores_dev`), run on the front's own stream with one
 synchronisation per round, and the per-query lists are handed back to the awaiting coroutines.  Lists the device form
 could not prove exact are redone through the host form, which widens the candidate set by itself.
 
@@ -28,7 +29,8 @@ one `hr_search_hybrid_dev` (both scans, the fused finishing kernel) + one `hr_po
 step — and the caller gets the fused top-k with the per-modality scores in ONE round instead of two.  A request of a
 diversifying profile (MMR; only from a manager created with mmr_on_device=True) takes the same round with the WHOLE fused
 list kept (4 x top_k entries) and one `hr_mmr_select_dev` behind it on the same stream; lambda is a per-query operand, so
-profiles that differ only in lambda share the round.
+profiles that differ only in lambda share the round.  A request with fusion="weighted" carries the fusion mode and its two norm
+codes in the key: it gets an engine whose post kernel fuses by weighted scores, and never shares a launch with an RRF request.
 
 One worker thread per manager; the event loop never blocks on the GPU.
 """
@@ -117,7 +119,7 @@ class RangedQuery:
 
 @dataclass
 class _Request:
-    kind: str                 # "dense" | "sparse" | "fuse"
+    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "hybrid" | "encode"
     key: Tuple                # requests with equal (kind, key) share a launch
     payload: Any
     future: Future = field(default_factory=Future)
@@ -146,7 +148,7 @@ class SearchCoalescer:
             self.window_s = max(self.window_s, 250e-6)
         self.stats = {"rounds": 0, "requests": 0, "dense_launches": 0, "sparse_launches": 0, "fuse_launches": 0,
                       "hybrid_launches": 0, "mmr_launches": 0, "encode_launches": 0, "encoded_texts": 0, "max_batch_seen": 0, "redone_unproven": 0,
-                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "busy_s": 0.0}
+                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "score_fuse_launches": 0, "busy_s": 0.0}
         self._engines: Dict[Tuple, Any] = {}   # hybrid engines per (top_k, rrf_k, mmr)
         self._inflight: List[_Request] = []    # the requests of the round in progress (failed as a whole if the worker dies)
         self._outbox: Dict[Any, list] = {}     # event loop -> [(asyncio future, ok, value)] of the round in progress
@@ -272,7 +274,7 @@ class SearchCoalescer:
         dev = torch.device("cuda", self.mgr.device)
         # one stream per kind of work: the dense and the sparse searches of a round run side by side (a lone retrieve()
         # overlaps its two scans, as its two worker threads did before the front existed)
-        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "hybrid", "encode")}
+        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "hybrid", "encode")}
         for reqs in self._rounds():
             groups: Dict[Tuple, List[_Request]] = {}
             for r in reqs:
@@ -317,6 +319,9 @@ class SearchCoalescer:
                     continue
                 if r.kind == "fuse":
                     _answer(r.future, self.mgr._fuse_rows_blocking, r.payload, r.key)
+                    continue
+                if r.kind == "fuse_scores":
+                    _answer(r.future, self.mgr._fuse_scores_blocking, r.payload, r.key)
                     continue
                 coll_name, top_k, expr, params_key, group_field, _ = r.key
                 if group_field is not None or self.mgr.collections[coll_name].handle is not cs:
@@ -381,6 +386,8 @@ class SearchCoalescer:
         for r in chunk:
             if kind == "fuse":
                 _answer(r.future, self.mgr._fuse_rows_blocking, r.payload, key)
+            elif kind == "fuse_scores":
+                _answer(r.future, self.mgr._fuse_scores_blocking, r.payload, key)
             elif kind == "hybrid":
                 _deliver(r.future, None)   # the caller falls back to two searches + a fusion
             elif kind == "encode":
@@ -492,16 +499,18 @@ class SearchCoalescer:
 
     # ------------------------------------------------------------------ hybrid (both searches + RRF of a request)
     def _enqueue_hybrid(self, torch, dev, stream, key, chunk):
-        top_k, expr, drop, rrf_k, mmr = key
+        top_k, expr, drop, rrf_k, mmr = key[:5]
+        fuse = key[5:]          # () = RRF, or ("weighted", norm code of the semantic list, of the sparse list)
         handle = self.mgr.collections["semantic_index"].handle.first
-        ekey = (top_k, rrf_k, mmr)
+        ekey = (top_k, rrf_k, mmr) + fuse
         eng = self._engines.get(ekey)
         if eng is None:
             if len(self._engines) >= 16:
                 self._engines.clear()
+            weighted = {"fusion": "weighted", "norms": (fuse[1], fuse[2], 0)} if fuse else {}
             eng = self._engines[ekey] = HybridSearchEngine(
                 handle, EngineConfig(top_k=top_k, rrf_k=rrf_k, enable_reranking=False,
-                                     fused_k=4 * top_k if mmr else None), device=str(dev))   # MMR: two 2 * top_k lists, whole
+                                     fused_k=4 * top_k if mmr else None, **weighted), device=str(dev))   # MMR: two 2 * top_k lists, whole
         # the fusion weights are per REQUEST (a weight_adapter may pick them per query, reference retrieval.py:251-262):
         # they travel as a [B, 3] operand of the post kernel, so requests with different weights still share the round
         wq = torch.from_numpy(np.array([[r.payload[2], r.payload[3], 0.0] for r in chunk], dtype=np.float64)).to(dev)
@@ -617,3 +626,37 @@ class SearchCoalescer:
         for i, r in enumerate(chunk):
             n = int(on[i])
             _deliver(r.future, (oi[i, :n].copy(), os_[i, :n].copy(), om[i, :n].copy()))
+
+    # ------------------------------------------------------------------ weighted score fusion
+    def _enqueue_fuse_scores(self, torch, dev, stream, key, chunk):
+        """The weighted score fusions of a round in ONE hr_fuse_scores_dev: key = the three norm codes, payload =
+        (((rows, scores) x 3), (wa, wb, wc)); the weights travel as the [B, 3] per-query operand."""
+        from . import _native as nat
+        B = len(chunk)
+        k = [max(len(r.payload[0][m][0]) for r in chunk) for m in range(3)]
+        k[0] = max(1, k[0])
+        total = sum(k)
+        ids = np.full((B, total), -1, dtype=np.int64)
+        sc = np.zeros((B, total), dtype=np.float32)
+        off = (0, k[0], k[0] + k[1])
+        for i, r in enumerate(chunk):
+            for m, (rows, scores) in enumerate(r.payload[0]):
+                ids[i, off[m]:off[m] + len(rows)] = rows
+                sc[i, off[m]:off[m] + len(rows)] = scores
+        d_ids, d_sc = torch.from_numpy(ids).to(dev), torch.from_numpy(sc).to(dev)
+        wq = torch.from_numpy(np.array([r.payload[1] for r in chunk], dtype=np.float64)).to(dev)
+        li = [d_ids[:, off[m]:off[m] + k[m]].contiguous() if k[m] else None for m in range(3)]
+        ls = [d_sc[:, off[m]:off[m] + k[m]].contiguous() if k[m] else None for m in range(3)]
+        oi = torch.empty((B, total), dtype=torch.int64, device=dev)
+        os_ = torch.empty((B, total), dtype=torch.float64, device=dev)
+        om = torch.empty((B, total), dtype=torch.int32, device=dev)
+        on = torch.empty((B,), dtype=torch.int32, device=dev)
+        args = []
+        for m in range(3):
+            args += [li[m].data_ptr() if k[m] else 0, ls[m].data_ptr() if k[m] else 0, k[m], int(key[m])]
+        nat.fuse_scores_dev(*args, B, 0.0, 0.0, 0.0, wq.data_ptr(), total, oi.data_ptr(), os_.data_ptr(), om.data_ptr(),
+                            on.data_ptr(), stream.cuda_stream)
+        self.stats["score_fuse_launches"] += 1
+        return {"oi": oi, "os": os_, "om": om, "on": on, "keep": (li, ls, wq)}
+
+    _scatter_fuse_scores = _scatter_fuse

@@ -157,6 +157,10 @@ class EngineConfig:
     # 4 * top_k entries of two 2 * top_k lists, batching.py) asks for more; the rerank step reads fused[:top_k], so this is
     # only valid with enable_reranking=False
     fused_k: Optional[int] = None
+    # "rrf", or "weighted": the post kernel fuses by weighted score fusion (hr_post_args::fusion = 1) with norms = the
+    # HR_NORM_* codes of the semantic, sparse and domain list (the table is in include/hbmrag.h)
+    fusion: str = "rrf"
+    norms: Tuple[int, int, int] = (0, 1, 0)
 
 
 class HybridSearchEngine:
@@ -172,6 +176,10 @@ class HybridSearchEngine:
         self.cfg = config or EngineConfig()
         if self.cfg.fused_k is not None and (self.cfg.enable_reranking or self.cfg.fused_k <= 0):
             raise ValueError("fused_k must be positive and needs enable_reranking=False")
+        if self.cfg.fusion not in ("rrf", "weighted"):
+            raise ValueError(f"fusion must be 'rrf' or 'weighted', got {self.cfg.fusion!r}")
+        if len(self.cfg.norms) != 3 or any(not 0 <= int(c) <= 4 for c in self.cfg.norms):
+            raise ValueError(f"norms must be three HR_NORM_* codes (0..4), got {self.cfg.norms!r}")
         self.group = process_group
         self.dist = None
         self.world, self.rank = 1, 0
@@ -313,6 +321,11 @@ class HybridSearchEngine:
                 a.ids[slot], a.k_in[slot] = b["dom_ids"].data_ptr(), cfg.top_k
             else:
                 a.ids[slot], a.k_in[slot] = b["ids"][m].data_ptr(), kp
+            if cfg.fusion == "weighted":
+                a.norm[slot] = int(cfg.norms[slot])
+                if n_lists == 1:     # the weighted fusion reads the scores beside the ids (RRF never does)
+                    a.scores[slot] = (b["dom_scores"] if slot == 2 else b["scores"][m]).data_ptr()
+        a.fusion = 1 if cfg.fusion == "weighted" else 0
         a.n_lists, a.rrf_k, a.top_k = n_lists, cfg.rrf_k, cfg.fused_k or cfg.top_k
         # the lists of an L2 shard are distances, smallest first: the merge of that modality runs ascending
         a.asc_mask = (1 if dense_ascending(self.h) else 0) | (4 if self.hd is not None and dense_ascending(self.hd) else 0)

@@ -1415,7 +1415,8 @@ class MilvusIndexManager:
 
     async def hybrid_search(self, dense_embedding, sparse_embedding, top_k: int, filters: Optional[str],
                             weights: Sequence[float], rrf_k: int = 60, semantic_params: Optional[Dict] = None,
-                            sparse_params: Optional[Dict] = None, mmr_lambda: Optional[float] = None):
+                            sparse_params: Optional[Dict] = None, mmr_lambda: Optional[float] = None,
+                            fusion: str = "rrf", norms: Optional[Sequence[int]] = None):
         """The semantic search (2 x top_k), the sparse search (2 x top_k) and their rank fusion for ONE request in ONE
         round of the batching front: what `search` + `search` + `fuse_rank_lists_async` return, cut to the fused top_k.
 
@@ -1426,7 +1427,13 @@ class MilvusIndexManager:
 
         With `mmr_lambda` the fused list is diversified before the cut (HybridRetriever._mmr_diversify over all of its up to
         4 x top_k entries, on the device): at most top_k entries in MMR order.  Only a manager created with
-        mmr_on_device=True whose collection lies on one shard answers that; every other one declines."""
+        mmr_on_device=True whose collection lies on one shard answers that; every other one declines.
+
+        fusion="weighted": the two lists are fused by weighted score fusion (hr_post_args::fusion = 1) instead of RRF;
+        norms = the HR_NORM_* codes of the semantic and the sparse list (None = "activation" by the collections' metrics).
+        The torchrun form declines such a request; MMR and the rerank consume the fused scores as they do RRF's."""
+        if fusion not in ("rrf", "weighted"):
+            raise ValueError(f"fusion must be 'rrf' or 'weighted', got {fusion!r}")
         if mmr_lambda is not None and not self.mmr_on_device:
             return None
         sem, spa = self.collections.get("semantic_index"), self.collections.get("sparse_index")
@@ -1437,6 +1444,15 @@ class MilvusIndexManager:
             return None        # (the torchrun form answers in one round when its shards allow it: shards.round_hybrid)
         if mmr_lambda is not None and front.collective:
             return None
+        fuse_key = ()       # RRF: the request key is what it was
+        if fusion == "weighted":
+            if front.collective:
+                return None    # shards.round_hybrid fuses by RRF: the general path serves a weighted request
+            from .retrieval import norm_code
+            codes = tuple(int(c) for c in norms) if norms is not None else (norm_code(sem.metric), norm_code("IP"))
+            if len(codes) != 2 or any(not 0 <= c <= 4 for c in codes):
+                raise ValueError(f"norms must be two HR_NORM_* codes (0..4), got {norms!r}")
+            fuse_key = ("weighted",) + codes
         try:
             if range_bounds(self._search_params(sem, semantic_params), sem.metric) is not None:
                 return None        # a range on the semantic list: the one-round path has no range form
@@ -1451,7 +1467,7 @@ class MilvusIndexManager:
             return None
         w = list(weights) + [0.0] * (2 - len(weights))
         mmr = mmr_lambda is not None
-        fut = front.submit_async("hybrid", (int(top_k), filters, drop, int(rrf_k), mmr),
+        fut = front.submit_async("hybrid", (int(top_k), filters, drop, int(rrf_k), mmr) + fuse_key,
                                  (dense_embedding, payload, float(w[0]), float(w[1]), float(mmr_lambda) if mmr else 0.0))
         try:
             # no timer of its own: the caller (HybridRetriever.retrieve) already bounds the whole request with
@@ -1503,6 +1519,53 @@ class MilvusIndexManager:
         if front is None or front.collective or max(len(x) for x in lists) > 256:
             return self._fuse_output(row_to_id, *await asyncio.to_thread(self._fuse_rows_blocking, lists, key))
         rows, scores, methods = await asyncio.wait_for(front.submit_async("fuse", key, lists),
+                                                       timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
+        return self._fuse_output(row_to_id, rows, scores, methods)
+
+    # ---- weighted score fusion (Milvus' WeightedRanker; the contract is in include/hbmrag.h) -----------------------------
+    @staticmethod
+    def _score_fuse_inputs(row_lists, id_lists, score_lists, weights, norms):
+        """-> (row -> id, (((rows int64, scores float32) x 3), (wa, wb, wc)), key = the three norm codes: requests with equal
+        codes share a launch, the weights are per-query operands of it)."""
+        row_to_id = {}
+        for rows, ids in zip(row_lists, id_lists):
+            for r, i in zip(rows, ids):
+                row_to_id.setdefault(int(r), i)
+        n = len(row_lists)
+        if not (len(score_lists) == n and len(norms) >= n and n <= 3):
+            raise ValueError("one score list and one norm code per list, up to three lists")
+        lists = tuple([(np.asarray(r, dtype=np.int64), np.asarray(s, dtype=np.float32)) for r, s in zip(row_lists, score_lists)]
+                      + [(np.zeros(0, np.int64), np.zeros(0, np.float32))] * (3 - n))
+        if any(len(r) != len(s) for r, s in lists):
+            raise ValueError("a list's rows and scores differ in length")
+        w = list(weights) + [0.0] * (3 - len(weights))
+        codes = [int(c) for c in norms] + [0] * (3 - len(norms))
+        if any(not 0 <= c <= 4 for c in codes):
+            raise ValueError(f"norm codes must be HR_NORM_* (0..4), got {codes}")
+        return row_to_id, (lists, (float(w[0]), float(w[1]), float(w[2]))), tuple(codes)
+
+    def _fuse_scores_blocking(self, payload, key):
+        return self._main.first.fuse_scores(payload[0], key, payload[1])
+
+    def fuse_score_lists(self, row_lists: Sequence[Sequence[int]], id_lists: Sequence[Sequence[Any]],
+                         score_lists: Sequence[Sequence[float]], weights: Sequence[float], norms: Sequence[int]):
+        """Weighted score fusion on the device (csrc/fuse.h) over row numbers and the lists' fp32 scores; norms = one
+        HR_NORM_* code per list.  Returns [(id, float64 score, [list indices])] in fused order."""
+        if self._main is None:
+            raise RuntimeError("no shard handle")
+        row_to_id, payload, key = self._score_fuse_inputs(row_lists, id_lists, score_lists, weights, norms)
+        return self._fuse_output(row_to_id, *self._fuse_scores_blocking(payload, key))
+
+    async def fuse_score_lists_async(self, row_lists, id_lists, score_lists, weights, norms):
+        """The same fusion for a caller on the event loop: concurrent callers share one hr_fuse_scores_dev launch (a
+        kind of its own in the batching front: never one launch with RRF requests)."""
+        if self._main is None:
+            raise RuntimeError("no shard handle")
+        row_to_id, payload, key = self._score_fuse_inputs(row_lists, id_lists, score_lists, weights, norms)
+        front = self._coalescer(self.collections["semantic_index"]) if "semantic_index" in self.collections else None
+        if front is None or front.collective or max(len(x[0]) for x in payload[0]) > 256:
+            return self._fuse_output(row_to_id, *await asyncio.to_thread(self._fuse_scores_blocking, payload, key))
+        rows, scores, methods = await asyncio.wait_for(front.submit_async("fuse_scores", key, payload),
                                                        timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
         return self._fuse_output(row_to_id, rows, scores, methods)
 

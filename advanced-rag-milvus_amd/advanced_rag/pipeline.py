@@ -54,6 +54,9 @@ class PipelineConfig:
     enable_audit_logging: bool = True
     enable_versioning: bool = True
     retention_days: int = 90
+    # RetrievalConfig.fusion / score_normalization: "rrf" as the reference, or "weighted" score fusion
+    fusion: str = "rrf"
+    score_normalization: str = "activation"
 
 
 @dataclass
@@ -87,7 +90,8 @@ class AdvancedRAGPipeline:
         self.retriever = HybridRetriever(
             index_manager=self.index_manager,
             config=RetrievalConfig(hybrid_alpha=self.config.hybrid_alpha, top_k=self.config.top_k,
-                                   enable_reranking=self.config.enable_reranking),
+                                   enable_reranking=self.config.enable_reranking, fusion=self.config.fusion,
+                                   score_normalization=self.config.score_normalization),
             learned_ranker=LearnedRanker())
         self.evaluator = RAGEvaluator()
         self.compliance = ComplianceManager(enable_audit=self.config.enable_audit_logging,

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import asyncio
 import logging
+import math
 import re
 from dataclasses import dataclass
 from datetime import datetime
@@ -24,7 +25,8 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
 
-from ._native import HR_MAX_TOPK   # importing the binding module does not load the library
+from ._native import (HR_MAX_TOPK, HR_NORM_ATAN, HR_NORM_ATAN_DIST, HR_NORM_COSINE, HR_NORM_MINMAX,   # importing the
+                      HR_NORM_MINMAX_DIST)                        # binding module does not load the library
 from .constants import RetrievalConstants
 from .ranker import LearnedRanker
 
@@ -34,6 +36,8 @@ _TROUBLE_WORDS = ("error", "exception", "stack trace", "failed", "failure", "bug
 _SUMMARY_WORDS = ("summarize", "summary", "tl;dr", "overview")
 _METHOD_ORDER = ("semantic", "sparse", "domain")
 FUSED_GROUP_FIELDS = ("doc_id", "chunk_index", "timestamp", "id", "chunk_id")   # what a hit dict shows of the groupable fields
+FUSION_MODES = ("rrf", "weighted")
+SCORE_NORMALIZATIONS = ("activation", "minmax")
 _METHODS_OF_MASK = tuple(tuple(m for b, m in enumerate(_METHOD_ORDER) if (mask >> b) & 1) for mask in range(8))
 
 
@@ -63,7 +67,9 @@ class QueryClassifier:
 
 @dataclass
 class RetrievalConfig:
-    hybrid_alpha: float = 0.7      # carried around but unused by the fusion math (as in the reference)
+    # carried around but unused by the fusion math (as in the reference) — also by fusion="weighted", whose weights are
+    # dense_weight / sparse_weight as for RRF
+    hybrid_alpha: float = 0.7
     top_k: int = 20
     rerank_top_k: int = 5
     enable_reranking: bool = True
@@ -83,8 +89,19 @@ class RetrievalConfig:
     # the dict form of a filter also takes {"field": {"$in": [...]}} and {"$nin": [...]} (-> `field in [..]` / `field not in
     # [..]`).  False = they are refused, as the reference refuses them.
     extended_filter_operators: bool = False
+    # how the modality lists are fused: "rrf" (reciprocal-rank fusion, the reference's) or "weighted" (Milvus'
+    # WeightedRanker: every list's scores normalised into [0, 1], then their weighted sum — score_fuse_lists below)
+    fusion: str = "rrf"
+    # with fusion="weighted": "activation" normalises by the list's metric (COSINE (1 + s) / 2, IP 0.5 + atan(s) / pi, L2
+    # 1 - 2 atan(s) / pi), "minmax" by the smallest and largest score of each list
+    score_normalization: str = "activation"
 
     def __post_init__(self):
+        if self.fusion not in FUSION_MODES:
+            raise ValueError(f"fusion must be one of {', '.join(FUSION_MODES)}, got {self.fusion!r}")
+        if self.score_normalization not in SCORE_NORMALIZATIONS:
+            raise ValueError(f"score_normalization must be one of {', '.join(SCORE_NORMALIZATIONS)}, "
+                             f"got {self.score_normalization!r}")
         if self.group_by_field is not None:
             # refused here, once: inside retrieve() a modality whose search raises degrades to "no hits".  token_count can be
             # grouped on by search(), but a hit does not show it, so the fused list could not be deduplicated on it
@@ -114,6 +131,79 @@ def rrf_rank_lists(lists: Sequence[Sequence[Any]], weights: Sequence[float], rrf
             if ent is None:
                 ent = table[doc_id] = [0.0, []]
             ent[0] += (1.0 / (rrf_k + rank)) * w
+            ent[1].append(li)
+    fused = [(doc_id, ent[0], ent[1]) for doc_id, ent in table.items()]
+    fused.sort(key=lambda t: t[1], reverse=True)  # stable: ties keep first-seen order
+    return fused
+
+
+_PI = float.fromhex("0x1.921fb54442d18p+1")         # 0x400921FB54442D18
+_HALF_PI = float.fromhex("0x1.921fb54442d18p+0")    # 0x3FF921FB54442D18
+_ATAN_SERIES = tuple((-1.0 if i & 1 else 1.0) * (1.0 / (2 * i + 1)) for i in range(12))
+
+
+def canonical_atan(x: float) -> float:
+    """The arctangent of the weighted score fusion: no table, no library call, every step one IEEE fp64 operation
+    (Python floats; math.sqrt is correctly rounded), so that this function and the HIP kernel (csrc/fuse.h) give the same
+    bits.  |x| > 1 is inverted, three half-angle steps, a 12-term series.  Within a few ulp of math.atan."""
+    x = float(x)
+    a = abs(x)
+    inv = a > 1.0
+    if inv:
+        a = 1.0 / a
+    for _ in range(3):
+        a = a / (1.0 + math.sqrt(1.0 + a * a))
+    t = a * a
+    p = _ATAN_SERIES[11]
+    for i in range(10, -1, -1):
+        p = _ATAN_SERIES[i] + t * p
+    r = 8.0 * (a * p)
+    if inv:
+        r = _HALF_PI - r
+    return math.copysign(r, x)
+
+
+def norm_code(metric: str, normalization: str = "activation") -> int:
+    """HR_NORM_* of a list ranked by `metric` ("COSINE", "IP" — also what sparse_index ranks by — or "L2")."""
+    dist = str(metric).upper() == "L2"
+    if normalization == "minmax":
+        return HR_NORM_MINMAX_DIST if dist else HR_NORM_MINMAX
+    if normalization != "activation":
+        raise ValueError(f"score_normalization must be one of {', '.join(SCORE_NORMALIZATIONS)}, got {normalization!r}")
+    return HR_NORM_ATAN_DIST if dist else HR_NORM_COSINE if str(metric).upper() == "COSINE" else HR_NORM_ATAN
+
+
+def normalise_scores(scores: Sequence[float], code: int, atan: Callable[[float], float] = canonical_atan) -> List[float]:
+    """One list's scores -> [0, 1] values by the table of include/hbmrag.h (every operation rounded on its own)."""
+    s = [float(np.float32(x)) for x in scores]      # the lists hold fp32 scores: widened, never rounded again
+    if code == HR_NORM_COSINE:
+        return [(1.0 + v) * 0.5 for v in s]
+    if code == HR_NORM_ATAN:
+        return [0.5 + atan(v) / _PI for v in s]
+    if code == HR_NORM_ATAN_DIST:
+        return [1.0 - (2.0 * atan(v)) / _PI for v in s]
+    if code not in (HR_NORM_MINMAX, HR_NORM_MINMAX_DIST):
+        raise ValueError(f"norm code {code!r} is not one of HR_NORM_*")
+    if not s:
+        return []
+    lo, hi = min(s), max(s)
+    if hi == lo:
+        return [1.0] * len(s)
+    return [(v - lo) / (hi - lo) for v in s] if code == HR_NORM_MINMAX else [(hi - v) / (hi - lo) for v in s]
+
+
+def score_fuse_lists(lists: Sequence[Tuple[Sequence[Any], Sequence[float]]], weights: Sequence[float],
+                     norms: Sequence[int], atan: Callable[[float], float] = canonical_atan):
+    """Host weighted score fusion over ranked (ids, fp32 scores) lists: returns [(id, float64 score, [list indices])]
+    in fused order.  Same arithmetic and ordering as the HIP kernel: score[id] = 0.0, then += n * w (multiply, then add)
+    for every list that holds the id, lists in the order given; the stable descending sort keeps first-seen order."""
+    table: Dict[Any, List] = {}
+    for li, ((ids, scores), w, code) in enumerate(zip(lists, weights, norms)):
+        for doc_id, n in zip(ids, normalise_scores(scores, code, atan)):
+            ent = table.get(doc_id)
+            if ent is None:
+                ent = table[doc_id] = [0.0, []]
+            ent[0] += n * w
             ent[1].append(li)
     fused = [(doc_id, ent[0], ent[1]) for doc_id, ent in table.items()]
     fused.sort(key=lambda t: t[1], reverse=True)  # stable: ties keep first-seen order
@@ -160,7 +250,8 @@ class HybridRetriever:
                                    dense_weight=base.dense_weight, sparse_weight=base.sparse_weight,
                                    enable_mmr=mmr, mmr_lambda=lam, group_by_field=base.group_by_field,
                                    group_size=base.group_size,
-                                   extended_filter_operators=base.extended_filter_operators)
+                                   extended_filter_operators=base.extended_filter_operators,
+                                   fusion=base.fusion, score_normalization=base.score_normalization)
 
         return {
             "default": base,
@@ -259,6 +350,8 @@ class HybridRetriever:
             return None
         cfg = self.config
         extra = {"mmr_lambda": cfg.mmr_lambda} if cfg.enable_mmr else {}
+        if cfg.fusion == "weighted":     # (a default config makes the call it always made)
+            extra.update(fusion="weighted", norms=tuple(self._list_norms()[:2]))
         saved = (cfg.dense_weight, cfg.sparse_weight)
         self._adapt_weights(query)   # the adapter sees only the query: applying it before the searches changes nothing
         try:
@@ -325,9 +418,32 @@ class HybridRetriever:
                                          self.config.semantic_search_params)
 
     # ------------------------------------------------------------------ fusion
+    def _list_norms(self) -> List[int]:
+        """HR_NORM_* of the semantic, sparse and domain lists for fusion="weighted": from the collections' metrics where the
+        manager shows them, else from the request's search params (sparse_index ranks by IP)."""
+        cfg = self.config
+        known = getattr(self.index_manager, "collections", None)
+
+        def metric(name: str) -> str:
+            coll = known.get(name) if isinstance(known, dict) else None
+            return getattr(coll, "metric", None) or (cfg.semantic_search_params or {}).get("metric_type", "COSINE")
+
+        n = cfg.score_normalization
+        return [norm_code(metric("semantic_index"), n), norm_code("IP", n), norm_code(metric("domain_index"), n)]
+
     def _rank_fusion(self, hit_lists: Sequence[List[Dict]], weights: Sequence[float]):
         """-> [(position_of_payload (list idx, rank idx), float64 score, [list indices])] in fused order."""
         id_lists = [[h["id"] for h in hits] for hits in hit_lists]
+        if self.config.fusion == "weighted":
+            norms, score_lists = self._list_norms(), [[h["score"] for h in hits] for hits in hit_lists]
+            device_fuse = getattr(self.index_manager, "fuse_score_lists", None)
+            rows = [[h.get("_row") for h in hits] for hits in hit_lists]
+            if device_fuse is not None and all(r is not None for lst in rows for r in lst) and any(rows):
+                try:
+                    return device_fuse(rows, id_lists, score_lists, list(weights), norms)
+                except Exception:  # pragma: no cover - fall through to the host arithmetic
+                    logger.exception("device score fusion failed; using host arithmetic")
+            return score_fuse_lists(list(zip(id_lists, score_lists)), weights, norms)
         device_fuse = getattr(self.index_manager, "fuse_rank_lists", None)
         if device_fuse is not None:
             rows = [[h.get("_row") for h in hits] for hits in hit_lists]
@@ -349,13 +465,19 @@ class HybridRetriever:
         retrieve() calls shares one device launch (index_manager.fuse_rank_lists_async); same arithmetic, same result."""
         hit_lists = [semantic_results or [], sparse_results or [], domain_results or []]
         weights = [self.config.dense_weight, self.config.sparse_weight, self.DOMAIN_WEIGHT]
-        device_fuse = getattr(self.index_manager, "fuse_rank_lists_async", None)
+        weighted = self.config.fusion == "weighted"
+        device_fuse = getattr(self.index_manager, "fuse_score_lists_async" if weighted else "fuse_rank_lists_async", None)
         ranked = None
         if device_fuse is not None:
             rows = [[h.get("_row") for h in hits] for hits in hit_lists]
             if all(r is not None for lst in rows for r in lst) and any(rows):
                 try:
-                    ranked = await device_fuse(rows, [[h["id"] for h in hits] for hits in hit_lists], list(weights), self.RRF_K)
+                    id_lists = [[h["id"] for h in hits] for hits in hit_lists]
+                    if weighted:
+                        ranked = await device_fuse(rows, id_lists, [[h["score"] for h in hits] for hits in hit_lists],
+                                                   list(weights), self._list_norms())
+                    else:
+                        ranked = await device_fuse(rows, id_lists, list(weights), self.RRF_K)
                 except Exception:  # pragma: no cover - fall through to the host arithmetic
                     logger.exception("device rank fusion failed; using host arithmetic")
         if ranked is None:

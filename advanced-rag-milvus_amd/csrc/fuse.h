@@ -1,4 +1,4 @@
-// Reciprocal-rank fusion and the cross-shard top-k merge.
+// Rank fusion (reciprocal-rank and weighted-score), the cross-shard top-k merge and the linear rerank.
 #pragma once
 #include "common.h"
 
@@ -7,7 +7,59 @@ namespace hbmrag {
 constexpr int kFuseMax = 3 * HR_MAX_TOPK;  // entries per query across the three lists
 constexpr size_t kMergeLdsMax = 60 * 1024;  // LDS staging of the cross-shard merge (~5000 entries); larger merges take the global form
 
-// One block (256 threads) per query.  Restates HybridRetriever._fuse_results
+// What one list entry adds to its id's fused score before the list's weight is applied: the only thing in which the
+// two fusions differ.  RrfContribution: 1 / (k + rank), no score is read.  ScoreContribution (weighted score fusion,
+// Milvus' WeightedRanker): the entry's own score, normalised into [0, 1] by the list's code (HR_NORM_*).
+struct RrfContribution {
+    static constexpr bool kScores = false;
+    int rrf_k;
+};
+struct ScoreContribution {
+    static constexpr bool kScores = true;
+    const float* sc[3];   // [B][k] scores beside the three id lists (NULL where the list has k = 0)
+    int norm[3];          // HR_NORM_* per list
+};
+
+// Canonical arctangent: no table and no library call, every operation a separately rounded IEEE fp64 one (division
+// and square root correctly rounded), so that the host restatement (retrieval.canonical_atan) gives the same bits.
+// |x| > 1 is inverted, three half-angle steps bring the argument below tan(pi / 32), a 12-term series does the rest.
+__device__ inline double canonical_atan(double x) {
+    double a = fabs(x);
+    const bool inv = a > 1.0;
+    if (inv) a = 1.0 / a;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a = a / __dadd_rn(1.0, __dsqrt_rn(__dadd_rn(1.0, __dmul_rn(a, a))));
+    const double t = __dmul_rn(a, a);
+    double p = -(1.0 / 23.0);
+    p = __dadd_rn(1.0 / 21.0, __dmul_rn(t, p));
+    p = __dadd_rn(-(1.0 / 19.0), __dmul_rn(t, p));
+    p = __dadd_rn(1.0 / 17.0, __dmul_rn(t, p));
+    p = __dadd_rn(-(1.0 / 15.0), __dmul_rn(t, p));
+    p = __dadd_rn(1.0 / 13.0, __dmul_rn(t, p));
+    p = __dadd_rn(-(1.0 / 11.0), __dmul_rn(t, p));
+    p = __dadd_rn(1.0 / 9.0, __dmul_rn(t, p));
+    p = __dadd_rn(-(1.0 / 7.0), __dmul_rn(t, p));
+    p = __dadd_rn(1.0 / 5.0, __dmul_rn(t, p));
+    p = __dadd_rn(-(1.0 / 3.0), __dmul_rn(t, p));
+    p = __dadd_rn(1.0, __dmul_rn(t, p));
+    double r = __dmul_rn(8.0, __dmul_rn(a, p));
+    if (inv) r = __dsub_rn(0x1.921fb54442d18p+0, r);   // pi / 2 = 0x3FF921FB54442D18
+    return copysign(r, x);
+}
+
+// One entry's score s of a list with smallest / largest score lo / hi -> its normalised value (include/hbmrag.h has the table).
+__device__ inline double fuse_normalise(int code, double s, double lo, double hi) {
+    constexpr double kPi = 0x1.921fb54442d18p+1;   // 0x400921FB54442D18
+    switch (code) {
+    case HR_NORM_COSINE: return __dmul_rn(__dadd_rn(1.0, s), 0.5);
+    case HR_NORM_ATAN: return __dadd_rn(0.5, canonical_atan(s) / kPi);
+    case HR_NORM_ATAN_DIST: return __dsub_rn(1.0, __dmul_rn(2.0, canonical_atan(s)) / kPi);
+    case HR_NORM_MINMAX: return hi == lo ? 1.0 : __dsub_rn(s, lo) / __dsub_rn(hi, lo);
+    default: return hi == lo ? 1.0 : __dsub_rn(hi, s) / __dsub_rn(hi, lo);   // HR_NORM_MINMAX_DIST
+    }
+}
+
+// One block (256 threads) per query.  With RrfContribution it restates HybridRetriever._fuse_results
 // (reference src/advanced_rag/retrieval.py:421-491) operation for operation:
 //   rrf = 1.0 / (k + rank)            (float64 division)
 //   score[id] += rrf * weight          (float64 multiply, then add; no FMA)
@@ -15,11 +67,16 @@ constexpr size_t kMergeLdsMax = 60 * 1024;  // LDS staging of the cross-shard me
 // list that saw it first (dict insertion order), and the final order is the
 // stable descending sort of the scores (list.sort(reverse=True)): ties keep
 // insertion order.  Outputs the first top_k fused entries.
-// (The body is a device function so that the stand-alone kernel and the fused post-exchange kernel below run the
+// With ScoreContribution the normalised score of the entry stands in place of rrf and nothing else changes: the
+// lists' scores are staged in sc[] as doubles, lists with a min-max code get a block min / max (one wave per list),
+// every entry is normalised in place, and an id's owning entry then overwrites its own slot with the fused score
+// (it reads its own slot and slots of entries that own nothing, which nobody writes).
+// (The body is a device function so that the stand-alone kernels and the fused post-exchange kernel below run the
 // very same instructions; q = the query this 256-thread block fuses.)
-__device__ inline void rrf_fuse_block(
+template <class C>
+__device__ inline void fuse_block(
     int q, const int64_t* __restrict__ ids_a, int ka, const int64_t* __restrict__ ids_b, int kb,
-    const int64_t* __restrict__ ids_c, int kc, double wa, double wb, double wc, int rrf_k,
+    const int64_t* __restrict__ ids_c, int kc, double wa, double wb, double wc, const C& c,
     int top_k, int64_t* __restrict__ out_ids, double* __restrict__ out_scores,
     int32_t* __restrict__ out_methods, int32_t* __restrict__ n_out) {
     __shared__ int64_t id[kFuseMax];
@@ -44,6 +101,38 @@ __device__ inline void rrf_fuse_block(
     for (int i = tid; i < na; i += 256) id[i] = la[i];
     for (int i = tid; i < nb; i += 256) id[na + i] = lb[i];
     for (int i = tid; i < nc; i += 256) id[na + nb + i] = lc[i];
+    if constexpr (C::kScores) {
+        __shared__ double s_lo[3], s_hi[3];
+        const int len[3] = {na, nb, nc}, off[3] = {0, na, na + nb}, kk[3] = {ka, kb, kc};
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+            for (int i = tid; i < len[l]; i += 256) sc[off[l] + i] = (double)c.sc[l][(int64_t)q * kk[l] + i];
+        __syncthreads();
+        const int wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+        for (int l = 0; l < 3; ++l) {
+            if (wave != l || c.norm[l] < HR_NORM_MINMAX) continue;   // wave l takes list l: the branch is wave-uniform
+            double lo = HUGE_VAL, hi = -HUGE_VAL;
+            for (int i = lane; i < len[l]; i += 64) {
+                const double v = sc[off[l] + i];
+                lo = v < lo ? v : lo;
+                hi = v > hi ? v : hi;
+            }
+            for (int d = 32; d; d >>= 1) {
+                const double o_lo = __shfl_xor(lo, d), o_hi = __shfl_xor(hi, d);
+                lo = o_lo < lo ? o_lo : lo;
+                hi = o_hi > hi ? o_hi : hi;
+            }
+            if (lane == 0) { s_lo[l] = lo; s_hi[l] = hi; }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int l = 0; l < 3; ++l) {
+            const bool mm = c.norm[l] >= HR_NORM_MINMAX;
+            const double lo = mm ? s_lo[l] : 0.0, hi = mm ? s_hi[l] : 0.0;
+            for (int i = tid; i < len[l]; i += 256) sc[off[l] + i] = fuse_normalise(c.norm[l], sc[off[l] + i], lo, hi);
+        }
+    }
     __syncthreads();
     // a entries own themselves (ids inside one list are unique: one hit per row)
     for (int i = tid; i < na; i += 256) owner[i] = -1;
@@ -77,14 +166,18 @@ __device__ inline void rrf_fuse_block(
     }
     __syncthreads();
     const int n_ids = na + s_new_c;
-    // scores, accumulated per owning entry in list order a, b, c
+    // scores, accumulated per owning entry in list order a, b, c; rank = position in its list, ent = its index in sc[]
+    auto contribution = [&](int rank, int ent) -> double {
+        if constexpr (C::kScores) return sc[ent];
+        else return 1.0 / (double)(c.rrf_k + rank + 1);
+    };
     for (int e = tid; e < na + nb + nc; e += 256) {
         if (owner[e] >= 0) continue;  // this entry's id was opened by an earlier list
         double s = 0.0;
         int m = 0;
         const int64_t me = id[e];
         if (e < na) {
-            s = __dadd_rn(s, __dmul_rn(1.0 / (double)(rrf_k + e + 1), wa));
+            s = __dadd_rn(s, __dmul_rn(contribution(e, e), wa));
             m |= HR_METHOD_SEMANTIC;
         }
         if (e < na + nb) {
@@ -93,7 +186,7 @@ __device__ inline void rrf_fuse_block(
             if (e >= na) r = e - na;
             else for (int j = nb - 1; j >= 0; --j) r = (owner[na + j] == e) ? j : r;   // the b entry that points here (at most one)
             if (r >= 0) {
-                s = __dadd_rn(s, __dmul_rn(1.0 / (double)(rrf_k + r + 1), wb));
+                s = __dadd_rn(s, __dmul_rn(contribution(r, na + r), wb));
                 m |= HR_METHOD_SPARSE;
             }
         }
@@ -102,7 +195,7 @@ __device__ inline void rrf_fuse_block(
             if (e >= na + nb) r = e - na - nb;
             else for (int j = nc - 1; j >= 0; --j) r = (owner[na + nb + j] == e) ? j : r;
             if (r >= 0) {
-                s = __dadd_rn(s, __dmul_rn(1.0 / (double)(rrf_k + r + 1), wc));
+                s = __dadd_rn(s, __dmul_rn(contribution(r, na + nb + r), wc));
                 m |= HR_METHOD_DOMAIN;
             }
         }
@@ -142,8 +235,24 @@ __global__ __launch_bounds__(256) void rrf_fuse_kernel(
     const int64_t* __restrict__ ids_c, int kc, double wa, double wb, double wc, int rrf_k,
     int top_k, int64_t* __restrict__ out_ids, double* __restrict__ out_scores,
     int32_t* __restrict__ out_methods, int32_t* __restrict__ n_out) {
-    rrf_fuse_block(blockIdx.x, ids_a, ka, ids_b, kb, ids_c, kc, wa, wb, wc, rrf_k, top_k, out_ids, out_scores,
-                   out_methods, n_out);
+    fuse_block(blockIdx.x, ids_a, ka, ids_b, kb, ids_c, kc, wa, wb, wc, RrfContribution{rrf_k}, top_k, out_ids, out_scores,
+               out_methods, n_out);
+}
+
+// Weighted score fusion of a batch: the lists' scores and norm codes travel in the ScoreContribution; w_query (optional)
+// holds [B][3] weights that replace wa, wb, wc per query.
+__global__ __launch_bounds__(256) void score_fuse_kernel(
+    const int64_t* __restrict__ ids_a, int ka, const int64_t* __restrict__ ids_b, int kb,
+    const int64_t* __restrict__ ids_c, int kc, ScoreContribution c, double wa, double wb, double wc,
+    const double* __restrict__ w_query, int top_k, int64_t* __restrict__ out_ids, double* __restrict__ out_scores,
+    int32_t* __restrict__ out_methods, int32_t* __restrict__ n_out) {
+    const int q = blockIdx.x;
+    if (w_query) {
+        wa = w_query[3 * (int64_t)q];
+        wb = w_query[3 * (int64_t)q + 1];
+        wc = w_query[3 * (int64_t)q + 2];
+    }
+    fuse_block(q, ids_a, ka, ids_b, kb, ids_c, kc, wa, wb, wc, c, top_k, out_ids, out_scores, out_methods, n_out);
 }
 
 // Cross-shard merge of one query: n_lists per-shard lists of k_in (score, id) pairs, each SORTED by score
@@ -340,6 +449,8 @@ struct PostArgs {
     hr_post_args a;
 };
 
+// WEIGHTED picks the fusion (hr_post_args::fusion), on the host: each instantiation holds one set of the fuse body's LDS arrays.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void post_lists_kernel(PostArgs pa) {
     extern __shared__ int64_t merge_lds[];
     const hr_post_args& a = pa.a;
@@ -370,9 +481,20 @@ __global__ __launch_bounds__(256) void post_lists_kernel(PostArgs pa) {
         w1 = a.w_query[3 * (int64_t)q + 1];
         w2 = a.w_query[3 * (int64_t)q + 2];
     }
-    rrf_fuse_block(q, fuse_ids[0], a.k_fuse[0], fuse_ids[1], a.k_in[1] ? a.k_fuse[1] : 0, fuse_ids[2],
-                   a.k_in[2] ? a.k_fuse[2] : 0, w0, w1, w2, a.rrf_k, a.top_k, a.fused_ids, a.fused_scores,
-                   a.fused_methods, a.fused_n);
+    const int kf1 = a.k_in[1] ? a.k_fuse[1] : 0, kf2 = a.k_in[2] ? a.k_fuse[2] : 0;
+    if constexpr (WEIGHTED) {
+        // the scores beside the fused ids: the lists as they came, or what the merge above has just written
+        ScoreContribution c;
+        for (int m = 0; m < 3; ++m) {
+            c.sc[m] = !a.k_in[m] ? nullptr : a.n_lists > 1 ? a.merged_scores[m] : a.scores[m];
+            c.norm[m] = a.norm[m];
+        }
+        fuse_block(q, fuse_ids[0], a.k_fuse[0], fuse_ids[1], kf1, fuse_ids[2], kf2, w0, w1, w2, c, a.top_k, a.fused_ids,
+                   a.fused_scores, a.fused_methods, a.fused_n);
+    } else {
+        fuse_block(q, fuse_ids[0], a.k_fuse[0], fuse_ids[1], kf1, fuse_ids[2], kf2, w0, w1, w2, RrfContribution{a.rrf_k},
+                   a.top_k, a.fused_ids, a.fused_scores, a.fused_methods, a.fused_n);
+    }
     if (!a.rerank) return;
     __syncthreads();
     rerank_linear_block(q, a.fused_ids, a.fused_scores, a.fused_methods, a.fused_n, a.recency, a.top_k, a.base_w,

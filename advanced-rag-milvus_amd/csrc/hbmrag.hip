@@ -123,7 +123,7 @@ struct Workspace : WorkspaceQueues {
     DevBuf d_radius, d_rfilter;                   // range search, host form: the callers' bounds
     DevBuf d_q, d_ids, d_scores, d_mask;          // host-form staging
     DevBuf d_qptr, d_qidx, d_qval;                // sparse query staging
-    DevBuf f_ids, f_out_ids, f_out_scores, f_out_meth, f_n;  // hr_fuse_rrf staging
+    DevBuf f_ids, f_sc, f_out_ids, f_out_scores, f_out_meth, f_n;  // hr_fuse_rrf / hr_fuse_scores staging
     ~Workspace() { delete sparse_ws; }
 };
 
@@ -1354,7 +1354,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11400; }  // 1.14.0: HR_COL_TOKENS / HR_OP_MATCH, the keyword leaf of hr_filter_eval_expr_dev
+int hr_version(void) { return 11500; }  // 1.15.0: weighted score fusion (hr_fuse_scores, hr_fuse_scores_dev, hr_post_args::fusion / norm)
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2028,6 +2028,28 @@ int hr_fuse_rrf_dev(const int64_t* d_ids_a, int ka, const int64_t* d_ids_b, int 
     return HR_OK;
 }
 
+int hr_fuse_scores_dev(const int64_t* d_ids_a, const float* d_sc_a, int ka, int norm_a, const int64_t* d_ids_b,
+                       const float* d_sc_b, int kb, int norm_b, const int64_t* d_ids_c, const float* d_sc_c, int kc,
+                       int norm_c, int B, double wa, double wb, double wc, const double* d_w_query, int top_k,
+                       int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_methods, int32_t* d_n_out, void* stream) {
+    if (B <= 0 || ka < 0 || kb < 0 || kc < 0 || top_k <= 0) return fail(nullptr, HR_EINVAL, "bad fuse sizes");
+    if (ka > HR_MAX_TOPK || kb > HR_MAX_TOPK || kc > HR_MAX_TOPK)
+        return fail(nullptr, HR_ELIMIT, "list longer than HR_MAX_TOPK=%d", HR_MAX_TOPK);
+    if ((ka && !d_ids_a) || (kb && !d_ids_b) || (kc && !d_ids_c) || !d_out_ids || !d_out_scores || !d_out_methods || !d_n_out)
+        return fail(nullptr, HR_EINVAL, "null buffer");
+    if ((ka && !d_sc_a) || (kb && !d_sc_b) || (kc && !d_sc_c)) return fail(nullptr, HR_EINVAL, "null score buffer of a used list");
+    const int norm[3] = {norm_a, norm_b, norm_c}, k[3] = {ka, kb, kc};
+    for (int m = 0; m < 3; ++m)
+        if (k[m] && (norm[m] < HR_NORM_COSINE || norm[m] > HR_NORM_MINMAX_DIST))
+            return fail(nullptr, HR_EINVAL, "norm code %d of list %d is not one of HR_NORM_*", norm[m], m);
+    ScoreContribution c{{d_sc_a, d_sc_b, d_sc_c}, {norm_a, norm_b, norm_c}};
+    hipLaunchKernelGGL(score_fuse_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, d_ids_a, ka, d_ids_b, kb, d_ids_c, kc,
+                       c, wa, wb, wc, d_w_query, top_k, d_out_ids, d_out_scores, d_out_methods, d_n_out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "score_fuse_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
 namespace {
 int merge_topk_impl(const float* d_scores, const int64_t* d_ids, int n_lists, int64_t score_stride, int64_t id_stride,
                     int B, int k_in, int k_out, int64_t* d_out_ids, float* d_out_scores, void* stream, int asc) {
@@ -2061,12 +2083,15 @@ int hr_post_lists_dev(const hr_post_args* a, int B, void* stream) {
     if (!a || B <= 0) return fail(nullptr, HR_EINVAL, "bad post-lists arguments");
     if (a->n_lists < 1 || a->top_k <= 0 || a->k_in[0] <= 0) return fail(nullptr, HR_EINVAL, "bad post-lists sizes");
     if (a->asc_mask & ~7) return fail(nullptr, HR_EINVAL, "asc_mask has bits beyond the three modalities");
+    if (a->fusion < 0 || a->fusion > 1) return fail(nullptr, HR_EINVAL, "fusion must be 0 (RRF) or 1 (weighted)");
     size_t lds = 0;
     for (int m = 0; m < 3; ++m) {
         if (a->k_in[m] < 0 || a->k_in[m] > HR_MAX_TOPK || a->k_fuse[m] > HR_MAX_TOPK)
             return fail(nullptr, HR_ELIMIT, "list longer than HR_MAX_TOPK=%d", HR_MAX_TOPK);
         if (!a->k_in[m]) continue;
         if (!a->ids[m] || a->k_fuse[m] <= 0) return fail(nullptr, HR_EINVAL, "null list / bad k_fuse of modality %d", m);
+        if (a->fusion == 1 && (!a->scores[m] || a->norm[m] < HR_NORM_COSINE || a->norm[m] > HR_NORM_MINMAX_DIST))
+            return fail(nullptr, HR_EINVAL, "weighted fusion needs the scores and a HR_NORM_* code of modality %d", m);
         if (a->n_lists == 1) {
             if (a->k_fuse[m] != a->k_in[m]) return fail(nullptr, HR_EINVAL, "k_fuse must equal k_in without a merge");
         } else {
@@ -2085,7 +2110,10 @@ int hr_post_lists_dev(const hr_post_args* a, int B, void* stream) {
         return fail(nullptr, HR_EINVAL, "bad flag buffers");
     PostArgs pa;
     pa.a = *a;
-    hipLaunchKernelGGL(post_lists_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, pa);
+    if (a->fusion == 1)
+        hipLaunchKernelGGL(post_lists_kernel<true>, dim3(B), dim3(256), lds, (hipStream_t)stream, pa);
+    else
+        hipLaunchKernelGGL(post_lists_kernel<false>, dim3(B), dim3(256), lds, (hipStream_t)stream, pa);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "post_lists_kernel: %s", hipGetErrorString(e));
     return HR_OK;
@@ -3240,6 +3268,59 @@ int hr_fuse_rrf(hr_index* h, const int64_t* ids_a, int na, const int64_t* ids_b,
     HR_TRY(hr_fuse_rrf_dev(d, ka, nb ? d + ka : nullptr, nb, nc ? d + ka + nb : nullptr, nc, 1, wa, wb, wc, rrf_k, total,
                            ws->f_out_ids.as<int64_t>(), ws->f_out_scores.as<double>(), ws->f_out_meth.as<int32_t>(),
                            ws->f_n.as<int32_t>(), s));
+    HIP_TRY(h, hipMemcpyAsync(out_ids, ws->f_out_ids.p, (size_t)total * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out_scores, ws->f_out_scores.p, (size_t)total * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out_methods, ws->f_out_meth.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(n_out, ws->f_n.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return HR_OK;
+}
+
+int hr_fuse_scores(hr_index* h, const int64_t* ids_a, const float* sc_a, int na, int norm_a, const int64_t* ids_b,
+                   const float* sc_b, int nb, int norm_b, const int64_t* ids_c, const float* sc_c, int nc, int norm_c,
+                   double wa, double wb, double wc, int64_t* out_ids, double* out_scores, int32_t* out_methods,
+                   int32_t* n_out) {
+    if (!h) return fail(nullptr, HR_EINVAL, "null handle");
+    if (na < 0 || nb < 0 || nc < 0) return fail(h, HR_EINVAL, "negative list length");
+    if (na > HR_MAX_TOPK || nb > HR_MAX_TOPK || nc > HR_MAX_TOPK)
+        return fail(h, HR_ELIMIT, "list longer than HR_MAX_TOPK=%d", HR_MAX_TOPK);
+    if ((na && (!ids_a || !sc_a)) || (nb && (!ids_b || !sc_b)) || (nc && (!ids_c || !sc_c)))
+        return fail(h, HR_EINVAL, "null list or score buffer of a used list");
+    const int norm[3] = {norm_a, norm_b, norm_c}, len[3] = {na, nb, nc};
+    for (int m = 0; m < 3; ++m)
+        if (len[m] && (norm[m] < HR_NORM_COSINE || norm[m] > HR_NORM_MINMAX_DIST))
+            return fail(h, HR_EINVAL, "norm code %d of list %d is not one of HR_NORM_*", norm[m], m);
+    if (na + nb + nc == 0) {
+        if (n_out) *n_out = 0;
+        return HR_OK;
+    }
+    if (!out_ids || !out_scores || !out_methods || !n_out) return fail(h, HR_EINVAL, "null buffer");
+    DeviceGuard dg(h->device);
+    PooledWs pooled(h);
+    Workspace* ws = pooled.w;
+    if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
+    hipStream_t s = ws->stream;
+    const int total = na + nb + nc;
+    const int ka = std::max(na, 1);  // kernel wants a readable first list
+    std::vector<int64_t> staged((size_t)ka + nb + nc, -1);
+    std::vector<float> staged_sc(staged.size(), 0.f);
+    if (na) std::memcpy(staged.data(), ids_a, (size_t)na * 8), std::memcpy(staged_sc.data(), sc_a, (size_t)na * 4);
+    if (nb) std::memcpy(staged.data() + ka, ids_b, (size_t)nb * 8), std::memcpy(staged_sc.data() + ka, sc_b, (size_t)nb * 4);
+    if (nc) std::memcpy(staged.data() + ka + nb, ids_c, (size_t)nc * 8), std::memcpy(staged_sc.data() + ka + nb, sc_c, (size_t)nc * 4);
+    HIP_TRY(h, ws->f_ids.ensure(staged.size() * 8));
+    HIP_TRY(h, ws->f_sc.ensure(staged.size() * 4));
+    HIP_TRY(h, ws->f_out_ids.ensure((size_t)total * 8));
+    HIP_TRY(h, ws->f_out_scores.ensure((size_t)total * 8));
+    HIP_TRY(h, ws->f_out_meth.ensure((size_t)total * 4));
+    HIP_TRY(h, ws->f_n.ensure(4));
+    HIP_TRY(h, hipMemcpyAsync(ws->f_ids.p, staged.data(), staged.size() * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipMemcpyAsync(ws->f_sc.p, staged_sc.data(), staged.size() * 4, hipMemcpyHostToDevice, s));
+    int64_t* d = ws->f_ids.as<int64_t>();
+    float* ds = ws->f_sc.as<float>();
+    HR_TRY(hr_fuse_scores_dev(d, ds, ka, na ? norm_a : HR_NORM_COSINE, nb ? d + ka : nullptr, nb ? ds + ka : nullptr, nb, norm_b,
+                              nc ? d + ka + nb : nullptr, nc ? ds + ka + nb : nullptr, nc, norm_c, 1, wa, wb, wc, nullptr,
+                              total, ws->f_out_ids.as<int64_t>(), ws->f_out_scores.as<double>(),
+                              ws->f_out_meth.as<int32_t>(), ws->f_n.as<int32_t>(), s));
     HIP_TRY(h, hipMemcpyAsync(out_ids, ws->f_out_ids.p, (size_t)total * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipMemcpyAsync(out_scores, ws->f_out_scores.p, (size_t)total * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(h, hipMemcpyAsync(out_methods, ws->f_out_meth.p, (size_t)total * 4, hipMemcpyDeviceToHost, s));

@@ -261,6 +261,44 @@ HR_API int hr_fuse_rrf(hr_index* h, const int64_t* ids_a, int na, const int64_t*
                 const int64_t* ids_c, int nc, double wa, double wb, double wc, int rrf_k,
                 int64_t* out_ids, double* out_scores, int32_t* out_methods, int32_t* n_out);
 
+/* ---- weighted score fusion (the second ranker of a hybrid search, beside RRF) ---------------------------------------
+ * Every list's scores are normalised into [0, 1] and an id's fused score is the weighted sum of its normalised scores.
+ * For an entry with fp32 score x let s = (double)x.  Every operation is a separately rounded IEEE fp64 operation, no
+ * FMA.  The normalisation n is chosen per list:
+ *   HR_NORM_COSINE       (1.0 + s) * 0.5                      COSINE lists
+ *   HR_NORM_ATAN         0.5 + catan(s) / PI                  IP lists, dense or sparse
+ *   HR_NORM_ATAN_DIST    1.0 - (2.0 * catan(s)) / PI          L2 lists (distances, ascending)
+ *   HR_NORM_MINMAX       (s - lo) / (hi - lo)                 any descending list; 1.0 when hi == lo
+ *   HR_NORM_MINMAX_DIST  (hi - s) / (hi - lo)                 L2 lists; 1.0 when hi == lo
+ * lo / hi = the smallest / largest score of the list's valid prefix for that query; PI = 0x400921FB54442D18.  Codes
+ * 0-2 follow the activation functions of Milvus' WeightedRanker, but THIS TABLE is the contract, not Milvus (which also
+ * rounds to float32; fp64 is kept here, as in the RRF path).  catan is a canonical arctangent without tables or library
+ * calls, so that host and device agree bit for bit:
+ *   a = |x|; inv = a > 1.0; if inv: a = 1.0 / a
+ *   3 times: a = a / (1.0 + sqrt(1.0 + a * a))
+ *   t = a * a; c_i = (-1)^i * (1.0 / (2 i + 1)), i = 0..11; p = c_11; for i = 10 .. 0: p = c_i + t * p
+ *   r = 8.0 * (a * p); if inv: r = 0x3FF921FB54442D18 - r; result = copysign(r, x)
+ * Fusion is hr_fuse_rrf's with n in place of 1 / (k + rank): lists are visited a (semantic) -> b (sparse) -> c (domain),
+ * an id keeps the slot of the first list that shows it, score[id] = 0.0, then += n * w_list (multiply, then add) for
+ * every list that holds the id; method bits as in RRF; the final order is the stable descending sort of the fused
+ * scores (ties keep first-seen order).  Weights are any doubles.  Scores must be finite.
+ * HR_EINVAL: a NULL score pointer of a used list, a norm code outside 0..4; HR_ELIMIT: a list longer than HR_MAX_TOPK.
+ * A refused call launches nothing and leaves the outputs alone. */
+enum { HR_NORM_COSINE = 0, HR_NORM_ATAN = 1, HR_NORM_ATAN_DIST = 2, HR_NORM_MINMAX = 3, HR_NORM_MINMAX_DIST = 4 };
+/* One query, host arrays (the form beside hr_fuse_rrf): out arrays hold na+nb+nc entries, *n_out the fused ids. */
+HR_API int hr_fuse_scores(hr_index* h, const int64_t* ids_a, const float* sc_a, int na, int norm_a,
+                   const int64_t* ids_b, const float* sc_b, int nb, int norm_b,
+                   const int64_t* ids_c, const float* sc_c, int nc, int norm_c, double wa, double wb, double wc,
+                   int64_t* out_ids, double* out_scores, int32_t* out_methods, int32_t* n_out);
+/* A batch, device arrays (the form beside hr_fuse_rrf_dev): ids / scores [B][ka], [B][kb], [B][kc] (k = 0 / NULL for
+ * none; the valid prefix of a list ends at its first id < 0); d_w_query (optional) = [B][3] doubles that replace
+ * wa, wb, wc per query; outputs [B][top_k] ids / fp64 scores / method bitmasks (-1 / 0.0 / 0 padded) and d_n_out[B]. */
+HR_API int hr_fuse_scores_dev(const int64_t* d_ids_a, const float* d_sc_a, int ka, int norm_a,
+                       const int64_t* d_ids_b, const float* d_sc_b, int kb, int norm_b,
+                       const int64_t* d_ids_c, const float* d_sc_c, int kc, int norm_c, int B,
+                       double wa, double wb, double wc, const double* d_w_query, int top_k, int64_t* d_out_ids,
+                       double* d_out_scores, int32_t* d_out_methods, int32_t* d_n_out, void* stream);
+
 /* ---- search (device buffers, asynchronous on `stream`) -------------------------
  * Same results as the host forms.  d_flags[B] (optional) receives 1 when the
  * candidate-generation bound proves the list exact, 0 when the caller must
@@ -425,10 +463,10 @@ HR_API int hr_mask_keep_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out
                             const int64_t* d_keys, const int64_t* d_keep, int n_keep, void* stream);
 
 /* Everything after the per-shard lists of a query batch in ONE launch (one block per query): [hr_merge_topk_dev of
- * every modality's exchanged lists] -> hr_fuse_rrf_dev -> [hr_rerank_linear_dev]; results are bit-identical to the
+ * every modality's exchanged lists] -> hr_fuse_rrf_dev (or hr_fuse_scores_dev: `fusion`) -> [hr_rerank_linear_dev]; results are bit-identical to the
  * separate calls (reference retrieval.py:421-491 fusion, :518-563 rerank, after the server-side shard merge of
  * indexing.py:234-239).  Modality m = 0 semantic, 1 sparse, 2 domain; k_in[m] = 0 leaves a modality out.
- *   n_lists = 1: ids[m] are [B][k_in[m]] lists fused as they are (k_fuse[m] must equal k_in[m]; scores/merged_* unused);
+ *   n_lists = 1: ids[m] are [B][k_in[m]] lists fused as they are (k_fuse[m] must equal k_in[m]; scores/merged_* unused by RRF);
  *   n_lists > 1: ids[m] / scores[m] point at list 0 of modality m inside the gathered buffer, list l lies l*id_stride
  *                int64s / l*score_stride floats further; the merged [B][k_fuse[m]] lists are written to merged_*[m]
  *                and fused.
@@ -470,6 +508,13 @@ typedef struct hr_post_args {
     /* optional: fusion weights per query, [B][3] doubles (semantic, sparse, domain) — the reference lets a
      * weight_adapter choose them per request (retrieval.py:251-262); NULL = `w` for every query of the batch */
     const double* w_query;
+    /* fusion: 0 = reciprocal-rank fusion (rrf_k), 1 = weighted score fusion (hr_fuse_scores_dev) with norm[m] = the
+     * HR_NORM_* code of modality m.  Weighted fusion reads the scores beside the fused ids: scores[m] ([B][k_in[m]],
+     * required then) when n_lists = 1, merged_scores[m] after the merge when n_lists > 1.  Zeros = RRF: the launch and
+     * its operands are what they were before these fields existed.  HR_EINVAL: fusion outside 0..1, a norm code of a
+     * used modality outside 0..4, a NULL scores[m] of a used modality. */
+    int32_t fusion;
+    int32_t norm[3];
 } hr_post_args;
 HR_API int hr_post_lists_dev(const hr_post_args* args, int B, void* stream);
 
