@@ -134,6 +134,47 @@ def deep_window(top_k, offset=0) -> int:
     return int(top_k) + int(offset)
 
 
+class SearchPath:
+    """ONE blocking request's way to its rows: one local GPU shard with the row mask in HBM (`shard` is its ShardHandle;
+    masks are packed CUDA tensors), or a host mask over every shard of the set (`shard` is None: several shards, the
+    torchrun form, stand-ins; masks are bool arrays).  query: the prepared query (a dense vector, or a sparse payload)."""
+
+    def __init__(self, manager: "MilvusIndexManager", coll: "ShardCollection", query, drop: float):
+        self.manager, self.coll, self.query, self.drop = manager, coll, query, drop
+        self.sparse = coll.kind == "sparse"
+        self.shard = manager._device_shard(coll.handle)
+        self._q_host = None
+
+    def base(self, filters: Optional[str]):
+        """The row mask of a filter expression + tombstones (None = all rows): cached and shared, never written."""
+        if self.shard is not None:
+            return self.manager._device_row_mask(filters, self.coll.kind)
+        return self.manager._row_mask(filters)
+
+    def search(self, mask, k: int, bounds: Optional[Tuple[float, float]] = None, offset: Optional[int] = None):
+        """(ids [k], scores [k]) under `mask` through the host forms, which are exact.  bounds: the range form (dense
+        only); offset: entries offset .. offset + k - 1 through the deep forms."""
+        on, m = (self.coll.handle, (mask,)) if self.shard is None else \
+            (self.shard, (None, mask.data_ptr() if mask is not None else 0))       # a ShardHandle: (rowmask, d_rowmask)
+        if self.sparse:
+            if offset is None:
+                ids, sc = on.search_sparse([self.query], k, self.drop, *m)
+            else:
+                ids, sc = on.search_sparse_deep([self.query], k, offset, self.drop, *m)
+            return ids[0], sc[0]
+        if self._q_host is None:
+            self._q_host = dense_rows_host([self.query])
+        if offset is not None:
+            ids, sc = on.search_dense_deep(self._q_host, k, offset, *m)
+        elif bounds is None:
+            ids, sc = on.search_dense(self._q_host, k, *m)
+        elif self.shard is not None:
+            ids, sc = on.search_dense_range(self._q_host, k, bounds[0], bounds[1], *m)
+        else:
+            ids, sc = on.search_dense(self._q_host, k, *m, bounds=bounds)
+        return ids[0], sc[0]
+
+
 class ShardCollection:
     """What `manager.collections[name]` holds: a named view of one ShardSet (the
     collection's shard handles, one per device) with the handful of Collection methods the reference calls
@@ -194,7 +235,7 @@ class MilvusIndexManager:
                  group_members: bool = False):
         self.host, self.port = host, port
         # grouping searches with group_size > 1 (the best group_size rows of each of the top_k best groups): off = such a
-        # request is refused, as before the second phase of _grouped_members_blocking existed
+        # request is refused, as before the fill phase of device_groups.grouped_search existed
         self.group_members = bool(group_members)
         # MMR profiles (troubleshooting, analysis) through the one-round path: the rows' token sets are mirrored into HBM
         # and hr_mmr_select_dev diversifies the fused lists there (hybrid_search(mmr_lambda=...)); off = the general path
@@ -377,6 +418,14 @@ class MilvusIndexManager:
             self._dev_filters = DeviceFilters(None if self._synthetic_rows else self._cols, main.first.device)
         return self._dev_filters
 
+    def _device_shard(self, shard_set):
+        """The ShardHandle of a shard set that is ONE local GPU shard whose filter masks live in HBM (the row mask of a
+        search never leaves the device), or None: several shards, the torchrun form, stand-ins without a device — those
+        take a host mask over every shard.  The evaluator asked for is the main collection's, for the domain set too."""
+        if getattr(shard_set, "n_shards", 1) == 1 and hasattr(shard_set, "handles") and self._filters_on_device() is not None:
+            return shard_set.first
+        return None
+
     def _token_sets_on_device(self):
         """The HBM mirror of the rows' token sets (what hr_mmr_select_dev reads), on the main shard's device."""
         if self._dev_tokens is None:
@@ -532,7 +581,7 @@ class MilvusIndexManager:
         keep = np.ones(n, dtype=bool)
         keep[: self._deleted.shape[0]] = ~self._deleted[:n]
         d_keep = 0
-        if self._filters_on_device() is not None and self._main.n_shards == 1:
+        if self._device_shard(self._main) is not None:      # (every set left here has `handles`: the loop above)
             d_mask = self._global_device_mask(None)      # alive rows, packed, already in HBM
             d_keep = d_mask.data_ptr() if d_mask is not None else 0
         # the same mask over the rows each set has: row r of one stays row r of the other
@@ -951,65 +1000,41 @@ class MilvusIndexManager:
                                group_by_field: Optional[str] = None, bounds: Optional[Tuple[float, float]] = None,
                                group_size: int = 1):
         """(row ids [k], scores [k]) of ONE query through the host forms (which escalate until the list is proven).  With
-        group_by_field: the exact grouped ranking (_grouped_lists_blocking), as many entries as there are groups, at most k —
-        with group_size > 1 up to group_size entries per group, a group's entries adjacent (_grouped_members_blocking).
+        group_by_field: the exact grouped ranking (device_groups.grouped_search), as many entries as there are groups, at
+        most k — with group_size > 1 up to group_size entries per group, a group's entries adjacent.
         bounds = (radius, range_filter) of a range search on a dense collection: the range forms of the same paths."""
         coll = self.collections[collection_name]
-        drop = float((params.get("params") or params).get("drop_ratio_search", 0.0))
-        if group_by_field is not None and group_size > 1:
-            return self._grouped_members_blocking(query, coll, int(top_k), filters, drop, group_by_field, int(group_size))
+        path = SearchPath(self, coll, query, float((params.get("params") or params).get("drop_ratio_search", 0.0)))
         if group_by_field is not None:
-            return self._grouped_lists_blocking(query, coll, int(top_k), filters, drop, group_by_field)
-        if bounds is not None:
-            return self._range_lists_blocking(query, coll, int(top_k), filters, bounds)
-        if getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and self._filters_on_device() is not None:
-            # one local GPU shard: the mask never leaves the device
-            h = coll.handle.first
-            d_mask = self._device_row_mask(filters, coll.kind)
-            ptr = d_mask.data_ptr() if d_mask is not None else 0
-            if coll.kind == "sparse":
-                ids, sc = h.search_sparse([query], top_k, drop, None, ptr)
-            elif hasattr(query, "is_cuda") and query.is_cuda and d_mask is None:
-                ids, sc = self._search_dense_device(h, query, top_k)
-            else:
-                ids, sc = h.search_dense(dense_rows_host([query]), top_k, None, ptr)
+            from .device_groups import grouped_search
+            window = self.group_window(int(top_k), int(group_size))
+            return grouped_search(self, path, int(top_k), filters, group_by_field, int(group_size), window)
+        k = top_k if bounds is None else int(top_k)    # (a range search has always taken int(top_k), a plain one top_k as given)
+        mask = path.base(filters)
+        if path.shard is not None and mask is None and not path.sparse and getattr(query, "is_cuda", False):
+            ids, sc = self._search_dense_device(path.shard, query, k, bounds)
             return ids[0], sc[0]
-        mask = self._row_mask(filters)
-        if coll.kind == "sparse":
-            ids, sc = coll.handle.search_sparse([query], top_k, drop, mask)
-        else:
-            ids, sc = coll.handle.search_dense(dense_rows_host([query]), top_k, mask)
-        return ids[0], sc[0]
-
-    def _range_lists_blocking(self, query, coll, top_k: int, filters: Optional[str], bounds: Tuple[float, float]):
-        """_search_lists_blocking for a range search on a dense collection: the same three paths (mask in HBM, query in
-        HBM, host mask over every shard) through hr_search_dense_range / hr_search_dense_range_dev."""
-        radius, range_filter = bounds
-        if getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and self._filters_on_device() is not None:
-            h = coll.handle.first
-            d_mask = self._device_row_mask(filters, coll.kind)
-            if hasattr(query, "is_cuda") and query.is_cuda and d_mask is None:
-                ids, sc = self._search_dense_range_device(h, query, top_k, bounds)
-            else:
-                ids, sc = h.search_dense_range(dense_rows_host([query]), top_k, radius, range_filter, None,
-                                               d_mask.data_ptr() if d_mask is not None else 0)
-            return ids[0], sc[0]
-        ids, sc = coll.handle.search_dense(dense_rows_host([query]), top_k, self._row_mask(filters), bounds=bounds)
-        return ids[0], sc[0]
+        return path.search(mask, k, bounds)
 
     @staticmethod
-    def _search_dense_range_device(handle, q_dev, top_k: int, bounds: Tuple[float, float]):
-        """_search_dense_device for a range search: an unproven list (rows within the scan's error of a bound, ties at the
-        candidate cut) is redone through the host form."""
+    def _search_dense_device(handle, q_dev, top_k: int, bounds: Optional[Tuple[float, float]] = None):
+        """Query already in HBM (device-resident embedding cache) and no row mask: device form, no upload, with `bounds`
+        the range form; an unproven list (ties at the candidate cut, rows within the scan's error of a bound) is redone
+        through the host form."""
         import torch
         q = dense_rows_device([q_dev], q_dev.device, handle.dim)
         ids, sc, flag = list_buffers(1, top_k, q.device)
-        rb = torch.tensor(bounds, dtype=torch.float64, device=q.device)
         stream = torch.cuda.current_stream(q.device)
-        handle.search_dense_range_dev(q.data_ptr(), 1, top_k, rb.data_ptr(), rb.data_ptr() + 8, ids.data_ptr(), sc.data_ptr(),
-                                      flag.data_ptr(), 0, stream.cuda_stream)
+        out = (ids.data_ptr(), sc.data_ptr(), flag.data_ptr(), 0, stream.cuda_stream)
+        if bounds is None:
+            handle.search_dense_dev(q.data_ptr(), 1, top_k, *out)
+        else:
+            rb = torch.tensor(bounds, dtype=torch.float64, device=q.device)
+            handle.search_dense_range_dev(q.data_ptr(), 1, top_k, rb.data_ptr(), rb.data_ptr() + 8, *out)
         stream.synchronize()
         if int(flag.item()) != 1:
+            if bounds is None:
+                return handle.search_dense(q.cpu().numpy(), top_k)
             return handle.search_dense_range(q.cpu().numpy(), top_k, bounds[0], bounds[1])
         return ids.cpu().numpy(), sc.cpu().numpy()
 
@@ -1020,237 +1045,6 @@ class MilvusIndexManager:
         if not 1 <= top_k <= HR_MAX_TOPK:
             raise ValueError(f"a grouping search takes 1 <= top_k <= HR_MAX_TOPK = {HR_MAX_TOPK}, got {top_k}")
         return min(HR_MAX_TOPK, GROUP_WINDOW_FACTOR * top_k * group_size)
-
-    def _grouped_lists_blocking(self, query, coll, top_k: int, filters: Optional[str], drop: float, field: str):
-        """The exact grouped ranking of ONE query: the first top_k rows of the collection's ranking (filter expression and
-        tombstones applied) whose group key differs from the key of every row before them -> (rows, scores), as many as
-        there are groups, at most top_k.
-
-        The ranking is read a window of K' rows at a time through the host forms, which are exact.  A window that holds
-        top_k new groups, or fewer than K' rows (the search ran out of qualifying rows), ends the loop.  Otherwise the
-        first row of every group of the window has been taken, so no other row of those groups can ever be selected:
-        they leave the working mask and the next window is searched without them.  The remaining ranking is the old one
-        minus rows that could not be selected, so the concatenation is the grouped ranking; every continuation removes at
-        least one whole group, so the loop ends."""
-        window = self.group_window(top_k)
-        n = self.num_rows
-        sparse = coll.kind == "sparse"
-        on_device = getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and \
-            self._filters_on_device() is not None
-        q_host = None if sparse else dense_rows_host([query])
-        rows_out: List[np.ndarray] = []
-        scores_out: List[np.ndarray] = []
-        got = 0
-        self._count("group_searches")
-        if on_device:
-            import torch
-            from .device_filters import mask_bytes
-            h = coll.handle.first
-            dev = torch.device("cuda", h.device)
-            nat = self._native
-            with torch.cuda.device(dev):
-                keys = self._group_keys_on_device().tensor(field, n)
-                base = self._device_row_mask(filters, coll.kind)     # cached and shared: never written here
-                work = None                                          # this query's mask once a group has been dropped
-                pos = torch.empty(window, dtype=torch.int32, device=dev)
-                sel_keys = torch.empty(window, dtype=torch.int64, device=dev)
-                counts = torch.empty(2, dtype=torch.int32, device=dev)    # [0] groups selected, [1] the flag
-                stream = torch.cuda.current_stream(dev)
-                while True:
-                    mask = work if work is not None else base
-                    ptr = mask.data_ptr() if mask is not None else 0
-                    if sparse:
-                        ids, sc = h.search_sparse([query], window, drop, None, ptr)
-                    else:
-                        ids, sc = h.search_dense(q_host, window, None, ptr)
-                    self._count("group_rounds")
-                    want = top_k - got
-                    d_ids = torch.from_numpy(ids).to(dev)
-                    nat.group_select_dev(d_ids.data_ptr(), 0, 1, window, keys.data_ptr(), n, 0, want, pos.data_ptr(),
-                                         sel_keys.data_ptr(), counts.data_ptr(), counts.data_ptr() + 4, stream.cuda_stream)
-                    n_sel, flag = (int(x) for x in counts.cpu().tolist())     # synchronises the stream
-                    at = pos[:n_sel].cpu().numpy()
-                    rows_out.append(ids[0][at])
-                    scores_out.append(sc[0][at])
-                    got += n_sel
-                    if flag == 1:
-                        break
-                    if work is None:
-                        work = torch.empty(mask_bytes(n), dtype=torch.uint8, device=dev)
-                    nat.mask_drop_groups_dev(ptr, work.data_ptr(), n, keys.data_ptr(), sel_keys.data_ptr(), n_sel,
-                                             stream.cuda_stream)
-                    stream.synchronize()      # the search reads the mask on a stream of its own
-                    self._count("group_continuations")
-        else:
-            keys = self._host_group_keys(field)
-            keep = self._row_mask(filters)                           # cached and shared: never written here
-            while True:
-                if sparse:
-                    ids, sc = coll.handle.search_sparse([query], window, drop, keep)
-                else:
-                    ids, sc = coll.handle.search_dense(q_host, window, keep)
-                self._count("group_rounds")
-                want = top_k - got
-                ids, sc = ids[0], sc[0]
-                n_valid = int(np.argmax(ids < 0)) if (ids < 0).any() else ids.shape[0]
-                seen, at = set(), []
-                for i, k in enumerate(keys[ids[:n_valid]].tolist()):
-                    if k not in seen:
-                        seen.add(k)
-                        if len(at) < want:
-                            at.append(i)
-                rows_out.append(ids[at])
-                scores_out.append(sc[at])
-                got += len(at)
-                if len(at) == want or n_valid < window:
-                    break
-                gone = np.isin(keys[:n], np.fromiter(seen, dtype=np.int64, count=len(seen)))
-                keep = ~gone if keep is None else (keep[:n] & ~gone)
-                self._count("group_continuations")
-        return np.concatenate(rows_out), np.concatenate(scores_out)
-
-    def _grouped_members_blocking(self, query, coll, top_k: int, filters: Optional[str], drop: float, field: str,
-                                  group_size: int):
-        """The exact grouped ranking of ONE query with group_size > 1 members per group: for the first top_k groups of the
-        collection's ranking R (groups ordered by their first row in R), the first min(group_size, members in R) rows of
-        each -> (rows, scores), groups in group order, a group's rows adjacent and in R order.
-
-        Phase 1 is _grouped_lists_blocking's loop — windows of K' rows, the groups already shown dropped from the mask
-        between windows — with a select that emits up to group_size members per group from the window in which the
-        group first appears.  A window is a prefix of the masked ranking, so a group with group_size members in it is
-        closed (they are its best), and so is every group of a window that was not full (the ranking ran out).
-
-        Phase 2 fills the open groups O: the base mask AND "key in O", one search of K2 = min(HR_MAX_TOPK, max(|O| *
-        group_size, K')) rows.  Restricting R to some groups keeps its order, so a group's first rows in that list are
-        its first rows in R.  A list that is not full closes every group; a full one spreads >= |O| * group_size rows over
-        at most |O| groups, so one of them holds group_size and closes: at most |O| rounds (top_k * group_size <=
-        HR_MAX_TOPK keeps K2 >= |O| * group_size)."""
-        g = group_size
-        window = self.group_window(top_k, g)
-        be = self._group_backend(query, coll, filters, drop, field)
-        groups: List[list] = []            # [key, rows, scores, closed] in group order
-        self._count("group_searches")
-        mask = be.base
-        while True:
-            ids, sc = be.search(mask, window)
-            self._count("group_rounds")
-            at, keys, n_valid = be.select(ids, top_k - len(groups), g)
-            for a, k in zip(at, keys):
-                groups.append([k, ids[a], sc[a], len(a) == g or n_valid < window])
-            if len(groups) == top_k or n_valid < window:
-                break
-            mask = be.drop(mask, keys)     # every group of the window was selected: none of their rows can be selected again
-            self._count("group_continuations")
-        open_ = [grp for grp in groups if not grp[3]]
-        if open_:
-            self._count("group_fill_searches")
-        while open_:
-            k2 = min(HR_MAX_TOPK, max(len(open_) * g, window))
-            ids, sc = be.search(be.keep([grp[0] for grp in open_]), k2)
-            self._count("group_fill_rounds")
-            at, keys, n_valid = be.select(ids, len(open_), g)
-            found = dict(zip(keys, at))
-            for grp in open_:
-                a = found.get(grp[0])
-                if a is not None and len(a) >= len(grp[1]):      # (both are prefixes of the group's rows in R)
-                    grp[1], grp[2] = ids[a], sc[a]
-                grp[3] = n_valid < k2 or len(grp[1]) == g
-            still = [grp for grp in open_ if not grp[3]]
-            if len(still) == len(open_):
-                raise RuntimeError("grouping search: a full fill window closed no group")      # the pigeonhole step failed
-            open_ = still
-        if not groups:
-            return np.zeros(0, np.int64), np.zeros(0, np.float32)
-        return np.concatenate([grp[1] for grp in groups]), np.concatenate([grp[2] for grp in groups])
-
-    def _group_backend(self, query, coll, filters: Optional[str], drop: float, field: str):
-        """What _grouped_members_blocking's two phases run on: the device form (one local GPU shard: hr_group_select_n_dev,
-        hr_mask_drop_groups_dev, hr_mask_keep_groups_dev, masks in HBM) or the host form (several shards, the torchrun
-        form, stand-in managers: numpy restatements of the kernels over boolean row masks).  Both offer
-        base / search(mask, k) -> (ids [k], scores [k]) / select(ids, k_out, g) -> (positions per group, keys, valid
-        entries) / drop(mask, keys) -> mask / keep(keys) -> base restricted to the keys."""
-        n = self.num_rows
-        sparse = coll.kind == "sparse"
-        q_host = None if sparse else dense_rows_host([query])
-        mgr = self
-        if getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and self._filters_on_device() is not None:
-            import torch
-            from .device_filters import mask_bytes
-            h = coll.handle.first
-            dev = torch.device("cuda", h.device)
-            nat = self._native
-
-            class Device:
-                def __init__(self):
-                    with torch.cuda.device(dev):
-                        self.keys = mgr._group_keys_on_device().tensor(field, n)
-                        self.base = mgr._device_row_mask(filters, coll.kind)     # cached and shared: never written here
-                        self.work = [None, None]                                 # this query's drop mask and keep mask
-                        self.pos = torch.empty(HR_MAX_TOPK, dtype=torch.int32, device=dev)
-                        self.sel_keys = torch.empty(HR_MAX_TOPK, dtype=torch.int64, device=dev)
-                        self.cnt = torch.empty(HR_MAX_TOPK + 1, dtype=torch.int32, device=dev)   # members per group, then the groups
-
-                def search(self, mask, k):
-                    ptr = mask.data_ptr() if mask is not None else 0
-                    ids, sc = h.search_sparse([query], k, drop, None, ptr) if sparse else h.search_dense(q_host, k, None, ptr)
-                    return ids[0], sc[0]
-
-                def select(self, ids, k_out, g):
-                    with torch.cuda.device(dev):
-                        stream = torch.cuda.current_stream(dev)
-                        d_ids = torch.from_numpy(ids).to(dev)
-                        nat.group_select_n_dev(d_ids.data_ptr(), 0, 1, len(ids), self.keys.data_ptr(), n, 0, k_out, g,
-                                               self.pos.data_ptr(), self.sel_keys.data_ptr(), self.cnt.data_ptr(),
-                                               self.cnt.data_ptr() + 4 * HR_MAX_TOPK, 0, stream.cuda_stream)
-                        cnt = self.cnt.cpu().numpy()                             # synchronises the stream
-                        n_sel = int(cnt[HR_MAX_TOPK])
-                        pos = self.pos[:k_out * g].cpu().numpy().astype(np.int64)
-                        keys = self.sel_keys[:n_sel].cpu().tolist()
-                    neg = np.flatnonzero(ids < 0)
-                    return ([pos[o * g:o * g + int(cnt[o])] for o in range(n_sel)], keys,
-                            int(neg[0]) if neg.size else len(ids))
-
-                def _mask_op(self, op, slot, mask, keys):
-                    with torch.cuda.device(dev):
-                        stream = torch.cuda.current_stream(dev)
-                        if self.work[slot] is None:
-                            self.work[slot] = torch.empty(mask_bytes(n), dtype=torch.uint8, device=dev)
-                        d_set = torch.tensor(keys, dtype=torch.int64, device=dev)
-                        op(mask.data_ptr() if mask is not None else 0, self.work[slot].data_ptr(), n, self.keys.data_ptr(),
-                           d_set.data_ptr(), len(keys), stream.cuda_stream)
-                        stream.synchronize()      # the search reads the mask on a stream of its own
-                    return self.work[slot]
-
-                def drop(self, mask, keys):
-                    return self._mask_op(nat.mask_drop_groups_dev, 0, mask, keys)
-
-                def keep(self, keys):
-                    return self._mask_op(nat.mask_keep_groups_dev, 1, self.base, keys)
-
-            return Device()
-
-        from .device_groups import group_select_n_host
-        host_keys = self._host_group_keys(field)
-
-        class Host:
-            base = mgr._row_mask(filters)                                        # cached and shared: never written here
-
-            def search(self, mask, k):
-                ids, sc = coll.handle.search_sparse([query], k, drop, mask) if sparse else coll.handle.search_dense(q_host, k, mask)
-                return ids[0], sc[0]
-
-            def select(self, ids, k_out, g):
-                return group_select_n_host(ids, host_keys, k_out, g)
-
-            def drop(self, mask, keys):
-                gone = np.isin(host_keys[:n], np.asarray(keys, dtype=np.int64))
-                return ~gone if mask is None else (mask[:n] & ~gone)
-
-            def keep(self, keys):
-                kept = np.isin(host_keys[:n], np.asarray(keys, dtype=np.int64))
-                return kept if self.base is None else (self.base[:n] & kept)
-
-        return Host()
 
     def _search_blocking(self, query_embedding, collection_name: str, top_k: int, filters: Optional[str],
                          search_params: Optional[Dict], group_by_field: Optional[str] = None,
@@ -1289,35 +1083,8 @@ class MilvusIndexManager:
         drop = float((params.get("params") or params).get("drop_ratio_search", 0.0))
         query = self._as_sparse_payload(query_embedding) if coll.kind == "sparse" else query_embedding
         self._count("deep_searches")
-        if getattr(coll.handle, "n_shards", 1) == 1 and hasattr(coll.handle, "handles") and self._filters_on_device() is not None:
-            h = coll.handle.first    # one local GPU shard: the mask never leaves the device
-            d_mask = self._device_row_mask(filters, coll.kind)
-            ptr = d_mask.data_ptr() if d_mask is not None else 0
-            if coll.kind == "sparse":
-                ids, sc = h.search_sparse_deep([query], top_k, offset, drop, None, ptr)
-            else:
-                ids, sc = h.search_dense_deep(dense_rows_host([query]), top_k, offset, None, ptr)
-        else:
-            mask = self._row_mask(filters)
-            if coll.kind == "sparse":
-                ids, sc = coll.handle.search_sparse_deep([query], top_k, offset, drop, mask)
-            else:
-                ids, sc = coll.handle.search_dense_deep(dense_rows_host([query]), top_k, offset, mask)
-        return self._format_hits(ids[0], sc[0])
-
-    @staticmethod
-    def _search_dense_device(handle, q_dev, top_k: int):
-        """Query already in HBM (device-resident embedding cache): device form, no upload; an unproven
-        list (ties at the candidate cut) is redone through the host form."""
-        import torch
-        q = dense_rows_device([q_dev], q_dev.device, handle.dim)
-        ids, sc, flag = list_buffers(1, top_k, q.device)
-        stream = torch.cuda.current_stream(q.device)
-        handle.search_dense_dev(q.data_ptr(), 1, top_k, ids.data_ptr(), sc.data_ptr(), flag.data_ptr(), 0, stream.cuda_stream)
-        stream.synchronize()
-        if int(flag.item()) != 1:
-            return handle.search_dense(q.cpu().numpy(), top_k)
-        return ids.cpu().numpy(), sc.cpu().numpy()
+        path = SearchPath(self, coll, query, drop)
+        return self._format_hits(*path.search(path.base(filters), top_k, offset=offset))
 
     # ---- coalescing front (batching.py) -------------------------------------------------------------------------
     def _coalescer(self, coll):
@@ -1735,8 +1502,7 @@ class MilvusIndexManager:
 
     def _query_rows(self, expr: Optional[str], limit: Optional[int], offset: int) -> Tuple[int, np.ndarray, bool]:
         """(rows that pass, the page's global rows, whether the page came from the device mask)."""
-        on_device = getattr(self._main, "n_shards", 1) == 1 and hasattr(self._main, "handles") and \
-            self._filters_on_device() is not None
+        on_device = self._device_shard(self._main) is not None
         total, rows = (self._query_rows_device if on_device else self._query_rows_host)(expr, limit, offset)
         return total, rows, on_device
 

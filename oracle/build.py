@@ -20,9 +20,17 @@ def build(force: bool = False) -> str:
     os.makedirs(OUT_DIR, exist_ok=True)
     if not force and os.path.exists(OUT) and os.path.getmtime(OUT) >= os.path.getmtime(SRC):
         return OUT
+    # compiled beside the target and moved into place: a process that loads the library while another one builds it
+    # (test runs that start together on a fresh tree) sees the old file or the whole new one, never a part of it
+    tmp = f"{OUT}.{os.getpid()}.tmp"
     cmd = ["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC",
-           "-Wall", "-o", OUT, SRC, "-lm"]
-    subprocess.run(cmd, check=True)
+           "-Wall", "-o", tmp, SRC, "-lm"]
+    try:
+        subprocess.run(cmd, check=True)
+        os.replace(tmp, OUT)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
     return OUT
 
 

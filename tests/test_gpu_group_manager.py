@@ -277,6 +277,54 @@ def test_two_shards_give_the_single_shard_lists(gpu, corpus):
         asyncio.run(two.close())
 
 
+def test_device_loop_and_host_loop_answer_and_count_alike(gpu, corpus):
+    """The one grouped loop on its two backends, for group_size 1 and 3: a manager on one shard without the front (every
+    request takes the blocking loop with the masks in HBM) and one with the same rows on two shards of the same device
+    (host masks) — equal lists, equal to the restatement over the ungrouped ranking, and equal counters request by request."""
+    X, csr, payload, q, sq = corpus
+    counters = ("group_searches", "group_rounds", "group_continuations", "group_fill_searches", "group_fill_rounds")
+    one = _manager(corpus, coalesce=False, group_members=True)
+    two = _manager(corpus, devices=[0, 0], group_members=True)
+
+    def restated(rows, keys, k, g):
+        groups = {}
+        for r in rows:
+            if int(keys[r]) in groups or len(groups) < k:
+                groups.setdefault(int(keys[r]), []).append(r)
+        return [r for members in groups.values() for r in members[:g]]
+
+    def asked(mgr, *args, **kw):
+        before = dict(mgr.stats)
+        hits = asyncio.run(mgr.search(*args, **kw))
+        return _lists(hits), tuple(mgr.stats[c] - before[c] for c in counters)
+
+    try:
+        assert one._coalescer(one.collections["semantic_index"]) is None and one._main.n_shards == 1
+        assert two._coalescer(two.collections["semantic_index"]) is None and two._main.n_shards == 2
+        for coll, query in (("semantic_index", q), ("sparse_index", sq)):
+            for expr in (None, 'chunk_index >= 2 and doc_id != "doc3"', "chunk_index > 100"):
+                rows, scores, ids = _lists(asyncio.run(one.search(query, coll, top_k=256, filters=expr)))
+                assert _lists(asyncio.run(two.search(query, coll, top_k=256, filters=expr))) == (rows, scores, ids)
+                assert (len(rows) == 0) == (expr == "chunk_index > 100") and len(rows) < 256
+                for field in ("doc_id", "chunk_index"):
+                    keys = one._cols.group_keys(field)
+                    for g in (1, 3):
+                        for top_k in (2, 5, 60):
+                            what = (coll, expr, field, g, top_k)
+                            want = restated(rows, keys, top_k, g)
+                            at = [rows.index(r) for r in want]
+                            a, used_a = asked(one, query, coll, top_k=top_k, filters=expr, group_by_field=field, group_size=g)
+                            b, used_b = asked(two, query, coll, top_k=top_k, filters=expr, group_by_field=field, group_size=g)
+                            assert a == b == (want, [scores[i] for i in at], [ids[i] for i in at]), what
+                            assert used_a == used_b and used_a[0] == 1, (what, used_a, used_b)
+                            if (expr, field, g, top_k) == (None, "doc_id", 1, 5):
+                                assert used_a[2] >= 1, what       # a window of 20 rows against the big document's 120
+        assert one._dev_groups is not None and two._dev_groups is None
+    finally:
+        asyncio.run(one.close())
+        asyncio.run(two.close())
+
+
 class _OneQueryGen:
     def __init__(self, q, sq):
         self.q, self.sq = q, sq

@@ -257,6 +257,56 @@ def test_host_loop_equals_the_restatement(host_manager, collection, field, top_k
     assert _rows(asyncio.run(mgr.search(query, collection, top_k=top_k, filters=expr)))[0] == rows[:top_k]
 
 
+TABLE_FIELDS = ("doc_id", "chunk_index", "id", "token_count", "timestamp")       # (the last two hold one value: one group)
+TABLE_TOP_K = (1, 2, 5, 20, 60, 256)
+TABLE_EXPRS = (None, "chunk_index >= 2", 'doc_id != "big"', "chunk_index > 100")  # the last keeps no row
+GROUP_COUNTERS = ("group_searches", "group_rounds", "group_continuations", "group_fill_searches", "group_fill_rounds")
+# What one group_by_field request (group_size 1) added to GROUP_COUNTERS, recorded by running this table on commit e9d4c67
+# (the parent of the change that made the grouped search one loop), whose group_size == 1 requests ran a loop of their own.
+# There every request added (1, rounds, continuations, 0, 0); below is "rounds continuations" per request, the top_k values
+# of a (collection, field) on one line each, the four expressions of a top_k together.
+TABLE_ROUNDS = {
+    ("semantic_index", "doc_id"): "1 0 1 0 1 0 1 0  2 1 2 1 1 0 1 0  2 1 2 1 1 0 1 0  2 1 2 1 1 0 1 0  2 1 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+    ("semantic_index", "chunk_index"): "1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  2 1 2 1 2 1 1 0  2 1 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+    ("semantic_index", "id"): "1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+    ("semantic_index", "token_count"): "1 0 1 0 1 0 1 0  2 1 2 1 2 1 1 0  2 1 2 1 2 1 1 0  2 1 2 1 2 1 1 0  2 1 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+    ("semantic_index", "timestamp"): "1 0 1 0 1 0 1 0  2 1 2 1 2 1 1 0  2 1 2 1 2 1 1 0  2 1 2 1 2 1 1 0  2 1 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+    ("sparse_index", "doc_id"): "1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  2 1 2 1 1 0 1 0  2 1 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+    ("sparse_index", "chunk_index"): "1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  2 1 2 1 2 1 1 0  2 1 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+    ("sparse_index", "id"): "1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+    ("sparse_index", "token_count"): "1 0 1 0 1 0 1 0  2 1 2 1 2 1 1 0  2 1 2 1 2 1 1 0  2 1 2 1 2 1 1 0  2 1 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+    ("sparse_index", "timestamp"): "1 0 1 0 1 0 1 0  2 1 2 1 2 1 1 0  2 1 2 1 2 1 1 0  2 1 2 1 2 1 1 0  2 1 1 0 1 0 1 0  1 0 1 0 1 0 1 0",
+}
+
+
+def _table_request(mgr, query, collection, field, top_k, expr, rankings):
+    """One request of the table: the grouped answer is the restatement over the ungrouped ranking -> the counters' delta."""
+    if (collection, expr) not in rankings:
+        rankings[collection, expr] = _rows(asyncio.run(mgr.search(query, collection, top_k=N, filters=expr)))
+    rows, scores, ids = rankings[collection, expr]
+    want = first_k_distinct(rows, mgr._cols.group_keys(field), top_k)
+    at = [rows.index(r) for r in want]
+    before = dict(mgr.stats)
+    got = asyncio.run(mgr.search(query, collection, top_k=top_k, filters=expr, group_by_field=field))
+    delta = tuple(mgr.stats[c] - before[c] for c in GROUP_COUNTERS)
+    assert _rows(got) == (want, [scores[i] for i in at], [ids[i] for i in at]), (collection, field, top_k, expr)
+    return delta
+
+
+@pytest.mark.parametrize("collection", ["semantic_index", "sparse_index"])
+@pytest.mark.parametrize("field", TABLE_FIELDS)
+def test_host_loop_answers_and_counts_as_the_parent_did(host_manager, collection, field):
+    mgr, q, sq = host_manager
+    query = {"indices": sq[0].tolist(), "values": sq[1].tolist()} if collection == "sparse_index" else q
+    rankings = {}
+    expected = iter(TABLE_ROUNDS[collection, field].split())
+    for top_k in TABLE_TOP_K:
+        for expr in TABLE_EXPRS:
+            delta = _table_request(mgr, query, collection, field, top_k, expr, rankings)
+            assert delta == (1, int(next(expected)), int(next(expected)), 0, 0), (collection, field, top_k, expr, delta)
+    assert rankings[collection, TABLE_EXPRS[-1]][0] == [] and next(expected, None) is None
+
+
 def test_host_loop_after_delete(host_manager):
     mgr, q, _ = host_manager
     best = asyncio.run(mgr.search(q, "semantic_index", top_k=30))
