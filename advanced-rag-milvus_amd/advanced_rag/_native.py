@@ -21,6 +21,10 @@ HR_METHOD_SEMANTIC, HR_METHOD_SPARSE, HR_METHOD_DOMAIN = 1, 2, 4
 HR_MAX_TOPK = 256
 # normalisation of one list's scores in the weighted score fusion (hr_fuse_scores_dev; the table is in include/hbmrag.h)
 HR_NORM_COSINE, HR_NORM_ATAN, HR_NORM_ATAN_DIST, HR_NORM_MINMAX, HR_NORM_MINMAX_DIST = 0, 1, 2, 3, 4
+# decay ranker (hr_decay_rerank_dev): curve codes, the identity normalisation and the float64 column kind, valid only there
+HR_DECAY_GAUSS, HR_DECAY_EXP, HR_DECAY_LINEAR = 0, 1, 2
+HR_NORM_NONE = -1
+HR_COL_F64 = 5        # beside HR_COL_I64 / HR_COL_F32 below
 HR_MAX_DEEP_K = 16384   # hr_search_*_deep, hr_deep_topk_dev: offset + k
 HR_N_PHASES = 10
 PHASE_NAMES = ("prep", "dense_scan", "group_select", "refine", "topk",
@@ -128,6 +132,9 @@ _SIGNATURES = {
                                      _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_group_select_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_decay_rerank_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
+                                       _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                       _c.c_void_p, _c.c_void_p]),
     "hr_mask_drop_groups_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "hr_group_select_n_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                          _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -659,6 +666,24 @@ def group_select_dev(d_ids: int, d_n: int, B: int, k_in: int, d_keys: int, key_r
     p = lambda x: _vp(x) if x else None
     rc = L.hr_group_select_dev(p(d_ids), p(d_n), B, k_in, p(d_keys), key_rows, first_row, k_out, p(d_out_pos), p(d_out_keys),
                                p(d_out_n), p(d_flags), p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+# one query's operands of hr_decay_rerank_dev (struct hr_decay_query): origin, offset, coef as float64, func and a reserved int32
+DECAY_QUERY_DTYPE = np.dtype([("origin", "<f8"), ("offset", "<f8"), ("coef", "<f8"), ("func", "<i4"), ("reserved", "<i4")])
+
+
+def decay_rerank_dev(d_ids: int, d_scores: int, score_is_f64: bool, d_n: int, B: int, k_in: int, d_col: int, col_kind: int,
+                     col_rows: int, first_row: int, d_params: int, norm: int, k_out: int, d_out_pos: int, d_out_ids: int,
+                     d_out_scores: int, d_out_n: int, stream: int = 0):
+    """hr_decay_rerank_dev: the decay ranker over a batch of ranked lists (device pointers; 0 = NULL; d_params = [B]
+    records of DECAY_QUERY_DTYPE on the device)."""
+    L = load_library()
+    p = lambda x: _vp(x) if x else None
+    rc = L.hr_decay_rerank_dev(p(d_ids), p(d_scores), 1 if score_is_f64 else 0, p(d_n), B, k_in, p(d_col), col_kind, col_rows,
+                               first_row, p(d_params), norm, k_out, p(d_out_pos), p(d_out_ids), p(d_out_scores), p(d_out_n),
+                               p(stream))
     if rc != 0:
         _raise_global(L, rc)
 

@@ -32,6 +32,12 @@ list kept (4 x top_k entries) and one `hr_mmr_select_dev` behind it on the same 
 profiles that differ only in lambda share the round.  A request with fusion="weighted" carries the fusion mode and its two norm
 codes in the key: it gets an engine whose post kernel fuses by weighted scores, and never shares a launch with an RRF request.
 
+Decay rerankings (search(..., ranker=DecayRanker(...)) behind its plain search, retrieve() with RetrievalConfig(decay=...)
+behind its fusion) are a kind of their own: the field, the norm code, the padded list length and the score type are the key;
+origin, offset, coefficient and function travel per query (hr_decay_query), so requests with different curves share ONE
+`hr_decay_rerank_dev` launch (stats["decay_launches"]).  In the one-round path the same kernel runs behind `hr_post_lists_dev`
+on the hybrid stream, over the whole fused list, before MMR or the cut.
+
 One worker thread per manager; the event loop never blocks on the GPU.
 """
 from __future__ import annotations
@@ -119,7 +125,7 @@ class RangedQuery:
 
 @dataclass
 class _Request:
-    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "hybrid" | "encode"
+    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "decay" | "hybrid" | "encode"
     key: Tuple                # requests with equal (kind, key) share a launch
     payload: Any
     future: Future = field(default_factory=Future)
@@ -148,7 +154,7 @@ class SearchCoalescer:
             self.window_s = max(self.window_s, 250e-6)
         self.stats = {"rounds": 0, "requests": 0, "dense_launches": 0, "sparse_launches": 0, "fuse_launches": 0,
                       "hybrid_launches": 0, "mmr_launches": 0, "encode_launches": 0, "encoded_texts": 0, "max_batch_seen": 0, "redone_unproven": 0,
-                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "score_fuse_launches": 0, "busy_s": 0.0}
+                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "score_fuse_launches": 0, "decay_launches": 0, "busy_s": 0.0}
         self._engines: Dict[Tuple, Any] = {}   # hybrid engines per (top_k, rrf_k, mmr)
         self._inflight: List[_Request] = []    # the requests of the round in progress (failed as a whole if the worker dies)
         self._outbox: Dict[Any, list] = {}     # event loop -> [(asyncio future, ok, value)] of the round in progress
@@ -274,7 +280,7 @@ class SearchCoalescer:
         dev = torch.device("cuda", self.mgr.device)
         # one stream per kind of work: the dense and the sparse searches of a round run side by side (a lone retrieve()
         # overlaps its two scans, as its two worker threads did before the front existed)
-        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "hybrid", "encode")}
+        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "decay", "hybrid", "encode")}
         for reqs in self._rounds():
             groups: Dict[Tuple, List[_Request]] = {}
             for r in reqs:
@@ -388,6 +394,8 @@ class SearchCoalescer:
                 _answer(r.future, self.mgr._fuse_rows_blocking, r.payload, key)
             elif kind == "fuse_scores":
                 _answer(r.future, self.mgr._fuse_scores_blocking, r.payload, key)
+            elif kind == "decay":
+                _answer(r.future, self.mgr._decay_rows_blocking, r.payload, key)
             elif kind == "hybrid":
                 _deliver(r.future, None)   # the caller falls back to two searches + a fusion
             elif kind == "encode":
@@ -500,9 +508,12 @@ class SearchCoalescer:
     # ------------------------------------------------------------------ hybrid (both searches + RRF of a request)
     def _enqueue_hybrid(self, torch, dev, stream, key, chunk):
         top_k, expr, drop, rrf_k, mmr = key[:5]
-        fuse = key[5:]          # () = RRF, or ("weighted", norm code of the semantic list, of the sparse list)
+        fuse, decay = key[5:], ()   # fuse: () = RRF, or ("weighted", norm code of the semantic list, of the sparse list)
+        if "decay" in fuse:         # then ("decay", field, norm code): the fused list is kept whole and reranked before MMR / the cut
+            fuse, decay = fuse[:fuse.index("decay")], fuse[fuse.index("decay") + 1:]
+        whole = mmr or bool(decay)
         handle = self.mgr.collections["semantic_index"].handle.first
-        ekey = (top_k, rrf_k, mmr) + fuse
+        ekey = (top_k, rrf_k, whole) + fuse
         eng = self._engines.get(ekey)
         if eng is None:
             if len(self._engines) >= 16:
@@ -510,7 +521,7 @@ class SearchCoalescer:
             weighted = {"fusion": "weighted", "norms": (fuse[1], fuse[2], 0)} if fuse else {}
             eng = self._engines[ekey] = HybridSearchEngine(
                 handle, EngineConfig(top_k=top_k, rrf_k=rrf_k, enable_reranking=False,
-                                     fused_k=4 * top_k if mmr else None, **weighted), device=str(dev))   # MMR: two 2 * top_k lists, whole
+                                     fused_k=4 * top_k if whole else None, **weighted), device=str(dev))   # MMR, decay: two 2 * top_k lists, whole
         # the fusion weights are per REQUEST (a weight_adapter may pick them per query, reference retrieval.py:251-262):
         # they travel as a [B, 3] operand of the post kernel, so requests with different weights still share the round
         wq = torch.from_numpy(np.array([[r.payload[2], r.payload[3], 0.0] for r in chunk], dtype=np.float64)).to(dev)
@@ -526,10 +537,29 @@ class SearchCoalescer:
         self.stats["sparse_launches"] += 1
         # the engine reuses ONE buffer set per batch size: another group (or the next chunk of this one) with the same B
         # is enqueued before this round is read back, so the results are copied out here, in stream order
+        if decay:
+            b = self._decay_fused(torch, dev, stream, decay, chunk, b)
         if mmr:
             return {"b": self._mmr_select(torch, dev, stream, top_k, chunk, b), "keep": (q, d_sparse, mask, wq)}
+        if decay:       # the cut: the first top_k of the reranked list
+            out = {k: b[k][:, :top_k].clone() for k in ("fused_ids", "fused_scores", "fused_methods", "fused_raw")}
+            out.update(fused_n=b["fused_n"].clamp(max=top_k), keep=b["keep"], **{k: b[k].clone() for k in ("ids", "scores", "flags")})
+            return {"b": out, "keep": (q, d_sparse, mask, wq)}
         out = {k: b[k].clone() for k in ("fused_ids", "fused_scores", "fused_methods", "fused_n", "ids", "scores", "flags")}
         return {"b": out, "keep": (q, d_sparse, mask, wq)}
+
+    def _decay_fused(self, torch, dev, stream, decay, chunk, b):
+        """The decay ranker over the whole fused lists of the batch (hr_decay_rerank_dev, same stream, behind the post kernel)
+        -> the engine's buffers with fused_ids / fused_scores in decayed order (scores = the final ones), the method bits
+        following through the positions, fused_raw = the fusion's scores in the same order."""
+        field, norm = decay
+        B, fk = len(chunk), int(b["fused_ids"].shape[1])
+        pos, oi, os_, on, keep = self._decay_launch(torch, dev, stream, field, norm, [r.payload[5] for r in chunk], b["fused_ids"],
+                                                    b["fused_scores"], True, b["fused_n"], B, fk)
+        at = pos.clamp(min=0).to(torch.int64)      # (-1 padding lies beyond fused_n: never read)
+        return {"fused_ids": oi, "fused_scores": os_, "fused_methods": b["fused_methods"].gather(1, at),
+                "fused_raw": b["fused_scores"].gather(1, at), "fused_n": on, "ids": b["ids"], "scores": b["scores"],
+                "flags": b["flags"], "keep": (keep, pos)}
 
     def _mmr_select(self, torch, dev, stream, top_k, chunk, b):
         """HybridRetriever._mmr_diversify over the whole fused lists of the batch (hr_mmr_select_dev, same stream) -> the
@@ -545,9 +575,9 @@ class SearchCoalescer:
                            rows, 0, lam.data_ptr(), top_k, pos.data_ptr(), n_sel.data_ptr(), stream.cuda_stream)
         self.stats["mmr_launches"] += 1
         at = pos.clamp(min=0).to(torch.int64)      # (-1 padding lies beyond fused_n: never read)
-        out = {k: b[k].gather(1, at) for k in ("fused_ids", "fused_scores", "fused_methods")}
+        out = {k: b[k].gather(1, at) for k in ("fused_ids", "fused_scores", "fused_methods", "fused_raw") if k in b}
         out.update(fused_n=n_sel, **{k: b[k].clone() for k in ("ids", "scores", "flags")})
-        out["keep"] = (lam, indptr, tok, pos)
+        out["keep"] = (lam, indptr, tok, pos, b.get("keep"))
         return out
 
     def _scatter_hybrid(self, key, chunk, st):
@@ -555,9 +585,10 @@ class SearchCoalescer:
         fi, fs = b["fused_ids"].cpu().numpy(), b["fused_scores"].cpu().numpy()
         fm, fn = b["fused_methods"].cpu().numpy(), b["fused_n"].cpu().numpy()
         ids, sc, fl = b["ids"].cpu().numpy(), b["scores"].cpu().numpy(), b["flags"].cpu().numpy()
-        self._scatter_hybrid_lists(chunk, fi, fs, fm, fn, ids, sc, fl.min(axis=0) == 1)
+        self._scatter_hybrid_lists(chunk, fi, fs, fm, fn, ids, sc, fl.min(axis=0) == 1,
+                                   b["fused_raw"].cpu().numpy() if "fused_raw" in b else None)
 
-    def _scatter_hybrid_lists(self, chunk, fi, fs, fm, fn, ids, sc, proven):
+    def _scatter_hybrid_lists(self, chunk, fi, fs, fm, fn, ids, sc, proven, raw=None):
         # score of a fused row in the list its payload comes from: the dense list if the row is in it, else the sparse one
         # (HybridRetriever._assemble_fused); rows are unique within a list
         in_d = fi[:, :, None] == ids[0][:, None, :]
@@ -570,7 +601,8 @@ class SearchCoalescer:
                 _deliver(r.future, None)
                 continue
             n = int(fn[i])
-            _deliver(r.future, (fi[i, :n].copy(), fs[i, :n].copy(), fm[i, :n].copy(), orig[i, :n].copy()))
+            res = (fi[i, :n].copy(), fs[i, :n].copy(), fm[i, :n].copy(), orig[i, :n].copy())
+            _deliver(r.future, res + (raw[i, :n].copy(),) if raw is not None else res)   # decay: the fusion's scores beside the final ones
 
     # ------------------------------------------------------------------ query encoder
     def _enqueue_encode(self, torch, dev, stream, key, chunk):
@@ -660,3 +692,48 @@ class SearchCoalescer:
         return {"oi": oi, "os": os_, "om": om, "on": on, "keep": (li, ls, wq)}
 
     _scatter_fuse_scores = _scatter_fuse
+
+    # ------------------------------------------------------------------ decay ranker
+    def _decay_launch(self, torch, dev, stream, field, norm, operands, d_ids, d_scores, f64, d_n, B, k_in):
+        """ONE hr_decay_rerank_dev over B lists already in HBM, whole lists out (k_out = k_in), on `stream`
+        -> (positions int32 [B, k_in], rows, float64 final scores, entries [B], what must stay alive)."""
+        from . import _native as nat
+        n_rows = self.mgr.num_rows
+        col, kind = self.mgr._decay_columns_on_device().tensor(field, n_rows, self.mgr._filters_on_device())
+        params = np.zeros(B, dtype=nat.DECAY_QUERY_DTYPE)
+        for i, (origin, offset, coef, func) in enumerate(operands):
+            params[i] = (origin, offset, coef, func, 0)
+        d_params = torch.from_numpy(params.view(np.uint8).reshape(B, -1)).to(dev)
+        pos = torch.empty((B, k_in), dtype=torch.int32, device=dev)
+        oi = torch.empty((B, k_in), dtype=torch.int64, device=dev)
+        os_ = torch.empty((B, k_in), dtype=torch.float64, device=dev)
+        on = torch.empty((B,), dtype=torch.int32, device=dev)
+        nat.decay_rerank_dev(d_ids.data_ptr(), d_scores.data_ptr(), f64, d_n.data_ptr(), B, k_in, col.data_ptr(), kind, n_rows, 0,
+                             d_params.data_ptr(), norm, k_in, pos.data_ptr(), oi.data_ptr(), os_.data_ptr(), on.data_ptr(),
+                             stream.cuda_stream)
+        self.stats["decay_launches"] += 1
+        return pos, oi, os_, on, (col, d_params)
+
+    def _enqueue_decay(self, torch, dev, stream, key, chunk):
+        """The decay rerankings of a round in ONE launch: key = (field, norm code, padded list length, scores are float64),
+        payload = (rows, scores, (origin, offset, coef, func))."""
+        field, norm, width, f64 = key
+        B = len(chunk)
+        ids = np.full((B, width), -1, dtype=np.int64)
+        sc = np.zeros((B, width), dtype=np.float64 if f64 else np.float32)
+        n = np.zeros(B, dtype=np.int32)
+        for i, r in enumerate(chunk):
+            rows, scores, _ = r.payload
+            n[i] = len(rows)
+            ids[i, :n[i]] = rows
+            sc[i, :n[i]] = scores
+        d_ids, d_sc, d_n = torch.from_numpy(ids).to(dev), torch.from_numpy(sc).to(dev), torch.from_numpy(n).to(dev)
+        pos, oi, os_, on, keep = self._decay_launch(torch, dev, stream, field, norm, [r.payload[2] for r in chunk], d_ids, d_sc,
+                                                    f64, d_n, B, width)
+        return {"pos": pos, "oi": oi, "os": os_, "on": on, "keep": (d_ids, d_sc, d_n, keep)}
+
+    def _scatter_decay(self, key, chunk, st):
+        pos, oi, os_, on = (st[k].cpu().numpy() for k in ("pos", "oi", "os", "on"))
+        for i, r in enumerate(chunk):
+            n = int(on[i])
+            _deliver(r.future, (pos[i, :n].copy(), oi[i, :n].copy(), os_[i, :n].copy()))

@@ -21,6 +21,10 @@ For grouping search (csrc/group.h) every groupable field hands out an int64 GROU
 integer field is its own key; the value of a string field gets its ordinal in a collection-wide dictionary, in first-seen
 order — equal keys mean equal values.  Built lazily, extended by later appends, gathered (never renumbered) by compact(),
 and never part of a snapshot: the TokenSetColumn pattern.
+
+For the decay ranker (csrc/decay.h) the `timestamp` column hands out EPOCH SECONDS per row (`PayloadColumns.epoch_seconds`):
+a float64 derived from the ISO text by decay.epoch_seconds, NaN where the text is empty or no ISO time.  The same pattern:
+built on first use, extended by appends, gathered by compact(), never part of a snapshot.
 """
 from __future__ import annotations
 
@@ -358,6 +362,47 @@ class GroupKeyColumn:
         return self._keys.nbytes
 
 
+class EpochColumn:
+    """Append-only float64 per global row of the timestamp column: decay.epoch_seconds of the row's text (seconds since
+    1970-01-01 UTC; NaN = the row has no time).  Rows are parsed once."""
+
+    def __init__(self):
+        self._a = np.empty(0, dtype=np.float64)
+        self._n = 0
+
+    def __len__(self) -> int:
+        return self._n
+
+    def extend(self, texts: Iterable[str]) -> None:
+        from .decay import epoch_seconds
+        new = [epoch_seconds(t) for t in texts]
+        if not new:
+            return
+        self._a = _grown(self._a, self._n + len(new))
+        self._a[self._n: self._n + len(new)] = new
+        self._n += len(new)
+
+    def compact(self, keep: np.ndarray) -> None:
+        """Drop the rows whose entry of the boolean `keep` is False; the others move up in order."""
+        self._a = self._a[: self._n][_keep_mask(keep, self._n)]
+        self._n = self._a.shape[0]
+
+    def sync(self, column: "StringColumn") -> "EpochColumn":
+        """Parse the rows of `column` this column does not hold yet."""
+        step = 1 << 16       # bounded temporaries
+        for a in range(self._n, len(column), step):
+            self.extend(column[a: min(len(column), a + step)])
+        return self
+
+    def array(self) -> np.ndarray:
+        """float64 [rows] view (no copy)."""
+        return self._a[: self._n]
+
+    @property
+    def nbytes(self) -> int:
+        return self._a.nbytes
+
+
 class PayloadColumns:
     """dict-like: columns["id"][row], columns["entropy"].array(), len(columns["id"])."""
 
@@ -372,6 +417,8 @@ class PayloadColumns:
         # the lazy build and the extension of a group-key column are read-modify-write: the searches of one request run in
         # different threads (a sharded manager has no front) and ask for the same field at once
         self._group_lock = threading.Lock()
+        self._epoch: Optional[EpochColumn] = None            # derived from "timestamp" on first use (the decay ranker's field)
+        self._epoch_lock = threading.Lock()
 
     def __getitem__(self, name: str):
         return self._c["id" if name == "chunk_id" else name]
@@ -430,6 +477,15 @@ class PayloadColumns:
                 col = self._group_keys[name] = GroupKeyColumn()
             return col.sync(self._c[name]).array()
 
+    def epoch_seconds(self) -> np.ndarray:
+        """float64 seconds since 1970-01-01 UTC of every row's timestamp (a view, no copy; NaN where the text is empty or
+        no ISO time): what the decay ranker reads for field="timestamp".  Built on first use — the host parses every row
+        once —, extended by what later appends added, gathered by compact(), never part of a snapshot."""
+        with self._epoch_lock:
+            if self._epoch is None:
+                self._epoch = EpochColumn()
+            return self._epoch.sync(self._c["timestamp"]).array()
+
     def compact(self, keep: np.ndarray) -> None:
         """Drop the rows whose entry of the boolean `keep` (one per row) is False from every column, one column at a
         time (the peak extra memory is one column), and from the token sets and the group keys as far as they are built."""
@@ -445,6 +501,9 @@ class PayloadColumns:
         with self._group_lock:
             for col in self._group_keys.values():
                 col.compact(keep[:len(col)])
+        with self._epoch_lock:
+            if self._epoch is not None:
+                self._epoch.compact(keep[:len(self._epoch)])
 
     def filter_columns(self) -> Dict[str, np.ndarray]:
         """What filters.evaluate takes: numpy arrays per field (string fields as unicode arrays — fine for small

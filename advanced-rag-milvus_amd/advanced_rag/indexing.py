@@ -36,6 +36,7 @@ import numpy as np
 
 from . import filters as _filters
 from .columns import FLOAT_COLUMNS, PayloadColumns, check_group_field
+from .decay import DecayRanker, decay_rerank
 from .constants import GROUP_WINDOW_FACTOR, QUERY_MAX_WINDOW, IndexingConstants
 from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache, get_semantic_cache
 from ._native import HR_MAX_TOPK   # importing the binding module does not load the library
@@ -259,6 +260,7 @@ class MilvusIndexManager:
         self._dev_filters = None
         self._dev_tokens = None    # device_tokens.DeviceTokenSets: the token sets of "content" in HBM, on first use
         self._dev_groups = None    # device_groups.DeviceGroupKeys: the group keys of the fields grouped on, on first use
+        self._dev_decay = None     # device_decay.DeviceDecayColumns: the epoch seconds a decay ranker reads, on first use
         # grouping searches answered by the blocking loop: searches, windows searched, windows that ended before the
         # top_k-th group and were continued without the groups they showed
         # group_fill_searches: grouping searches with group_size > 1 that needed the fill phase (a group's members were
@@ -266,8 +268,11 @@ class MilvusIndexManager:
         # queries: query() calls answered; query_device: those whose page came from hr_mask_rows_dev (mask never left HBM)
         # search_by_ids: search_by_ids() calls whose ids were resolved and whose stored vectors were fetched
         # deep_searches: searches with offset + top_k > HR_MAX_TOPK, answered by the deep forms (a full refine of the shard)
+        # decay_host_reranks: decay rerankings answered by the Python restatement instead of hr_decay_rerank_dev (sharded
+        # managers, lists beyond 3 * HR_MAX_TOPK entries, the front's one-by-one fallback after a refused batch)
         self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
-                      "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0, "deep_searches": 0}
+                      "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0, "deep_searches": 0,
+                      "decay_host_reranks": 0}
         self._stats_lock = threading.Lock()    # the loop runs in worker threads and in the front's thread at once
         self._deleted: Optional[np.ndarray] = None
         self._mask_cache: Dict[Any, Optional[np.ndarray]] = {}   # (expr, rows, delete epoch) -> boolean row filter
@@ -328,7 +333,7 @@ class MilvusIndexManager:
 
     def _forget_masks(self, rebuild_filters: bool):
         """Drop every cached row mask, host and HBM: the rows changed.  After an APPEND (_append_payload, add_rows) the device
-        filter columns, the token sets and the group keys stay: they grow in place, every row is uploaded once.  After the row
+        filter columns, the token sets, the group keys and the epoch seconds stay: they grow in place, every row is uploaded once.  After the row
         space was REPLACED (attach_shards, add_rows_synthetic, load_snapshot, compact) they go too (rebuild_filters) and are
         rebuilt on first use.  close() drops HBM masks only."""
         self._mask_cache.clear()
@@ -337,6 +342,7 @@ class MilvusIndexManager:
             self._dev_filters = None
             self._dev_tokens = None
             self._dev_groups = None
+            self._dev_decay = None
 
     def _initialize_collections(self):
         self._main = ShardSet([self._shard_handle("main", d) for d in self.devices])
@@ -441,6 +447,14 @@ class MilvusIndexManager:
                 from .device_groups import DeviceGroupKeys
                 self._dev_groups = DeviceGroupKeys(None if self._synthetic_rows else self._cols, self._main.first.device)
             return self._dev_groups
+
+    def _decay_columns_on_device(self):
+        """The HBM mirror of what a decay ranker reads (hr_decay_rerank_dev's d_col), on the main shard's device."""
+        with self._mask_lock:
+            if self._dev_decay is None:
+                from .device_decay import DeviceDecayColumns
+                self._dev_decay = DeviceDecayColumns(None if self._synthetic_rows else self._cols, self._main.first.device)
+            return self._dev_decay
 
     def _host_group_keys(self, field: str) -> np.ndarray:
         """int64 group key per global row on the host (collections whose masks are host arrays: several shards, the
@@ -1125,7 +1139,8 @@ class MilvusIndexManager:
 
     async def search(self, query_embedding, collection_name: str, top_k: int = 20, filters: Optional[str] = None,
                      search_params: Optional[Dict] = None, *, group_by_field: Optional[str] = None,
-                     group_size: int = 1, strict_group_size: Optional[bool] = None, offset: int = 0) -> List[Dict[str, Any]]:
+                     group_size: int = 1, strict_group_size: Optional[bool] = None, offset: int = 0,
+                     ranker: Optional[DecayRanker] = None) -> List[Dict[str, Any]]:
         """Collection.search (reference indexing.py:503-525).  offset=o: hits o .. o + top_k - 1 of the ranking, with
         W = o + top_k <= QUERY_MAX_WINDOW (deep_window).  W <= HR_MAX_TOPK is the plain search at top_k = W with the first o
         hits cut; a deeper window takes the deep search (exact, a full read of the shard per query; not with
@@ -1134,7 +1149,14 @@ class MilvusIndexManager:
         shorter list.  F is an integer or a string field of the schema (chunk_index, token_count, doc_id, id / chunk_id,
         timestamp).  group_size=g > 1 is served by a manager created with group_members=True: up to g rows of each of the
         top_k best groups as one flat list, groups in ranking order, a group's rows adjacent and in ranking order; top_k * g
-        <= HR_MAX_TOPK.  The answer is exact (pymilvus' strict_group_size=True), so strict_group_size changes nothing."""
+        <= HR_MAX_TOPK.  The answer is exact (pymilvus' strict_group_size=True), so strict_group_size changes nothing.
+        ranker=DecayRanker(...) (pymilvus' decay ranker): the first W = max(top_k, ranker.candidates or top_k) <= HR_MAX_TOPK
+        hits of the plain ranking are re-scored as normalised score x decay(|field - origin|) and re-sorted (stable), the best
+        top_k returned: "score" is the final score, "raw_score" the hit's own.  Not with group_by_field, offset or a deep
+        window (ValueError); NotImplementedError in the torchrun form."""
+        if ranker is not None:
+            return await self._search_decayed(query_embedding, collection_name, top_k, filters, search_params, ranker,
+                                              group_by_field, group_size, strict_group_size, offset)
         if group_by_field is not None or group_size != 1 or strict_group_size is not None:
             self._check_group_request(group_by_field, group_size, top_k, strict_group_size)
         group_size = int(group_size)
@@ -1183,7 +1205,8 @@ class MilvusIndexManager:
     async def hybrid_search(self, dense_embedding, sparse_embedding, top_k: int, filters: Optional[str],
                             weights: Sequence[float], rrf_k: int = 60, semantic_params: Optional[Dict] = None,
                             sparse_params: Optional[Dict] = None, mmr_lambda: Optional[float] = None,
-                            fusion: str = "rrf", norms: Optional[Sequence[int]] = None):
+                            fusion: str = "rrf", norms: Optional[Sequence[int]] = None,
+                            decay: Optional[DecayRanker] = None):
         """The semantic search (2 x top_k), the sparse search (2 x top_k) and their rank fusion for ONE request in ONE
         round of the batching front: what `search` + `search` + `fuse_rank_lists_async` return, cut to the fused top_k.
 
@@ -1198,9 +1221,19 @@ class MilvusIndexManager:
 
         fusion="weighted": the two lists are fused by weighted score fusion (hr_post_args::fusion = 1) instead of RRF;
         norms = the HR_NORM_* codes of the semantic and the sparse list (None = "activation" by the collections' metrics).
-        The torchrun form declines such a request; MMR and the rerank consume the fused scores as they do RRF's."""
+        The torchrun form declines such a request; MMR and the rerank consume the fused scores as they do RRF's.
+
+        decay=DecayRanker(...): the WHOLE fused list (4 x top_k entries, as for MMR) is reranked by hr_decay_rerank_dev behind
+        the post kernel on the same stream — fused scores are not renormalised: identity, or min-max — and handed to MMR or
+        the cut in decayed order.  The second element of a result is then the final score and the hit carries "fused_score".
+        The torchrun form declines."""
         if fusion not in ("rrf", "weighted"):
             raise ValueError(f"fusion must be 'rrf' or 'weighted', got {fusion!r}")
+        if decay is not None:
+            if not isinstance(decay, DecayRanker):
+                raise ValueError(f"decay must be a DecayRanker or None, got {decay!r}")
+            from .device_decay import check_decay_field
+            check_decay_field(decay.field, bool(self._synthetic_rows))
         if mmr_lambda is not None and not self.mmr_on_device:
             return None
         sem, spa = self.collections.get("semantic_index"), self.collections.get("sparse_index")
@@ -1234,8 +1267,13 @@ class MilvusIndexManager:
             return None
         w = list(weights) + [0.0] * (2 - len(weights))
         mmr = mmr_lambda is not None
-        fut = front.submit_async("hybrid", (int(top_k), filters, drop, int(rrf_k), mmr) + fuse_key,
-                                 (dense_embedding, payload, float(w[0]), float(w[1]), float(mmr_lambda) if mmr else 0.0))
+        request = (dense_embedding, payload, float(w[0]), float(w[1]), float(mmr_lambda) if mmr else 0.0)
+        if decay is not None:       # field and norm code in the key, the curve's operands per query
+            if front.collective:
+                return None
+            fuse_key += ("decay", decay.field, decay.norm_code("IP", fused=True))
+            request += (decay.operands(),)
+        fut = front.submit_async("hybrid", (int(top_k), filters, drop, int(rrf_k), mmr) + fuse_key, request)
         try:
             # no timer of its own: the caller (HybridRetriever.retrieve) already bounds the whole request with
             # RetrievalConstants.TIMEOUT_SECONDS, and a wait_for here is a task + a timer handle per request on the event
@@ -1245,8 +1283,11 @@ class MilvusIndexManager:
             return None
         if res is None:
             return None
-        rows, fused_scores, methods, orig = res
+        rows, fused_scores, methods, orig = res[:4]
         hits = self._format_hits(rows, orig)
+        if decay is not None:
+            for hit, raw in zip(hits, res[4].tolist()):
+                hit["fused_score"] = raw
         return list(zip(hits, fused_scores.tolist(), methods.tolist()))
 
     @staticmethod
@@ -1335,6 +1376,101 @@ class MilvusIndexManager:
         rows, scores, methods = await asyncio.wait_for(front.submit_async("fuse_scores", key, payload),
                                                        timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
         return self._fuse_output(row_to_id, rows, scores, methods)
+
+    # ---- decay ranker (pymilvus' decay ranker; the contract is in include/hbmrag.h, the restatement in decay.py) ---------
+    def _decay_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
+        """(collection, W, norm code) of a search with a ranker, or the refusal — before anything is searched."""
+        if not isinstance(ranker, DecayRanker):
+            raise ValueError(f"ranker must be a DecayRanker or None, got {ranker!r}")
+        if collection_name not in self.collections:
+            raise ValueError(f"Collection {collection_name} not found")
+        coll = self.collections[collection_name]
+        if group_by_field is not None or group_size != 1 or strict_group_size is not None:
+            raise ValueError("ranker cannot be combined with group_by_field")
+        if isinstance(offset, (bool, np.bool_)) or not isinstance(offset, (int, np.integer)) or offset != 0:
+            raise ValueError(f"ranker cannot be combined with offset, got offset={offset!r}")
+        if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
+            raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
+        window = ranker.window(top_k)
+        if window > HR_MAX_TOPK:
+            raise ValueError(f"ranker reranks the best max(top_k, candidates) = {window} rows: a deep window (> HR_MAX_TOPK = "
+                             f"{HR_MAX_TOPK}) is not built")
+        from .device_decay import check_decay_field
+        check_decay_field(ranker.field, bool(self._synthetic_rows))
+        if hasattr(coll.handle, "round"):
+            raise NotImplementedError("the decay ranker is not built for the torchrun form (CollectiveShardSet)")
+        return coll, window, ranker.norm_code("IP" if coll.kind == "sparse" else coll.metric)
+
+    async def _search_decayed(self, query_embedding, collection_name, top_k, filters, search_params, ranker, group_by_field,
+                              group_size, strict_group_size, offset) -> List[Dict[str, Any]]:
+        coll, window, norm = self._decay_request(collection_name, top_k, ranker, group_by_field, group_size,
+                                                 strict_group_size, offset)
+        operands = ranker.operands()       # origin=None reads the clock here, once per request
+        hits = await self.search(query_embedding, collection_name, window, filters, search_params)
+        if not hits:
+            return hits
+        rows = np.asarray([h["_row"] for h in hits], dtype=np.int64)
+        scores = np.asarray([h["score"] for h in hits], dtype=np.float32)      # fp32 list scores, widened by _format_hits
+        pos, _, final = await self._decay_rows_async(rows, scores, ranker.field, operands, norm)
+        out = []
+        for p, f in zip(pos[:int(top_k)], final[:int(top_k)]):
+            hit = hits[int(p)]
+            hit["raw_score"], hit["score"] = hit["score"], float(f)
+            out.append(hit)
+        return out
+
+    def _decay_rows_blocking(self, payload, key):
+        """The host restatement over row numbers (sharded managers, stand-ins, the front's one-by-one fallback):
+        payload = (rows int64, scores, operands), key = (field, norm, ...) -> (positions, rows, float64 final scores)."""
+        from .device_decay import host_values
+        rows, scores, operands = payload
+        self._count("decay_host_reranks")
+        values = host_values(None if self._synthetic_rows else self._cols, key[0], self.num_rows, rows)
+        pos, ids, final = decay_rerank(np.asarray(rows).tolist(), [float(x) for x in scores], values.tolist(), operands,
+                                       int(key[1]), len(rows))
+        return np.asarray(pos, dtype=np.int32), np.asarray(ids, dtype=np.int64), np.asarray(final, dtype=np.float64)
+
+    async def _decay_rows_async(self, rows: np.ndarray, scores: np.ndarray, field: str, operands, norm: int):
+        """(positions, rows, final scores) of ONE list in decayed order, whole.  On one GPU shard through the batching front:
+        the field, the norm code, the padded list length and the score type are the request key, the operands travel per
+        query, so concurrent requests with different curves share one hr_decay_rerank_dev launch.  Everything else is
+        reranked on the host by the restatement, with the same result, and counted in stats["decay_host_reranks"]: a manager
+        without a front (sharded, coalesce=False), a list longer than 3 * HR_MAX_TOPK entries (three modality lists at a
+        large top_k on the general path) and, inside the front, the requests of a batch whose launch was refused."""
+        n, K = len(rows), HR_MAX_TOPK
+        width = next(w for w in (K // 4, K, 3 * K, n) if n <= w)      # few distinct launch shapes
+        key = (field, int(norm), width, scores.dtype == np.float64)
+        payload = (rows, scores, tuple(operands))
+        front = self._coalescer(self.collections["semantic_index"]) if "semantic_index" in self.collections else None
+        if front is None or front.collective or n > 3 * K or self._device_shard(self._main) is None:
+            return await asyncio.to_thread(self._decay_rows_blocking, payload, key)
+        return await asyncio.wait_for(front.submit_async("decay", key, payload),
+                                      timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
+
+    def _decay_list_request(self, rows, scores, ranker: DecayRanker, operands=None):
+        if not isinstance(ranker, DecayRanker):
+            raise ValueError(f"decay must be a DecayRanker, got {ranker!r}")
+        from .device_decay import check_decay_field
+        check_decay_field(ranker.field, bool(self._synthetic_rows))
+        rows, scores = np.asarray(rows, dtype=np.int64), np.asarray(scores, dtype=np.float64)
+        if rows.shape != scores.shape or rows.ndim != 1:
+            raise ValueError("a list's rows and scores differ in length")
+        return rows, scores, tuple(operands) if operands is not None else ranker.operands(), ranker.norm_code("IP", fused=True)
+
+    def decay_rerank_lists(self, rows, scores, ranker: DecayRanker, operands=None):
+        """The decay ranker over ONE fused list (row numbers and float64 fused scores), blocking, through the host
+        restatement: -> (positions into the list, float64 final scores) in decayed order.  Fused scores are not
+        renormalised: identity, or min-max with normalization="minmax"."""
+        rows, scores, operands, norm = self._decay_list_request(rows, scores, ranker, operands)
+        pos, _, final = self._decay_rows_blocking((rows, scores, operands), (ranker.field, norm))
+        return pos, final
+
+    async def decay_rerank_lists_async(self, rows, scores, ranker: DecayRanker, operands=None):
+        """decay_rerank_lists for a caller on the event loop: on one GPU shard concurrent callers share one
+        hr_decay_rerank_dev launch (a kind of its own in the batching front); sharded managers use the restatement."""
+        rows, scores, operands, norm = self._decay_list_request(rows, scores, ranker, operands)
+        pos, _, final = await self._decay_rows_async(rows, scores, ranker.field, operands, norm)
+        return pos, final
 
     # ------------------------------------------------------------------ embeddings
     async def _run_encoder(self, fn, *args):
@@ -1662,21 +1798,25 @@ class MilvusIndexManager:
 
     async def search_by_ids(self, ids, collection_name: str, top_k: int = 20, filters: Optional[str] = None,
                             search_params: Optional[Dict] = None, *, group_by_field: Optional[str] = None,
-                            group_size: int = 1, strict_group_size: Optional[bool] = None) -> List[List[Dict[str, Any]]]:
+                            group_size: int = 1, strict_group_size: Optional[bool] = None,
+                            ranker: Optional[DecayRanker] = None) -> List[List[Dict[str, Any]]]:
         """pymilvus' search by primary key ("more like this entity"): one hit list per id of `ids`, in request order, each
         exactly what search() returns for that entity's STORED vector of the named collection with the same arguments —
         the fp32-widened stored row of a dense collection, the stored payload of sparse_index; filters, range params and
-        grouping pass through untouched.  The entity itself is NOT excluded (it is its own best hit wherever the metric
+        grouping and `ranker` pass through untouched.  The entity itself is NOT excluded (it is its own best hit wherever the metric
         makes it so): a `range_filter` or the filter `id not in [...]` drops it.  A duplicate id gives two equal lists; of
         several live rows with one id (a re-ingest without a delete) the lowest row is used.  The vectors are fetched once
         for all ids and make one hop through the host; the searches are search() calls, so concurrent ones share the
         batching front's launches.  ValueError: `ids` empty or not a list, an id that is not a string, an id no live row
         carries (a deleted entity is not found), and whatever the filter language (its list cap) and search() (a sparse
         row of more than HR_MAX_QUERY_NNZ entries) refuse.  NotImplementedError in the torchrun form."""
+        if ranker is not None:      # refused before the vectors are fetched
+            self._decay_request(collection_name, top_k, ranker, group_by_field, group_size, strict_group_size, 0)
         queries = await asyncio.to_thread(self._stored_queries_blocking, ids, collection_name)
+        extra = {"ranker": ranker} if ranker is not None else {}
         return list(await asyncio.gather(*(self.search(q, collection_name, top_k, filters, search_params,
                                                        group_by_field=group_by_field, group_size=group_size,
-                                                       strict_group_size=strict_group_size) for q in queries)))
+                                                       strict_group_size=strict_group_size, **extra) for q in queries)))
 
     def _search_by_ids_blocking(self, ids, collection_name: str, top_k: int, filters: Optional[str],
                                 search_params: Optional[Dict], group_by_field: Optional[str], group_size: int,

@@ -57,6 +57,8 @@ class PipelineConfig:
     # RetrievalConfig.fusion / score_normalization: "rrf" as the reference, or "weighted" score fusion
     fusion: str = "rrf"
     score_normalization: str = "activation"
+    # RetrievalConfig.decay: a decay.DecayRanker over the fused list (freshness or any numeric field), or None
+    decay: Optional[Any] = None
 
 
 @dataclass
@@ -91,7 +93,7 @@ class AdvancedRAGPipeline:
             index_manager=self.index_manager,
             config=RetrievalConfig(hybrid_alpha=self.config.hybrid_alpha, top_k=self.config.top_k,
                                    enable_reranking=self.config.enable_reranking, fusion=self.config.fusion,
-                                   score_normalization=self.config.score_normalization),
+                                   score_normalization=self.config.score_normalization, decay=self.config.decay),
             learned_ranker=LearnedRanker())
         self.evaluator = RAGEvaluator()
         self.compliance = ComplianceManager(enable_audit=self.config.enable_audit_logging,

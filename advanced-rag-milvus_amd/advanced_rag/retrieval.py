@@ -25,6 +25,7 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
 
+from .decay import decay_rerank
 from ._native import (HR_MAX_TOPK, HR_NORM_ATAN, HR_NORM_ATAN_DIST, HR_NORM_COSINE, HR_NORM_MINMAX,   # importing the
                       HR_NORM_MINMAX_DIST)                        # binding module does not load the library
 from .constants import RetrievalConstants
@@ -95,8 +96,17 @@ class RetrievalConfig:
     # with fusion="weighted": "activation" normalises by the list's metric (COSINE (1 + s) / 2, IP 0.5 + atan(s) / pi, L2
     # 1 - 2 atan(s) / pi), "minmax" by the smallest and largest score of each list
     score_normalization: str = "activation"
+    # decay ranker (decay.DecayRanker) over the WHOLE fused list, right after the fusion and before the group pass, MMR and
+    # the cut: score = fused score x decay(|field - origin|), "fused_score" keeps the fusion's.  RRF and weighted fused
+    # scores are not renormalised: normalization="activation" means identity on a fused list, "minmax" rescales by the
+    # list's smallest and largest fused score.  `candidates` is not used here (the whole fused list is the window).
+    decay: Optional[Any] = None
 
     def __post_init__(self):
+        if self.decay is not None:
+            from .decay import DecayRanker
+            if not isinstance(self.decay, DecayRanker):
+                raise ValueError(f"decay must be a DecayRanker or None, got {self.decay!r}")
         if self.fusion not in FUSION_MODES:
             raise ValueError(f"fusion must be one of {', '.join(FUSION_MODES)}, got {self.fusion!r}")
         if self.score_normalization not in SCORE_NORMALIZATIONS:
@@ -173,9 +183,13 @@ def norm_code(metric: str, normalization: str = "activation") -> int:
     return HR_NORM_ATAN_DIST if dist else HR_NORM_COSINE if str(metric).upper() == "COSINE" else HR_NORM_ATAN
 
 
-def normalise_scores(scores: Sequence[float], code: int, atan: Callable[[float], float] = canonical_atan) -> List[float]:
-    """One list's scores -> [0, 1] values by the table of include/hbmrag.h (every operation rounded on its own)."""
-    s = [float(np.float32(x)) for x in scores]      # the lists hold fp32 scores: widened, never rounded again
+def normalise_scores(scores: Sequence[float], code: int, atan: Callable[[float], float] = canonical_atan,
+                     widened: bool = False) -> List[float]:
+    """One list's scores -> [0, 1] values by the table of include/hbmrag.h (every operation rounded on its own).
+    widened: the scores are doubles already (fp32 scores widened by the caller, or the fp64 scores of a fused list: the
+    decay ranker's) and are taken as they are."""
+    # the lists hold fp32 scores: widened, never rounded again
+    s = [float(x) for x in scores] if widened else [float(np.float32(x)) for x in scores]
     if code == HR_NORM_COSINE:
         return [(1.0 + v) * 0.5 for v in s]
     if code == HR_NORM_ATAN:
@@ -251,7 +265,7 @@ class HybridRetriever:
                                    enable_mmr=mmr, mmr_lambda=lam, group_by_field=base.group_by_field,
                                    group_size=base.group_size,
                                    extended_filter_operators=base.extended_filter_operators,
-                                   fusion=base.fusion, score_normalization=base.score_normalization)
+                                   fusion=base.fusion, score_normalization=base.score_normalization, decay=base.decay)
 
         return {
             "default": base,
@@ -352,6 +366,8 @@ class HybridRetriever:
         extra = {"mmr_lambda": cfg.mmr_lambda} if cfg.enable_mmr else {}
         if cfg.fusion == "weighted":     # (a default config makes the call it always made)
             extra.update(fusion="weighted", norms=tuple(self._list_norms()[:2]))
+        if cfg.decay is not None:
+            extra.update(decay=cfg.decay)
         saved = (cfg.dense_weight, cfg.sparse_weight)
         self._adapt_weights(query)   # the adapter sees only the query: applying it before the searches changes nothing
         try:
@@ -458,7 +474,40 @@ class HybridRetriever:
                       domain_results: Optional[List[Dict]] = None) -> List[Dict[str, Any]]:
         hit_lists = [semantic_results or [], sparse_results or [], domain_results or []]
         weights = [self.config.dense_weight, self.config.sparse_weight, self.DOMAIN_WEIGHT]
-        return self._assemble_fused(hit_lists, self._rank_fusion(hit_lists, weights))
+        ranked = self._rank_fusion(hit_lists, weights)
+        if self.config.decay is not None and ranked:
+            rows, scores, values, operands, norm = self._decay_inputs(hit_lists, ranked)
+            device = getattr(self.index_manager, "decay_rerank_lists", None)
+            order = device(rows, scores, self.config.decay, operands) if device is not None and rows is not None else \
+                decay_rerank(list(range(len(ranked))), scores, values, operands, norm, len(ranked))[::2]
+            return self._assemble_fused(hit_lists, *self._decay_ranked(ranked, *order))
+        return self._assemble_fused(hit_lists, ranked)
+
+    def _decay_inputs(self, hit_lists, ranked):
+        """What the decay ranker takes for a fused list: (rows or None when a hit carries no row number, float64 fused scores,
+        the field values as a hit's metadata shows them — for a manager that cannot look rows up —, operands, norm code)."""
+        from .decay import DECAY_FIELDS, epoch_seconds
+        spec = self.config.decay
+        payload: Dict[Any, Dict] = {}
+        for hits in hit_lists:
+            for hit in hits:
+                payload.setdefault(hit["id"], hit)
+        rows = [payload[doc_id].get("_row") for doc_id, _, _ in ranked]
+        values = []
+        for doc_id, _, _ in ranked:
+            v = (payload[doc_id].get("metadata") or {}).get(spec.field)
+            if DECAY_FIELDS[spec.field] == "epoch":
+                values.append(epoch_seconds(v))
+            else:
+                values.append(float(v) if isinstance(v, (int, float)) and not isinstance(v, bool) else float("nan"))
+        return (rows if all(r is not None for r in rows) else None, [float(s) for _, s, _ in ranked], values, spec.operands(),
+                spec.norm_code("IP", fused=True))
+
+    @staticmethod
+    def _decay_ranked(ranked, pos, final):
+        """The fused ranking reordered by the decay ranker -> (ranked with the final scores, id -> fused score)."""
+        fused_of = {doc_id: score for doc_id, score, _ in ranked}
+        return [(ranked[int(p)][0], float(f), ranked[int(p)][2]) for p, f in zip(pos, final)], fused_of
 
     async def _fuse_results_async(self, semantic_results, sparse_results, domain_results=None) -> List[Dict[str, Any]]:
         """_fuse_results for a caller on the event loop: with the HBM index manager the rank fusion of concurrent
@@ -482,9 +531,17 @@ class HybridRetriever:
                     logger.exception("device rank fusion failed; using host arithmetic")
         if ranked is None:
             ranked = self._rank_fusion(hit_lists, weights)
+        if self.config.decay is not None and ranked:
+            rows, scores, values, operands, norm = self._decay_inputs(hit_lists, ranked)
+            device = getattr(self.index_manager, "decay_rerank_lists_async", None)
+            if device is not None and rows is not None:
+                order = await device(rows, scores, self.config.decay, operands)
+            else:
+                order = decay_rerank(list(range(len(ranked))), scores, values, operands, norm, len(ranked))[::2]
+            return self._assemble_fused(hit_lists, *self._decay_ranked(ranked, *order))
         return self._assemble_fused(hit_lists, ranked)
 
-    def _assemble_fused(self, hit_lists, ranked) -> List[Dict[str, Any]]:
+    def _assemble_fused(self, hit_lists, ranked, fused_of: Optional[Dict[Any, float]] = None) -> List[Dict[str, Any]]:
         # payload of an id = the hit from the semantic list if present (overwritten
         # by a later semantic duplicate), else the first sparse/domain hit
         payload: Dict[Any, Dict] = {}
@@ -496,6 +553,9 @@ class HybridRetriever:
 
         now = datetime.utcnow()
         fused = [self._finish_fused_hit(payload[doc_id], score, seen_in, now) for doc_id, score, seen_in in ranked]
+        if fused_of is not None:      # a decay ranker reordered the list: "score" is the final one, the fusion's is kept
+            for hit, (doc_id, _, _) in zip(fused, ranked):
+                hit["fused_score"] = fused_of[doc_id]
         if self.config.group_by_field is not None:
             fused = self._first_per_group(fused, self.config.group_by_field, self.config.group_size)
         if self.config.enable_mmr and fused:

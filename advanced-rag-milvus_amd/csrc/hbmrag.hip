@@ -26,6 +26,7 @@
 #include "common.h"
 #include "attention.h"
 #include "compact.h"
+#include "decay.h"
 #include "deep.h"
 #include "encoder_layer.h"
 #include "scan_plan.h"
@@ -1354,7 +1355,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11500; }  // 1.15.0: weighted score fusion (hr_fuse_scores, hr_fuse_scores_dev, hr_post_args::fusion / norm)
+int hr_version(void) { return 11600; }  // 1.16.0: decay ranker (hr_decay_rerank_dev)
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2393,6 +2394,24 @@ int hr_group_select_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_i
                        k_out, d_out_pos, d_out_keys, d_out_n, d_flags);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "group_select_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+int hr_decay_rerank_dev(const int64_t* d_ids, const void* d_scores, int score_is_f64, const int32_t* d_n, int B, int k_in,
+                        const void* d_col, int col_kind, int64_t col_rows, int64_t first_row, const hr_decay_query* d_params,
+                        int norm, int k_out, int32_t* d_out_pos, int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_n,
+                        void* stream) {
+    if (B < 0 || k_in <= 0 || k_out <= 0 || k_out > k_in || col_rows < 0 || first_row < 0) return fail(nullptr, HR_EINVAL, "bad decay sizes");
+    if (k_in > kFuseMax) return fail(nullptr, HR_ELIMIT, "k_in exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+    if (norm < HR_NORM_NONE || norm > HR_NORM_MINMAX_DIST) return fail(nullptr, HR_EINVAL, "bad norm code %d", norm);
+    if (col_kind != HR_COL_I64 && col_kind != HR_COL_F32 && col_kind != HR_COL_F64) return fail(nullptr, HR_EINVAL, "bad column kind %d", col_kind);
+    if (B == 0) return HR_OK;
+    if (!d_ids || !d_scores || !d_params || !d_out_pos || !d_out_ids || !d_out_scores || !d_out_n) return fail(nullptr, HR_EINVAL, "null buffer");
+    if (col_rows > 0 && !d_col) return fail(nullptr, HR_EINVAL, "col_rows > 0 needs the column");
+    hipLaunchKernelGGL(decay_rerank_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, d_ids, d_scores, score_is_f64, d_n, k_in, d_col,
+                       col_kind, col_rows, first_row, d_params, norm, k_out, d_out_pos, d_out_ids, d_out_scores, d_out_n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "decay_rerank_kernel: %s", hipGetErrorString(e));
     return HR_OK;
 }
 

@@ -462,6 +462,51 @@ HR_API int hr_group_select_n_dev(const int64_t* d_ids, const int32_t* d_n, int B
 HR_API int hr_mask_keep_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out, int64_t n_rows,
                             const int64_t* d_keys, const int64_t* d_keep, int n_keep, void* stream);
 
+/* ---- decay ranker (the third ranker of a search, beside RRF and the weighted ranker) -------------------------------
+ * Re-ranks B ranked lists by  final = n(score) * decay(|field - origin|):  relevance damped by the distance of a
+ * numeric field (a timestamp, a chunk index, ...) from an origin.  The forms follow the decay functions of Milvus /
+ * Elasticsearch, but THIS TABLE is the contract, not Milvus.  Every operation is a separately rounded IEEE fp64
+ * operation, no FMA; division is correctly rounded.  For a list entry with score s (fp32 widened, or fp64) and field
+ * value v widened to double ((double)v for int64: exact below 2^53):
+ *   t = v - origin;  a = |t|;  u = a - offset;  d = u > 0 ? u : 0
+ *   f = HR_DECAY_GAUSS : cexp(coef * (d * d))          coef = ln(decay) / (scale * scale)
+ *       HR_DECAY_EXP   : cexp(coef * d)                coef = ln(decay) / scale
+ *       HR_DECAY_LINEAR: g = 1.0 - d * coef; g > 0 ? g : 0.0      coef = (1 - decay) / scale
+ *   v is NaN (the row has no value), or the id lies outside [first_row, first_row + col_rows):  f = 0.0
+ *   final = n(s) * f
+ * coef is computed by the caller (scale > 0, offset >= 0, 0 < decay < 1, so coef < 0 for gauss / exp and > 0 for
+ * linear) and travels as an operand: the device needs no logarithm.  An infinite d gives f = 0.  A `func` outside 0..2
+ * cannot be seen on the host, because the operands live on the device: it is DEFINED to give f = 0 for that query.
+ * n is the identity (HR_NORM_NONE, valid only in this entry point) or one of the five HR_NORM_* codes, exactly as in
+ * weighted score fusion; lo / hi are taken over the list's valid prefix.  Scores must be finite.
+ * The output order is the stable descending sort of `final` (ties keep input order, so a list whose rows all lack the
+ * field keeps its order with all-zero scores), cut to k_out.
+ * cexp is a canonical exponential without tables or library calls, so that host and device agree bit for bit:
+ *   x is NaN -> 0.0;  x >= 0 -> 1.0 (covers -0.0);  x < -708.0 -> 0.0
+ *   k = rint(x * 0x1.71547652b82fep+0)                    (ties to even)
+ *   r = (x - k * 0x1.62e42fee00000p-1) - k * 0x1.a39ef35793c76p-33
+ *   c_i = 1.0 / i!  (i = 0..13, each the correctly rounded double);  p = c_13;  for i = 12 .. 0: p = c_i + r * p
+ *   result = ldexp(p, (int)k)                              (exact: k >= -1021, the result is normal)
+ * d_ids / d_scores [B][k_in] (d_scores fp64 when score_is_f64 != 0, else fp32); the valid prefix of list q is d_n[q]
+ * entries (clamped into [0, k_in]), or with d_n == NULL the entries before the first id < 0, as in hr_group_select_dev.
+ * d_col: the field's column, col_rows values of kind HR_COL_I64, HR_COL_F32 or HR_COL_F64 (the last valid only here;
+ * the filter entry points keep refusing it), row r at d_col[r - first_row]; it may be NULL iff col_rows == 0.
+ * d_params: DEVICE array of B operand sets, so that queries with different curves share one launch.
+ * Out, [B][k_out]: d_out_pos positions into the query's list (-1 padded), d_out_ids (-1 padded), d_out_scores the
+ * final scores (0.0 padded); d_out_n[B] the entries written.
+ * 1 <= k_out <= k_in <= 3 * HR_MAX_TOPK (HR_ELIMIT for a k_in beyond; HR_EINVAL for the other orderings).  HR_EINVAL:
+ * a NULL required buffer, a norm outside -1..4, a col_kind outside the three, negative B / col_rows / first_row.  A
+ * refused call launches nothing and leaves the outputs alone.  B == 0: HR_OK, nothing is launched.  Asynchronous on
+ * `stream`.  The result is a function of the inputs alone: ranks come from comparisons, no atomic decides anything. */
+enum { HR_DECAY_GAUSS = 0, HR_DECAY_EXP = 1, HR_DECAY_LINEAR = 2 };
+enum { HR_COL_F64 = 5 };       /* valid only in hr_decay_rerank_dev */
+enum { HR_NORM_NONE = -1 };    /* valid only in hr_decay_rerank_dev */
+typedef struct hr_decay_query { double origin, offset, coef; int32_t func, reserved; } hr_decay_query;
+HR_API int hr_decay_rerank_dev(const int64_t* d_ids, const void* d_scores, int score_is_f64, const int32_t* d_n,
+                        int B, int k_in, const void* d_col, int col_kind, int64_t col_rows, int64_t first_row,
+                        const hr_decay_query* d_params /* device, [B] */, int norm, int k_out,
+                        int32_t* d_out_pos, int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_n, void* stream);
+
 /* Everything after the per-shard lists of a query batch in ONE launch (one block per query): [hr_merge_topk_dev of
  * every modality's exchanged lists] -> hr_fuse_rrf_dev (or hr_fuse_scores_dev: `fusion`) -> [hr_rerank_linear_dev]; results are bit-identical to the
  * separate calls (reference retrieval.py:421-491 fusion, :518-563 rerank, after the server-side shard merge of
