@@ -444,6 +444,11 @@ class _Base:
                 mapped[ours] = sd[theirs]
         own.update({k: v.to(own[k].dtype) for k, v in mapped.items() if k in own and own[k].shape == v.shape})
         self.module.load_state_dict(own)
+        # graphs captured before the load replay the kernels of the model as it was (the tanh-GELU epilogue): drop them,
+        # the next small batch captures anew
+        import threading
+        with self.__dict__.setdefault("_graph_lock", threading.Lock()):
+            self.__dict__.pop("_graphs", None)
         return self
 
 

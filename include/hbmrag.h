@@ -751,14 +751,17 @@ HR_API int hr_embed_layernorm_f16_dev(const int64_t* d_ids, const int64_t* d_typ
  * projection reads (the PyTorch SDPA call plus the permute / transpose copies around it, in one kernel):
  *   d_qkv [n_seq][T][3][heads][head_dim] fp16, d_lengths[n_seq] valid tokens per sequence (padding at the tail; NULL = T),
  *   d_out [n_seq][T][heads * head_dim] fp16 = softmax(scale * Q K^T, keys < length) V per head, fp32 accumulation.
- * T <= 1024 at head_dim 32, <= 512 at 64 (K and V of a (sequence, head) are staged in LDS); HR_ELIMIT beyond. */
+ * T <= 1024 at head_dim 32, <= 512 at 64 (K and V of a (sequence, head) are staged in LDS); HR_ELIMIT beyond.
+ * A length above T counts as T; a length of 0 or below leaves the sequence without a key, and ALL its output rows are
+ * zeros (not NaN).  Rows at or beyond a sequence's length are computed like any other (their values depend on the
+ * padding's contents); the rows below it depend on nothing at or beyond it. */
 HR_API int hr_attention_f16_dev(const void* d_qkv, const int32_t* d_lengths, void* d_out, int64_t n_seq, int T, int heads,
                          int head_dim, float scale, void* stream);
 /* The same kernel with its operands by pointer and stride (in halves, multiples of 8): query rows at
- * d_q + seq * q_seq_stride + token * q_token_stride + head * 32, key / value rows at d_k / d_v + seq * kv_seq_stride +
- * token * kv_token_stride + head * 32; the first n_queries (<= T) tokens of a sequence are its queries;
- * d_out [n_seq][n_queries][heads * 32].  The cross-encoder's last layer, whose head reads token 0 only, calls it with
- * n_queries = 1 over a [n_seq][T][2][heads][32] key / value buffer (advanced_rag/encoders.py). */
+ * d_q + seq * q_seq_stride + token * q_token_stride + head * head_dim, key / value rows at d_k / d_v + seq * kv_seq_stride +
+ * token * kv_token_stride + head * head_dim; the first n_queries (<= T) tokens of a sequence are its queries;
+ * d_out [n_seq][n_queries][heads * head_dim].  The cross-encoder's last layer, whose head reads token 0 only, calls it with
+ * n_queries = 1 over a [n_seq][T][2][heads][head_dim] key / value buffer (advanced_rag/encoders.py). */
 HR_API int hr_attention_rows_f16_dev(const void* d_q, int64_t q_seq_stride, int64_t q_token_stride, const void* d_k, const void* d_v,
                               int64_t kv_seq_stride, int64_t kv_token_stride, const int32_t* d_lengths, void* d_out,
                               int64_t n_seq, int T, int n_queries, int heads, int head_dim, float scale, void* stream);
@@ -778,6 +781,8 @@ HR_API int hr_attention_rows_f16_dev(const void* d_q, int64_t q_seq_stride, int6
  * = X[16 tile + c][32 s + 16 (j >> 2) + 4 g + (j & 3)], 1 KiB per (16-row tile, k-step); buffers hold ceil(rows / 16) tiles.
  * It is the accumulator layout of two neighbouring output tiles AND the B operand of the next product in accumulator k
  * order, so rows move with 16-byte accesses contiguous over the wave.  Row-major stays available per operand.
+ * The PAD ROWS of the last tile (rows .. 16 ceil(rows / 16) - 1) may hold anything, NaN bit patterns included: the kernels
+ * read them as part of whole tiles, use them for no stored row, and never write them.
  *
  * hr_linear_rows_f16_dev:  d_out[r][0..N) (row-major, row stride out_stride halves) = x[r][0..K) W^T + bias.  d_x: row-major
  *   [rows][K] (x_fr = 0: d_w_packed pieces [N/16][K/32] in natural k order) or FR (x_fr = 1: accumulator k order).
