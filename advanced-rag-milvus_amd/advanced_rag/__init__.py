@@ -5,7 +5,7 @@ shard store driven through libhbmrag (HIP kernels for gfx950)."""
 from .pipeline import AdvancedRAGPipeline, PipelineConfig, PipelineStage, RetrievalResult
 from .diagnostics import DocumentDiagnostics, DiagnosticMetrics
 from .chunking import AdaptiveChunker, ChunkMetadata, Chunk
-from .indexing import MilvusIndexManager, HbmIndexManager, IndexType, IndexConfig
+from .indexing import MilvusIndexManager, HbmIndexManager, IndexType, IndexConfig, SearchIterator
 from .retrieval import HybridRetriever, RetrievalConfig, CrossEncoderReranker, QueryClassifier
 from .ranker import LearnedRanker, LearnedRankerConfig
 from .semantic_enrichment import SemanticEnricher, EnrichmentResult
@@ -19,7 +19,7 @@ __version__ = "1.0.0"
 __all__ = [
     "AdvancedRAGPipeline", "PipelineConfig", "PipelineStage", "RetrievalResult",
     "DocumentDiagnostics", "DiagnosticMetrics", "AdaptiveChunker", "ChunkMetadata", "Chunk",
-    "MilvusIndexManager", "HbmIndexManager", "IndexType", "IndexConfig",
+    "MilvusIndexManager", "HbmIndexManager", "IndexType", "IndexConfig", "SearchIterator",
     "HybridRetriever", "RetrievalConfig", "CrossEncoderReranker", "QueryClassifier",
     "LearnedRanker", "LearnedRankerConfig", "SemanticEnricher", "EnrichmentResult",
     "QueryDecomposer", "DecompositionResult", "RAGEvaluator", "EvaluationMetrics", "DriftReport",

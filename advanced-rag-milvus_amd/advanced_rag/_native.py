@@ -173,6 +173,13 @@ _SIGNATURES = {
     "hr_deep_topk_scratch_bytes": (_c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
     "hr_deep_topk_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int64,
                                     _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_search_dense_deep_after": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                              _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p]),
+    "hr_search_sparse_deep_after": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p,
+                                               _c.c_void_p, _c.c_void_p, _c.c_float, _c.c_void_p, _c.c_int, _c.c_void_p,
+                                               _c.c_void_p]),
+    "hr_deep_topk_window_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int64,
+                                           _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_set_profiling": (_c.c_int, [_c.c_void_p, _c.c_int]),
     "hr_last_kernel_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
     "hr_last_compact_ms": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int]),
@@ -498,6 +505,54 @@ class ShardHandle:
                                                     _vp(m), 1 if d_rowmask else 0, _vp(ids), _vp(sc)))
         return ids, sc
 
+    @staticmethod
+    def _cursor(after, B: int):
+        """The cursor operand of the *_deep_after forms: None, or (scores [B], ids [B]) / (scores, ids, has [B]) -> the three
+        arrays the library reads (all None = no query has a cursor)."""
+        if after is None:
+            return None, None, None
+        score = np.ascontiguousarray(np.broadcast_to(np.asarray(after[0], dtype=np.float32), (B,)))
+        ids = np.ascontiguousarray(np.broadcast_to(np.asarray(after[1], dtype=np.int64), (B,)))
+        has = np.ones(B, np.uint8) if len(after) < 3 or after[2] is None else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(after[2]), (B,)).astype(bool), dtype=np.uint8)
+        return score, ids, has
+
+    def search_dense_deep_after(self, q: np.ndarray, k: int, after=None, bounds=None, rowmask: Optional[np.ndarray] = None,
+                                d_rowmask: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """The search iterator's page (hr_search_dense_deep_after): the first k <= HR_MAX_DEEP_K entries of the collection's
+        exact ranking that come strictly after the cursor `after` = (scores [B], ids [B][, has [B]]), None = from the top.
+        bounds = (radius, range_filter) of a range search, each None, a number or one per query: float64 as in
+        search_dense_range, handed to the library as the fp32 that keeps the same fp32 scores (f32_bound)."""
+        q = np.ascontiguousarray(np.atleast_2d(q), dtype=np.float32)
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != shard dim {self.dim}")
+        B = q.shape[0]
+        a_sc, a_id, a_has = self._cursor(after, B)
+        up = self.metric == HR_METRIC_L2
+        r, f = (None, None) if bounds is None else (self._bounds(bounds[0], B, "radius"), self._bounds(bounds[1], B, "range_filter"))
+        r, f = (None if r is None else f32_bound(r, up)), (None if f is None else f32_bound(f, up))
+        ids = np.empty((B, max(k, 0)), dtype=np.int64)
+        sc = np.empty((B, max(k, 0)), dtype=np.float32)
+        m = d_rowmask if d_rowmask else self._mask(rowmask, self.num_rows)
+        self._check(self._lib.hr_search_dense_deep_after(self._h, _vp(q), B, k, _vp(a_sc), _vp(a_id), _vp(a_has), _vp(r), _vp(f),
+                                                         _vp(m), 1 if d_rowmask else 0, _vp(ids), _vp(sc)))
+        return ids, sc
+
+    def search_sparse_deep_after(self, queries: Sequence[Tuple[Sequence[int], Sequence[float]]], k: int, after=None,
+                                 drop_ratio: float = 0.0, rowmask: Optional[np.ndarray] = None,
+                                 d_rowmask: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+        """hr_search_sparse_deep_after: the sparse ranking (positive scores only) after the cursor, as search_dense_deep_after."""
+        B = len(queries)
+        indptr, idx, val = csr_of_queries(queries)
+        a_sc, a_id, a_has = self._cursor(after, B)
+        ids = np.empty((B, max(k, 0)), dtype=np.int64)
+        sc = np.empty((B, max(k, 0)), dtype=np.float32)
+        m = d_rowmask if d_rowmask else self._mask(rowmask, self.num_sparse_rows)
+        self._check(self._lib.hr_search_sparse_deep_after(self._h, _vp(indptr), _vp(idx), _vp(val), B, k, _vp(a_sc), _vp(a_id),
+                                                          _vp(a_has), float(drop_ratio), _vp(m), 1 if d_rowmask else 0, _vp(ids),
+                                                          _vp(sc)))
+        return ids, sc
+
     def fuse_rrf(self, ids_a, ids_b, ids_c=(), wa: float = 0.7, wb: float = 0.3, wc: float = 0.2, rrf_k: int = 60):
         a = np.ascontiguousarray(ids_a, dtype=np.int64)
         b = np.ascontiguousarray(ids_b, dtype=np.int64)
@@ -691,6 +746,31 @@ def decay_rerank_dev(d_ids: int, d_scores: int, score_is_f64: bool, d_n: int, B:
 def mask_rows_scratch_bytes(n_rows: int) -> int:
     """hr_mask_rows_scratch_bytes: device scratch hr_mask_rows_dev needs for a mask of n_rows rows."""
     return int(load_library().hr_mask_rows_scratch_bytes(n_rows))
+
+
+def f32_bound(x, up: bool) -> np.ndarray:
+    """A range bound given as float64 -> the fp32 that cuts the fp32 scores at the same place: the largest fp32 <= x (COSINE
+    and IP: score > x and score <= x both hold for the same fp32 scores as with x rounded down), up=True the smallest fp32
+    >= x (L2: distance >= x, distance < x)."""
+    x = np.asarray(x, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        f = np.atleast_1d(x.astype(np.float32))
+    x = np.atleast_1d(x)
+    off = (f.astype(np.float64) < x) if up else (f.astype(np.float64) > x)
+    f[off] = np.nextafter(f[off], np.float32(np.inf if up else -np.inf))
+    return np.ascontiguousarray(f)
+
+
+def deep_topk_window_dev(d_scores: int, d_rows: int, n: int, B: int, k: int, ascending: bool, row_offset: int, d_bounds: int,
+                         d_out_ids: int, d_out_scores: int, d_scratch: int, stream: int = 0) -> None:
+    """hr_deep_topk_window_dev: the first k of [B][n] candidates whose ranking key lies inside the query's open interval
+    d_bounds [B][2] (uint64, device), by (score desc, row asc); scratch as deep_topk_dev at window k."""
+    L = load_library()
+    rc = L.hr_deep_topk_window_dev(_vp(d_scores), _vp(d_rows), n, B, k, 1 if ascending else 0, row_offset,
+                                   _vp(d_bounds) if d_bounds else None, _vp(d_out_ids), _vp(d_out_scores), _vp(d_scratch),
+                                   _vp(stream) if stream else None)
+    if rc != 0:
+        _raise_global(L, rc)
 
 
 def deep_topk_scratch_bytes(n: int, B: int, window: int) -> int:

@@ -40,7 +40,7 @@ from .decay import DecayRanker, decay_rerank
 from .constants import GROUP_WINDOW_FACTOR, QUERY_MAX_WINDOW, IndexingConstants
 from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache, get_semantic_cache
 from ._native import HR_MAX_TOPK   # importing the binding module does not load the library
-from .shards import PartialAppend, ShardSet, is_native_handle
+from .shards import PartialAppend, ShardSet, cursor_key_interval, is_native_handle, ord_f32, rank_key  # noqa: F401 (re-exported)
 from .staging import dense_rows_device, dense_rows_host, list_buffers
 
 logger = logging.getLogger(__name__)
@@ -135,6 +135,103 @@ def deep_window(top_k, offset=0) -> int:
     return int(top_k) + int(offset)
 
 
+def iterator_window(batch_size, limit=None) -> Tuple[int, Optional[int]]:
+    """(batch_size, limit) of a search iterator: batch_size an integer in 1 .. QUERY_MAX_WINDOW (one page is one deep
+    selection), limit None or an integer >= 1; bool and floats are refused, as deep_window refuses them."""
+    for name, v in (("batch_size", batch_size),) + ((("limit", limit),) if limit is not None else ()):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 1 <= batch_size <= QUERY_MAX_WINDOW:
+        raise ValueError(f"batch_size must be in 1 .. {QUERY_MAX_WINDOW}, got {batch_size}")
+    if limit is not None and limit < 1:
+        raise ValueError(f"limit must be None or >= 1, got {limit}")
+    return int(batch_size), None if limit is None else int(limit)
+
+
+def iterate_ranking(ids, scores, batch_size, limit=None):
+    """The pages a search iterator returns for a ranking that is already sorted: ids / scores [n] in ranking order (a -1 id
+    ends the ranking) -> (ids, scores) slices of batch_size entries, the last one shorter, `limit` entries in all."""
+    batch_size, limit = iterator_window(batch_size, limit)
+    ids, scores = np.asarray(ids), np.asarray(scores)
+    pad = np.flatnonzero(ids < 0)
+    n = int(pad[0]) if len(pad) else len(ids)
+    if limit is not None:
+        n = min(n, limit)
+    for lo in range(0, n, batch_size):
+        yield ids[lo:min(lo + batch_size, n)], scores[lo:min(lo + batch_size, n)]
+
+
+class SearchIterator:
+    """pymilvus' search_iterator on one collection: the ranking of ONE query page by page, to any depth.
+
+    A page is the first min(batch_size, remaining limit) rows of the collection's ranking (filter, tombstones and range
+    applied as search() applies them) that come strictly after the last hit returned: one call of the cursor forms
+    (hr_search_*_deep_after), i.e. one full refine of the shard, whatever the depth.  The iterator holds the last hit's
+    (score, row), the count and the manager's row-space generation; nothing is kept on the device between pages, so a
+    page sees the collection as it is when the page is asked for: a row deleted meanwhile and not yet returned does not
+    appear, an appended row appears if its place is after the cursor, no hit is returned twice.  compact(), load_snapshot()
+    and attach_shards() renumber or replace the rows a cursor speaks of: next() then raises RuntimeError."""
+
+    def __init__(self, manager: "MilvusIndexManager", query_embedding, collection_name: str, batch_size=1000, limit=None,
+                 filters: Optional[str] = None, search_params: Optional[Dict] = None):
+        self.batch_size, self.limit = iterator_window(batch_size, limit)
+        if collection_name not in manager.collections:
+            raise ValueError(f"Collection {collection_name} not found")
+        coll = manager.collections[collection_name]
+        params = manager._search_params(coll, search_params)
+        self._bounds = manager._range_request(coll, params, None)      # ValueError on the sparse collection, as search()
+        if hasattr(coll.handle, "round"):
+            raise NotImplementedError("search_iterator is not built for the torchrun form (CollectiveShardSet)")
+        self._manager, self._name, self._filters = manager, collection_name, filters
+        self._drop = float((params.get("params") or params).get("drop_ratio_search", 0.0))
+        self._query = manager._as_sparse_payload(query_embedding) if coll.kind == "sparse" else query_embedding
+        self._generation = manager._row_space_generation
+        self._after: Optional[Tuple[float, int]] = None
+        self.returned = 0
+        self._done = False
+        if self._bounds is not None:
+            try:
+                cursor_key_interval(None, self._bounds, coll.metric)
+            except ValueError:          # the bounds differ as float64 but no fp32 score lies between them
+                self._done = True
+
+    def next_blocking(self) -> List[Dict[str, Any]]:
+        """The next page as the usual hit dicts; [] once the ranking or `limit` is exhausted, and from then on."""
+        if self._done:
+            return []
+        m = self._manager
+        if m._row_space_generation != self._generation:
+            raise RuntimeError(f"the row space of {self._name} was replaced by {m._row_space_reason} since this iterator was "
+                               "created: its cursor names a row of the old numbering; create a new iterator")
+        k = self.batch_size if self.limit is None else min(self.batch_size, self.limit - self.returned)
+        hits = m._iterator_page_blocking(self._query, self._name, k, self._after, self._filters, self._bounds, self._drop)
+        if hits:
+            self._after = (hits[-1]["score"], hits[-1]["_row"])
+            self.returned += len(hits)
+        if len(hits) < k or (self.limit is not None and self.returned >= self.limit):
+            self._done = True
+        return hits
+
+    async def next(self) -> List[Dict[str, Any]]:
+        try:
+            return await asyncio.wait_for(asyncio.to_thread(self.next_blocking), timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
+        except asyncio.TimeoutError:
+            logging.error("shard search timeout for collection %s", self._name)
+            raise Exception(f"Search timeout for collection {self._name}")
+
+    def close(self) -> None:
+        self._done = True
+
+    def __aiter__(self):
+        return self
+
+    async def __anext__(self) -> List[Dict[str, Any]]:
+        page = await self.next()
+        if not page:
+            raise StopAsyncIteration
+        return page
+
+
 class SearchPath:
     """ONE blocking request's way to its rows: one local GPU shard with the row mask in HBM (`shard` is its ShardHandle;
     masks are packed CUDA tensors), or a host mask over every shard of the set (`shard` is None: several shards, the
@@ -173,6 +270,20 @@ class SearchPath:
             ids, sc = on.search_dense_range(self._q_host, k, bounds[0], bounds[1], *m)
         else:
             ids, sc = on.search_dense(self._q_host, k, *m, bounds=bounds)
+        return ids[0], sc[0]
+
+    def after(self, mask, k: int, after: Optional[Tuple[float, int]], bounds: Optional[Tuple[float, float]] = None):
+        """(ids [k], scores [k]): the first k entries of the ranking under `mask` strictly after the cursor `after` =
+        (score, row) (None: from the top) through the cursor forms; bounds: a range search's (dense only)."""
+        on, m = (self.coll.handle, (mask,)) if self.shard is None else \
+            (self.shard, (None, mask.data_ptr() if mask is not None else 0))
+        cursor = None if after is None else ([after[0]], [after[1]])
+        if self.sparse:
+            ids, sc = on.search_sparse_deep_after([self.query], k, cursor, self.drop, *m)
+            return ids[0], sc[0]
+        if self._q_host is None:
+            self._q_host = dense_rows_host([self.query])
+        ids, sc = on.search_dense_deep_after(self._q_host, k, cursor, bounds, *m)
         return ids[0], sc[0]
 
 
@@ -218,6 +329,11 @@ class ShardCollection:
               offset: int = 0) -> List[Dict[str, Any]]:
         """pymilvus' Collection.query(expr, output_fields, limit, offset), synchronous (MilvusIndexManager.query)."""
         return self.manager._query_blocking(self.name, expr, output_fields, limit, offset)
+
+    def search_iterator(self, query_embedding, batch_size=1000, limit=None, filters: Optional[str] = None,
+                        search_params: Optional[Dict] = None) -> SearchIterator:
+        """pymilvus' Collection.search_iterator, synchronous: page with it.next_blocking() (MilvusIndexManager.search_iterator)."""
+        return self.manager.search_iterator(query_embedding, self.name, batch_size, limit, filters, search_params)
 
     def search_by_ids(self, ids, top_k: int = 20, filters: Optional[str] = None, search_params: Optional[Dict] = None, *,
                       group_by_field: Optional[str] = None, group_size: int = 1,
@@ -268,11 +384,16 @@ class MilvusIndexManager:
         # queries: query() calls answered; query_device: those whose page came from hr_mask_rows_dev (mask never left HBM)
         # search_by_ids: search_by_ids() calls whose ids were resolved and whose stored vectors were fetched
         # deep_searches: searches with offset + top_k > HR_MAX_TOPK, answered by the deep forms (a full refine of the shard)
+        # iterator_pages: pages a SearchIterator fetched (each one call of the cursor forms: a full refine of the shard)
         # decay_host_reranks: decay rerankings answered by the Python restatement instead of hr_decay_rerank_dev (sharded
         # managers, lists beyond 3 * HR_MAX_TOPK entries, the front's one-by-one fallback after a refused batch)
         self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
                       "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0, "deep_searches": 0,
-                      "decay_host_reranks": 0}
+                      "decay_host_reranks": 0, "iterator_pages": 0}
+        # bumped by what renumbers or replaces the rows (compact, load_snapshot, attach_shards): a SearchIterator's cursor
+        # names a row, so an iterator created under another generation refuses to go on
+        self._row_space_generation = 0
+        self._row_space_reason = ""
         self._stats_lock = threading.Lock()    # the loop runs in worker threads and in the front's thread at once
         self._deleted: Optional[np.ndarray] = None
         self._mask_cache: Dict[Any, Optional[np.ndarray]] = {}   # (expr, rows, delete epoch) -> boolean row filter
@@ -330,6 +451,10 @@ class MilvusIndexManager:
         if sparse:
             self.collections["sparse_index"] = ShardCollection(self, "sparse_index", "sparse", self._main,
                                                                self.sparse_dim, "IP")
+
+    def _new_row_space(self, reason: str) -> None:
+        self._row_space_generation += 1
+        self._row_space_reason = reason
 
     def _forget_masks(self, rebuild_filters: bool):
         """Drop every cached row mask, host and HBM: the rows changed.  After an APPEND (_append_payload, add_rows) the device
@@ -389,6 +514,7 @@ class MilvusIndexManager:
         self._register_main_collections(bool(handles[0].sparse_dim))
         self._synthetic_rows = int(synthetic_rows)
         self._forget_masks(rebuild_filters=True)
+        self._new_row_space("attach_shards()")
 
     def serve(self):
         """Ranks > 0 of the torchrun form: answer rank 0's searches until it calls stop_workers()."""
@@ -605,6 +731,7 @@ class MilvusIndexManager:
         self._deleted = None
         self._delete_epoch += 1
         self._forget_masks(rebuild_filters=True)
+        self._new_row_space("compact()")
         out["rows_after"] = self.num_rows
         out["device_bytes_after"] = sum(int(getattr(s, "device_bytes", 0)) for s in sets)
         return out
@@ -852,6 +979,7 @@ class MilvusIndexManager:
                 self._domain.adopt(dom, [z[f"rows_domain_{s}"] for s in range(n_shards)])
             self._load_payload(z, with_columns=True)
         self._forget_masks(rebuild_filters=True)
+        self._new_row_space("load_snapshot()")
 
     def _load_payload(self, z, with_columns: bool):
         """The host half of a snapshot (payload.npz): the synthetic-row count and, with_columns, the tombstones and the columns."""
@@ -1099,6 +1227,24 @@ class MilvusIndexManager:
         self._count("deep_searches")
         path = SearchPath(self, coll, query, drop)
         return self._format_hits(*path.search(path.base(filters), top_k, offset=offset))
+
+    def _iterator_page_blocking(self, query, collection_name: str, k: int, after: Optional[Tuple[float, int]],
+                                filters: Optional[str], bounds: Optional[Tuple[float, float]], drop: float) -> List[Dict[str, Any]]:
+        """One page of a SearchIterator: the first k hits of ONE query's ranking strictly after `after` = (score, row) through
+        the cursor forms (hr_search_*_deep_after), the row mask taken as _deep_blocking takes it.  Not through the front."""
+        self._count("iterator_pages")
+        path = SearchPath(self, self.collections[collection_name], query, drop)
+        return self._format_hits(*path.after(path.base(filters), k, after, bounds))
+
+    def search_iterator(self, query_embedding, collection_name: str, batch_size=1000, limit=None,
+                        filters: Optional[str] = None, search_params: Optional[Dict] = None) -> SearchIterator:
+        """pymilvus' search_iterator: the collection's ranking for one query, `batch_size` <= 16 384 hits a page, `limit` hits
+        in all (None: to the end of the ranking, however deep).  `await it.next()` / `async for page in it` / it.close();
+        search_params as search() takes them, radius / range_filter on the dense collections included ("every row with
+        cosine > 0.6").  Every page is one full refine of the shard whatever its depth (SearchIterator).  ValueError at
+        creation: batch_size or limit out of range, what search() refuses for the collection; NotImplementedError in the
+        torchrun form.  Not built: grouping, ranker=, hybrid_search / retrieve()."""
+        return SearchIterator(self, query_embedding, collection_name, batch_size, limit, filters, search_params)
 
     # ---- coalescing front (batching.py) -------------------------------------------------------------------------
     def _coalescer(self, coll):

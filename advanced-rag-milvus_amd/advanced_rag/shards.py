@@ -78,6 +78,78 @@ def merge_deep_lists(ids: Sequence[np.ndarray], scores: Sequence[np.ndarray], to
     return np.ascontiguousarray(m_ids[:, offset:]), np.ascontiguousarray(m_sc[:, offset:])
 
 
+# ---- ranking keys on the host: the numpy twins of ord_f32 / rank_key (csrc/common.h) and deep_key_interval (csrc/deep.h)
+KEY_EVERYTHING = (0, 2 ** 64 - 1)     # the open interval that holds every key of a finite score
+
+
+def ord_f32(score) -> np.ndarray:
+    """fp32 -> uint32 of the same order (+0.0 above -0.0): sign bit set = all bits flipped, else the sign bit set."""
+    u = np.asarray(score, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+
+
+def rank_key(score, row) -> np.ndarray:
+    """The unique 64-bit ranking key of (score, row), row in 0 .. 2^32 - 1: (score desc, row asc) <=> key desc."""
+    return (ord_f32(score).astype(np.uint64) << np.uint64(32)) | (np.uint64(0xFFFFFFFF) - np.asarray(row).astype(np.uint64))
+
+
+def cursor_key_interval(after, bounds, metric: str, row_offset: int = 0) -> Tuple[int, int]:
+    """What the library makes of one query's cursor and range bounds (hr_search_*_deep_after): the open interval (lo, hi)
+    of ranking keys a page is selected from, as Python integers.
+
+    after = (score, id) of the last hit seen, or None: kept are the rows strictly after it — score worse, or score equal
+    and id larger.  id is any integer, a position, not a row that has to exist: with id - row_offset below 0 every row of
+    that score follows, beyond the 32-bit row space none does.  bounds = (radius, range_filter) as range_bounds() returns
+    them, or None; a side may be None or infinite (unbounded).  Under L2 the cursor's score and the bounds are distances
+    and are negated into the key domain.  A bound is first taken to the fp32 that cuts the fp32 scores where the float64
+    does (_native.f32_bound); a zero bound is +0.0, so that -0.0 and +0.0 scores fall on the same side, while the cursor's
+    score is used bit for bit.  ValueError: a non-finite cursor score, a NaN bound, an empty interval (range_bounds' rule)."""
+    from ._native import f32_bound
+    if metric not in ("L2", "IP", "COSINE"):
+        raise ValueError(f"unknown metric_type {metric!r}")
+    l2 = metric == "L2"
+    lo, hi = KEY_EVERYTHING
+    if bounds is not None:
+        radius = (np.inf if l2 else -np.inf) if bounds[0] is None else float(bounds[0])
+        range_filter = (-np.inf if l2 else np.inf) if bounds[1] is None else float(bounds[1])
+        if radius != radius or range_filter != range_filter:
+            raise ValueError("NaN range bound")
+        radius, range_filter = float(f32_bound(radius, l2)[0]), float(f32_bound(range_filter, l2)[0])
+        if (range_filter >= radius) if l2 else (radius >= range_filter):
+            raise ValueError(f"empty range for {metric}: radius={radius}, range_filter={range_filter}")
+        above, upto = (-radius, -range_filter) if l2 else (radius, range_filter)     # kept: above < score <= upto
+        if above != -np.inf:
+            lo = (int(ord_f32(np.float32(above) + np.float32(0.0))) << 32) | 0xFFFFFFFF     # x + 0.0: -0.0 becomes +0.0
+        if upto != np.inf:
+            hi = (int(ord_f32(np.float32(upto) + np.float32(0.0))) + 1) << 32
+    if after is not None:
+        with np.errstate(over="ignore"):
+            score = np.float32(after[0])
+        if not np.isfinite(score):
+            raise ValueError(f"non-finite cursor score {after[0]!r}")
+        top = int(ord_f32(-score if l2 else score)) << 32
+        row = int(after[1]) - int(row_offset)
+        hi = min(hi, top + (1 << 32) if row < 0 else top if row > 0xFFFFFFFF else top | (0xFFFFFFFF - row))
+    return lo, hi
+
+
+def page_after(ids: np.ndarray, scores: np.ndarray, k: int, after, bounds, ascending: bool) -> Tuple[np.ndarray, np.ndarray]:
+    """The cursor forms restated on complete rankings: ids / scores [B, n] (-1 padded, in ranking order) -> the first k
+    entries of each that lie inside the query's key interval, [B, k], -1 / 0 padded.  after = (scores [B], ids [B], has
+    [B]) or None.  Used for shard stand-ins that rank on the host."""
+    B = ids.shape[0]
+    out_ids, out_sc = empty_lists(B, k)
+    metric = "L2" if ascending else "IP"
+    for b in range(B):
+        cur = None if after is None or not after[2][b] else (after[0][b], after[1][b])
+        lo, hi = cursor_key_interval(cur, bounds, metric)
+        live = np.flatnonzero(ids[b] >= 0)
+        key = rank_key(-scores[b][live] if ascending else scores[b][live], ids[b][live])
+        take = live[(key > np.uint64(lo)) & (key < np.uint64(hi))][:k]
+        out_ids[b, :len(take)], out_sc[b, :len(take)] = ids[b][take], scores[b][take]
+    return out_ids, out_sc
+
+
 class PartialAppend(RuntimeError):
     """A multi-shard append failed after some pieces had gone in: global rows [base, end) exist in the shards."""
 
@@ -328,6 +400,57 @@ class ShardSet:
             return h.search_sparse_deep(queries, k, offset, drop_ratio, *self._local_mask(0, keep))
         return self._deep("search_sparse", "num_sparse_rows", len(queries), k, offset, False,
                           lambda form, s: form(queries, offset + k, drop_ratio, *self._local_mask(s, keep)))
+
+    # ---- the search iterator's page: the first k entries of the ranking strictly after a cursor (hr_search_*_deep_after)
+    @staticmethod
+    def _cursor(after, B: int):
+        """after = None or (scores, rows[, has]) per query -> None or three arrays [B] (float32, int64 GLOBAL rows, bool)."""
+        if after is None:
+            return None
+        has = np.ones(B, bool) if len(after) < 3 or after[2] is None else np.broadcast_to(np.asarray(after[2], dtype=bool), (B,))
+        return (np.broadcast_to(np.asarray(after[0], dtype=np.float32), (B,)),
+                np.broadcast_to(np.asarray(after[1], dtype=np.int64), (B,)), has)
+
+    def _after(self, name: str, rows_attr: str, B: int, k: int, after, bounds, ascending: bool, call, full):
+        """Every shard's page behind the SAME cursor, translated into the shard's own ids (the last of its rows at or before
+        the cursor's global row: rows_of is ascending), merged on the host.  A row among the first k of the collection after
+        the cursor is among the first k of its own shard after it (the argument of merge_deep_lists), so the merge is exact.
+        call(form, s, after_s) -> the shard's page; a stand-in without the cursor form ranks all its n rows (full(form, s, n),
+        as _deep_of) and the page is cut on the host (page_after)."""
+        after = self._cursor(after, B)
+
+        def one(s):
+            h = self.handles[s]
+            n = getattr(h, rows_attr)
+            if n == 0:
+                return empty_lists(B, k)
+            mine = after
+            if after is not None and self.n_shards > 1:
+                local = np.searchsorted(self.rows_of[s], after[1], side="right") - 1 + int(getattr(h, "row_offset", 0))
+                mine = (after[0], local.astype(np.int64), after[2])
+            form = getattr(h, name + "_deep_after", None)
+            if form is not None:
+                return call(form, s, mine)
+            ids, sc = full(self._deep_of(h, name), s, n)
+            return page_after(ids, sc, k, mine, bounds, ascending)
+        parts = self._fan_out(one)
+        if self.n_shards == 1:
+            return parts[0]
+        ids = [to_global(li, self.rows_of[s]) for s, (li, _) in enumerate(parts)]
+        return merge_lists(ids, [sc for _, sc in parts], k, ascending)
+
+    def search_dense_deep_after(self, q: np.ndarray, k: int, after=None, bounds=None, keep: Optional[np.ndarray] = None):
+        """The first k <= HR_MAX_DEEP_K entries of the dense ranking strictly after the cursor after = (scores [B], GLOBAL rows
+        [B][, has [B]]) (None: from the top), cut to bounds = (radius, range_filter) when given.  The cursor is a position:
+        its row need not exist (any more).  One shard: the call passed through; several: _after."""
+        return self._after("search_dense", "num_rows", np.atleast_2d(q).shape[0], k, after, bounds, self.dense_ascending,
+                           lambda form, s, a: form(q, k, a, bounds, *self._local_mask(s, keep)),
+                           lambda form, s, n: form(q, n, *self._local_mask(s, keep)))
+
+    def search_sparse_deep_after(self, queries, k: int, after=None, drop_ratio: float = 0.0, keep: Optional[np.ndarray] = None):
+        return self._after("search_sparse", "num_sparse_rows", len(queries), k, after, None, False,
+                           lambda form, s, a: form(queries, k, a, drop_ratio, *self._local_mask(s, keep)),
+                           lambda form, s, n: form(queries, n, drop_ratio, *self._local_mask(s, keep)))
 
     # ------------------------------------------------------------------ read path
     def _locate(self, global_rows):

@@ -15,6 +15,12 @@
 //
 // Ties at the W-th score are ties of the upper 32 bits only: the lower four passes resolve them by the row bits exactly as
 // block_kth_largest (select.h) does, and when every score is equal they decide alone.
+//
+// A ranking is a total order on unique keys, so "the next k rows after the last hit seen" and "the rows whose score lies
+// in a range" are both one open key interval (lo, hi) per query (deep_key_interval below).  The windowed instantiations
+// of the hist and gather kernels turn a key outside it into 0 where the key is formed; nothing else changes, and a
+// query with fewer than W keys inside behaves as one with masked rows does: the zeros are counted as the smallest keys,
+// the threshold may end at 0, and the gather, which never takes a 0, counts exactly the valid keys.
 #pragma once
 #include "common.h"
 
@@ -40,6 +46,7 @@ struct DeepArgs {
     DeepState* state;                    // [B]
     unsigned* hist;                      // [B][kDeepPasses][256]
     unsigned long long* keys;            // [B][W]
+    const unsigned long long* bounds;    // [B][2] or null: the windowed kernels keep bounds[q][0] < key < bounds[q][1]
 };
 
 __device__ inline uint64_t deep_key(const float* __restrict__ sc, const int32_t* __restrict__ rw, int64_t i) {
@@ -47,6 +54,38 @@ __device__ inline uint64_t deep_key(const float* __restrict__ sc, const int32_t*
     return r < 0 ? 0ull : rank_key(sc[i], (uint32_t)r);
 }
 
+// WIN: a key outside the query's open interval (lo, hi) is an invalid candidate (0), like a masked row: every pass below
+// treats it as the smallest key there is, and the gather never takes it.
+template <bool WIN>
+__device__ inline uint64_t deep_key(const float* __restrict__ sc, const int32_t* __restrict__ rw, int64_t i, uint64_t lo,
+                                    uint64_t hi) {
+    const uint64_t kk = deep_key(sc, rw, i);
+    if constexpr (WIN) return (kk > lo && kk < hi) ? kk : 0ull;
+    return kk;
+}
+
+// The open key interval of one query of the cursor forms (hr_search_*_deep_after), host side.  Scores are in the KEY
+// domain (an L2 caller negates its distances and bounds first): kept are the keys of rows with above < score <= upto
+// (-inf / +inf = that side open) that come strictly after the cursor (after_score, after_row) in the ranking: score
+// worse, or score equal and row larger.  after_row is a position, any int64: below 0 every row of that score follows,
+// beyond the 32-bit row space none does.  A zero BOUND is +0.0, so that both zeros fall on the side float comparison
+// puts them; the cursor's score is taken bit for bit.
+inline void deep_key_interval(bool has_after, float after_score, int64_t after_row, float above, float upto,
+                              unsigned long long out[2]) {
+    const auto canon = [](float x) { return x == 0.f ? 0.f : x; };
+    unsigned long long lo = 0ull, hi = ~0ull;
+    if (above != -__builtin_inff()) lo = ((unsigned long long)ord_f32(canon(above)) << 32) | 0xFFFFFFFFull;
+    if (upto != __builtin_inff()) hi = ((unsigned long long)ord_f32(canon(upto)) + 1ull) << 32;
+    if (has_after) {
+        const unsigned long long s = (unsigned long long)ord_f32(after_score) << 32;
+        const unsigned long long c = after_row < 0 ? s + (1ull << 32) : after_row > 0xFFFFFFFFll ? s : s | (0xFFFFFFFFull - (unsigned long long)after_row);
+        if (c < hi) hi = c;
+    }
+    out[0] = lo;
+    out[1] = hi;
+}
+
+template <bool WIN>
 __global__ __launch_bounds__(kDeepHistThreads) void deep_hist_kernel(DeepArgs a, int pass) {
     __shared__ unsigned bins[256];
     const int q = blockIdx.y;
@@ -58,8 +97,9 @@ __global__ __launch_bounds__(kDeepHistThreads) void deep_hist_kernel(DeepArgs a,
     const int32_t* __restrict__ rw = a.row + (int64_t)q * a.n;
     const int shift = 56 - 8 * pass;
     const int64_t stride = (int64_t)gridDim.x * kDeepHistThreads;
+    const uint64_t lo = WIN ? a.bounds[2 * q] : 0ull, hi = WIN ? a.bounds[2 * q + 1] : 0ull;
     for (int64_t i = (int64_t)blockIdx.x * kDeepHistThreads + threadIdx.x; i < a.n; i += stride) {
-        const uint64_t kk = deep_key(sc, rw, i);
+        const uint64_t kk = deep_key<WIN>(sc, rw, i, lo, hi);
         const bool hit = (kk & st.mask) == st.prefix;
         const unsigned d = (unsigned)(kk >> shift) & 255u;
         // the upper digits of a shard's scores are nearly all equal: a wave whose hits share one digit adds once
@@ -105,6 +145,7 @@ __global__ __launch_bounds__(64) void deep_pick_kernel(DeepArgs a, int pass) {
     }
 }
 
+template <bool WIN>
 __global__ __launch_bounds__(kDeepHistThreads) void deep_gather_kernel(DeepArgs a) {
     const int q = blockIdx.y;
     const uint64_t thr = a.state[q].prefix;
@@ -112,8 +153,9 @@ __global__ __launch_bounds__(kDeepHistThreads) void deep_gather_kernel(DeepArgs 
     const int32_t* __restrict__ rw = a.row + (int64_t)q * a.n;
     unsigned long long* out = a.keys + (int64_t)q * a.W;
     const int64_t stride = (int64_t)gridDim.x * kDeepHistThreads;
+    const uint64_t lo = WIN ? a.bounds[2 * q] : 0ull, hi = WIN ? a.bounds[2 * q + 1] : 0ull;
     for (int64_t i = (int64_t)blockIdx.x * kDeepHistThreads + threadIdx.x; i < a.n; i += stride) {
-        const uint64_t kk = deep_key(sc, rw, i);
+        const uint64_t kk = deep_key<WIN>(sc, rw, i, lo, hi);
         const bool take = kk != 0 && kk >= thr;      // unique keys: exactly min(W, valid) of them
         const unsigned long long takers = __ballot(take);
         if (takers == 0) continue;

@@ -1355,7 +1355,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11600; }  // 1.16.0: decay ranker (hr_decay_rerank_dev)
+int hr_version(void) { return 11700; }  // 1.17.0: search iterator (hr_search_*_deep_after, hr_deep_topk_window_dev)
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -3054,8 +3054,12 @@ size_t hr_deep_topk_scratch_bytes(int64_t n, int B, int window) {
     return deep_zeroed_bytes(B) + (size_t)B * window * sizeof(unsigned long long);
 }
 
-int hr_deep_topk_dev(const float* d_scores, const int32_t* d_rows, int64_t n, int B, int k, int offset, int ascending,
-                     int64_t row_offset, int64_t* d_out_ids, float* d_out_scores, void* d_scratch, void* stream) {
+namespace {
+// hr_deep_topk_dev and, with d_bounds, hr_deep_topk_window_dev: the same sixteen + two launches, the hist and gather
+// kernels in their windowed instantiation when there is an interval to apply.
+int deep_topk_launch(const float* d_scores, const int32_t* d_rows, int64_t n, int B, int k, int offset, int ascending,
+                     int64_t row_offset, int64_t* d_out_ids, float* d_out_scores, void* d_scratch, void* stream,
+                     const unsigned long long* d_bounds) {
     HR_TRY(check_deep_window(nullptr, k, offset));
     if (n < 0) return fail(nullptr, HR_EINVAL, "n must not be negative");
     if (B < 1) return fail(nullptr, HR_EINVAL, "batch size must be positive (got %d)", B);
@@ -3080,15 +3084,18 @@ int hr_deep_topk_dev(const float* d_scores, const int32_t* d_rows, int64_t n, in
     a.state = reinterpret_cast<DeepState*>(base);
     a.hist = reinterpret_cast<unsigned*>(base + deep_align((size_t)B * sizeof(DeepState)));
     a.keys = reinterpret_cast<unsigned long long*>(base + deep_zeroed_bytes(B));
+    a.bounds = d_bounds;
     HIP_TRY(nullptr, hipMemsetAsync(base, 0, deep_zeroed_bytes(B), s));
     // blocks per query: 8 keys per thread at least, and no more than a few rounds of the chip
     const unsigned blocks = (unsigned)std::min<int64_t>(std::max<int64_t>((n + kDeepHistThreads * 8 - 1) / (kDeepHistThreads * 8), 1),
                                                         std::max(1, 4096 / B));
+    const auto hist = d_bounds ? deep_hist_kernel<true> : deep_hist_kernel<false>;
     for (int pass = 0; pass < kDeepPasses; ++pass) {
-        hipLaunchKernelGGL(deep_hist_kernel, dim3(blocks, B), dim3(kDeepHistThreads), 0, s, a, pass);
+        hipLaunchKernelGGL(hist, dim3(blocks, B), dim3(kDeepHistThreads), 0, s, a, pass);
         hipLaunchKernelGGL(deep_pick_kernel, dim3(B), dim3(64), 0, s, a, pass);
     }
-    hipLaunchKernelGGL(deep_gather_kernel, dim3(blocks, B), dim3(kDeepHistThreads), 0, s, a);
+    hipLaunchKernelGGL(d_bounds ? deep_gather_kernel<true> : deep_gather_kernel<false>, dim3(blocks, B), dim3(kDeepHistThreads), 0,
+                       s, a);
     HIP_TRY(nullptr, hipGetLastError());
     const int P = deep_sort_slots(W);
     if ((size_t)P * sizeof(unsigned long long) > 48 * 1024)   // per device, idempotent: set where the default does not reach
@@ -3099,6 +3106,20 @@ int hr_deep_topk_dev(const float* d_scores, const int32_t* d_rows, int64_t n, in
     HIP_TRY(nullptr, hipGetLastError());
     return HR_OK;
 }
+}  // namespace
+
+int hr_deep_topk_dev(const float* d_scores, const int32_t* d_rows, int64_t n, int B, int k, int offset, int ascending,
+                     int64_t row_offset, int64_t* d_out_ids, float* d_out_scores, void* d_scratch, void* stream) {
+    return deep_topk_launch(d_scores, d_rows, n, B, k, offset, ascending, row_offset, d_out_ids, d_out_scores, d_scratch, stream,
+                            nullptr);
+}
+
+int hr_deep_topk_window_dev(const float* d_scores, const int32_t* d_rows, int64_t n, int B, int k, int ascending,
+                            int64_t row_offset, const unsigned long long* d_bounds, int64_t* d_out_ids, float* d_out_scores,
+                            void* d_scratch, void* stream) {
+    return deep_topk_launch(d_scores, d_rows, n, B, k, 0, ascending, row_offset, d_out_ids, d_out_scores, d_scratch, stream,
+                            d_bounds);
+}
 
 namespace {
 constexpr size_t kDeepCandidateCap = (size_t)512 << 20;   // transient candidate arrays of one pass of queries
@@ -3108,7 +3129,8 @@ constexpr size_t kDeepCandidateCap = (size_t)512 << 20;   // transient candidate
 // c0 .. c0 + nq - 1 into bufs.  Every buffer that grows with the shard is a local of this call.
 extern "C++" template <typename Stage, typename Refine>
 int deep_host(hr_index* h, int B, int k, int offset, int64_t hr_index::*rows, bool ascending, int ph_refine, int ph_topk,
-              const uint8_t* rowmask, bool mask_on_device, int64_t* out_ids, float* out_scores, Stage stage, Refine refine) {
+              const uint8_t* rowmask, bool mask_on_device, int64_t* out_ids, float* out_scores, Stage stage, Refine refine,
+              const unsigned long long* bounds = nullptr) {
     std::shared_lock<std::shared_mutex> lk(h->rw);
     DeviceGuard dg(h->device);
     const int64_t n_rows = h->*rows;
@@ -3124,7 +3146,7 @@ int deep_host(hr_index* h, int B, int k, int offset, int64_t hr_index::*rows, bo
     const int C = (int)C64;
     const size_t per_query = (size_t)n_slots * 8 + (size_t)C * 4;
     int Bp = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, kDeepCandidateCap / per_query));
-    DevBuf cscore, crow, cand, acut, scratch, d_ids, d_scores;
+    DevBuf cscore, crow, cand, acut, scratch, d_ids, d_scores, d_bounds;
     for (;; Bp = (Bp + 1) / 2) {
         const bool ok = cscore.alloc_exact((size_t)Bp * n_slots * 4) == hipSuccess &&
                         crow.alloc_exact((size_t)Bp * n_slots * 4) == hipSuccess &&
@@ -3137,7 +3159,8 @@ int deep_host(hr_index* h, int B, int k, int offset, int64_t hr_index::*rows, bo
     }
     if (acut.alloc_exact((size_t)Bp * 4) != hipSuccess || d_ids.alloc_exact((size_t)B * k * 8) != hipSuccess ||
         d_scores.alloc_exact((size_t)B * k * 4) != hipSuccess ||
-        scratch.alloc_exact(hr_deep_topk_scratch_bytes(n_slots, Bp, k + offset)) != hipSuccess) {
+        scratch.alloc_exact(hr_deep_topk_scratch_bytes(n_slots, Bp, k + offset)) != hipSuccess ||
+        (bounds && d_bounds.alloc_exact((size_t)B * 16) != hipSuccess)) {
         (void)hipGetLastError();
         return fail(h, HR_ENOMEM, "deep search: list buffers do not fit");
     }
@@ -3146,6 +3169,7 @@ int deep_host(hr_index* h, int B, int k, int offset, int64_t hr_index::*rows, bo
     if (!ws) return fail(h, HR_ENOMEM, "workspace allocation failed");
     hipStream_t s = ws->stream;
     HR_TRY(stage(ws, s));
+    if (bounds) HIP_TRY(h, hipMemcpyAsync(d_bounds.p, bounds, (size_t)B * 16, hipMemcpyHostToDevice, s));
     const uint8_t* d_mask = mask_on_device ? rowmask : nullptr;
     if (rowmask && !mask_on_device) {
         const size_t mb = (size_t)(n_rows + 7) / 8;
@@ -3173,8 +3197,9 @@ int deep_host(hr_index* h, int B, int k, int offset, int64_t hr_index::*rows, bo
         }
         if (rc != HR_OK) break;
         Span sp(h, s, ph_topk);
-        rc = hr_deep_topk_dev(cscore.as<float>(), crow.as<int32_t>(), n_slots, nq, k, offset, ascending, h->row_offset,
-                              d_ids.as<int64_t>() + (size_t)c0 * k, d_scores.as<float>() + (size_t)c0 * k, scratch.p, s);
+        rc = deep_topk_launch(cscore.as<float>(), crow.as<int32_t>(), n_slots, nq, k, offset, ascending, h->row_offset,
+                              d_ids.as<int64_t>() + (size_t)c0 * k, d_scores.as<float>() + (size_t)c0 * k, scratch.p, s,
+                              bounds ? d_bounds.as<unsigned long long>() + (size_t)c0 * 2 : nullptr);
         if (rc != HR_OK) rc = fail(h, rc, "deep selection: %s", std::string(g_last_error).c_str());
     }
     if (rc != HR_OK) {
@@ -3198,12 +3223,10 @@ int check_deep_args(hr_index* h, int B, int k, int offset, bool dense) {
 }
 }  // namespace
 
-int hr_search_dense_deep(hr_index* h, const float* q, int B, int k, int offset, const uint8_t* rowmask, int mask_on_device,
-                         int64_t* out_ids, float* out_scores) {
-    HR_TRY(check_deep_args(h, B, k, offset, true));
-    if (!q || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
-    for (int64_t i = 0; i < (int64_t)B * h->dim; ++i)
-        if (!std::isfinite(q[i])) return fail(h, HR_EINVAL, "non-finite value in query %lld", (long long)(i / h->dim));
+namespace {
+// The dense deep forms after their argument checks; bounds: the cursor form's key intervals ([B][2], host), or null.
+int dense_deep_host(hr_index* h, const float* q, int B, int k, int offset, const uint8_t* rowmask, int mask_on_device,
+                    int64_t* out_ids, float* out_scores, const unsigned long long* bounds) {
     Workspace* held = nullptr;
     return deep_host(
         h, B, k, offset, &hr_index::n_rows, h->metric == HR_METRIC_L2, PH_REFINE, PH_TOPK, rowmask, mask_on_device != 0, out_ids,
@@ -3224,14 +3247,20 @@ int hr_search_dense_deep(hr_index* h, const float* q, int B, int k, int offset, 
             f.d_q = held->d_q.as<float>() + (size_t)c0 * h->dim;
             b.qn2 = held->qn2.as<double>() + c0;
             return launch_refine(h, s, nq, f, b);
-        });
+        },
+        bounds);
 }
 
-int hr_search_sparse_deep(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B, int k,
-                          int offset, float drop_ratio, const uint8_t* rowmask, int mask_on_device, int64_t* out_ids,
-                          float* out_scores) {
-    HR_TRY(check_deep_args(h, B, k, offset, false));
-    if (!q_indptr || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
+int check_dense_deep_buffers(hr_index* h, const float* q, int B, const int64_t* out_ids, const float* out_scores) {
+    if (!q || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
+    for (int64_t i = 0; i < (int64_t)B * h->dim; ++i)
+        if (!std::isfinite(q[i])) return fail(h, HR_EINVAL, "non-finite value in query %lld", (long long)(i / h->dim));
+    return HR_OK;
+}
+
+int sparse_deep_host(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B, int k, int offset,
+                     float drop_ratio, const uint8_t* rowmask, int mask_on_device, int64_t* out_ids, float* out_scores,
+                     const unsigned long long* bounds) {
     SparseQueries sq;
     HR_TRY(prep_sparse_queries(h, q_indptr, q_idx, q_val, B, drop_ratio, &sq));
     Workspace* held = nullptr;
@@ -3252,7 +3281,74 @@ int hr_search_sparse_deep(hr_index* h, const int64_t* q_indptr, const int32_t* q
             f.q_val = held->d_qval.as<float>();
             f.stride = (int)round_up(std::max(sq.max_nnz, 1), 64);
             return launch_refine(h, s, nq, f, b);
-        });
+        },
+        bounds);
+}
+}  // namespace
+
+int hr_search_dense_deep(hr_index* h, const float* q, int B, int k, int offset, const uint8_t* rowmask, int mask_on_device,
+                         int64_t* out_ids, float* out_scores) {
+    HR_TRY(check_deep_args(h, B, k, offset, true));
+    HR_TRY(check_dense_deep_buffers(h, q, B, out_ids, out_scores));
+    return dense_deep_host(h, q, B, k, offset, rowmask, mask_on_device, out_ids, out_scores, nullptr);
+}
+
+int hr_search_sparse_deep(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B, int k,
+                          int offset, float drop_ratio, const uint8_t* rowmask, int mask_on_device, int64_t* out_ids,
+                          float* out_scores) {
+    HR_TRY(check_deep_args(h, B, k, offset, false));
+    if (!q_indptr || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
+    return sparse_deep_host(h, q_indptr, q_idx, q_val, B, k, offset, drop_ratio, rowmask, mask_on_device, out_ids, out_scores,
+                            nullptr);
+}
+
+namespace {
+// The cursor forms' operands -> the key interval of every query ([B][2], deep_key_interval), refused before anything is
+// launched or written.  A cursor counts where all three arrays are given and has_after[b] is set; ids become rows here.
+int deep_after_intervals(hr_index* h, int B, bool l2, const float* after_score, const int64_t* after_id, const uint8_t* has_after,
+                         const float* radius, const float* range_filter, std::vector<unsigned long long>* out) {
+    out->resize((size_t)B * 2);
+    const bool cursors = after_score && after_id && has_after;
+    for (int b = 0; b < B; ++b) {
+        const float r = radius ? radius[b] : (l2 ? INFINITY : -INFINITY);
+        const float f = range_filter ? range_filter[b] : (l2 ? -INFINITY : INFINITY);
+        if (std::isnan(r) || std::isnan(f)) return fail(h, HR_EINVAL, "NaN range bound in query %d", b);
+        if (l2 ? f >= r : r >= f)
+            return fail(h, HR_EINVAL, "empty range in query %d: radius %g, range_filter %g (%s)", b, (double)r, (double)f,
+                        l2 ? "L2 keeps range_filter <= distance < radius" : "kept are radius < score <= range_filter");
+        const bool has = cursors && has_after[b];
+        float s = 0.f;
+        int64_t row = 0;
+        if (has) {
+            if (!std::isfinite(after_score[b])) return fail(h, HR_EINVAL, "non-finite after_score in query %d", b);
+            s = l2 ? -after_score[b] : after_score[b];
+            if (__builtin_sub_overflow(after_id[b], h->row_offset, &row)) row = after_id[b] < 0 ? -1 : INT64_MAX;
+        }
+        deep_key_interval(has, s, row, l2 ? -r : r, l2 ? -f : f, out->data() + (size_t)b * 2);
+    }
+    return HR_OK;
+}
+}  // namespace
+
+int hr_search_dense_deep_after(hr_index* h, const float* q, int B, int k, const float* after_score, const int64_t* after_id,
+                               const uint8_t* has_after, const float* radius, const float* range_filter, const uint8_t* rowmask,
+                               int mask_on_device, int64_t* out_ids, float* out_scores) {
+    HR_TRY(check_deep_args(h, B, k, 0, true));
+    HR_TRY(check_dense_deep_buffers(h, q, B, out_ids, out_scores));
+    std::vector<unsigned long long> bounds;
+    HR_TRY(deep_after_intervals(h, B, h->metric == HR_METRIC_L2, after_score, after_id, has_after, radius, range_filter, &bounds));
+    return dense_deep_host(h, q, B, k, 0, rowmask, mask_on_device, out_ids, out_scores, bounds.data());
+}
+
+int hr_search_sparse_deep_after(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B, int k,
+                                const float* after_score, const int64_t* after_id, const uint8_t* has_after, float drop_ratio,
+                                const uint8_t* rowmask, int mask_on_device, int64_t* out_ids, float* out_scores) {
+    HR_TRY(check_deep_args(h, B, k, 0, false));
+    if (!q_indptr || !out_ids || !out_scores) return fail(h, HR_EINVAL, "null buffer");
+    std::vector<unsigned long long> bounds;
+    HR_TRY(deep_after_intervals(h, B, false, after_score, after_id, has_after, nullptr, nullptr, &bounds));
+    return sparse_deep_host(h, q_indptr, q_idx, q_val, B, k, 0, drop_ratio, rowmask, mask_on_device, out_ids, out_scores,
+                            bounds.data());
 }
 
 int hr_fuse_rrf(hr_index* h, const int64_t* ids_a, int na, const int64_t* ids_b, int nb, const int64_t* ids_c, int nc,

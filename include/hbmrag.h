@@ -253,6 +253,43 @@ HR_API size_t hr_deep_topk_scratch_bytes(int64_t n, int B, int window);
 HR_API int hr_deep_topk_dev(const float* d_scores, const int32_t* d_rows, int64_t n, int B, int k, int offset, int ascending,
                             int64_t row_offset, int64_t* d_out_ids, float* d_out_scores, void* d_scratch, void* stream);
 
+/* ---- search iterator: the next k entries of a ranking after a cursor, at any depth ---------------------------------
+ * hr_search_dense_deep_after / hr_search_sparse_deep_after are the two deep host forms with `offset` replaced by
+ * per-query operands, each [B] on the host, any of them NULL = no query has one:
+ *   after_score, after_id, has_after   the cursor of query b where has_after[b] != 0 (all three arrays given);
+ *   radius, range_filter (dense)       the bounds of a range search, NULL / -+inf = that side unbounded.
+ * R is the ranking defined above hr_search_dense_deep, cut to the rows in range by the rules of hr_search_dense_range
+ * decided on the fp32 score the hit carries (COSINE, IP: radius < score <= range_filter; L2: range_filter <= distance <
+ * radius).  The result is the first k <= HR_MAX_DEEP_K entries of R that come strictly AFTER (after_score, after_id):
+ * score worse, or score equal and id larger.  Ids are the handle's (row + row_offset); under L2 cursor and hits are
+ * distances.  after_id may be ANY int64: below the row offset, beyond the last row, the id of a masked or deleted row.
+ * It is a position in the order, not a row that has to exist, so several shards share one cursor and a delete between
+ * two pages is harmless.  Feeding the last hit of a page back gives the next page: R is walked to its end, past
+ * HR_MAX_DEEP_K rows, with nothing kept on the device between the calls; every call costs one full refine of the shard.
+ *   The library turns cursor and bounds into one open interval of ranking keys per query.  +0.0 and -0.0 are different
+ *   keys but equal floats: a zero BOUND puts both zeros on the side float comparison puts them; the cursor's score is
+ *   taken bit for bit (it is a score the library returned).
+ *   HR_EINVAL: a non-finite after_score where has_after is set, a NaN bound, an empty interval (hr_search_dense_range's
+ *   rule), and what the deep forms refuse; HR_ELIMIT: k > HR_MAX_DEEP_K.  A refused call launches and writes nothing.
+ *   Memory, HR_ENOMEM and the profiling spans are those of the deep forms (+ 16 bytes per query). */
+HR_API int hr_search_dense_deep_after(hr_index* h, const float* q, int B, int k, const float* after_score,
+                                      const int64_t* after_id, const uint8_t* has_after, const float* radius,
+                                      const float* range_filter, const uint8_t* rowmask, int mask_on_device,
+                                      int64_t* out_ids, float* out_scores);
+HR_API int hr_search_sparse_deep_after(hr_index* h, const int64_t* q_indptr, const int32_t* q_idx, const float* q_val, int B,
+                                       int k, const float* after_score, const int64_t* after_id, const uint8_t* has_after,
+                                       float drop_ratio, const uint8_t* rowmask, int mask_on_device, int64_t* out_ids,
+                                       float* out_scores);
+/* hr_deep_topk_dev with a per-query open key interval instead of an offset: d_bounds [B][2] on the device, kept are the
+ * candidates with d_bounds[b][0] < rank_key(score, row) < d_bounds[b][1], where rank_key = (ord(score) << 32) |
+ * (0xFFFFFFFF - row) and ord maps an fp32 to a uint32 of the same order (sign bit set: all bits flipped, else the sign bit
+ * set).  The first k of them in ranking order are written, then -1 / 0: a query whose interval holds nothing writes only
+ * padding.  d_bounds NULL = no interval (hr_deep_topk_dev at offset 0).  Scratch: hr_deep_topk_scratch_bytes(n, B, k).
+ * Refusals as hr_deep_topk_dev. */
+HR_API int hr_deep_topk_window_dev(const float* d_scores, const int32_t* d_rows, int64_t n, int B, int k, int ascending,
+                                   int64_t row_offset, const unsigned long long* d_bounds, int64_t* d_out_ids,
+                                   float* d_out_scores, void* d_scratch, void* stream);
+
 /* Reciprocal-rank fusion of up to three ranked id lists of ONE query
  * (reference HybridRetriever._fuse_results, retrieval.py:421-491), executed
  * by the device kernel.  ids < 0 end a list.  out arrays hold na+nb+nc
