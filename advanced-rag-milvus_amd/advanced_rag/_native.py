@@ -21,7 +21,8 @@ HR_METHOD_SEMANTIC, HR_METHOD_SPARSE, HR_METHOD_DOMAIN = 1, 2, 4
 HR_MAX_TOPK = 256
 # normalisation of one list's scores in the weighted score fusion (hr_fuse_scores_dev; the table is in include/hbmrag.h)
 HR_NORM_COSINE, HR_NORM_ATAN, HR_NORM_ATAN_DIST, HR_NORM_MINMAX, HR_NORM_MINMAX_DIST = 0, 1, 2, 3, 4
-# decay ranker (hr_decay_rerank_dev): curve codes, the identity normalisation and the float64 column kind, valid only there
+# decay ranker (hr_decay_rerank_dev): curve codes, the identity normalisation (also hr_mmr_select_vec_dev's) and the float64
+# column kind, valid only there
 HR_DECAY_GAUSS, HR_DECAY_EXP, HR_DECAY_LINEAR = 0, 1, 2
 HR_NORM_NONE = -1
 HR_COL_F64 = 5        # beside HR_COL_I64 / HR_COL_F32 below
@@ -130,6 +131,9 @@ _SIGNATURES = {
                                         _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_mmr_select_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                      _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_mmr_vec_scratch_bytes": (_c.c_size_t, [_c.c_void_p, _c.c_int, _c.c_int]),
+    "hr_mmr_select_vec_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int,
+                                         _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_group_select_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_decay_rerank_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
@@ -378,6 +382,21 @@ class ShardHandle:
         self._check(self._lib.hr_get_dense_rows_dev(self._h, _vp(d_rows) if d_rows else None, n, out_dtype,
                                                     _vp(d_out) if d_out else None, out_stride or self.dim,
                                                     _vp(d_missing) if d_missing else None, _vp(stream) if stream else None))
+
+    def mmr_vec_scratch_bytes(self, B: int, k_in: int) -> int:
+        """hr_mmr_vec_scratch_bytes: the bytes of d_scratch that mmr_select_vec_dev needs for B lists of k_in entries."""
+        return int(self._lib.hr_mmr_vec_scratch_bytes(self._h, B, k_in))
+
+    def mmr_select_vec_dev(self, d_ids: int, d_scores: int, score_is_f64: bool, norm: int, d_n: int, B: int, k_in: int,
+                           d_lambda: int, k_out: int, d_scratch: int, d_out_pos: int, d_out_val: int, d_out_n: int,
+                           stream: int = 0):
+        """hr_mmr_select_vec_dev (device pointers; 0 = NULL; asynchronous on `stream`): greedy MMR over B ranked lists on
+        the cosine of the stored rows, lambda per query at d_lambda -> list positions in pick order, the value of every
+        pick, the picks per query."""
+        p = lambda x: _vp(x) if x else None  # noqa: E731
+        self._check(self._lib.hr_mmr_select_vec_dev(self._h, p(d_ids), p(d_scores), 1 if score_is_f64 else 0, norm, p(d_n), B, k_in,
+                                                    p(d_lambda), k_out, p(d_scratch), p(d_out_pos), p(d_out_val), p(d_out_n),
+                                                    p(stream)))
 
     def get_sparse_rows(self, rows) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """hr_get_sparse_rows: the stored sparse rows with the given GLOBAL ids (any order, repeats allowed) as one CSR

@@ -38,6 +38,11 @@ origin, offset, coefficient and function travel per query (hr_decay_query), so r
 `hr_decay_rerank_dev` launch (stats["decay_launches"]).  In the one-round path the same kernel runs behind `hr_post_lists_dev`
 on the hybrid stream, over the whole fused list, before MMR or the cut.
 
+Vector MMR selections (search(..., ranker=MMRRanker(...)) behind its plain search, retrieve() with
+RetrievalConfig(mmr_similarity="embedding") behind its fusion) are wired the same way, kind "mmr": the collection, the padded
+list length, the norm code and the score type are the key, lambda travels per query, and the requests of a round share ONE
+`hr_mmr_select_vec_dev` launch (counted in stats["mmr_launches"] beside the token-Jaccard launches).
+
 One worker thread per manager; the event loop never blocks on the GPU.
 """
 from __future__ import annotations
@@ -125,7 +130,7 @@ class RangedQuery:
 
 @dataclass
 class _Request:
-    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "decay" | "hybrid" | "encode"
+    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "decay" | "mmr" | "hybrid" | "encode"
     key: Tuple                # requests with equal (kind, key) share a launch
     payload: Any
     future: Future = field(default_factory=Future)
@@ -280,7 +285,7 @@ class SearchCoalescer:
         dev = torch.device("cuda", self.mgr.device)
         # one stream per kind of work: the dense and the sparse searches of a round run side by side (a lone retrieve()
         # overlaps its two scans, as its two worker threads did before the front existed)
-        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "decay", "hybrid", "encode")}
+        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "decay", "mmr", "hybrid", "encode")}
         for reqs in self._rounds():
             groups: Dict[Tuple, List[_Request]] = {}
             for r in reqs:
@@ -396,6 +401,8 @@ class SearchCoalescer:
                 _answer(r.future, self.mgr._fuse_scores_blocking, r.payload, key)
             elif kind == "decay":
                 _answer(r.future, self.mgr._decay_rows_blocking, r.payload, key)
+            elif kind == "mmr":
+                _answer(r.future, self.mgr._mmr_rows_blocking, r.payload, key)
             elif kind == "hybrid":
                 _deliver(r.future, None)   # the caller falls back to two searches + a fusion
             elif kind == "encode":
@@ -737,3 +744,37 @@ class SearchCoalescer:
         for i, r in enumerate(chunk):
             n = int(on[i])
             _deliver(r.future, (pos[i, :n].copy(), oi[i, :n].copy(), os_[i, :n].copy()))
+
+    # ------------------------------------------------------------------ vector MMR
+    def _enqueue_mmr(self, torch, dev, stream, key, chunk):
+        """The vector MMR selections of a round in ONE hr_mmr_select_vec_dev launch: key = (collection, padded list length,
+        norm code, scores are float64), payload = (rows, scores, lambda, k_out).  lambda travels per query; the launch
+        selects the largest k_out asked for, and a greedy selection's shorter answers are prefixes of its longer ones."""
+        coll_name, width, norm, f64 = key
+        handle = self.mgr.collections[coll_name].handle.first
+        B = len(chunk)
+        k_out = min(width, max(int(r.payload[3]) for r in chunk))
+        ids = np.full((B, width), -1, dtype=np.int64)
+        sc = np.zeros((B, width), dtype=np.float64 if f64 else np.float32)
+        n = np.zeros(B, dtype=np.int32)
+        lam = np.zeros(B, dtype=np.float64)
+        for i, r in enumerate(chunk):
+            rows, scores, lam[i], _ = r.payload
+            n[i] = len(rows)
+            ids[i, :n[i]] = rows
+            sc[i, :n[i]] = scores
+        d_ids, d_sc, d_n, d_lam = (torch.from_numpy(a).to(dev) for a in (ids, sc, n, lam))
+        scratch = torch.empty(max(handle.mmr_vec_scratch_bytes(B, width), 16), dtype=torch.uint8, device=dev)
+        pos = torch.empty((B, k_out), dtype=torch.int32, device=dev)
+        val = torch.empty((B, k_out), dtype=torch.float64, device=dev)
+        on = torch.empty((B,), dtype=torch.int32, device=dev)
+        handle.mmr_select_vec_dev(d_ids.data_ptr(), d_sc.data_ptr(), f64, norm, d_n.data_ptr(), B, width, d_lam.data_ptr(), k_out,
+                                  scratch.data_ptr(), pos.data_ptr(), val.data_ptr(), on.data_ptr(), stream.cuda_stream)
+        self.stats["mmr_launches"] += 1
+        return {"pos": pos, "val": val, "on": on, "keep": (d_ids, d_sc, d_n, d_lam, scratch)}
+
+    def _scatter_mmr(self, key, chunk, st):
+        pos, val, on = (st[k].cpu().numpy() for k in ("pos", "val", "on"))
+        for i, r in enumerate(chunk):
+            n = min(int(on[i]), int(r.payload[3]))
+            _deliver(r.future, (pos[i, :n].copy(), val[i, :n].copy()))

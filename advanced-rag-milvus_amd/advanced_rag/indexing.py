@@ -37,6 +37,7 @@ import numpy as np
 from . import filters as _filters
 from .columns import FLOAT_COLUMNS, PayloadColumns, check_group_field
 from .decay import DecayRanker, decay_rerank
+from .mmr import MMRRanker, vector_mmr
 from .constants import GROUP_WINDOW_FACTOR, QUERY_MAX_WINDOW, IndexingConstants
 from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache, get_semantic_cache
 from ._native import HR_MAX_TOPK   # importing the binding module does not load the library
@@ -387,9 +388,11 @@ class MilvusIndexManager:
         # iterator_pages: pages a SearchIterator fetched (each one call of the cursor forms: a full refine of the shard)
         # decay_host_reranks: decay rerankings answered by the Python restatement instead of hr_decay_rerank_dev (sharded
         # managers, lists beyond 3 * HR_MAX_TOPK entries, the front's one-by-one fallback after a refused batch)
+        # mmr_host_selects: vector MMR selections answered by the Python restatement instead of hr_mmr_select_vec_dev (the
+        # same cases)
         self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
                       "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0, "deep_searches": 0,
-                      "decay_host_reranks": 0, "iterator_pages": 0}
+                      "decay_host_reranks": 0, "iterator_pages": 0, "mmr_host_selects": 0}
         # bumped by what renumbers or replaces the rows (compact, load_snapshot, attach_shards): a SearchIterator's cursor
         # names a row, so an iterator created under another generation refuses to go on
         self._row_space_generation = 0
@@ -1286,7 +1289,7 @@ class MilvusIndexManager:
     async def search(self, query_embedding, collection_name: str, top_k: int = 20, filters: Optional[str] = None,
                      search_params: Optional[Dict] = None, *, group_by_field: Optional[str] = None,
                      group_size: int = 1, strict_group_size: Optional[bool] = None, offset: int = 0,
-                     ranker: Optional[DecayRanker] = None) -> List[Dict[str, Any]]:
+                     ranker: Optional[Any] = None) -> List[Dict[str, Any]]:
         """Collection.search (reference indexing.py:503-525).  offset=o: hits o .. o + top_k - 1 of the ranking, with
         W = o + top_k <= QUERY_MAX_WINDOW (deep_window).  W <= HR_MAX_TOPK is the plain search at top_k = W with the first o
         hits cut; a deeper window takes the deep search (exact, a full read of the shard per query; not with
@@ -1299,7 +1302,14 @@ class MilvusIndexManager:
         ranker=DecayRanker(...) (pymilvus' decay ranker): the first W = max(top_k, ranker.candidates or top_k) <= HR_MAX_TOPK
         hits of the plain ranking are re-scored as normalised score x decay(|field - origin|) and re-sorted (stable), the best
         top_k returned: "score" is the final score, "raw_score" the hit's own.  Not with group_by_field, offset or a deep
-        window (ValueError); NotImplementedError in the torchrun form."""
+        window (ValueError); NotImplementedError in the torchrun form.
+        ranker=MMRRanker(...) (vector MMR, what RAG stacks call max_marginal_relevance_search): the first W hits of the plain
+        ranking are diversified on the cosine of their STORED embeddings (include/hbmrag.h, hr_mmr_select_vec_dev) and the
+        best top_k returned in pick order: "score" stays the hit's own, "mmr_value" is the value it was picked with.  Dense
+        collections only (ValueError on sparse_index); otherwise refused like the decay ranker."""
+        if isinstance(ranker, MMRRanker):
+            return await self._search_mmr(query_embedding, collection_name, top_k, filters, search_params, ranker,
+                                          group_by_field, group_size, strict_group_size, offset)
         if ranker is not None:
             return await self._search_decayed(query_embedding, collection_name, top_k, filters, search_params, ranker,
                                               group_by_field, group_size, strict_group_size, offset)
@@ -1527,7 +1537,7 @@ class MilvusIndexManager:
     def _decay_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
         """(collection, W, norm code) of a search with a ranker, or the refusal — before anything is searched."""
         if not isinstance(ranker, DecayRanker):
-            raise ValueError(f"ranker must be a DecayRanker or None, got {ranker!r}")
+            raise ValueError(f"ranker must be a DecayRanker, an MMRRanker or None, got {ranker!r}")
         if collection_name not in self.collections:
             raise ValueError(f"Collection {collection_name} not found")
         coll = self.collections[collection_name]
@@ -1564,6 +1574,112 @@ class MilvusIndexManager:
             hit["raw_score"], hit["score"] = hit["score"], float(f)
             out.append(hit)
         return out
+
+    # ---- vector MMR (the contract is in include/hbmrag.h, the restatement in mmr.py) ----------------------------------------
+    def _ranker_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
+        """The refusals of a search with a ranker of either kind, before anything is searched."""
+        check = self._mmr_request if isinstance(ranker, MMRRanker) else self._decay_request
+        return check(collection_name, top_k, ranker, group_by_field, group_size, strict_group_size, offset)
+
+    def _mmr_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
+        """(collection, W, norm code) of a search with an MMRRanker, or the refusal — before anything is searched."""
+        if collection_name not in self.collections:
+            raise ValueError(f"Collection {collection_name} not found")
+        coll = self.collections[collection_name]
+        if coll.kind == "sparse":
+            raise ValueError(f"vector MMR diversifies on stored dense embeddings: {collection_name} has none")
+        if group_by_field is not None or group_size != 1 or strict_group_size is not None:
+            raise ValueError("ranker cannot be combined with group_by_field")
+        if isinstance(offset, (bool, np.bool_)) or not isinstance(offset, (int, np.integer)) or offset != 0:
+            raise ValueError(f"ranker cannot be combined with offset, got offset={offset!r}")
+        if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
+            raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
+        window = ranker.window(top_k)
+        if window > HR_MAX_TOPK:
+            raise ValueError(f"ranker diversifies the best max(top_k, candidates) = {window} rows: a deep window (> HR_MAX_TOPK = "
+                             f"{HR_MAX_TOPK}) is not built")
+        norm = ranker.norm_code(coll.metric)
+        if hasattr(coll.handle, "round"):
+            raise NotImplementedError("vector MMR is not built for the torchrun form (CollectiveShardSet)")
+        return coll, window, norm
+
+    async def _search_mmr(self, query_embedding, collection_name, top_k, filters, search_params, ranker, group_by_field,
+                          group_size, strict_group_size, offset) -> List[Dict[str, Any]]:
+        _, window, norm = self._mmr_request(collection_name, top_k, ranker, group_by_field, group_size, strict_group_size, offset)
+        hits = await self.search(query_embedding, collection_name, window, filters, search_params)
+        if not hits:
+            return hits
+        rows = np.asarray([h["_row"] for h in hits], dtype=np.int64)
+        scores = np.asarray([h["score"] for h in hits], dtype=np.float32)      # fp32 list scores, widened by _format_hits
+        pos, val = await self._mmr_rows_async(collection_name, rows, scores, float(ranker.lambda_mult), int(top_k), norm)
+        out = []
+        for p, v in zip(pos, val):
+            hit = hits[int(p)]
+            hit["mmr_value"] = float(v)
+            out.append(hit)
+        return out
+
+    def _mmr_rows_blocking(self, payload, key):
+        """The host restatement over row numbers (sharded managers, stand-ins, the front's one-by-one fallback):
+        payload = (rows int64, scores, lambda, k_out), key = (collection, width, norm, ...) -> (positions, float64 values).
+        A row outside the collection (-1: a hit without a row number) has the zero vector."""
+        rows, scores, lam, k_out = payload
+        coll = self.collections[key[0]]
+        self._count("mmr_host_selects")
+        rows = np.asarray(rows, dtype=np.int64)
+        inside = (rows >= 0) & (rows < coll.handle.num_rows)
+        vectors = np.zeros((len(rows), int(coll.dim)), dtype=np.float32)
+        if inside.any():
+            vectors[inside] = coll.handle.get_dense_rows(rows[inside])
+        pos, val = vector_mmr([float(x) for x in scores], vectors, lam, k_out, int(key[2]))
+        return np.asarray(pos, dtype=np.int32), np.asarray(val, dtype=np.float64)
+
+    async def _mmr_rows_async(self, collection_name: str, rows: np.ndarray, scores: np.ndarray, lam: float, k_out: int, norm: int):
+        """(positions in pick order, the value of every pick) of ONE list.  On one GPU shard through the batching front:
+        the collection, the padded list length, the norm code and the score type are the request key, lambda travels per
+        query, so concurrent requests with different lambdas share one hr_mmr_select_vec_dev launch.  Everything else is
+        selected on the host by the restatement, over the vectors of ShardSet.get_dense_rows, with the same result, and
+        counted in stats["mmr_host_selects"]."""
+        n, K = len(rows), HR_MAX_TOPK
+        width = next(w for w in (K // 4, K, 3 * K, n) if n <= w)      # few distinct launch shapes
+        key = (collection_name, width, int(norm), scores.dtype == np.float64)
+        payload = (rows, scores, float(lam), max(1, min(int(k_out), n)))
+        coll = self.collections[collection_name]
+        front = self._coalescer(coll)
+        if front is None or front.collective or n > 3 * K or self._device_shard(coll.handle) is None:
+            return await asyncio.to_thread(self._mmr_rows_blocking, payload, key)
+        return await asyncio.wait_for(front.submit_async("mmr", key, payload),
+                                      timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
+
+    def _mmr_list_request(self, rows, scores, lam, k):
+        rows = np.asarray([-1 if r is None else int(r) for r in rows], dtype=np.int64)
+        scores = np.asarray(scores, dtype=np.float64)
+        if rows.shape != scores.shape or rows.ndim != 1:
+            raise ValueError("a list's rows and scores differ in length")
+        if "semantic_index" not in self.collections:
+            raise ValueError("Collection semantic_index not found")
+        return rows, scores, float(lam), int(k)
+
+    def mmr_select_lists(self, rows, scores, lam: float, k: int):
+        """Vector MMR over ONE fused list (row numbers, None for a hit without one, and float64 fused scores), blocking,
+        through the host restatement: -> list positions in pick order, at most k.  The similarity is the cosine of the
+        semantic_index stored vectors; the scores are taken as they are."""
+        rows, scores, lam, k = self._mmr_list_request(rows, scores, lam, k)
+        if not len(rows):
+            return []
+        from ._native import HR_NORM_NONE
+        pos, _ = self._mmr_rows_blocking((rows, scores, lam, max(1, k)), ("semantic_index", len(rows), HR_NORM_NONE))
+        return [int(p) for p in pos[:k]]
+
+    async def mmr_select_lists_async(self, rows, scores, lam: float, k: int):
+        """mmr_select_lists for a caller on the event loop: on one GPU shard concurrent callers share one
+        hr_mmr_select_vec_dev launch (a kind of its own in the batching front); sharded managers use the restatement."""
+        rows, scores, lam, k = self._mmr_list_request(rows, scores, lam, k)
+        if not len(rows):
+            return []
+        from ._native import HR_NORM_NONE
+        pos, _ = await self._mmr_rows_async("semantic_index", rows, scores, lam, max(1, k), HR_NORM_NONE)
+        return [int(p) for p in pos[:k]]
 
     def _decay_rows_blocking(self, payload, key):
         """The host restatement over row numbers (sharded managers, stand-ins, the front's one-by-one fallback):
@@ -1945,7 +2061,7 @@ class MilvusIndexManager:
     async def search_by_ids(self, ids, collection_name: str, top_k: int = 20, filters: Optional[str] = None,
                             search_params: Optional[Dict] = None, *, group_by_field: Optional[str] = None,
                             group_size: int = 1, strict_group_size: Optional[bool] = None,
-                            ranker: Optional[DecayRanker] = None) -> List[List[Dict[str, Any]]]:
+                            ranker: Optional[Any] = None) -> List[List[Dict[str, Any]]]:
         """pymilvus' search by primary key ("more like this entity"): one hit list per id of `ids`, in request order, each
         exactly what search() returns for that entity's STORED vector of the named collection with the same arguments —
         the fp32-widened stored row of a dense collection, the stored payload of sparse_index; filters, range params and
@@ -1957,7 +2073,7 @@ class MilvusIndexManager:
         carries (a deleted entity is not found), and whatever the filter language (its list cap) and search() (a sparse
         row of more than HR_MAX_QUERY_NNZ entries) refuse.  NotImplementedError in the torchrun form."""
         if ranker is not None:      # refused before the vectors are fetched
-            self._decay_request(collection_name, top_k, ranker, group_by_field, group_size, strict_group_size, 0)
+            self._ranker_request(collection_name, top_k, ranker, group_by_field, group_size, strict_group_size, 0)
         queries = await asyncio.to_thread(self._stored_queries_blocking, ids, collection_name)
         extra = {"ranker": ranker} if ranker is not None else {}
         return list(await asyncio.gather(*(self.search(q, collection_name, top_k, filters, search_params,

@@ -59,6 +59,8 @@ class PipelineConfig:
     score_normalization: str = "activation"
     # RetrievalConfig.decay: a decay.DecayRanker over the fused list (freshness or any numeric field), or None
     decay: Optional[Any] = None
+    # RetrievalConfig.mmr_similarity: what the diversifying profiles compare, "tokens" (as the reference) or "embedding"
+    mmr_similarity: str = "tokens"
 
 
 @dataclass
@@ -93,7 +95,8 @@ class AdvancedRAGPipeline:
             index_manager=self.index_manager,
             config=RetrievalConfig(hybrid_alpha=self.config.hybrid_alpha, top_k=self.config.top_k,
                                    enable_reranking=self.config.enable_reranking, fusion=self.config.fusion,
-                                   score_normalization=self.config.score_normalization, decay=self.config.decay),
+                                   score_normalization=self.config.score_normalization, decay=self.config.decay,
+                                   mmr_similarity=self.config.mmr_similarity),
             learned_ranker=LearnedRanker())
         self.evaluator = RAGEvaluator()
         self.compliance = ComplianceManager(enable_audit=self.config.enable_audit_logging,

@@ -101,8 +101,13 @@ class RetrievalConfig:
     # scores are not renormalised: normalization="activation" means identity on a fused list, "minmax" rescales by the
     # list's smallest and largest fused score.  `candidates` is not used here (the whole fused list is the window).
     decay: Optional[Any] = None
+    # what enable_mmr diversifies on: "tokens" (the reference's token-Jaccard of the contents) or "embedding" (vector MMR: the
+    # cosine of the hits' stored semantic_index vectors, mmr.py; such a request takes the general path)
+    mmr_similarity: str = "tokens"
 
     def __post_init__(self):
+        if self.mmr_similarity not in ("tokens", "embedding"):
+            raise ValueError(f"mmr_similarity must be 'tokens' or 'embedding', got {self.mmr_similarity!r}")
         if self.decay is not None:
             from .decay import DecayRanker
             if not isinstance(self.decay, DecayRanker):
@@ -265,7 +270,8 @@ class HybridRetriever:
                                    enable_mmr=mmr, mmr_lambda=lam, group_by_field=base.group_by_field,
                                    group_size=base.group_size,
                                    extended_filter_operators=base.extended_filter_operators,
-                                   fusion=base.fusion, score_normalization=base.score_normalization, decay=base.decay)
+                                   fusion=base.fusion, score_normalization=base.score_normalization, decay=base.decay,
+                                   mmr_similarity=base.mmr_similarity)
 
         return {
             "default": base,
@@ -357,7 +363,8 @@ class HybridRetriever:
         one_round = getattr(self.index_manager, "hybrid_search", None)
         if self.config.group_by_field is not None:
             return None        # the one-round path does not group: the general path serves the request
-        if one_round is None or (self.config.enable_mmr and not getattr(self.index_manager, "mmr_on_device", False)):
+        if one_round is None or (self.config.enable_mmr and (not getattr(self.index_manager, "mmr_on_device", False)
+                                                             or self.config.mmr_similarity == "embedding")):
             return None
         known = getattr(self.index_manager, "collections", None)
         if known is None or "sparse_index" not in known or "semantic_index" not in known:
@@ -483,6 +490,27 @@ class HybridRetriever:
             return self._assemble_fused(hit_lists, *self._decay_ranked(ranked, *order))
         return self._assemble_fused(hit_lists, ranked)
 
+    # ---- vector MMR (RetrievalConfig.mmr_similarity="embedding") ----
+    def _mmr_embedding_host(self, fused):
+        """Without a manager that holds the vectors every hit has the zero vector: all similarities are 0."""
+        from .mmr import vector_mmr
+        pos, _ = vector_mmr([float(h["score"]) for h in fused], np.zeros((len(fused), 1), dtype=np.float32),
+                            self.config.mmr_lambda, self.config.top_k)
+        return pos
+
+    def _mmr_embedding(self, fused: List[Dict[str, Any]], rows) -> List[Dict[str, Any]]:
+        select = getattr(self.index_manager, "mmr_select_lists", None)
+        pos = select(rows, [float(h["score"]) for h in fused], self.config.mmr_lambda, self.config.top_k) \
+            if select is not None else self._mmr_embedding_host(fused)
+        return [fused[int(p)] for p in pos]
+
+    async def _mmr_embedding_async(self, fused: List[Dict[str, Any]], rows) -> List[Dict[str, Any]]:
+        select = getattr(self.index_manager, "mmr_select_lists_async", None)
+        if select is None:
+            return self._mmr_embedding(fused, rows)
+        pos = await select(rows, [float(h["score"]) for h in fused], self.config.mmr_lambda, self.config.top_k)
+        return [fused[int(p)] for p in pos]
+
     def _decay_inputs(self, hit_lists, ranked):
         """What the decay ranker takes for a fused list: (rows or None when a hit carries no row number, float64 fused scores,
         the field values as a hit's metadata shows them — for a manager that cannot look rows up —, operands, norm code)."""
@@ -538,10 +566,15 @@ class HybridRetriever:
                 order = await device(rows, scores, self.config.decay, operands)
             else:
                 order = decay_rerank(list(range(len(ranked))), scores, values, operands, norm, len(ranked))[::2]
-            return self._assemble_fused(hit_lists, *self._decay_ranked(ranked, *order))
-        return self._assemble_fused(hit_lists, ranked)
+            ranked, fused_of = self._decay_ranked(ranked, *order)
+        else:
+            fused_of = None
+        pending: List[Any] = []      # vector MMR: the rows of the fused hits, the selection goes through the manager's front
+        fused = self._assemble_fused(hit_lists, ranked, fused_of, mmr_rows=pending)
+        return await self._mmr_embedding_async(fused, pending) if pending else fused
 
-    def _assemble_fused(self, hit_lists, ranked, fused_of: Optional[Dict[Any, float]] = None) -> List[Dict[str, Any]]:
+    def _assemble_fused(self, hit_lists, ranked, fused_of: Optional[Dict[Any, float]] = None,
+                        mmr_rows: Optional[List[Any]] = None) -> List[Dict[str, Any]]:
         # payload of an id = the hit from the semantic list if present (overwritten
         # by a later semantic duplicate), else the first sparse/domain hit
         payload: Dict[Any, Dict] = {}
@@ -551,13 +584,23 @@ class HybridRetriever:
             for hit in hits:
                 payload.setdefault(hit["id"], hit)
 
+        embedding = self.config.enable_mmr and self.config.mmr_similarity == "embedding"
+        # the row numbers, before _finish_fused_hit pops them (None: another manager's hit, the zero vector)
+        rows = [payload[doc_id].get("_row") for doc_id, _, _ in ranked] if embedding else None
         now = datetime.utcnow()
         fused = [self._finish_fused_hit(payload[doc_id], score, seen_in, now) for doc_id, score, seen_in in ranked]
+        row_of = {id(hit): row for hit, row in zip(fused, rows)} if embedding else None
         if fused_of is not None:      # a decay ranker reordered the list: "score" is the final one, the fusion's is kept
             for hit, (doc_id, _, _) in zip(fused, ranked):
                 hit["fused_score"] = fused_of[doc_id]
         if self.config.group_by_field is not None:
             fused = self._first_per_group(fused, self.config.group_by_field, self.config.group_size)
+        if embedding and fused:
+            rows = [row_of[id(hit)] for hit in fused]      # the group pass may have dropped hits
+            if mmr_rows is not None:
+                mmr_rows.extend(rows)
+                return fused
+            return self._mmr_embedding(fused, rows)
         if self.config.enable_mmr and fused:
             return self._mmr_diversify(fused, self.config.top_k, self.config.mmr_lambda)
         return fused

@@ -1355,7 +1355,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11700; }  // 1.17.0: search iterator (hr_search_*_deep_after, hr_deep_topk_window_dev)
+int hr_version(void) { return 11800; }  // 1.18.0: vector MMR (hr_mmr_select_vec_dev, hr_mmr_vec_scratch_bytes)
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2544,6 +2544,52 @@ int hr_get_dense_rows_dev(hr_index* h, const int64_t* d_rows, int64_t n, int out
     std::shared_lock<std::shared_mutex> lk(h->rw);
     DeviceGuard dg(h->device);
     return get_rows_enqueue(h, (hipStream_t)stream, d_rows, n, out_dtype, d_out, out_stride, d_missing);
+}
+
+// ---- vector MMR (mmr.h: mmr_select_vec_kernel) ------------------------------------------------------------------------
+namespace {
+// Elements between two gathered rows: dim rounded up to whole 16-byte chunks of the shard's element type.
+int64_t mmr_vec_stride(const hr_index* h) {
+    const int64_t e = h->dtype == HR_F16 ? 8 : 4;
+    return (h->dim + e - 1) / e * e;
+}
+}  // namespace
+
+size_t hr_mmr_vec_scratch_bytes(const hr_index* h, int B, int k_in) {
+    if (!h || h->dim == 0 || B <= 0 || k_in <= 0) return 0;
+    return (size_t)B * (size_t)k_in * (size_t)mmr_vec_stride(h) * (h->dtype == HR_F16 ? 2 : 4);
+}
+
+int hr_mmr_select_vec_dev(hr_index* h, const int64_t* d_ids, const void* d_scores, int score_is_f64, int norm,
+                          const int32_t* d_n, int B, int k_in, const double* d_lambda, int k_out, void* d_scratch,
+                          int32_t* d_out_pos, double* d_out_val, int32_t* d_out_n, void* stream) {
+    HR_TRY(check_get_rows(h, 0));
+    if (B < 0 || k_in <= 0 || k_out <= 0 || k_out > k_in) return fail(h, HR_EINVAL, "bad mmr sizes");
+    if (k_in > kFuseMax) return fail(h, HR_ELIMIT, "k_in exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+    if (norm < HR_NORM_NONE || norm > HR_NORM_MINMAX_DIST) return fail(h, HR_EINVAL, "bad norm code %d", norm);
+    if (B == 0) return HR_OK;
+    if (!d_ids || !d_scores || !d_n || !d_lambda || !d_scratch || !d_out_pos || !d_out_val || !d_out_n)
+        return fail(h, HR_EINVAL, "null buffer");
+    if (((uintptr_t)d_ids | (uintptr_t)d_lambda | (uintptr_t)d_out_val | (score_is_f64 ? (uintptr_t)d_scores : 0)) & 7)
+        return fail(h, HR_EINVAL, "d_ids, d_lambda, d_out_val and fp64 scores must be 8-byte aligned");
+    if (((uintptr_t)d_scores | (uintptr_t)d_n | (uintptr_t)d_out_pos | (uintptr_t)d_out_n) & 3)
+        return fail(h, HR_EINVAL, "fp32 scores, d_n, d_out_pos and d_out_n must be 4-byte aligned");
+    if ((uintptr_t)d_scratch & 15) return fail(h, HR_EINVAL, "d_scratch must be 16-byte aligned");
+    std::shared_lock<std::shared_mutex> lk(h->rw);
+    DeviceGuard dg(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t stride = mmr_vec_stride(h);
+    HR_TRY(get_rows_enqueue(h, s, d_ids, (int64_t)B * k_in, h->dtype == HR_F16 ? HR_F16 : HR_F32, d_scratch, stride, nullptr));
+#define HR_MMR_VEC(STORE)                                                                                                      \
+    hipLaunchKernelGGL(mmr_select_vec_kernel<STORE>, dim3(B), dim3(256), 0, s, d_ids, d_scores, score_is_f64, norm, d_n, k_in, \
+                       (const STORE*)d_scratch, stride, (int)h->dim, h->norm2.as<double>(), h->n_rows, h->row_offset, d_lambda, \
+                       k_out, d_out_pos, d_out_val, d_out_n)
+    if (h->dtype == HR_F16) HR_MMR_VEC(_Float16);
+    else HR_MMR_VEC(float);
+#undef HR_MMR_VEC
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, HR_EHIP, "mmr_select_vec_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
 }
 
 int hr_get_dense_rows(hr_index* h, const int64_t* rows, int64_t n, float* out) {

@@ -439,6 +439,47 @@ HR_API int hr_mmr_select_dev(const int64_t* d_ids, const double* d_scores, const
                       const int64_t* d_tok_indptr, const int32_t* d_tok, int64_t tok_rows, int64_t first_row,
                       const double* d_lambda, int k_out, int32_t* d_out_pos, int32_t* d_out_n, void* stream);
 
+/* ---- vector MMR: the same greedy selection on the cosine of the STORED embeddings ---------------------------------------
+ * What RAG stacks call max_marginal_relevance_search, without fetching fetch_k vectors per query to the host.  For query
+ * q take its list of n valid entries in list order (n = d_n[q] clamped into [0, k_in]): global row ids id_i and scores
+ * s_i (fp32 widened to double, or fp64 when score_is_f64 != 0).  Every operation below is a separately rounded IEEE fp64
+ * operation, no FMA; division and square root are correctly rounded.
+ *   relevance    rel_i = n(s_i): n is the identity (HR_NORM_NONE) or one of the five HR_NORM_* codes, exactly as
+ *                hr_decay_rerank_dev applies them; lo / hi are taken over the list's valid prefix (by comparisons that a
+ *                NaN score never wins), the arithmetic is the table of the weighted fusion.
+ *   similarity   sim(i, j) = (double) c32(i, j), where c32 is the canonical COSINE score the library reports for the
+ *                stored row id_i when the query is the stored row id_j widened exactly to fp32:
+ *                  S = the k-ordered sequential fp64 sum of the exact products x_i[k] * x_j[k]
+ *                  d = N_i * N_j, N = the row's canonical fp64 sum of squares (the store's norm2)
+ *                  c = d > 0 ? S / sqrt(d) : 0;   c32 = (float) c
+ *                ALWAYS cosine, whatever the collection's metric (IP and L2 shards keep norm2 too).  Symmetric bit for
+ *                bit: products and the norm product commute.  An id outside [row_offset, row_offset + hr_num_rows) has
+ *                the zero vector: its similarity to everyone is 0.  A duplicate id gets what the formula gives (1.0 or
+ *                one ulp below).
+ *   selection    the rule of hr_mmr_select_dev with one difference.  First pick: val_i = rel_i.  Afterwards
+ *                val_i = lambda * rel_i - (1 - lambda) * m_i (two products and one subtraction, 1 - lambda computed
+ *                once), m_i = the maximum of sim(i, s) over the selected s.  THE DIFFERENCE: m_i starts from the
+ *                similarity to the first selected member, not from 0 — cosine can be negative, and an anti-parallel
+ *                candidate is rewarded.  Every step takes the live candidate with the largest val > -1e9, among equals
+ *                the first in list order; NaN is never selected; the selection stops at min(k_out, n) or when nobody
+ *                qualifies.
+ * d_ids / d_scores [B][k_in]; d_lambda[B]: lambda per query, so that requests with different lambdas share one launch.
+ * Out: d_out_pos [B][k_out] list positions in pick order (-1 padded); d_out_val [B][k_out] val at the time of each pick
+ * (0.0 padded); d_out_n[B] the picks per query.
+ * d_scratch: hr_mmr_vec_scratch_bytes(h, B, k_in) bytes, 16-byte aligned: the candidates' rows, gathered once per call
+ * (B * k_in rows of dim elements rounded up to 16 bytes, in the shard's element type).  Its contents are scratch.
+ * 1 <= k_out <= k_in <= 3 * HR_MAX_TOPK (HR_ELIMIT for a k_in beyond; HR_EINVAL for the other orderings).  B == 0: HR_OK,
+ * nothing is launched.  HR_ESTATE before hr_finalize and on a handle without a dense collection.  HR_EINVAL: a NULL
+ * handle or buffer, a misaligned one (8 bytes: d_ids, d_lambda, d_out_val, fp64 scores; 4 bytes: fp32 scores, d_n,
+ * d_out_pos, d_out_n; 16 bytes: d_scratch), a norm outside -1..4, negative B.  A refused call launches and writes
+ * nothing.  Asynchronous on `stream`; allocates nothing; takes the handle's shared lock while it enqueues, like
+ * hr_get_dense_rows_dev (the caller keeps writers away until `stream` has passed).  The result is a function of the
+ * inputs alone: positions decide ties, no atomic decides anything. */
+HR_API size_t hr_mmr_vec_scratch_bytes(const hr_index* h, int B, int k_in);
+HR_API int hr_mmr_select_vec_dev(hr_index* h, const int64_t* d_ids, const void* d_scores, int score_is_f64, int norm,
+                          const int32_t* d_n, int B, int k_in, const double* d_lambda, int k_out, void* d_scratch,
+                          int32_t* d_out_pos, double* d_out_val, int32_t* d_out_n, void* stream);
+
 /* ---- grouping search: Collection.search(..., group_by_field=F) ---------------------------------------------------
  * Milvus' grouping search returns the best entity of each of the k best groups.  A group key is an int64 per row
  * (d_keys[r - first_row], key_rows entries): an integer field as it is, or the ordinal of a string field's value in a
@@ -537,7 +578,7 @@ HR_API int hr_mask_keep_groups_dev(const uint8_t* d_mask_in, uint8_t* d_mask_out
  * `stream`.  The result is a function of the inputs alone: ranks come from comparisons, no atomic decides anything. */
 enum { HR_DECAY_GAUSS = 0, HR_DECAY_EXP = 1, HR_DECAY_LINEAR = 2 };
 enum { HR_COL_F64 = 5 };       /* valid only in hr_decay_rerank_dev */
-enum { HR_NORM_NONE = -1 };    /* valid only in hr_decay_rerank_dev */
+enum { HR_NORM_NONE = -1 };    /* valid only in hr_decay_rerank_dev and hr_mmr_select_vec_dev */
 typedef struct hr_decay_query { double origin, offset, coef; int32_t func, reserved; } hr_decay_query;
 HR_API int hr_decay_rerank_dev(const int64_t* d_ids, const void* d_scores, int score_is_f64, const int32_t* d_n,
                         int B, int k_in, const void* d_col, int col_kind, int64_t col_rows, int64_t first_row,
