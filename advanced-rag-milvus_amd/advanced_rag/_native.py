@@ -21,6 +21,9 @@ HR_METHOD_SEMANTIC, HR_METHOD_SPARSE, HR_METHOD_DOMAIN = 1, 2, 4
 HR_MAX_TOPK = 256
 # normalisation of one list's scores in the weighted score fusion (hr_fuse_scores_dev; the table is in include/hbmrag.h)
 HR_NORM_COSINE, HR_NORM_ATAN, HR_NORM_ATAN_DIST, HR_NORM_MINMAX, HR_NORM_MINMAX_DIST = 0, 1, 2, 3, 4
+# multi-list fusion (hr_fuse_lists_dev): the list limit and the two modes
+HR_MAX_FUSE_LISTS = 16
+HR_FUSE_RRF, HR_FUSE_WEIGHTED = 0, 1
 # decay ranker (hr_decay_rerank_dev): curve codes, the identity normalisation (also hr_mmr_select_vec_dev's) and the float64
 # column kind, valid only there
 HR_DECAY_GAUSS, HR_DECAY_EXP, HR_DECAY_LINEAR = 0, 1, 2
@@ -97,6 +100,9 @@ _SIGNATURES = {
     "hr_fuse_scores_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int] * 3 +
                            [_c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_void_p, _c.c_int, _c.c_void_p,
                             _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_fuse_lists_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p,
+                                     _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                     _c.c_void_p]),
     "hr_search_dense_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_search_dense_range_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
@@ -716,6 +722,24 @@ def fuse_scores_dev(d_a: int, d_sa: int, ka: int, norm_a: int, d_b: int, d_sb: i
     rc = L.hr_fuse_scores_dev(p(d_a), p(d_sa), ka, norm_a, p(d_b), p(d_sb), kb, norm_b, p(d_c), p(d_sc), kc, norm_c, B,
                               wa, wb, wc, p(d_w_query), top_k, p(d_out_ids), p(d_out_scores), p(d_out_methods),
                               p(d_n_out), p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+def fuse_lists_dev(d_ids: int, d_scores: int, n_lists: int, k_in: int, B: int, mode: int, rrf_k: int, norms, weights,
+                   d_w_query: int, top_k: int, d_out_ids: int, d_out_scores: int, d_out_lists: int, d_n_out: int,
+                   stream: int = 0):
+    """hr_fuse_lists_dev: fusion of n_lists ranked lists per query (device pointers; 0 = NULL).  norms: n_lists HR_NORM_*
+    codes or None (host side), weights: n_lists numbers or None (host side; d_w_query then carries them per query)."""
+    L = load_library()
+    p = lambda v: _vp(v) if v else None
+    h_norms = None if norms is None else np.ascontiguousarray(norms, dtype=np.int32)
+    h_w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+    for name, arr in (("norms", h_norms), ("weights", h_w)):
+        if arr is not None and arr.shape != (max(int(n_lists), 0),):
+            raise ValueError(f"{name} must hold one value per list ({n_lists}), got shape {arr.shape}")
+    rc = L.hr_fuse_lists_dev(p(d_ids), p(d_scores), n_lists, k_in, B, mode, rrf_k, _vp(h_norms), _vp(h_w), p(d_w_query),
+                             top_k, p(d_out_ids), p(d_out_scores), p(d_out_lists), p(d_n_out), p(stream))
     if rc != 0:
         _raise_global(L, rc)
 

@@ -7,7 +7,7 @@ scan of the whole shard, so the counterpart of the server's request queue is thi
 round of scans is in flight — or within a short window of the first call of a round — are packed per
 (collection, top_k, filter expression, search params) into ONE `hr_search_dense_dev` / `hr_search_sparse_dev` batch
 (and the rank fusions of the same callers into one `hr_fuse_rrf_dev`, or — weighted score fusions, a kind of their own —
-into one `hr_fuse_scores_dev`), run on the front's own stream with one
+into one `hr_fuse_scores_dev`; fusions of up to 16 lists, kind "fuse_n", into one `hr_fuse_lists_dev`), run on the front's own stream with one
 synchronisation per round, and the per-query lists are handed back to the awaiting coroutines.  Lists the device form
 could not prove exact are redone through the host form, which widens the candidate set by itself.
 
@@ -130,7 +130,7 @@ class RangedQuery:
 
 @dataclass
 class _Request:
-    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "decay" | "mmr" | "hybrid" | "encode"
+    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "fuse_n" | "decay" | "mmr" | "hybrid" | "encode"
     key: Tuple                # requests with equal (kind, key) share a launch
     payload: Any
     future: Future = field(default_factory=Future)
@@ -159,7 +159,7 @@ class SearchCoalescer:
             self.window_s = max(self.window_s, 250e-6)
         self.stats = {"rounds": 0, "requests": 0, "dense_launches": 0, "sparse_launches": 0, "fuse_launches": 0,
                       "hybrid_launches": 0, "mmr_launches": 0, "encode_launches": 0, "encoded_texts": 0, "max_batch_seen": 0, "redone_unproven": 0,
-                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "score_fuse_launches": 0, "decay_launches": 0, "busy_s": 0.0}
+                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "score_fuse_launches": 0, "decay_launches": 0, "fuse_n_launches": 0, "busy_s": 0.0}
         self._engines: Dict[Tuple, Any] = {}   # hybrid engines per (top_k, rrf_k, mmr)
         self._inflight: List[_Request] = []    # the requests of the round in progress (failed as a whole if the worker dies)
         self._outbox: Dict[Any, list] = {}     # event loop -> [(asyncio future, ok, value)] of the round in progress
@@ -285,7 +285,7 @@ class SearchCoalescer:
         dev = torch.device("cuda", self.mgr.device)
         # one stream per kind of work: the dense and the sparse searches of a round run side by side (a lone retrieve()
         # overlaps its two scans, as its two worker threads did before the front existed)
-        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "decay", "mmr", "hybrid", "encode")}
+        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "fuse_n", "decay", "mmr", "hybrid", "encode")}
         for reqs in self._rounds():
             groups: Dict[Tuple, List[_Request]] = {}
             for r in reqs:
@@ -333,6 +333,9 @@ class SearchCoalescer:
                     continue
                 if r.kind == "fuse_scores":
                     _answer(r.future, self.mgr._fuse_scores_blocking, r.payload, r.key)
+                    continue
+                if r.kind == "fuse_n":
+                    _answer(r.future, self.mgr._fuse_lists_blocking, r.payload, r.key)
                     continue
                 coll_name, top_k, expr, params_key, group_field, _ = r.key
                 if group_field is not None or self.mgr.collections[coll_name].handle is not cs:
@@ -399,6 +402,8 @@ class SearchCoalescer:
                 _answer(r.future, self.mgr._fuse_rows_blocking, r.payload, key)
             elif kind == "fuse_scores":
                 _answer(r.future, self.mgr._fuse_scores_blocking, r.payload, key)
+            elif kind == "fuse_n":
+                _answer(r.future, self.mgr._fuse_lists_blocking, r.payload, key)
             elif kind == "decay":
                 _answer(r.future, self.mgr._decay_rows_blocking, r.payload, key)
             elif kind == "mmr":
@@ -699,6 +704,30 @@ class SearchCoalescer:
         return {"oi": oi, "os": os_, "om": om, "on": on, "keep": (li, ls, wq)}
 
     _scatter_fuse_scores = _scatter_fuse
+
+    # ------------------------------------------------------------------ multi-list fusion
+    def _enqueue_fuse_n(self, torch, dev, stream, key, chunk):
+        """The multi-list fusions of a round in ONE hr_fuse_lists_dev: key = (mode, n_lists, padded k_in, norm codes, rrf_k,
+        top_k), payload = (((rows, scores) per list), weights); lists are padded with -1 and the weights travel as the
+        [B, n_lists] per-query operand, so requests with different weights share the launch."""
+        from . import _native as nat
+        from .multi_search import stage_fuse_lists
+        mode, n_lists, k_in, norms, rrf_k, top_k = key
+        B = len(chunk)
+        ids, sc, wq = stage_fuse_lists([r.payload for r in chunk], key)
+        d_ids, d_wq = torch.from_numpy(ids).to(dev), torch.from_numpy(wq).to(dev)
+        d_sc = torch.from_numpy(sc).to(dev) if sc is not None else None
+        oi = torch.empty((B, top_k), dtype=torch.int64, device=dev)
+        os_ = torch.empty((B, top_k), dtype=torch.float64, device=dev)
+        om = torch.empty((B, top_k), dtype=torch.int32, device=dev)
+        on = torch.empty((B,), dtype=torch.int32, device=dev)
+        nat.fuse_lists_dev(d_ids.data_ptr(), d_sc.data_ptr() if d_sc is not None else 0, n_lists, k_in, B, mode, rrf_k, norms,
+                           None, d_wq.data_ptr(), top_k, oi.data_ptr(), os_.data_ptr(), om.data_ptr(), on.data_ptr(),
+                           stream.cuda_stream)
+        self.stats["fuse_n_launches"] += 1
+        return {"oi": oi, "os": os_, "om": om, "on": on, "keep": (d_ids, d_sc, d_wq)}
+
+    _scatter_fuse_n = _scatter_fuse
 
     # ------------------------------------------------------------------ decay ranker
     def _decay_launch(self, torch, dev, stream, field, norm, operands, d_ids, d_scores, f64, d_n, B, k_in):

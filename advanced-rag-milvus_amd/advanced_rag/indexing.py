@@ -390,9 +390,10 @@ class MilvusIndexManager:
         # managers, lists beyond 3 * HR_MAX_TOPK entries, the front's one-by-one fallback after a refused batch)
         # mmr_host_selects: vector MMR selections answered by the Python restatement instead of hr_mmr_select_vec_dev (the
         # same cases)
+        # multi_searches: multi_search() calls that passed their checks
         self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
                       "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0, "deep_searches": 0,
-                      "decay_host_reranks": 0, "iterator_pages": 0, "mmr_host_selects": 0}
+                      "decay_host_reranks": 0, "iterator_pages": 0, "mmr_host_selects": 0, "multi_searches": 0}
         # bumped by what renumbers or replaces the rows (compact, load_snapshot, attach_shards): a SearchIterator's cursor
         # names a row, so an iterator created under another generation refuses to go on
         self._row_space_generation = 0
@@ -1194,12 +1195,16 @@ class MilvusIndexManager:
     def _search_blocking(self, query_embedding, collection_name: str, top_k: int, filters: Optional[str],
                          search_params: Optional[Dict], group_by_field: Optional[str] = None,
                          group_size: int = 1) -> List[Dict[str, Any]]:
+        return self._format_hits(*self._search_blocking_lists(query_embedding, collection_name, top_k, filters, search_params,
+                                                              group_by_field, group_size))
+
+    def _search_blocking_lists(self, query_embedding, collection_name: str, top_k: int, filters: Optional[str],
+                               search_params: Optional[Dict], group_by_field: Optional[str] = None, group_size: int = 1):
         coll = self.collections[collection_name]
         params = self._search_params(coll, search_params)
         bounds = self._range_request(coll, params, group_by_field)
         query = self._as_sparse_payload(query_embedding) if coll.kind == "sparse" else query_embedding
-        return self._format_hits(*self._search_lists_blocking(query, collection_name, top_k, filters, params, group_by_field,
-                                                              bounds, group_size))
+        return self._search_lists_blocking(query, collection_name, top_k, filters, params, group_by_field, bounds, group_size)
 
     def _deep_request(self, coll, top_k, offset, search_params: Optional[Dict], group_by_field: Optional[str],
                       group_size: int) -> int:
@@ -1336,6 +1341,14 @@ class MilvusIndexManager:
             # the plain search at depth W (through the batching front as any other), the first `offset` hits cut
             hits = await self.search(query_embedding, collection_name, window, filters, search_params)
             return hits[int(offset):]
+        return self._format_hits(*await self._search_lists_async(query_embedding, collection_name, top_k, filters,
+                                                                 search_params, group_by_field, group_size))
+
+    async def _search_lists_async(self, query_embedding, collection_name: str, top_k, filters: Optional[str],
+                                  search_params: Optional[Dict], group_by_field: Optional[str] = None, group_size: int = 1):
+        """(row ids, scores) of a search at top_k <= HR_MAX_TOPK, before _format_hits: through the batching front as a
+        raw-list request (an unproven list is redone through the blocking path there), else the blocking path in a thread."""
+        coll = self.collections[collection_name]
         front = self._coalescer(coll)
         try:
             if front is not None:
@@ -1348,10 +1361,9 @@ class MilvusIndexManager:
                 fut = front.submit_async("sparse" if coll.kind == "sparse" else "dense",
                                          (collection_name, int(top_k), filters, self._params_key(params), group_by_field,
                                           group_size), query)
-                ids, sc = await asyncio.wait_for(fut, timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
-                return self._format_hits(ids, sc)
+                return await asyncio.wait_for(fut, timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
             return await asyncio.wait_for(
-                asyncio.to_thread(self._search_blocking, query_embedding, collection_name, top_k, filters,
+                asyncio.to_thread(self._search_blocking_lists, query_embedding, collection_name, top_k, filters,
                                   search_params, group_by_field, group_size),
                 timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
         except asyncio.TimeoutError:
@@ -1532,6 +1544,90 @@ class MilvusIndexManager:
         rows, scores, methods = await asyncio.wait_for(front.submit_async("fuse_scores", key, payload),
                                                        timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
         return self._fuse_output(row_to_id, rows, scores, methods)
+
+    # ---- multi-list fusion and multi_search (pymilvus' hybrid_search(reqs, rerank, limit); multi_search.py) -----------------
+    def _fuse_lists_blocking(self, payload, key):
+        """One fusion request alone (managers without a front, the front's one-by-one fallback): hr_fuse_lists_dev with
+        B = 1 on the first shard's device, synchronised.  A CPU stand-in manager uses the two restatements.
+        -> (rows int64, fp64 fused scores, list masks int32), at most key's top_k entries."""
+        from .multi_search import fuse_lists_host, stage_fuse_lists
+        first = getattr(self._main, "first", None)
+        if first is None or not hasattr(first, "_h"):
+            return fuse_lists_host(payload, key)
+        import torch
+        from . import _native as nat
+        mode, n_lists, k_in, norms, rrf_k, top_k = key
+        ids, sc, _ = stage_fuse_lists([payload], key)
+        dev = torch.device("cuda", first.device)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            d_ids = torch.from_numpy(ids).to(dev)
+            d_sc = torch.from_numpy(sc).to(dev) if sc is not None else None
+            oi = torch.empty((1, top_k), dtype=torch.int64, device=dev)
+            os_ = torch.empty((1, top_k), dtype=torch.float64, device=dev)
+            om = torch.empty((1, top_k), dtype=torch.int32, device=dev)
+            on = torch.empty((1,), dtype=torch.int32, device=dev)
+            nat.fuse_lists_dev(d_ids.data_ptr(), d_sc.data_ptr() if d_sc is not None else 0, n_lists, k_in, 1, mode, rrf_k,
+                               norms, payload[1], 0, top_k, oi.data_ptr(), os_.data_ptr(), om.data_ptr(), on.data_ptr(),
+                               stream.cuda_stream)
+            stream.synchronize()
+            n = int(on.item())
+            return oi[0, :n].cpu().numpy(), os_[0, :n].cpu().numpy(), om[0, :n].cpu().numpy()
+
+    async def fuse_lists_async(self, row_lists, score_lists, weights, *, mode: str = "rrf", norms: Optional[Sequence[int]] = None,
+                               rrf_k: int = 60, top_k: Optional[int] = None):
+        """Fusion of up to 16 ranked lists of row numbers (score_lists: their fp32 scores, read for mode="weighted" with one
+        HR_NORM_* code per list in `norms`) -> (rows int64, fp64 fused scores, list masks: bit l = list l) in fused order,
+        at most top_k (default: all, up to 3 * HR_MAX_TOPK).  On one GPU shard through the batching front (kind "fuse_n"):
+        concurrent callers with equal (mode, lists, padded length, norms, rrf_k, top_k) share one hr_fuse_lists_dev launch,
+        their weights travel per query.  Other managers fuse one request at a time (_fuse_lists_blocking)."""
+        from . import _native as nat
+        from .multi_search import check_fuse_lists
+        if mode not in ("rrf", "weighted"):
+            raise ValueError(f"mode must be 'rrf' or 'weighted', got {mode!r}")
+        payload, key = check_fuse_lists(row_lists, score_lists, weights, nat.HR_FUSE_WEIGHTED if mode == "weighted" else nat.HR_FUSE_RRF,
+                                        norms, rrf_k, top_k)
+        front = self._coalescer(self.collections["semantic_index"]) if "semantic_index" in self.collections else None
+        if front is None or front.collective or self._device_shard(self._main) is None:
+            return await asyncio.to_thread(self._fuse_lists_blocking, payload, key)
+        return await asyncio.wait_for(front.submit_async("fuse_n", key, payload), timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
+
+    def _multi_request(self, requests, ranker, limit):
+        """The refusals of multi_search, before anything is searched -> (requests, multi_search.FusionPlan)."""
+        from .multi_search import check_ranker, check_requests
+        reqs = check_requests(requests, self.collections)
+        metrics = []
+        for r in reqs:
+            coll = self.collections[r.collection_name]
+            if hasattr(coll.handle, "round"):
+                raise NotImplementedError("multi_search is not built for the torchrun form (CollectiveShardSet)")
+            self._range_request(coll, self._search_params(coll, r.search_params), None)   # metric mismatch, bad or unsupported range
+            metrics.append("IP" if coll.kind == "sparse" else coll.metric)
+        return reqs, check_ranker(ranker, len(reqs), metrics, limit)
+
+    async def multi_search(self, requests, ranker, limit: int = 20) -> List[Dict[str, Any]]:
+        """pymilvus' Collection.hybrid_search(reqs, rerank, limit): 1 .. 16 SearchRequests, each exactly the plain search() of
+        its collection at top_k = request.limit with its own filter and params, fused by an RRFRanker or a WeightedRanker
+        into one ranking of at most `limit` <= 3 * HR_MAX_TOPK rows.  The three collections share one row space, so requests
+        may name any of them; the fusion key is the global row number.  The sub-searches go to the batching front as raw
+        lists (same-key ones share one scan launch), the lists to hr_fuse_lists_dev (kind "fuse_n"), and only the fused rows
+        are formatted.  A hit's "score" is the fused fp64 score, "original_score" its score in the first request that holds
+        it, "requests" the ascending indices of the requests that hold it.  A failing sub-search fails the call."""
+        reqs, plan = self._multi_request(requests, ranker, limit)
+        self._count("multi_searches")
+        lists = await asyncio.gather(*[self._search_lists_async(r.data, r.collection_name, r.limit, r.filters, r.search_params)
+                                       for r in reqs])
+        rows, scores, masks = await self.fuse_lists_async(
+            [l[0] for l in lists], [l[1] for l in lists], plan.weights, mode="weighted" if plan.norms is not None else "rrf",
+            norms=plan.norms, rrf_k=plan.rrf_k, top_k=plan.limit)
+        from .multi_search import lists_of_mask
+        hits = self._format_hits(rows, scores)
+        for hit, m in zip(hits, masks.tolist()):
+            held = lists_of_mask(m)
+            ids, sc = lists[held[0]]
+            hit["requests"] = held
+            hit["original_score"] = float(sc[int(np.flatnonzero(np.asarray(ids) == hit["_row"])[0])])
+        return hits
 
     # ---- decay ranker (pymilvus' decay ranker; the contract is in include/hbmrag.h, the restatement in decay.py) ---------
     def _decay_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):

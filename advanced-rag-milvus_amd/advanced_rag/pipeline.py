@@ -174,13 +174,18 @@ class AdvancedRAGPipeline:
         return out, metrics
 
     async def plan_and_execute(self, query: str, filters: Optional[Dict[str, Any]] = None,
-                               context: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+                               context: Optional[Dict[str, Any]] = None, fuse: bool = False) -> Dict[str, Any]:
+        """fuse=True: the dict also carries "fused", the sub-queries' lists fused into ONE ranking
+        (HybridRetriever.retrieve_multi: RAG-fusion); the default returns what it always returned."""
         plan: DecompositionResult = self.decomposer.decompose(query)
         answers = []
         for sub in plan.sub_queries:
             results, metrics = await self.retrieve(query=sub, filters=filters, context=context)
             answers.append({"query": sub, "results": results, "metrics": metrics})
-        return {"decomposition": {"sub_queries": plan.sub_queries, "strategy": plan.strategy}, "subqueries": answers}
+        out = {"decomposition": {"sub_queries": plan.sub_queries, "strategy": plan.strategy}, "subqueries": answers}
+        if fuse:
+            out["fused"] = await self.retriever.retrieve_multi(plan.sub_queries, filters)
+        return out
 
     async def detect_drift(self, sample_queries: List[str]) -> Dict[str, Any]:
         return await self.evaluator.detect_drift(queries=sample_queries, index_manager=self.index_manager)

@@ -333,6 +333,90 @@ class HybridRetriever:
         fused = await self._fuse_results_async(hit_lists[0], hit_lists[1], hit_lists[2] if len(hit_lists) > 2 else [])
         return self._tag_profile(fused, profile)[:self.config.top_k]
 
+    # ------------------------------------------------------------------ several wordings, one ranking
+    MAX_WORDINGS = 8
+
+    async def retrieve_multi(self, queries: Sequence[str], filters: Optional[Dict[str, Any]] = None,
+                             profile_hint: Optional[str] = None,
+                             query_weights: Optional[Sequence[float]] = None) -> List[Dict[str, Any]]:
+        """RAG-fusion: 1 .. 8 wordings of one question, fused into ONE ranking.  The profile is picked from queries[0]; every
+        wording is embedded once and searched on semantic_index and sparse_index at 2 * top_k (<= HR_MAX_TOPK); the lists
+        are fused in the order sem_0, spa_0, sem_1, spa_1, ... with weights dense_weight * qw_i and sparse_weight * qw_i
+        (query_weights, default 1.0) by config.fusion — through the manager's `fuse_lists_async` (hr_fuse_lists_dev) where it
+        has one, else by the restatements — and cut to 3 * HR_MAX_TOPK entries.  Then retrieve()'s tail: the decay ranker,
+        the group pass, MMR and the cut.  A hit's `retrieval_methods` is the ordered set of modalities of the lists that
+        hold it, `queries` the wordings that found it.  One wording gives what retrieve() of it gives.  The timeout and the
+        "a failing modality degrades to no hits" rule are retrieve()'s."""
+        if isinstance(queries, str) or not isinstance(queries, (list, tuple)) or not 1 <= len(queries) <= self.MAX_WORDINGS:
+            raise ValueError(f"retrieve_multi takes a list of 1 .. {self.MAX_WORDINGS} queries, got {queries!r}")
+        if not all(isinstance(q, str) for q in queries):
+            raise ValueError("every query must be a string")
+        qw = [1.0] * len(queries) if query_weights is None else list(query_weights)
+        if len(qw) != len(queries):
+            raise ValueError(f"{len(qw)} query_weights for {len(queries)} queries")
+        for w in qw:
+            if isinstance(w, bool) or not isinstance(w, (int, float)) or not math.isfinite(w):
+                raise ValueError(f"a query weight must be a finite number, got {w!r}")
+        budget = float(getattr(RetrievalConstants, "TIMEOUT_SECONDS", 0.3))
+        try:
+            return await asyncio.wait_for(self._retrieve_multi_inner(list(queries), filters, profile_hint, [float(w) for w in qw]),
+                                          timeout=budget)
+        except asyncio.TimeoutError:
+            logger.warning("HybridRetriever.retrieve_multi timed out after %.3f seconds", budget)
+            return []
+
+    async def _retrieve_multi_inner(self, queries, filters, profile_hint, qw) -> List[Dict[str, Any]]:
+        profile = self._pick_profile(queries[0], profile_hint)
+        self.config = self.profiles.get(profile, self.config)
+        cfg = self.config
+        if 2 * cfg.top_k * cfg.group_size > HR_MAX_TOPK:
+            raise ValueError(f"retrieve_multi searches 2 * top_k rows per list: 2 * top_k * group_size <= {HR_MAX_TOPK}, "
+                             f"got 2 * {cfg.top_k} * {cfg.group_size}")
+        embedded = [(await self._get_semantic_embedding(q), await self._get_sparse_embedding(q)) for q in queries]
+        expr = self._build_filter_expression(filters) if filters else None
+        lists = await asyncio.gather(*[s for d, p in embedded for s in (self._search_semantic(d, expr), self._search_sparse(p, expr))])
+        self._adapt_weights(queries[0])
+        weights = [w * q for q in qw for w in (cfg.dense_weight, cfg.sparse_weight)]
+        ranked = await self._rank_fusion_multi(lists, weights)
+        # payload of an id: its first semantic hit, else its first sparse hit (one wording: exactly retrieve()'s choice)
+        by_modality = [[], [], []]
+        found: Dict[Any, List[str]] = {}
+        seen = (set(), set())
+        for l, hits in enumerate(lists):
+            for hit in hits:
+                if hit["id"] not in seen[l % 2]:
+                    seen[l % 2].add(hit["id"])
+                    by_modality[l % 2].append(hit)
+        for doc_id, _, seen_in in ranked:
+            found[doc_id] = [queries[i] for i in sorted({l // 2 for l in seen_in})]
+        ranked = [(doc_id, score, sorted({l % 2 for l in seen_in})) for doc_id, score, seen_in in ranked]
+        fused = await self._finish_ranked_async(by_modality, ranked)
+        for hit in fused:
+            hit["queries"] = found[hit["id"]]
+        return self._tag_profile(fused, profile)[:cfg.top_k]
+
+    async def _rank_fusion_multi(self, hit_lists, weights):
+        """-> [(id, float64 score, [list indices])] in fused order, at most 3 * HR_MAX_TOPK entries."""
+        cut = 3 * HR_MAX_TOPK
+        weighted = self.config.fusion == "weighted"
+        norms = [self._list_norms()[l % 2] for l in range(len(hit_lists))] if weighted else None
+        id_lists = [[h["id"] for h in hits] for hits in hit_lists]
+        score_lists = [[h["score"] for h in hits] for hits in hit_lists]
+        device_fuse = getattr(self.index_manager, "fuse_lists_async", None)
+        rows = [[h.get("_row") for h in hits] for hits in hit_lists]
+        if device_fuse is not None and all(r is not None for lst in rows for r in lst) and any(rows):
+            try:
+                row_to_id = {r: i for rs, ids in zip(rows, id_lists) for r, i in zip(rs, ids)}
+                f_rows, f_scores, f_masks = await device_fuse(rows, score_lists, weights, mode="weighted" if weighted else "rrf",
+                                                              norms=norms, rrf_k=self.RRF_K)
+                return [(row_to_id[int(r)], float(s), [l for l in range(len(hit_lists)) if (int(m) >> l) & 1])
+                        for r, s, m in zip(f_rows, f_scores, f_masks)]
+            except Exception:  # pragma: no cover - fall through to the host arithmetic
+                logger.exception("device multi-list fusion failed; using host arithmetic")
+        if weighted:
+            return score_fuse_lists(list(zip(id_lists, score_lists)), weights, norms)[:cut]
+        return rrf_rank_lists(id_lists, weights, self.RRF_K)[:cut]
+
     def _adapt_weights(self, query: str) -> None:
         if self.weight_adapter:
             try:
@@ -559,6 +643,10 @@ class HybridRetriever:
                     logger.exception("device rank fusion failed; using host arithmetic")
         if ranked is None:
             ranked = self._rank_fusion(hit_lists, weights)
+        return await self._finish_ranked_async(hit_lists, ranked)
+
+    async def _finish_ranked_async(self, hit_lists, ranked) -> List[Dict[str, Any]]:
+        """What follows a rank fusion: the decay ranker, the hit dicts, the group pass and MMR (the cut is the caller's)."""
         if self.config.decay is not None and ranked:
             rows, scores, values, operands, norm = self._decay_inputs(hit_lists, ranked)
             device = getattr(self.index_manager, "decay_rerank_lists_async", None)

@@ -35,6 +35,7 @@
 #include "filter.h"
 #include "finish.h"
 #include "fuse.h"
+#include "fuse_lists.h"
 #include "group.h"
 #include "mmr.h"
 #include "query.h"
@@ -1355,7 +1356,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11800; }  // 1.18.0: vector MMR (hr_mmr_select_vec_dev, hr_mmr_vec_scratch_bytes)
+int hr_version(void) { return 11900; }  // 1.19.0: multi-list fusion (hr_fuse_lists_dev)
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2048,6 +2049,54 @@ int hr_fuse_scores_dev(const int64_t* d_ids_a, const float* d_sc_a, int ka, int 
                        c, wa, wb, wc, d_w_query, top_k, d_out_ids, d_out_scores, d_out_methods, d_n_out);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "score_fuse_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+int hr_fuse_lists_dev(const int64_t* d_ids, const float* d_scores, int n_lists, int k_in, int B, int mode, int rrf_k,
+                      const int32_t* norms, const double* weights, const double* d_w_query, int top_k, int64_t* d_out_ids,
+                      double* d_out_scores, int32_t* d_out_lists, int32_t* d_n_out, void* stream) {
+    if (n_lists < 1 || k_in < 1 || top_k < 1 || B < 0) return fail(nullptr, HR_EINVAL, "bad fuse-lists sizes");
+    if (mode != HR_FUSE_RRF && mode != HR_FUSE_WEIGHTED) return fail(nullptr, HR_EINVAL, "mode %d is neither HR_FUSE_RRF nor HR_FUSE_WEIGHTED", mode);
+    if (n_lists > HR_MAX_FUSE_LISTS) return fail(nullptr, HR_ELIMIT, "more than HR_MAX_FUSE_LISTS=%d lists", HR_MAX_FUSE_LISTS);
+    if (k_in > HR_MAX_TOPK) return fail(nullptr, HR_ELIMIT, "list longer than HR_MAX_TOPK=%d", HR_MAX_TOPK);
+    if (top_k > 3 * HR_MAX_TOPK) return fail(nullptr, HR_ELIMIT, "top_k beyond 3 * HR_MAX_TOPK=%d", 3 * HR_MAX_TOPK);
+    if (!d_ids || !d_out_ids || !d_out_scores || !d_out_lists || !d_n_out) return fail(nullptr, HR_EINVAL, "null buffer");
+    if (!weights && !d_w_query) return fail(nullptr, HR_EINVAL, "neither host weights nor per-query weights");
+    const bool weighted = mode == HR_FUSE_WEIGHTED;
+    if (weighted && (!d_scores || !norms)) return fail(nullptr, HR_EINVAL, "weighted fusion needs the scores and the norm codes");
+    auto off = [](const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; };
+    if (off(d_ids, 8) || off(d_out_ids, 8) || off(d_out_scores, 8) || off(d_w_query, 8) || off(weights, 8) ||
+        off(d_scores, 4) || off(norms, 4) || off(d_out_lists, 4) || off(d_n_out, 4))
+        return fail(nullptr, HR_EINVAL, "misaligned buffer");
+    FuseListsArgs a{};
+    a.rrf_k = rrf_k;
+    for (int l = 0; l < n_lists; ++l) {
+        if (weighted) {
+            if (norms[l] < HR_NORM_COSINE || norms[l] > HR_NORM_MINMAX_DIST)
+                return fail(nullptr, HR_EINVAL, "norm code %d of list %d is not one of HR_NORM_*", norms[l], l);
+            a.norm[l] = norms[l];
+        }
+        if (weights) {
+            if (!std::isfinite(weights[l])) return fail(nullptr, HR_EINVAL, "non-finite weight of list %d", l);
+            a.w[l] = weights[l];
+        }
+    }
+    if (B == 0) return HR_OK;
+    const FuseListsShape sh = fuse_lists_shape(n_lists, k_in);
+    const size_t lds = fuse_lists_lds_bytes(sh);
+    const void* kern = weighted ? (const void*)fuse_lists_kernel<true> : (const void*)fuse_lists_kernel<false>;
+    if (lds > 48 * 1024) {   // the attribute is per device and idempotent: set on every large launch, it costs no launch
+        hipError_t e0 = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fuse_lists_lds_bytes(fuse_lists_shape(HR_MAX_FUSE_LISTS, HR_MAX_TOPK)));
+        if (e0 != hipSuccess) return fail(nullptr, HR_EHIP, "hipFuncSetAttribute: %s", hipGetErrorString(e0));
+    }
+    if (weighted)
+        hipLaunchKernelGGL(fuse_lists_kernel<true>, dim3(B), dim3(256), lds, (hipStream_t)stream, d_ids, d_scores, sh, a,
+                           d_w_query, top_k, d_out_ids, d_out_scores, d_out_lists, d_n_out);
+    else
+        hipLaunchKernelGGL(fuse_lists_kernel<false>, dim3(B), dim3(256), lds, (hipStream_t)stream, d_ids, d_scores, sh, a,
+                           d_w_query, top_k, d_out_ids, d_out_scores, d_out_lists, d_n_out);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "fuse_lists_kernel: %s", hipGetErrorString(e));
     return HR_OK;
 }
 

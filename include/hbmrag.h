@@ -336,6 +336,35 @@ HR_API int hr_fuse_scores_dev(const int64_t* d_ids_a, const float* d_sc_a, int k
                        double wa, double wb, double wc, const double* d_w_query, int top_k, int64_t* d_out_ids,
                        double* d_out_scores, int32_t* d_out_methods, int32_t* d_n_out, void* stream);
 
+/* ---- multi-list fusion: up to HR_MAX_FUSE_LISTS ranked lists per query (RAG-fusion, pymilvus hybrid_search(reqs)) ----
+ * The contract of the two fusions above with "three lists" replaced by "L lists"; retrieval.rrf_rank_lists and
+ * retrieval.score_fuse_lists restate it.  For one query, list l = 0 .. n_lists-1 is a ranked run of non-negative ids
+ * (unique inside the list) whose valid prefix ends at its first id < 0.  Lists are visited in index order, entries in
+ * rank order; an id keeps the slot of its first appearance.  score[id] = 0.0, then, for every list that holds the id
+ * in ASCENDING list order, score += c * w_list: one separately rounded fp64 multiply, one separately rounded fp64 add,
+ * no FMA.  HR_FUSE_RRF: c = 1.0 / (double)(rrf_k + rank), rank from 1.  HR_FUSE_WEIGHTED: c = n(score) by the HR_NORM_*
+ * table above, lo / hi over the list's valid prefix.  Output: the stable descending sort of the fused scores (ties keep
+ * first-seen order), cut to top_k, and per id the bit mask of the lists that hold it (bit l = list l; for L <= 3 these
+ * are the HR_METHOD_* bits and all outputs equal hr_fuse_rrf_dev / hr_fuse_scores_dev bit for bit).  The result is a
+ * function of the inputs alone: no floating-point atomic and no thread order decides anything.
+ *   d_ids [B][n_lists][k_in] int64, d_scores [B][n_lists][k_in] fp32 (NULL allowed for HR_FUSE_RRF: never read);
+ *   norms: HOST array of n_lists HR_NORM_* codes (read for HR_FUSE_WEIGHTED only; NULL allowed for RRF);
+ *   weights: HOST array of n_lists doubles; d_w_query (optional) DEVICE [B][n_lists] doubles that replace them per query;
+ *   outputs [B][top_k]: ids (-1 padded), fp64 fused scores (0.0 padded), list masks (0 padded); d_n_out[B].
+ * 1 <= n_lists <= HR_MAX_FUSE_LISTS, 1 <= k_in <= HR_MAX_TOPK, 1 <= top_k <= 3 * HR_MAX_TOPK: HR_ELIMIT beyond the
+ * upper limits.  HR_EINVAL: a value below a lower limit or a negative B, a mode outside 0..1, a NULL required buffer,
+ * NULL weights with NULL d_w_query, NULL scores or norms in weighted mode, a norm outside 0..4 in weighted mode, a
+ * misaligned buffer (8 bytes: ids, fp64 arrays; 4 bytes: the rest), a non-finite host weight.  B == 0: HR_OK, nothing is
+ * launched.  A refused call launches and writes nothing.  Asynchronous on `stream`; allocates nothing, needs no handle.
+ * Scores and weights must be finite.  Whatever the ids are (duplicates inside a list included) the kernel stays inside
+ * its buffers and terminates; only the values of such a query are unspecified. */
+#define HR_MAX_FUSE_LISTS 16
+enum { HR_FUSE_RRF = 0, HR_FUSE_WEIGHTED = 1 };
+HR_API int hr_fuse_lists_dev(const int64_t* d_ids, const float* d_scores, int n_lists, int k_in, int B, int mode,
+                             int rrf_k, const int32_t* norms, const double* weights, const double* d_w_query,
+                             int top_k, int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_lists,
+                             int32_t* d_n_out, void* stream);
+
 /* ---- search (device buffers, asynchronous on `stream`) -------------------------
  * Same results as the host forms.  d_flags[B] (optional) receives 1 when the
  * candidate-generation bound proves the list exact, 0 when the caller must
