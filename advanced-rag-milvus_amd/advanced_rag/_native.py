@@ -28,6 +28,10 @@ HR_FUSE_RRF, HR_FUSE_WEIGHTED = 0, 1
 # column kind, valid only there
 HR_DECAY_GAUSS, HR_DECAY_EXP, HR_DECAY_LINEAR = 0, 1, 2
 HR_NORM_NONE = -1
+# boost ranker (hr_boost_rerank_dev): functions per query, hr_boost_func::flags, and the codes of both modes
+HR_MAX_BOOST_FUNCS = 8
+HR_BOOST_ACTIVE, HR_BOOST_RANDOM = 1, 2
+HR_BOOST_MULTIPLY, HR_BOOST_SUM = 0, 1
 HR_COL_F64 = 5        # beside HR_COL_I64 / HR_COL_F32 below
 HR_MAX_DEEP_K = 16384   # hr_search_*_deep, hr_deep_topk_dev: offset + k
 HR_N_PHASES = 10
@@ -142,6 +146,9 @@ _SIGNATURES = {
                                          _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_group_select_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                        _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_boost_rerank_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
+                                       _c.c_int64, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                       _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_decay_rerank_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
                                        _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                        _c.c_void_p, _c.c_void_p]),
@@ -782,6 +789,25 @@ def decay_rerank_dev(d_ids: int, d_scores: int, score_is_f64: bool, d_n: int, B:
     rc = L.hr_decay_rerank_dev(p(d_ids), p(d_scores), 1 if score_is_f64 else 0, p(d_n), B, k_in, p(d_col), col_kind, col_rows,
                                first_row, p(d_params), norm, k_out, p(d_out_pos), p(d_out_ids), p(d_out_scores), p(d_out_n),
                                p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+# one function of hr_boost_rerank_dev (struct hr_boost_func, 56 bytes): two device pointers, their row counts, weight, seed, flags
+BOOST_FUNC_DTYPE = np.dtype([("mask", "<u8"), ("key_col", "<u8"), ("mask_rows", "<i8"), ("key_rows", "<i8"), ("weight", "<f8"),
+                             ("seed", "<u8"), ("flags", "<i4"), ("reserved", "<i4")])
+
+
+def boost_rerank_dev(d_ids: int, d_scores: int, score_is_f64: bool, d_n: int, B: int, k_in: int, d_funcs: int, n_funcs: int,
+                     first_row: int, function_mode: int, boost_mode: int, norm: int, ascending: bool, k_out: int,
+                     d_out_pos: int, d_out_ids: int, d_out_scores: int, d_out_matched: int, d_out_n: int, stream: int = 0):
+    """hr_boost_rerank_dev: the boost ranker over a batch of ranked lists (device pointers; 0 = NULL; d_funcs = [B, n_funcs]
+    records of BOOST_FUNC_DTYPE on the device)."""
+    L = load_library()
+    p = lambda x: _vp(x) if x else None
+    rc = L.hr_boost_rerank_dev(p(d_ids), p(d_scores), 1 if score_is_f64 else 0, p(d_n), B, k_in, p(d_funcs), n_funcs, first_row,
+                               function_mode, boost_mode, norm, 1 if ascending else 0, k_out, p(d_out_pos), p(d_out_ids),
+                               p(d_out_scores), p(d_out_matched), p(d_out_n), p(stream))
     if rc != 0:
         _raise_global(L, rc)
 

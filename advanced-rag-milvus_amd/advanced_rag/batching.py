@@ -43,6 +43,15 @@ RetrievalConfig(mmr_similarity="embedding") behind its fusion) are wired the sam
 list length, the norm code and the score type are the key, lambda travels per query, and the requests of a round share ONE
 `hr_mmr_select_vec_dev` launch (counted in stats["mmr_launches"] beside the token-Jaccard launches).
 
+Boost rerankings (search(..., ranker=BoostRanker | FunctionScore) behind its plain search, retrieve() with
+RetrievalConfig(boost=...) behind its fusion) are kind "boost": both modes, the norm code, the direction, the padded list
+length and the score type are the key; the functions travel per query (hr_boost_func: the cached device mask of the
+function's filter, the group-key tensor of a keyed draw, weight, seed), padded to the chunk's largest number with inactive
+slots, so requests with different filters, weights and seeds share ONE `hr_boost_rerank_dev` launch
+(stats["boost_launches"]).  The launch state holds the mask and key tensors until the stream has been synchronised: the
+32-entry mask cache may evict one meanwhile.  In the one-round path the kernel runs behind `hr_post_lists_dev`, before the
+decay ranker when both are set.
+
 One worker thread per manager; the event loop never blocks on the GPU.
 """
 from __future__ import annotations
@@ -130,7 +139,7 @@ class RangedQuery:
 
 @dataclass
 class _Request:
-    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "fuse_n" | "decay" | "mmr" | "hybrid" | "encode"
+    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "fuse_n" | "decay" | "boost" | "mmr" | "hybrid" | "encode"
     key: Tuple                # requests with equal (kind, key) share a launch
     payload: Any
     future: Future = field(default_factory=Future)
@@ -159,7 +168,7 @@ class SearchCoalescer:
             self.window_s = max(self.window_s, 250e-6)
         self.stats = {"rounds": 0, "requests": 0, "dense_launches": 0, "sparse_launches": 0, "fuse_launches": 0,
                       "hybrid_launches": 0, "mmr_launches": 0, "encode_launches": 0, "encoded_texts": 0, "max_batch_seen": 0, "redone_unproven": 0,
-                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "score_fuse_launches": 0, "decay_launches": 0, "fuse_n_launches": 0, "busy_s": 0.0}
+                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "score_fuse_launches": 0, "decay_launches": 0, "fuse_n_launches": 0, "boost_launches": 0, "busy_s": 0.0}
         self._engines: Dict[Tuple, Any] = {}   # hybrid engines per (top_k, rrf_k, mmr)
         self._inflight: List[_Request] = []    # the requests of the round in progress (failed as a whole if the worker dies)
         self._outbox: Dict[Any, list] = {}     # event loop -> [(asyncio future, ok, value)] of the round in progress
@@ -285,7 +294,7 @@ class SearchCoalescer:
         dev = torch.device("cuda", self.mgr.device)
         # one stream per kind of work: the dense and the sparse searches of a round run side by side (a lone retrieve()
         # overlaps its two scans, as its two worker threads did before the front existed)
-        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "fuse_n", "decay", "mmr", "hybrid", "encode")}
+        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "fuse_n", "decay", "boost", "mmr", "hybrid", "encode")}
         for reqs in self._rounds():
             groups: Dict[Tuple, List[_Request]] = {}
             for r in reqs:
@@ -406,6 +415,8 @@ class SearchCoalescer:
                 _answer(r.future, self.mgr._fuse_lists_blocking, r.payload, key)
             elif kind == "decay":
                 _answer(r.future, self.mgr._decay_rows_blocking, r.payload, key)
+            elif kind == "boost":
+                _answer(r.future, self.mgr._boost_rows_blocking, r.payload, key)
             elif kind == "mmr":
                 _answer(r.future, self.mgr._mmr_rows_blocking, r.payload, key)
             elif kind == "hybrid":
@@ -523,7 +534,10 @@ class SearchCoalescer:
         fuse, decay = key[5:], ()   # fuse: () = RRF, or ("weighted", norm code of the semantic list, of the sparse list)
         if "decay" in fuse:         # then ("decay", field, norm code): the fused list is kept whole and reranked before MMR / the cut
             fuse, decay = fuse[:fuse.index("decay")], fuse[fuse.index("decay") + 1:]
-        whole = mmr or bool(decay)
+        boost = ()
+        if "boost" in fuse:         # before it ("boost", function mode, boost mode, norm code, direction): reranked before the decay ranker
+            fuse, boost = fuse[:fuse.index("boost")], fuse[fuse.index("boost") + 1:]
+        whole = mmr or bool(decay) or bool(boost)
         handle = self.mgr.collections["semantic_index"].handle.first
         ekey = (top_k, rrf_k, whole) + fuse
         eng = self._engines.get(ekey)
@@ -549,11 +563,13 @@ class SearchCoalescer:
         self.stats["sparse_launches"] += 1
         # the engine reuses ONE buffer set per batch size: another group (or the next chunk of this one) with the same B
         # is enqueued before this round is read back, so the results are copied out here, in stream order
+        if boost:       # (the functions are the request's last operand, behind the decay ranker's)
+            b = self._boost_fused(torch, dev, stream, boost, chunk, b)
         if decay:
             b = self._decay_fused(torch, dev, stream, decay, chunk, b)
         if mmr:
             return {"b": self._mmr_select(torch, dev, stream, top_k, chunk, b), "keep": (q, d_sparse, mask, wq)}
-        if decay:       # the cut: the first top_k of the reranked list
+        if decay or boost:       # the cut: the first top_k of the reranked list
             out = {k: b[k][:, :top_k].clone() for k in ("fused_ids", "fused_scores", "fused_methods", "fused_raw")}
             out.update(fused_n=b["fused_n"].clamp(max=top_k), keep=b["keep"], **{k: b[k].clone() for k in ("ids", "scores", "flags")})
             return {"b": out, "keep": (q, d_sparse, mask, wq)}
@@ -568,6 +584,17 @@ class SearchCoalescer:
         B, fk = len(chunk), int(b["fused_ids"].shape[1])
         pos, oi, os_, on, keep = self._decay_launch(torch, dev, stream, field, norm, [r.payload[5] for r in chunk], b["fused_ids"],
                                                     b["fused_scores"], True, b["fused_n"], B, fk)
+        at = pos.clamp(min=0).to(torch.int64)      # (-1 padding lies beyond fused_n: never read)
+        return {"fused_ids": oi, "fused_scores": os_, "fused_methods": b["fused_methods"].gather(1, at),
+                "fused_raw": b.get("fused_raw", b["fused_scores"]).gather(1, at), "fused_n": on, "ids": b["ids"],
+                "scores": b["scores"], "flags": b["flags"], "keep": (keep, pos, b.get("keep"))}
+
+    def _boost_fused(self, torch, dev, stream, boost, chunk, b):
+        """The boost ranker over the whole fused lists of the batch (hr_boost_rerank_dev, same stream, behind the post kernel)
+        -> the engine's buffers in boosted order, as _decay_fused returns them."""
+        B, fk = len(chunk), int(b["fused_ids"].shape[1])
+        pos, oi, os_, _, on, keep = self._boost_launch(torch, dev, stream, boost, [r.payload[-1] for r in chunk], b["fused_ids"],
+                                                       b["fused_scores"], True, b["fused_n"], B, fk)
         at = pos.clamp(min=0).to(torch.int64)      # (-1 padding lies beyond fused_n: never read)
         return {"fused_ids": oi, "fused_scores": os_, "fused_methods": b["fused_methods"].gather(1, at),
                 "fused_raw": b["fused_scores"].gather(1, at), "fused_n": on, "ids": b["ids"], "scores": b["scores"],
@@ -773,6 +800,68 @@ class SearchCoalescer:
         for i, r in enumerate(chunk):
             n = int(on[i])
             _deliver(r.future, (pos[i, :n].copy(), oi[i, :n].copy(), os_[i, :n].copy()))
+
+    # ------------------------------------------------------------------ boost ranker
+    def _boost_launch(self, torch, dev, stream, modes, functions, d_ids, d_scores, f64, d_n, B, k_in):
+        """ONE hr_boost_rerank_dev over B lists already in HBM, whole lists out (k_out = k_in), on `stream`: modes =
+        (function mode, boost mode, norm code, direction), functions = per query the (filter, weight, seed or None, key field
+        or None) of its functions -> (positions int32 [B, k_in], rows, float64 final scores, matched bits, entries [B], what
+        must stay alive: the masks and key tensors among it)."""
+        from . import _native as nat
+        fmode, bmode, norm, asc = modes
+        n_rows = self.mgr.num_rows
+        n_funcs = max(len(f) for f in functions)
+        rec = np.zeros((B, n_funcs), dtype=nat.BOOST_FUNC_DTYPE)       # flags 0: the inactive padding
+        masks, keys = {}, {}
+        for i, funcs in enumerate(functions):
+            for j, (expr, weight, seed, field) in enumerate(funcs):
+                m = k = None
+                if expr is not None:
+                    if expr not in masks:
+                        masks[expr] = self.mgr._global_device_mask(expr)
+                    m = masks[expr]
+                if seed is not None and field is not None:
+                    if field not in keys:
+                        keys[field] = self.mgr._group_keys_on_device().tensor(field, n_rows)
+                    k = keys[field]
+                rec[i, j] = (m.data_ptr() if m is not None else 0, k.data_ptr() if k is not None else 0, n_rows,
+                             n_rows if k is not None else 0, weight, seed or 0,
+                             nat.HR_BOOST_ACTIVE | (nat.HR_BOOST_RANDOM if seed is not None else 0), 0)
+        d_funcs = torch.from_numpy(rec.view(np.uint8).reshape(B, -1)).to(dev)
+        pos = torch.empty((B, k_in), dtype=torch.int32, device=dev)
+        oi = torch.empty((B, k_in), dtype=torch.int64, device=dev)
+        os_ = torch.empty((B, k_in), dtype=torch.float64, device=dev)
+        om = torch.empty((B, k_in), dtype=torch.int32, device=dev)
+        on = torch.empty((B,), dtype=torch.int32, device=dev)
+        nat.boost_rerank_dev(d_ids.data_ptr(), d_scores.data_ptr(), f64, d_n.data_ptr(), B, k_in, d_funcs.data_ptr(), n_funcs, 0,
+                             fmode, bmode, norm, bool(asc), k_in, pos.data_ptr(), oi.data_ptr(), os_.data_ptr(), om.data_ptr(),
+                             on.data_ptr(), stream.cuda_stream)
+        self.stats["boost_launches"] += 1
+        return pos, oi, os_, om, on, (masks, keys, d_funcs)
+
+    def _enqueue_boost(self, torch, dev, stream, key, chunk):
+        """The boost rerankings of a round in ONE launch: key = (function mode, boost mode, norm code, direction, padded list
+        length, scores are float64), payload = (rows, scores, functions)."""
+        width, f64 = key[4:]
+        B = len(chunk)
+        ids = np.full((B, width), -1, dtype=np.int64)
+        sc = np.zeros((B, width), dtype=np.float64 if f64 else np.float32)
+        n = np.zeros(B, dtype=np.int32)
+        for i, r in enumerate(chunk):
+            rows, scores, _ = r.payload
+            n[i] = len(rows)
+            ids[i, :n[i]] = rows
+            sc[i, :n[i]] = scores
+        d_ids, d_sc, d_n = torch.from_numpy(ids).to(dev), torch.from_numpy(sc).to(dev), torch.from_numpy(n).to(dev)
+        pos, oi, os_, om, on, keep = self._boost_launch(torch, dev, stream, key[:4], [r.payload[2] for r in chunk], d_ids, d_sc,
+                                                        f64, d_n, B, width)
+        return {"pos": pos, "oi": oi, "os": os_, "om": om, "on": on, "keep": (d_ids, d_sc, d_n, keep)}
+
+    def _scatter_boost(self, key, chunk, st):
+        pos, oi, os_, om, on = (st[k].cpu().numpy() for k in ("pos", "oi", "os", "om", "on"))
+        for i, r in enumerate(chunk):
+            n = int(on[i])
+            _deliver(r.future, (pos[i, :n].copy(), oi[i, :n].copy(), os_[i, :n].copy(), om[i, :n].copy()))
 
     # ------------------------------------------------------------------ vector MMR
     def _enqueue_mmr(self, torch, dev, stream, key, chunk):

@@ -36,6 +36,7 @@ import numpy as np
 
 from . import filters as _filters
 from .columns import FLOAT_COLUMNS, PayloadColumns, check_group_field
+from .boost import BoostRanker, FunctionScore, boost_rerank, matched_functions
 from .decay import DecayRanker, decay_rerank
 from .mmr import MMRRanker, vector_mmr
 from .constants import GROUP_WINDOW_FACTOR, QUERY_MAX_WINDOW, IndexingConstants
@@ -386,6 +387,7 @@ class MilvusIndexManager:
         # search_by_ids: search_by_ids() calls whose ids were resolved and whose stored vectors were fetched
         # deep_searches: searches with offset + top_k > HR_MAX_TOPK, answered by the deep forms (a full refine of the shard)
         # iterator_pages: pages a SearchIterator fetched (each one call of the cursor forms: a full refine of the shard)
+        # boost_host_reranks: the same for boost rerankings (hr_boost_rerank_dev)
         # decay_host_reranks: decay rerankings answered by the Python restatement instead of hr_decay_rerank_dev (sharded
         # managers, lists beyond 3 * HR_MAX_TOPK entries, the front's one-by-one fallback after a refused batch)
         # mmr_host_selects: vector MMR selections answered by the Python restatement instead of hr_mmr_select_vec_dev (the
@@ -393,7 +395,7 @@ class MilvusIndexManager:
         # multi_searches: multi_search() calls that passed their checks
         self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
                       "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0, "deep_searches": 0,
-                      "decay_host_reranks": 0, "iterator_pages": 0, "mmr_host_selects": 0, "multi_searches": 0}
+                      "decay_host_reranks": 0, "boost_host_reranks": 0, "iterator_pages": 0, "mmr_host_selects": 0, "multi_searches": 0}
         # bumped by what renumbers or replaces the rows (compact, load_snapshot, attach_shards): a SearchIterator's cursor
         # names a row, so an iterator created under another generation refuses to go on
         self._row_space_generation = 0
@@ -1311,10 +1313,18 @@ class MilvusIndexManager:
         ranker=MMRRanker(...) (vector MMR, what RAG stacks call max_marginal_relevance_search): the first W hits of the plain
         ranking are diversified on the cosine of their STORED embeddings (include/hbmrag.h, hr_mmr_select_vec_dev) and the
         best top_k returned in pick order: "score" stays the hit's own, "mmr_value" is the value it was picked with.  Dense
-        collections only (ValueError on sparse_index); otherwise refused like the decay ranker."""
+        collections only (ValueError on sparse_index); otherwise refused like the decay ranker.
+        ranker=BoostRanker(...) | FunctionScore(...) (pymilvus' boost ranker and function score): the first W hits of the
+        plain ranking are re-scored by the filter expressions their rows match (include/hbmrag.h, hr_boost_rerank_dev) and
+        re-sorted (stable), the best top_k returned: "score" is the final score, "raw_score" the hit's own, "boosted_by" the
+        indices of the functions that matched.  On every collection; refused like the decay ranker, and for whatever the
+        filter language refuses in a function's filter."""
         if isinstance(ranker, MMRRanker):
             return await self._search_mmr(query_embedding, collection_name, top_k, filters, search_params, ranker,
                                           group_by_field, group_size, strict_group_size, offset)
+        if isinstance(ranker, (BoostRanker, FunctionScore)):
+            return await self._search_boosted(query_embedding, collection_name, top_k, filters, search_params, ranker,
+                                              group_by_field, group_size, strict_group_size, offset)
         if ranker is not None:
             return await self._search_decayed(query_embedding, collection_name, top_k, filters, search_params, ranker,
                                               group_by_field, group_size, strict_group_size, offset)
@@ -1374,7 +1384,7 @@ class MilvusIndexManager:
                             weights: Sequence[float], rrf_k: int = 60, semantic_params: Optional[Dict] = None,
                             sparse_params: Optional[Dict] = None, mmr_lambda: Optional[float] = None,
                             fusion: str = "rrf", norms: Optional[Sequence[int]] = None,
-                            decay: Optional[DecayRanker] = None):
+                            decay: Optional[DecayRanker] = None, boost: Optional[Any] = None):
         """The semantic search (2 x top_k), the sparse search (2 x top_k) and their rank fusion for ONE request in ONE
         round of the batching front: what `search` + `search` + `fuse_rank_lists_async` return, cut to the fused top_k.
 
@@ -1394,9 +1404,15 @@ class MilvusIndexManager:
         decay=DecayRanker(...): the WHOLE fused list (4 x top_k entries, as for MMR) is reranked by hr_decay_rerank_dev behind
         the post kernel on the same stream — fused scores are not renormalised: identity, or min-max — and handed to MMR or
         the cut in decayed order.  The second element of a result is then the final score and the hit carries "fused_score".
-        The torchrun form declines."""
+        The torchrun form declines.
+
+        boost=FunctionScore | BoostRanker: the same with hr_boost_rerank_dev, BEFORE the decay ranker when both are set;
+        "fused_score" stays the fusion's."""
         if fusion not in ("rrf", "weighted"):
             raise ValueError(f"fusion must be 'rrf' or 'weighted', got {fusion!r}")
+        if boost is not None:
+            boost = FunctionScore.of(boost, "boost")
+            self._check_boost_functions(boost)      # a filter the language refuses is refused here, not inside a shared launch
         if decay is not None:
             if not isinstance(decay, DecayRanker):
                 raise ValueError(f"decay must be a DecayRanker or None, got {decay!r}")
@@ -1439,8 +1455,15 @@ class MilvusIndexManager:
         if decay is not None:       # field and norm code in the key, the curve's operands per query
             if front.collective:
                 return None
-            fuse_key += ("decay", decay.field, decay.norm_code("IP", fused=True))
+            decay_key = ("decay", decay.field, decay.norm_code("IP", fused=True))
             request += (decay.operands(),)
+        if boost is not None:       # both modes, norm code and direction in the key (before the decay ranker's part), the functions per query
+            if front.collective or self._device_shard(self._main) is None:
+                return None
+            fuse_key += ("boost",) + boost.launch_key("IP", fused=True)
+            request += (boost.operands(),)
+        if decay is not None:
+            fuse_key += decay_key
         fut = front.submit_async("hybrid", (int(top_k), filters, drop, int(rrf_k), mmr) + fuse_key, request)
         try:
             # no timer of its own: the caller (HybridRetriever.retrieve) already bounds the whole request with
@@ -1453,7 +1476,7 @@ class MilvusIndexManager:
             return None
         rows, fused_scores, methods, orig = res[:4]
         hits = self._format_hits(rows, orig)
-        if decay is not None:
+        if decay is not None or boost is not None:
             for hit, raw in zip(hits, res[4].tolist()):
                 hit["fused_score"] = raw
         return list(zip(hits, fused_scores.tolist(), methods.tolist()))
@@ -1633,7 +1656,7 @@ class MilvusIndexManager:
     def _decay_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
         """(collection, W, norm code) of a search with a ranker, or the refusal — before anything is searched."""
         if not isinstance(ranker, DecayRanker):
-            raise ValueError(f"ranker must be a DecayRanker, an MMRRanker or None, got {ranker!r}")
+            raise ValueError(f"ranker must be a DecayRanker, an MMRRanker, a BoostRanker, a FunctionScore or None, got {ranker!r}")
         if collection_name not in self.collections:
             raise ValueError(f"Collection {collection_name} not found")
         coll = self.collections[collection_name]
@@ -1671,10 +1694,128 @@ class MilvusIndexManager:
             out.append(hit)
         return out
 
+    # ---- boost ranker / function score (the contract is in include/hbmrag.h, the restatement in boost.py) ------------------
+    def _check_boost_functions(self, spec: FunctionScore) -> None:
+        """ValueError for what this collection cannot serve of a function score: a random_score field a payload-free
+        collection cannot derive, and whatever the filter language refuses for a function's filter (its caps, TEXT_MATCH on
+        a payload-free collection): the masks are evaluated here, into the caches the rerank reads."""
+        for f in spec.functions:
+            if f.field is not None and self._synthetic_rows:
+                from .device_groups import check_synthetic_group_field
+                check_synthetic_group_field(f.field)
+        device = self._device_shard(self._main) is not None
+        for f in spec.functions:
+            if f.filter is not None:
+                (self._global_device_mask if device else self._row_mask)(f.filter)
+
+    def _boost_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
+        """(collection, W, FunctionScore, launch key) of a search with a boost ranker, or the refusal — before anything is searched."""
+        spec = FunctionScore.of(ranker)
+        if collection_name not in self.collections:
+            raise ValueError(f"Collection {collection_name} not found")
+        coll = self.collections[collection_name]
+        if group_by_field is not None or group_size != 1 or strict_group_size is not None:
+            raise ValueError("ranker cannot be combined with group_by_field")
+        if isinstance(offset, (bool, np.bool_)) or not isinstance(offset, (int, np.integer)) or offset != 0:
+            raise ValueError(f"ranker cannot be combined with offset, got offset={offset!r}")
+        if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
+            raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
+        window = spec.window(top_k)
+        if window > HR_MAX_TOPK:
+            raise ValueError(f"ranker reranks the best max(top_k, candidates) = {window} rows: a deep window (> HR_MAX_TOPK = "
+                             f"{HR_MAX_TOPK}) is not built")
+        if hasattr(coll.handle, "round"):
+            raise NotImplementedError("the boost ranker is not built for the torchrun form (CollectiveShardSet)")
+        self._check_boost_functions(spec)
+        return coll, window, spec, spec.launch_key("IP" if coll.kind == "sparse" else coll.metric)
+
+    async def _search_boosted(self, query_embedding, collection_name, top_k, filters, search_params, ranker, group_by_field,
+                              group_size, strict_group_size, offset) -> List[Dict[str, Any]]:
+        _, window, spec, modes = await asyncio.to_thread(self._boost_request, collection_name, top_k, ranker, group_by_field,
+                                                         group_size, strict_group_size, offset)
+        hits = await self.search(query_embedding, collection_name, window, filters, search_params)
+        if not hits:
+            return hits
+        rows = np.asarray([h["_row"] for h in hits], dtype=np.int64)
+        scores = np.asarray([h["score"] for h in hits], dtype=np.float32)      # fp32 list scores, widened by _format_hits
+        pos, _, final, matched = await self._boost_rows_async(rows, scores, spec.operands(), modes)
+        out = []
+        for p, f, m in zip(pos[:int(top_k)], final[:int(top_k)], matched[:int(top_k)]):
+            hit = hits[int(p)]
+            hit["raw_score"], hit["score"], hit["boosted_by"] = hit["score"], float(f), matched_functions(int(m))
+            out.append(hit)
+        return out
+
+    def _boost_rows_blocking(self, payload, key):
+        """The host restatement over row numbers (sharded managers, stand-ins, the front's one-by-one fallback):
+        payload = (rows int64, scores, functions), key = (function mode, boost mode, norm, direction, ...) -> (positions, rows,
+        float64 final scores, matched bits).  A function's rows are _row_mask(filter): the host view of the mask the device
+        form reads; its keys the host group keys."""
+        rows, scores, functions = payload
+        self._count("boost_host_reranks")
+        n_rows = self.num_rows
+        rows = np.asarray(rows, dtype=np.int64)
+        inside = (rows >= 0) & (rows < n_rows)
+        at = np.where(inside, rows, 0)
+        matches, specs = [], []
+        for expr, weight, seed, field in functions:
+            keep = self._row_mask(expr) if expr is not None else None
+            matches.append([True] * len(rows) if keep is None else (inside & keep[:n_rows][at] if n_rows else inside).tolist())
+            if seed is None:
+                specs.append(weight)
+            else:
+                keys = rows if field is None or not n_rows else np.where(inside, self._host_group_keys(field)[:n_rows][at], rows)
+                specs.append((weight, seed, keys.tolist()))
+        pos, ids, final, hit = boost_rerank(rows.tolist(), [float(x) for x in scores], matches, specs, int(key[0]), int(key[1]),
+                                            int(key[2]), bool(key[3]), len(rows))
+        return (np.asarray(pos, dtype=np.int32), np.asarray(ids, dtype=np.int64), np.asarray(final, dtype=np.float64),
+                np.asarray(hit, dtype=np.int32))
+
+    async def _boost_rows_async(self, rows: np.ndarray, scores: np.ndarray, functions, modes):
+        """(positions, rows, final scores, matched bits) of ONE list in boosted order, whole.  On one GPU shard through the
+        batching front: both modes, the norm code, the direction, the padded list length and the score type are the request
+        key, the functions travel per query, so concurrent requests with different filters, weights and seeds share one
+        hr_boost_rerank_dev launch.  Everything else is reranked on the host by the restatement, with the same result, and
+        counted in stats["boost_host_reranks"]: a manager without a front (sharded, coalesce=False), a list longer than
+        3 * HR_MAX_TOPK entries and, inside the front, the requests of a batch whose launch was refused."""
+        n, K = len(rows), HR_MAX_TOPK
+        width = next(w for w in (K // 4, K, 3 * K, n) if n <= w)      # few distinct launch shapes
+        key = tuple(int(m) for m in modes) + (width, scores.dtype == np.float64)
+        payload = (rows, scores, tuple(functions))
+        front = self._coalescer(self.collections["semantic_index"]) if "semantic_index" in self.collections else None
+        if front is None or front.collective or n > 3 * K or self._device_shard(self._main) is None:
+            return await asyncio.to_thread(self._boost_rows_blocking, payload, key)
+        return await asyncio.wait_for(front.submit_async("boost", key, payload),
+                                      timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
+
+    def _boost_list_request(self, rows, scores, spec):
+        spec = FunctionScore.of(spec, "boost")
+        self._check_boost_functions(spec)           # a filter the language refuses is refused here, not inside a shared launch
+        rows, scores = np.asarray(rows, dtype=np.int64), np.asarray(scores, dtype=np.float64)
+        if rows.shape != scores.shape or rows.ndim != 1:
+            raise ValueError("a list's rows and scores differ in length")
+        return rows, scores, spec.operands(), spec.launch_key("IP", fused=True)
+
+    def boost_rerank_lists(self, rows, scores, spec):
+        """The boost ranker over ONE fused list (row numbers and float64 fused scores), blocking, through the host
+        restatement: -> (positions into the list, float64 final scores) in boosted order.  Fused scores are not
+        renormalised: identity, or min-max with normalization="minmax"; the order is descending."""
+        rows, scores, functions, modes = self._boost_list_request(rows, scores, spec)
+        pos, _, final, _ = self._boost_rows_blocking((rows, scores, functions), modes)
+        return pos, final
+
+    async def boost_rerank_lists_async(self, rows, scores, spec):
+        """boost_rerank_lists for a caller on the event loop: on one GPU shard concurrent callers share one
+        hr_boost_rerank_dev launch (a kind of its own in the batching front); sharded managers use the restatement."""
+        rows, scores, functions, modes = self._boost_list_request(rows, scores, spec)
+        pos, _, final, _ = await self._boost_rows_async(rows, scores, functions, modes)
+        return pos, final
+
     # ---- vector MMR (the contract is in include/hbmrag.h, the restatement in mmr.py) ----------------------------------------
     def _ranker_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
         """The refusals of a search with a ranker of either kind, before anything is searched."""
-        check = self._mmr_request if isinstance(ranker, MMRRanker) else self._decay_request
+        check = self._mmr_request if isinstance(ranker, MMRRanker) else \
+            self._boost_request if isinstance(ranker, (BoostRanker, FunctionScore)) else self._decay_request
         return check(collection_name, top_k, ranker, group_by_field, group_size, strict_group_size, offset)
 
     def _mmr_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):

@@ -59,6 +59,8 @@ class PipelineConfig:
     score_normalization: str = "activation"
     # RetrievalConfig.decay: a decay.DecayRanker over the fused list (freshness or any numeric field), or None
     decay: Optional[Any] = None
+    # RetrievalConfig.boost: a boost.FunctionScore (or a bare boost.BoostRanker) over the fused list, before the decay ranker, or None
+    boost: Optional[Any] = None
     # RetrievalConfig.mmr_similarity: what the diversifying profiles compare, "tokens" (as the reference) or "embedding"
     mmr_similarity: str = "tokens"
 
@@ -96,7 +98,7 @@ class AdvancedRAGPipeline:
             config=RetrievalConfig(hybrid_alpha=self.config.hybrid_alpha, top_k=self.config.top_k,
                                    enable_reranking=self.config.enable_reranking, fusion=self.config.fusion,
                                    score_normalization=self.config.score_normalization, decay=self.config.decay,
-                                   mmr_similarity=self.config.mmr_similarity),
+                                   mmr_similarity=self.config.mmr_similarity, boost=self.config.boost),
             learned_ranker=LearnedRanker())
         self.evaluator = RAGEvaluator()
         self.compliance = ComplianceManager(enable_audit=self.config.enable_audit_logging,

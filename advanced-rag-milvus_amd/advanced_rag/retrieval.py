@@ -104,8 +104,18 @@ class RetrievalConfig:
     # what enable_mmr diversifies on: "tokens" (the reference's token-Jaccard of the contents) or "embedding" (vector MMR: the
     # cosine of the hits' stored semantic_index vectors, mmr.py; such a request takes the general path)
     mmr_similarity: str = "tokens"
+    # boost ranker (boost.FunctionScore, or a bare boost.BoostRanker) over the WHOLE fused list, right after the fusion and
+    # BEFORE the decay ranker (both may be set), the group pass, MMR and the cut: score = fused score (x or +) the combined
+    # weight of the functions whose filter the hit's row matches, "fused_score" keeps the fusion's.  On a fused list
+    # "none" and "activation" mean identity, "minmax" rescales by the list's extremes; the order is descending.
+    # `candidates` is not used here (the whole fused list is the window).
+    boost: Optional[Any] = None
 
     def __post_init__(self):
+        if self.boost is not None:
+            from .boost import BoostRanker, FunctionScore
+            if not isinstance(self.boost, (BoostRanker, FunctionScore)):
+                raise ValueError(f"boost must be a FunctionScore, a BoostRanker or None, got {self.boost!r}")
         if self.mmr_similarity not in ("tokens", "embedding"):
             raise ValueError(f"mmr_similarity must be 'tokens' or 'embedding', got {self.mmr_similarity!r}")
         if self.decay is not None:
@@ -270,7 +280,7 @@ class HybridRetriever:
                                    enable_mmr=mmr, mmr_lambda=lam, group_by_field=base.group_by_field,
                                    group_size=base.group_size,
                                    extended_filter_operators=base.extended_filter_operators,
-                                   fusion=base.fusion, score_normalization=base.score_normalization, decay=base.decay,
+                                   fusion=base.fusion, score_normalization=base.score_normalization, decay=base.decay, boost=base.boost,
                                    mmr_similarity=base.mmr_similarity)
 
         return {
@@ -459,6 +469,8 @@ class HybridRetriever:
             extra.update(fusion="weighted", norms=tuple(self._list_norms()[:2]))
         if cfg.decay is not None:
             extra.update(decay=cfg.decay)
+        if cfg.boost is not None:
+            extra.update(boost=cfg.boost)
         saved = (cfg.dense_weight, cfg.sparse_weight)
         self._adapt_weights(query)   # the adapter sees only the query: applying it before the searches changes nothing
         try:
@@ -566,13 +578,18 @@ class HybridRetriever:
         hit_lists = [semantic_results or [], sparse_results or [], domain_results or []]
         weights = [self.config.dense_weight, self.config.sparse_weight, self.DOMAIN_WEIGHT]
         ranked = self._rank_fusion(hit_lists, weights)
+        fused_of = None
+        if self.config.boost is not None and ranked:
+            device = self._boost_device("boost_rerank_lists")
+            ranked, fused_of = self._decay_ranked(ranked, *device(*self._boost_inputs(hit_lists, ranked), self.config.boost))
         if self.config.decay is not None and ranked:
             rows, scores, values, operands, norm = self._decay_inputs(hit_lists, ranked)
             device = getattr(self.index_manager, "decay_rerank_lists", None)
             order = device(rows, scores, self.config.decay, operands) if device is not None and rows is not None else \
                 decay_rerank(list(range(len(ranked))), scores, values, operands, norm, len(ranked))[::2]
-            return self._assemble_fused(hit_lists, *self._decay_ranked(ranked, *order))
-        return self._assemble_fused(hit_lists, ranked)
+            ranked, before = self._decay_ranked(ranked, *order)
+            fused_of = before if fused_of is None else fused_of      # (the fusion's scores, not the boosted ones)
+        return self._assemble_fused(hit_lists, ranked, fused_of)
 
     # ---- vector MMR (RetrievalConfig.mmr_similarity="embedding") ----
     def _mmr_embedding_host(self, fused):
@@ -615,6 +632,26 @@ class HybridRetriever:
         return (rows if all(r is not None for r in rows) else None, [float(s) for _, s, _ in ranked], values, spec.operands(),
                 spec.norm_code("IP", fused=True))
 
+    def _boost_device(self, name: str):
+        """The manager's boost rerank of a fused list.  The functions are filter expressions over the collection's rows: only
+        a manager that holds the rows can say which hits match, so there is no stand-alone host form."""
+        device = getattr(self.index_manager, name, None)
+        if device is None:
+            raise ValueError(f"RetrievalConfig(boost=...) needs an index manager with {name}")
+        return device
+
+    @staticmethod
+    def _boost_inputs(hit_lists, ranked):
+        """(rows, float64 fused scores) of a fused list for the manager's boost rerank."""
+        payload: Dict[Any, Dict] = {}
+        for hits in hit_lists:
+            for hit in hits:
+                payload.setdefault(hit["id"], hit)
+        rows = [payload[doc_id].get("_row") for doc_id, _, _ in ranked]
+        if any(r is None for r in rows):
+            raise ValueError("RetrievalConfig(boost=...) needs hits that carry their row number")
+        return rows, [float(s) for _, s, _ in ranked]
+
     @staticmethod
     def _decay_ranked(ranked, pos, final):
         """The fused ranking reordered by the decay ranker -> (ranked with the final scores, id -> fused score)."""
@@ -646,7 +683,12 @@ class HybridRetriever:
         return await self._finish_ranked_async(hit_lists, ranked)
 
     async def _finish_ranked_async(self, hit_lists, ranked) -> List[Dict[str, Any]]:
-        """What follows a rank fusion: the decay ranker, the hit dicts, the group pass and MMR (the cut is the caller's)."""
+        """What follows a rank fusion: the boost ranker, the decay ranker, the hit dicts, the group pass and MMR (the cut is
+        the caller's)."""
+        boosted_of = None
+        if self.config.boost is not None and ranked:
+            device = self._boost_device("boost_rerank_lists_async")
+            ranked, boosted_of = self._decay_ranked(ranked, *await device(*self._boost_inputs(hit_lists, ranked), self.config.boost))
         if self.config.decay is not None and ranked:
             rows, scores, values, operands, norm = self._decay_inputs(hit_lists, ranked)
             device = getattr(self.index_manager, "decay_rerank_lists_async", None)
@@ -655,8 +697,9 @@ class HybridRetriever:
             else:
                 order = decay_rerank(list(range(len(ranked))), scores, values, operands, norm, len(ranked))[::2]
             ranked, fused_of = self._decay_ranked(ranked, *order)
+            fused_of = fused_of if boosted_of is None else boosted_of      # (the fusion's scores, not the boosted ones)
         else:
-            fused_of = None
+            fused_of = boosted_of
         pending: List[Any] = []      # vector MMR: the rows of the fused hits, the selection goes through the manager's front
         fused = self._assemble_fused(hit_lists, ranked, fused_of, mmr_rows=pending)
         return await self._mmr_embedding_async(fused, pending) if pending else fused

@@ -25,6 +25,7 @@
 
 #include "common.h"
 #include "attention.h"
+#include "boost.h"
 #include "compact.h"
 #include "decay.h"
 #include "deep.h"
@@ -1356,7 +1357,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 11900; }  // 1.19.0: multi-list fusion (hr_fuse_lists_dev)
+int hr_version(void) { return 12000; }  // 1.20.0: boost ranker / function score (hr_boost_rerank_dev)
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2461,6 +2462,27 @@ int hr_decay_rerank_dev(const int64_t* d_ids, const void* d_scores, int score_is
                        col_kind, col_rows, first_row, d_params, norm, k_out, d_out_pos, d_out_ids, d_out_scores, d_out_n);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "decay_rerank_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+int hr_boost_rerank_dev(const int64_t* d_ids, const void* d_scores, int score_is_f64, const int32_t* d_n, int B, int k_in,
+                        const hr_boost_func* d_funcs, int n_funcs, int64_t first_row, int function_mode, int boost_mode, int norm,
+                        int ascending, int k_out, int32_t* d_out_pos, int64_t* d_out_ids, double* d_out_scores,
+                        int32_t* d_out_matched, int32_t* d_out_n, void* stream) {
+    if (B < 0 || k_in <= 0 || k_out <= 0 || k_out > k_in || n_funcs <= 0 || first_row < 0) return fail(nullptr, HR_EINVAL, "bad boost sizes");
+    if (k_in > kFuseMax) return fail(nullptr, HR_ELIMIT, "k_in exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+    if (n_funcs > HR_MAX_BOOST_FUNCS) return fail(nullptr, HR_ELIMIT, "n_funcs exceeds HR_MAX_BOOST_FUNCS = %d", HR_MAX_BOOST_FUNCS);
+    if (norm < HR_NORM_NONE || norm > HR_NORM_MINMAX_DIST) return fail(nullptr, HR_EINVAL, "bad norm code %d", norm);
+    if (function_mode < HR_BOOST_MULTIPLY || function_mode > HR_BOOST_SUM || boost_mode < HR_BOOST_MULTIPLY || boost_mode > HR_BOOST_SUM)
+        return fail(nullptr, HR_EINVAL, "bad boost modes %d / %d", function_mode, boost_mode);
+    if (B == 0) return HR_OK;
+    if (!d_ids || !d_scores || !d_funcs || !d_out_pos || !d_out_ids || !d_out_scores || !d_out_matched || !d_out_n)
+        return fail(nullptr, HR_EINVAL, "null buffer");
+    hipLaunchKernelGGL(boost_rerank_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, d_ids, d_scores, score_is_f64, d_n, k_in, d_funcs,
+                       n_funcs, first_row, function_mode, boost_mode, norm, ascending ? 1 : 0, k_out, d_out_pos, d_out_ids, d_out_scores,
+                       d_out_matched, d_out_n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "boost_rerank_kernel: %s", hipGetErrorString(e));
     return HR_OK;
 }
 

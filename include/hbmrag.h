@@ -614,6 +614,55 @@ HR_API int hr_decay_rerank_dev(const int64_t* d_ids, const void* d_scores, int s
                         const hr_decay_query* d_params /* device, [B] */, int norm, int k_out,
                         int32_t* d_out_pos, int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_n, void* stream);
 
+/* ---- boost ranker / function score (the ranker that re-scores by FILTER MATCHES) -----------------------------------
+ * Re-ranks B ranked lists by  final = n(score) (x or +) f,  f the combined value of the functions whose row mask holds
+ * the entry's row.  The forms follow the boost ranker and function score of Milvus 2.6, but THIS TABLE is the contract,
+ * not Milvus.  Every operation is a separately rounded IEEE fp64 operation, no FMA.  Lists, valid prefix (d_n, or the
+ * first id < 0), score widening, norm (-1..4) and lo / hi are exactly as in hr_decay_rerank_dev.
+ * For an entry with id i, r = i - first_row, and the functions j = 0 .. n_funcs - 1 of its query:
+ *   match   function j matches iff it is HR_BOOST_ACTIVE and (mask == NULL, or 0 <= r < mask_rows and bit r of mask is
+ *           set: bit r % 8 of byte r / 8, as every rowmask).  A function without HR_BOOST_ACTIVE matches nothing: it is
+ *           the padding that lets queries with fewer functions share a launch.
+ *   draw    (HR_BOOST_RANDOM)  key = (uint64)(key_col && 0 <= r < key_rows ? key_col[r] : i);  G = 0x9E3779B97F4A7C15;
+ *           fin(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 (mod
+ *           2^64);  h = fin(seed + G);  z = fin((h ^ key) + G);  u = (double)(z >> 11) * 2^-53  (exact, in [0, 1))
+ *   value   v_j = HR_BOOST_RANDOM ? weight * u : weight                          (one rounded fp64 multiply)
+ *   factor  over the matching functions IN ASCENDING j: the first gives f = v_j, each later one f = f * v_j
+ *           (function_mode HR_BOOST_MULTIPLY) or f = f + v_j (HR_BOOST_SUM), each separately rounded
+ *   final   no function matches: n(s), bit for bit; otherwise n(s) * f (boost_mode HR_BOOST_MULTIPLY) or n(s) + f
+ *           (HR_BOOST_SUM)
+ *   order   stable sort of final, descending when ascending == 0 and ascending otherwise; ties (-0.0 == 0.0 is one)
+ *           keep input order; a NaN final ranks after every number in either direction, NaNs keep input order; cut to
+ *           k_out
+ * Known answers of the draw, (seed, key) -> u:  (0, 0) -> 0.6524484863740322;  (126, 0) -> 0.4642177690240783;
+ * (126, 1) -> 0.9170314847966232;  (126, -1) -> 0.1269855469743124;  (2^64 - 1, 2^62) -> 0.2569625771059303;
+ * (1, 126) -> 0.3342356104450862.
+ * d_funcs: DEVICE array [B][n_funcs] of operand structs, so that queries with different masks, weights and seeds share
+ * one launch; their contents cannot be seen on the host and are never refused: whatever they hold gives what the table
+ * says (a negative mask_rows or key_rows is an empty range).
+ * Out, [B][k_out]: d_out_pos, d_out_ids, d_out_scores and d_out_n[B] as hr_decay_rerank_dev writes and pads them;
+ * d_out_matched[q][rank] = bit j set iff function j matched the entry, 0 in the padding.
+ * 1 <= k_out <= k_in <= 3 * HR_MAX_TOPK (HR_ELIMIT for a k_in beyond; HR_EINVAL for the other orderings); 1 <= n_funcs
+ * <= HR_MAX_BOOST_FUNCS (HR_ELIMIT beyond, HR_EINVAL below).  HR_EINVAL: a NULL required buffer, a mode outside 0..1, a
+ * norm outside -1..4, negative B / first_row.  A refused call launches nothing and leaves the outputs alone.  B == 0:
+ * HR_OK, nothing is launched.  Asynchronous on `stream`.  The result is a function of the inputs alone. */
+#define HR_MAX_BOOST_FUNCS 8
+enum { HR_BOOST_ACTIVE = 1, HR_BOOST_RANDOM = 2 };          /* hr_boost_func::flags */
+enum { HR_BOOST_MULTIPLY = 0, HR_BOOST_SUM = 1 };           /* function_mode and boost_mode */
+typedef struct hr_boost_func {
+    const uint8_t* mask;      /* device, packed as every rowmask; NULL = every entry matches */
+    const int64_t* key_col;   /* device; only read with HR_BOOST_RANDOM; NULL = the draw is keyed by the id */
+    int64_t mask_rows, key_rows;
+    double weight;
+    uint64_t seed;
+    int32_t flags, reserved;
+} hr_boost_func;              /* 56 bytes */
+HR_API int hr_boost_rerank_dev(const int64_t* d_ids, const void* d_scores, int score_is_f64, const int32_t* d_n,
+                        int B, int k_in, const hr_boost_func* d_funcs /* device, [B][n_funcs] */, int n_funcs,
+                        int64_t first_row, int function_mode, int boost_mode, int norm, int ascending, int k_out,
+                        int32_t* d_out_pos, int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_matched,
+                        int32_t* d_out_n, void* stream);
+
 /* Everything after the per-shard lists of a query batch in ONE launch (one block per query): [hr_merge_topk_dev of
  * every modality's exchanged lists] -> hr_fuse_rrf_dev (or hr_fuse_scores_dev: `fusion`) -> [hr_rerank_linear_dev]; results are bit-identical to the
  * separate calls (reference retrieval.py:421-491 fusion, :518-563 rerank, after the server-side shard merge of
