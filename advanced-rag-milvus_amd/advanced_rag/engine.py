@@ -433,6 +433,17 @@ class PipelinedSearchEngine(HybridSearchEngine):
     once the light stream has passed the returned `done` event (or after `synchronize()`).
     Requires the sparse modality (the two-phase C entry points are hybrid).  The optional domain
     list (engine built with domain_handle) is searched on the heavy stream right behind the batch's scans.
+
+    Slot reuse.  Batch i takes native slot i % depth.  The buffer sets (lists, fused and rerank outputs, the
+    `done` event) are kept per (slot, B), but the native workspace that the prep and the scan write and the finish reads
+    (group maxima, prepared queries, the sparse queries' scale and error terms) is per SLOT only.  With mixed batch
+    sizes the `done` event of the buffer set a batch is about to use therefore says nothing about the batch that last
+    used the slot: it belongs to another batch size, or was recorded when the buffer set was created.  A batch of equal
+    or smaller size reallocates nothing in the workspace, so nothing else would hold its prep and scan back either, and
+    they would overwrite what the previous batch's finish still has to read.  The rule `submit` keeps: the prep and the
+    scan of a batch do not start before the batch that last used the same native slot, at whatever batch size, has
+    recorded `done` (in exclusive-hook mode `done` is recorded behind that batch's hook).  For equal-size batches this
+    is the wait on the buffer set's own event; otherwise it is one more event wait.
     """
 
     def __init__(self, handle, config: Optional[EngineConfig] = None, process_group=None, device: Optional[str] = None,
@@ -483,6 +494,7 @@ class PipelinedSearchEngine(HybridSearchEngine):
         if not prep_stream:
             self.prep = None
         self._slot_bufs = [dict() for _ in range(depth)]
+        self._slot_last = [None] * depth    # per native slot: the buffer set of the batch that used it last
         self._n = 0
         # optional callable(buffers) run on the light stream after fusion/rerank of every batch, before the
         # batch is marked done (e.g. a cross-encoder forward over the fused candidates)
@@ -536,8 +548,14 @@ class PipelinedSearchEngine(HybridSearchEngine):
         kp = b["kp"]
         indptr, idx, val, max_nnz = sparse
         nnz = int(idx.shape[0])
+        # the batch that used this native slot last: its finish reads the slot's workspace until its "done", and with
+        # another batch size that event is not the one of this buffer set (class docstring)
+        prev, self._slot_last[slot] = self._slot_last[slot], b
+        first = self.prep if self.prep is not None else self.heavy
+        if prev is not None and prev is not b:
+            first.wait_event(prev["done"])
         if self.prep is not None:
-            self.prep.wait_event(b["done"])  # the batch that used this slot before has been finished
+            self.prep.wait_event(b["done"])  # the batch that used this buffer set before has been finished
             self.h.hybrid_prep_dev(q.data_ptr(), indptr.data_ptr(), idx.data_ptr(), val.data_ptr(), B, nnz, int(max_nnz),
                                    kp, slot, self.prep.cuda_stream)
             b["prep_done"].record(self.prep)

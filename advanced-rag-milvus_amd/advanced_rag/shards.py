@@ -18,6 +18,7 @@ a boolean array over global rows and are cut into per-shard bitmasks.
 """
 from __future__ import annotations
 
+import threading
 from concurrent.futures import ThreadPoolExecutor
 from typing import List, Optional, Sequence, Tuple
 
@@ -166,6 +167,12 @@ class ShardSet:
         self.rows_of: List[np.ndarray] = [np.zeros(0, np.int64) for _ in handles]  # global row of each local row
         self._n = 0
         self._packed = None   # (filter array, {shard: packed mask}) of the filter used last
+        # Searches with different filters run at the same time (the requests of one multi_search, each in its thread; the
+        # shards of one search in the pool's threads).  The lock makes "look up or build" one step.  A search is handed a
+        # raw device pointer into the entry, and another thread's filter may replace the entry while that search runs: each
+        # thread keeps the entry it was handed last alive until it asks for the next one.
+        self._packed_lock = threading.Lock()
+        self._packed_held = threading.local()
         self._pool = ThreadPoolExecutor(max_workers=len(handles), thread_name_prefix="shard-") if len(handles) > 1 else None
 
     # ------------------------------------------------------------------ shape
@@ -312,20 +319,22 @@ class ShardSet:
         pointer — no gather over the rows and no N/8-byte upload per search."""
         if keep is None:
             return ()
-        ent = self._packed
-        if ent is None or ent[0] is not keep:
-            self._packed = ent = (keep, {})
-        hit = ent[1].get(s)
-        if hit is None:
-            own = keep if (self.n_shards == 1 and len(self.rows_of[0]) == len(keep)) else keep[self.rows_of[s]]
-            packed = np.packbits(own, bitorder="little")
-            h = self.handles[s]
-            if is_native_handle(h):   # keep the mask in its HBM
-                import torch
-                hit = (None, torch.from_numpy(packed).to(f"cuda:{h.device}"))
-            else:
-                hit = (packed, None)
-            ent[1][s] = hit
+        with self._packed_lock:
+            ent = self._packed
+            if ent is None or ent[0] is not keep:
+                self._packed = ent = (keep, {})
+            hit = ent[1].get(s)
+            if hit is None:
+                own = keep if (self.n_shards == 1 and len(self.rows_of[0]) == len(keep)) else keep[self.rows_of[s]]
+                packed = np.packbits(own, bitorder="little")
+                h = self.handles[s]
+                if is_native_handle(h):   # keep the mask in its HBM
+                    import torch
+                    hit = (None, torch.from_numpy(packed).to(f"cuda:{h.device}"))
+                else:
+                    hit = (packed, None)
+                ent[1][s] = hit
+        self._packed_held.hit = hit   # the caller's search reads the device copy by address after the entry may be gone
         packed, dev = hit
         return (packed,) if dev is None else (None, dev.data_ptr())
 

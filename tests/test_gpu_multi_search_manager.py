@@ -220,6 +220,36 @@ def test_retrieve_multi_against_the_restatement_and_against_retrieve(gpu, long_t
             assert _fused_key(one) == _fused_key(many) and len(one) == top_k
 
 
+def test_a_search_keeps_its_shard_mask_while_another_filter_takes_the_cache(gpu, corpus):
+    """The requests of one multi_search run in threads of their own, and the semantic and the sparse collection share one
+    ShardSet, which keeps the packed device mask of the filter used LAST.  A search is handed a raw device pointer into
+    that entry: when another thread's filter replaces the entry, the mask under the pointer must stay allocated and
+    intact until the first thread's search is over.  (It was freed, and the next upload or allocation of that size got
+    its block: searches of two shards then ran under another filter's, or another shard's, mask now and then.)"""
+    import threading
+    Q = corpus[4]
+    two = manager(corpus, devices=[0, 0])
+    try:
+        ss = two._main
+        a = np.random.default_rng(3).random(N) < 0.5
+        b = ~a
+        h = ss.handles[0]
+        own = np.packbits(a[ss.rows_of[0]], bitorder="little")
+        want = h.search_dense(Q[:1], 40, own)                    # the host form under a's local mask, uploaded by the call
+        args = ss._local_mask(0, a)                              # what a search of THIS thread is handed
+        assert args[0] is None and args[1]
+        t = threading.Thread(target=ss._local_mask, args=(0, b))  # another thread's filter takes the cache entry
+        t.start()
+        t.join()
+        grab = [torch.zeros(own.size, dtype=torch.uint8, device="cuda") for _ in range(16)]   # a freed block would be handed out here
+        torch.cuda.synchronize()
+        assert all(g.data_ptr() != args[1] for g in grab)
+        have = h.search_dense(Q[:1], 40, *args)
+        assert np.array_equal(have[0], want[0]) and np.array_equal(have[1].view(np.uint32), want[1].view(np.uint32))
+    finally:
+        asyncio.run(two.close())
+
+
 def test_two_shards_give_the_same_answer(gpu, long_timeout, corpus, one_shard):
     reqs = requests(corpus)
     texts = [f"wording q{i}" for i in (0, 3, 1)]
