@@ -32,6 +32,9 @@ HR_NORM_NONE = -1
 HR_MAX_BOOST_FUNCS = 8
 HR_BOOST_ACTIVE, HR_BOOST_RANDOM = 1, 2
 HR_BOOST_MULTIPLY, HR_BOOST_SUM = 0, 1
+# late-interaction rerank (hr_maxsim_rerank_dev): query tokens per query and the token dimension
+HR_MAX_QUERY_TOKENS = 64
+HR_MAX_TOKEN_DIM = 256
 HR_COL_F64 = 5        # beside HR_COL_I64 / HR_COL_F32 below
 HR_MAX_DEEP_K = 16384   # hr_search_*_deep, hr_deep_topk_dev: offset + k
 HR_N_PHASES = 10
@@ -152,6 +155,9 @@ _SIGNATURES = {
     "hr_decay_rerank_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int,
                                        _c.c_int64, _c.c_int64, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                        _c.c_void_p, _c.c_void_p]),
+    "hr_maxsim_rerank_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
+                                        _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_void_p,
+                                        _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_mask_drop_groups_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "hr_group_select_n_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                          _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -808,6 +814,19 @@ def boost_rerank_dev(d_ids: int, d_scores: int, score_is_f64: bool, d_n: int, B:
     rc = L.hr_boost_rerank_dev(p(d_ids), p(d_scores), 1 if score_is_f64 else 0, p(d_n), B, k_in, p(d_funcs), n_funcs, first_row,
                                function_mode, boost_mode, norm, 1 if ascending else 0, k_out, p(d_out_pos), p(d_out_ids),
                                p(d_out_scores), p(d_out_matched), p(d_out_n), p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+def maxsim_rerank_dev(d_ids: int, d_n: int, B: int, k_in: int, d_qtok: int, d_qn: int, tq_stride: int, dim: int, d_indptr: int,
+                      d_tok: int, tok_rows: int, first_row: int, k_out: int, d_out_pos: int, d_out_ids: int, d_out_scores: int,
+                      d_out_n: int, stream: int = 0):
+    """hr_maxsim_rerank_dev: the late-interaction rerank over a batch of ranked lists (device pointers; 0 = NULL; d_qtok =
+    fp16 [B, tq_stride, dim], d_qn = int32 [B], the token store as CSR over rows first_row .. first_row + tok_rows)."""
+    L = load_library()
+    p = lambda x: _vp(x) if x else None
+    rc = L.hr_maxsim_rerank_dev(p(d_ids), p(d_n), B, k_in, p(d_qtok), p(d_qn), tq_stride, dim, p(d_indptr), p(d_tok), tok_rows,
+                                first_row, k_out, p(d_out_pos), p(d_out_ids), p(d_out_scores), p(d_out_n), p(stream))
     if rc != 0:
         _raise_global(L, rc)
 

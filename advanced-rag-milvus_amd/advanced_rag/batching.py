@@ -52,6 +52,11 @@ slots, so requests with different filters, weights and seeds share ONE `hr_boost
 32-entry mask cache may evict one meanwhile.  In the one-round path the kernel runs behind `hr_post_lists_dev`, before the
 decay ranker when both are set.
 
+Late-interaction rerankings (search(..., ranker=MaxSimRanker(...)) behind its plain search, retrieve() with
+RetrievalConfig(late_interaction=True) behind its fusion) are kind "maxsim": the collection, the padded list length and the
+token dim are the key; the query tokens are padded to the batch's largest Tq and the token count travels per query, so
+requests with different token counts share ONE `hr_maxsim_rerank_dev` launch (stats["maxsim_launches"]).
+
 One worker thread per manager; the event loop never blocks on the GPU.
 """
 from __future__ import annotations
@@ -139,7 +144,7 @@ class RangedQuery:
 
 @dataclass
 class _Request:
-    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "fuse_n" | "decay" | "boost" | "mmr" | "hybrid" | "encode"
+    kind: str                 # "dense" | "sparse" | "fuse" | "fuse_scores" | "fuse_n" | "decay" | "boost" | "mmr" | "maxsim" | "hybrid" | "encode"
     key: Tuple                # requests with equal (kind, key) share a launch
     payload: Any
     future: Future = field(default_factory=Future)
@@ -168,7 +173,7 @@ class SearchCoalescer:
             self.window_s = max(self.window_s, 250e-6)
         self.stats = {"rounds": 0, "requests": 0, "dense_launches": 0, "sparse_launches": 0, "fuse_launches": 0,
                       "hybrid_launches": 0, "mmr_launches": 0, "encode_launches": 0, "encoded_texts": 0, "max_batch_seen": 0, "redone_unproven": 0,
-                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "score_fuse_launches": 0, "decay_launches": 0, "fuse_n_launches": 0, "boost_launches": 0, "busy_s": 0.0}
+                      "group_launches": 0, "redone_grouped": 0, "range_launches": 0, "score_fuse_launches": 0, "decay_launches": 0, "fuse_n_launches": 0, "boost_launches": 0, "maxsim_launches": 0, "busy_s": 0.0}
         self._engines: Dict[Tuple, Any] = {}   # hybrid engines per (top_k, rrf_k, mmr)
         self._inflight: List[_Request] = []    # the requests of the round in progress (failed as a whole if the worker dies)
         self._outbox: Dict[Any, list] = {}     # event loop -> [(asyncio future, ok, value)] of the round in progress
@@ -294,7 +299,7 @@ class SearchCoalescer:
         dev = torch.device("cuda", self.mgr.device)
         # one stream per kind of work: the dense and the sparse searches of a round run side by side (a lone retrieve()
         # overlaps its two scans, as its two worker threads did before the front existed)
-        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "fuse_n", "decay", "boost", "mmr", "hybrid", "encode")}
+        streams = {k: torch.cuda.Stream(dev) for k in ("dense", "sparse", "fuse", "fuse_scores", "fuse_n", "decay", "boost", "mmr", "maxsim", "hybrid", "encode")}
         for reqs in self._rounds():
             groups: Dict[Tuple, List[_Request]] = {}
             for r in reqs:
@@ -419,6 +424,8 @@ class SearchCoalescer:
                 _answer(r.future, self.mgr._boost_rows_blocking, r.payload, key)
             elif kind == "mmr":
                 _answer(r.future, self.mgr._mmr_rows_blocking, r.payload, key)
+            elif kind == "maxsim":
+                _answer(r.future, self.mgr._maxsim_rows_blocking, r.payload, key)
             elif kind == "hybrid":
                 _deliver(r.future, None)   # the caller falls back to two searches + a fusion
             elif kind == "encode":
@@ -896,3 +903,35 @@ class SearchCoalescer:
         for i, r in enumerate(chunk):
             n = min(int(on[i]), int(r.payload[3]))
             _deliver(r.future, (pos[i, :n].copy(), val[i, :n].copy()))
+
+    # ------------------------------------------------------------------ late interaction (MaxSim)
+    def _enqueue_maxsim(self, torch, dev, stream, key, chunk):
+        """The late-interaction rerankings of a round in ONE hr_maxsim_rerank_dev launch: key = (collection, padded list
+        length, token dim), payload = (rows, fp16 query tokens [Tq, dim]).  The query tokens are padded to the batch's
+        largest Tq and d_qn travels per query, so requests with different token counts share the launch.  Whole lists out."""
+        from . import _native as nat
+        _, width, dim = key
+        B = len(chunk)
+        tq = max(int(r.payload[1].shape[0]) for r in chunk)
+        ids = np.full((B, width), -1, dtype=np.int64)
+        n = np.zeros(B, dtype=np.int32)
+        qt = np.zeros((B, tq, dim), dtype=np.float16)
+        qn = np.zeros(B, dtype=np.int32)
+        for i, r in enumerate(chunk):
+            rows, tokens = r.payload
+            n[i], qn[i] = len(rows), tokens.shape[0]
+            ids[i, :n[i]] = rows
+            qt[i, :qn[i]] = tokens
+        d_ids, d_n, d_qt, d_qn = (torch.from_numpy(a).to(dev) for a in (ids, n, qt, qn))
+        indptr, val, tok_rows = self.mgr._token_vectors_on_device().tensors()
+        pos = torch.empty((B, width), dtype=torch.int32, device=dev)
+        oi = torch.empty((B, width), dtype=torch.int64, device=dev)
+        os_ = torch.empty((B, width), dtype=torch.float64, device=dev)
+        on = torch.empty((B,), dtype=torch.int32, device=dev)
+        nat.maxsim_rerank_dev(d_ids.data_ptr(), d_n.data_ptr(), B, width, d_qt.data_ptr(), d_qn.data_ptr(), tq, dim,
+                              indptr.data_ptr() if tok_rows else 0, val.data_ptr() if tok_rows else 0, tok_rows, 0, width,
+                              pos.data_ptr(), oi.data_ptr(), os_.data_ptr(), on.data_ptr(), stream.cuda_stream)
+        self.stats["maxsim_launches"] += 1
+        return {"pos": pos, "oi": oi, "os": os_, "on": on, "keep": (d_ids, d_n, d_qt, d_qn, indptr, val)}
+
+    _scatter_maxsim = _scatter_decay

@@ -319,6 +319,81 @@ class TokenSetColumn:
         return self._indptr.nbytes + self._tok.nbytes
 
 
+class TokenVectorColumn:
+    """Append-only CSR over global rows: row r holds T_r >= 0 token vectors of `dim` fp16 elements, the stored bits of the
+    late-interaction rerank (csrc/maxsim.h).  A row appended without vectors has T_r = 0.  Values are kept flat (one
+    growable fp16 buffer, 3/2 growth) and handed out as [n_tok, dim] views."""
+
+    def __init__(self, dim: int):
+        self.dim = int(dim)
+        self._indptr = np.zeros(1, dtype=np.int64)
+        self._val = np.empty(0, dtype=np.float16)
+        self._n = 0
+
+    def __len__(self) -> int:
+        return self._n
+
+    def extend(self, indptr: np.ndarray, values: np.ndarray) -> None:
+        """Append len(indptr) - 1 rows: indptr int64 non-decreasing from 0, values fp16 [indptr[-1], dim] (checked by the
+        caller: indexing.MilvusIndexManager._checked_token_vectors)."""
+        indptr = np.asarray(indptr, dtype=np.int64)
+        rows = indptr.shape[0] - 1
+        if rows <= 0:
+            return
+        used, add = int(self._indptr[self._n]), int(indptr[-1])
+        self._val = _grown(self._val, (used + add) * self.dim)
+        self._val[used * self.dim: (used + add) * self.dim] = np.asarray(values, dtype=np.float16).reshape(-1)[: add * self.dim]
+        self._indptr = _grown(self._indptr, self._n + rows + 1)
+        self._indptr[self._n + 1: self._n + rows + 1] = indptr[1:] + used
+        self._n += rows
+
+    def pad_to(self, n_rows: int) -> "TokenVectorColumn":
+        """Rows this column does not hold yet, up to n_rows, get no vectors."""
+        if n_rows > self._n:
+            self._indptr = _grown(self._indptr, n_rows + 1)
+            self._indptr[self._n + 1: n_rows + 1] = self._indptr[self._n]
+            self._n = n_rows
+        return self
+
+    def compact(self, keep: np.ndarray) -> None:
+        """Drop the rows whose entry of the boolean `keep` is False; every survivor keeps its vectors."""
+        keep = _keep_mask(keep, self._n)
+        self._indptr, val = _gather_csr(self._indptr[: self._n + 1], self.values(), keep)
+        self._val = np.ascontiguousarray(val).reshape(-1)
+        self._n = self._indptr.shape[0] - 1
+
+    def indptr(self) -> np.ndarray:
+        """int64 [rows + 1] view (no copy)."""
+        return self._indptr[: self._n + 1]
+
+    def values(self) -> np.ndarray:
+        """fp16 [n_tok, dim] view of every row's vectors, row after row (no copy)."""
+        used = int(self._indptr[self._n])
+        return self._val[: used * self.dim].reshape(used, self.dim)
+
+    def row(self, r: int) -> np.ndarray:
+        if not 0 <= r < self._n:
+            raise IndexError(r)
+        return self.values()[self._indptr[r]: self._indptr[r + 1]]
+
+    def gather(self, rows) -> Tuple[np.ndarray, np.ndarray]:
+        """(indptr from 0, values) of the given rows in the given order; a row outside the column has no vectors.  Bounded
+        by what the rows hold, not by the column."""
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        ok = (rows >= 0) & (rows < self._n)
+        at = np.where(ok, rows, 0)
+        beg = np.where(ok, self._indptr[at], 0)
+        cnt = np.where(ok, self._indptr[at + 1] - self._indptr[at], 0) if self._n else np.zeros(len(rows), dtype=np.int64)
+        out = np.zeros(len(rows) + 1, dtype=np.int64)
+        np.cumsum(cnt, out=out[1:])
+        take = np.repeat(beg - out[:-1], cnt) + np.arange(int(out[-1]), dtype=np.int64)
+        return out, self.values()[take]
+
+    @property
+    def nbytes(self) -> int:
+        return self._indptr.nbytes + self._val.nbytes
+
+
 class GroupKeyColumn:
     """Append-only int64 group key per global row of one string column: the ordinal of the row's value in one dictionary
     per collection and field, value -> ordinal in first-seen order.  Rows are keyed once; an ordinal, once given, never
@@ -419,6 +494,8 @@ class PayloadColumns:
         self._group_lock = threading.Lock()
         self._epoch: Optional[EpochColumn] = None            # derived from "timestamp" on first use (the decay ranker's field)
         self._epoch_lock = threading.Lock()
+        self._token_vectors: Optional[TokenVectorColumn] = None   # the late-interaction store, when the manager has a token_dim
+        self._tokvec_lock = threading.Lock()
 
     def __getitem__(self, name: str):
         return self._c["id" if name == "chunk_id" else name]
@@ -486,10 +563,34 @@ class PayloadColumns:
                 self._epoch = EpochColumn()
             return self._epoch.sync(self._c["timestamp"]).array()
 
+    def enable_token_vectors(self, dim: int, reset: bool = False) -> None:
+        """Give the collection a token-vector column of `dim` elements per vector (rows so far have none); reset = drop
+        the vectors a column of that dim already holds."""
+        with self._tokvec_lock:
+            if reset or self._token_vectors is None or self._token_vectors.dim != int(dim):
+                self._token_vectors = TokenVectorColumn(dim)
+
+    def token_vectors(self) -> Optional[TokenVectorColumn]:
+        """The token vectors of every row (None when the collection keeps none): rows appended without vectors are padded
+        with T_r = 0 here, so the column always covers n_rows.  Gathered by compact(), never part of a snapshot."""
+        with self._tokvec_lock:
+            return None if self._token_vectors is None else self._token_vectors.pad_to(self.n_rows)
+
+    def extend_token_vectors(self, base: int, indptr: np.ndarray, values: np.ndarray) -> None:
+        """The vectors of the rows appended at global row `base` (rows before it that have none yet are padded)."""
+        with self._tokvec_lock:
+            col = self._token_vectors.pad_to(base)
+            if len(col) != base:
+                raise ValueError(f"token vectors for row {base} arrive after row {len(col)} was written")
+            col.extend(indptr, values)
+
     def compact(self, keep: np.ndarray) -> None:
         """Drop the rows whose entry of the boolean `keep` (one per row) is False from every column, one column at a
         time (the peak extra memory is one column), and from the token sets and the group keys as far as they are built."""
         keep = _keep_mask(keep, self.n_rows)
+        with self._tokvec_lock:
+            if self._token_vectors is not None:
+                self._token_vectors.pad_to(self.n_rows).compact(keep)
         for col in self._c.values():
             col.compact(keep)
         if self._token_sets is not None:

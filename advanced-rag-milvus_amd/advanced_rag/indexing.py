@@ -35,9 +35,10 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import filters as _filters
-from .columns import FLOAT_COLUMNS, PayloadColumns, check_group_field
+from .columns import TokenVectorColumn, FLOAT_COLUMNS, PayloadColumns, check_group_field
 from .boost import BoostRanker, FunctionScore, boost_rerank, matched_functions
 from .decay import DecayRanker, decay_rerank
+from .maxsim import MaxSimRanker, as_fp16_tokens, check_token_dim, maxsim_rerank_csr
 from .mmr import MMRRanker, vector_mmr
 from .constants import GROUP_WINDOW_FACTOR, QUERY_MAX_WINDOW, IndexingConstants
 from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache, get_semantic_cache
@@ -351,8 +352,11 @@ class MilvusIndexManager:
                  *, dtype: str = "float16", device: int = 0, devices: Optional[Sequence[int]] = None,
                  enable_domain: bool = True, device_embedding_cache: int = 0, coalesce: bool = True,
                  semantic_metric: str = "COSINE", domain_metric: str = "COSINE", mmr_on_device: bool = False,
-                 group_members: bool = False):
+                 group_members: bool = False, token_dim: Optional[int] = None):
         self.host, self.port = host, port
+        # late interaction: token_dim = elements per stored token vector (a multiple of 8 in 8..256); None = the collection
+        # keeps no token vectors, MaxSimRanker is refused and every call is as before
+        self.token_dim = check_token_dim(token_dim) if token_dim is not None else None
         # grouping searches with group_size > 1 (the best group_size rows of each of the top_k best groups): off = such a
         # request is refused, as before the fill phase of device_groups.grouped_search existed
         self.group_members = bool(group_members)
@@ -379,6 +383,9 @@ class MilvusIndexManager:
         self._dev_tokens = None    # device_tokens.DeviceTokenSets: the token sets of "content" in HBM, on first use
         self._dev_groups = None    # device_groups.DeviceGroupKeys: the group keys of the fields grouped on, on first use
         self._dev_decay = None     # device_decay.DeviceDecayColumns: the epoch seconds a decay ranker reads, on first use
+        self._dev_tokvec = None    # device_token_vectors.DeviceTokenVectors: the rows' token vectors in HBM, on first use
+        if self.token_dim is not None:
+            self._cols.enable_token_vectors(self.token_dim)
         # grouping searches answered by the blocking loop: searches, windows searched, windows that ended before the
         # top_k-th group and were continued without the groups they showed
         # group_fill_searches: grouping searches with group_size > 1 that needed the fill phase (a group's members were
@@ -393,9 +400,12 @@ class MilvusIndexManager:
         # mmr_host_selects: vector MMR selections answered by the Python restatement instead of hr_mmr_select_vec_dev (the
         # same cases)
         # multi_searches: multi_search() calls that passed their checks
+        # maxsim_host_reranks: late-interaction rerankings answered by the numpy restatement instead of hr_maxsim_rerank_dev
+        # (sharded managers, stand-ins without a device, the front's one-by-one fallback)
         self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
                       "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0, "deep_searches": 0,
-                      "decay_host_reranks": 0, "boost_host_reranks": 0, "iterator_pages": 0, "mmr_host_selects": 0, "multi_searches": 0}
+                      "decay_host_reranks": 0, "boost_host_reranks": 0, "iterator_pages": 0, "mmr_host_selects": 0, "multi_searches": 0,
+                      "maxsim_host_reranks": 0}
         # bumped by what renumbers or replaces the rows (compact, load_snapshot, attach_shards): a SearchIterator's cursor
         # names a row, so an iterator created under another generation refuses to go on
         self._row_space_generation = 0
@@ -474,6 +484,7 @@ class MilvusIndexManager:
             self._dev_tokens = None
             self._dev_groups = None
             self._dev_decay = None
+            self._dev_tokvec = None
 
     def _initialize_collections(self):
         self._main = ShardSet([self._shard_handle("main", d) for d in self.devices])
@@ -587,6 +598,14 @@ class MilvusIndexManager:
                 from .device_decay import DeviceDecayColumns
                 self._dev_decay = DeviceDecayColumns(None if self._synthetic_rows else self._cols, self._main.first.device)
             return self._dev_decay
+
+    def _token_vectors_on_device(self):
+        """The HBM mirror of the rows' token vectors (what hr_maxsim_rerank_dev reads), on the main shard's device."""
+        with self._mask_lock:
+            if self._dev_tokvec is None:
+                from .device_token_vectors import DeviceTokenVectors
+                self._dev_tokvec = DeviceTokenVectors(self._cols, self._main.first.device)
+            return self._dev_tokvec
 
     def _host_group_keys(self, field: str) -> np.ndarray:
         """int64 group key per global row on the host (collections whose masks are host arrays: several shards, the
@@ -784,6 +803,13 @@ class MilvusIndexManager:
                 sparse_batch = self._checked_sparse_csr(await self._run_encoder(gen.encode_sparse_csr, texts), len(chunks))
             except Exception as e:
                 logger.warning("batched sparse payloads failed (%s); encoding chunk by chunk", e)
+        # token vectors of the whole call from ONE hook call; a failure costs the vectors (T_r = 0), never the rows
+        token_batch = None
+        if self.token_dim is not None and chunks and gen is not None and hasattr(gen, "encode_token_vectors"):
+            try:
+                token_batch = self._checked_token_vectors(await self._run_encoder(gen.encode_token_vectors, texts), len(chunks))
+            except Exception as e:
+                summary["errors"].append({"token_vectors_error": str(e)})
         rows_dense, rows_domain, sp_ptr, sp_idx, sp_val, kept, kept_idx = [], [], [0], [], [], [], []
         n_sparse_ok = 0
         for i, chunk in enumerate(chunks):
@@ -849,6 +875,7 @@ class MilvusIndexManager:
             # together, and whatever fails afterwards is padded rather than left short
             dense_rows = device_rows(dense_dev) if dense_dev is not None else np.stack(rows_dense)
             self._check_dense_rows(dense_rows, self._main)    # refused whole, before anything is appended
+            base_row = self.num_rows
             try:
                 _, _, sparse_err = await asyncio.to_thread(self._main.add, dense_rows, sparse_csr)
             except PartialAppend as pa:
@@ -858,6 +885,10 @@ class MilvusIndexManager:
                 summary["indexed_semantic"] = pa.end - pa.base
                 raise pa.cause
             self._append_payload(kept)
+            if token_batch is not None:
+                col = TokenVectorColumn(self.token_dim)
+                col.extend(*token_batch)
+                self._cols.extend_token_vectors(base_row, *col.gather(kept_idx))
             summary["indexed_semantic"] = len(kept)
             if use_sparse:
                 if sparse_err is None:
@@ -911,13 +942,19 @@ class MilvusIndexManager:
         return dense.shape[0], None, sparse_err
 
     def add_rows(self, dense: np.ndarray, sparse_csr=None, ids: Optional[Sequence[str]] = None,
-                 contents: Optional[Sequence[str]] = None, **scalar_columns):
+                 contents: Optional[Sequence[str]] = None, token_vectors=None, **scalar_columns):
         """Bulk ingest of pre-computed vectors (benchmarks, snapshots): dense [n, dim]
-        float16/float32, optional CSR triple (indptr, indices, values)."""
+        float16/float32, optional CSR triple (indptr, indices, values).  token_vectors=(indptr, values): the rows' token
+        vectors for the late-interaction rerank (a manager with token_dim), values [indptr[-1], token_dim] rounded to fp16
+        by numpy's astype; refused whole, before any shard is touched, when the CSR is malformed or not finite as fp16."""
         if self._synthetic_rows:
             raise ValueError("shard is in synthetic-payload mode; use add_rows_synthetic")
+        if token_vectors is not None:
+            token_vectors = self._checked_token_vectors(token_vectors, len(dense))
         base = self.num_rows
         n, failed, sparse_err = self._add_to_main(dense, sparse_csr)
+        if token_vectors is not None and n:
+            self._cols.extend_token_vectors(base, token_vectors[0][: n + 1], token_vectors[1][: int(token_vectors[0][n])])
         c = self._cols
         defaults = {"doc_id": lambda r: f"doc{r // 10}", "chunk_index": lambda r: r % 10, "token_count": lambda r: 0,
                     "entropy": lambda r: 0.0, "redundancy": lambda r: 0.0, "domain_density": lambda r: 0.0,
@@ -935,6 +972,58 @@ class MilvusIndexManager:
             raise failed
         if sparse_err is not None:  # the rows are in (with empty sparse rows); the caller still hears about it
             raise sparse_err
+
+    def _checked_token_vectors(self, token_vectors, n_rows: int):
+        """(indptr int64 [n_rows + 1], values fp16 [indptr[-1], token_dim]) of a batch, or ValueError: a manager without
+        token_dim, an indptr that is not non-decreasing from 0 or names another row count, values of another shape or
+        not finite as stored in fp16."""
+        if self.token_dim is None:
+            raise ValueError("token vectors need a manager created with token_dim=...")
+        try:
+            indptr, values = token_vectors
+        except (TypeError, ValueError):
+            raise ValueError("token_vectors must be a pair (indptr, values)") from None
+        indptr = np.asarray(indptr)
+        if indptr.ndim != 1 or indptr.dtype.kind not in "iu" or indptr.shape[0] != n_rows + 1:
+            raise ValueError(f"token_vectors indptr must hold {n_rows + 1} integers (one row per appended row), got shape {indptr.shape}")
+        indptr = indptr.astype(np.int64)
+        if indptr[0] != 0 or (np.diff(indptr) < 0).any():
+            raise ValueError("token_vectors indptr must be non-decreasing from 0")
+        values = as_fp16_tokens("token_vectors values", values, self.token_dim)
+        if values.shape[0] != int(indptr[-1]):
+            raise ValueError(f"token_vectors values hold {values.shape[0]} vectors, indptr names {int(indptr[-1])}")
+        return indptr, values
+
+    def save_token_vectors(self, path: str) -> None:
+        """Write the token vectors of every row to ONE .npz (indptr, values, token_dim): they are no part of a snapshot,
+        whose layout is pinned."""
+        col = self._token_vector_column()
+        with open(path, "wb") as f:
+            np.savez(f, indptr=col.indptr(), values=col.values(), token_dim=np.int64(col.dim))
+
+    def load_token_vectors(self, path: str) -> None:
+        """Replace the token vectors of every row by the ones save_token_vectors wrote.  ValueError when the file's row
+        count or dim is not this manager's."""
+        cur = self._token_vector_column()
+        with np.load(path, allow_pickle=False) as z:
+            indptr, values, dim = z["indptr"].astype(np.int64), z["values"], int(z["token_dim"])
+        if dim != self.token_dim:
+            raise ValueError(f"the file holds token vectors of dim {dim}, this manager was created with token_dim={self.token_dim}")
+        if indptr.shape[0] - 1 != len(cur):
+            raise ValueError(f"the file holds token vectors of {indptr.shape[0] - 1} rows, the collection holds {len(cur)}")
+        indptr, values = self._checked_token_vectors((indptr, values), len(cur))
+        self._cols.enable_token_vectors(self.token_dim, reset=True)
+        self._cols.extend_token_vectors(0, indptr, values)
+        with self._mask_lock:
+            self._dev_tokvec = None
+
+    def _token_vector_column(self):
+        """The host token-vector column covering every row, or ValueError for a manager without token_dim."""
+        if self.token_dim is None:
+            raise ValueError("token vectors need a manager created with token_dim=...")
+        if self._synthetic_rows:
+            raise ValueError("a synthetic-payload collection keeps no token vectors")
+        return self._cols.token_vectors()
 
     def add_rows_synthetic(self, dense: np.ndarray, sparse_csr=None):
         """Bulk ingest without host payload columns: ids/metadata are derived from the row
@@ -993,6 +1082,8 @@ class MilvusIndexManager:
         if with_columns:
             self._deleted = z["deleted"].copy() if z["deleted"].size else None
             self._cols = PayloadColumns()
+            if self.token_dim is not None:       # the token vectors are no part of a snapshot: load_token_vectors()
+                self._cols.enable_token_vectors(self.token_dim)
             for k in self._cols:
                 self._cols[k].extend(z[f"col_{k}"].tolist())
 
@@ -1318,13 +1409,21 @@ class MilvusIndexManager:
         plain ranking are re-scored by the filter expressions their rows match (include/hbmrag.h, hr_boost_rerank_dev) and
         re-sorted (stable), the best top_k returned: "score" is the final score, "raw_score" the hit's own, "boosted_by" the
         indices of the functions that matched.  On every collection; refused like the decay ranker, and for whatever the
-        filter language refuses in a function's filter."""
+        filter language refuses in a function's filter.
+        ranker=MaxSimRanker(query_tokens, candidates=None) (late interaction, ColBERT-style MaxSim; a manager created with
+        token_dim): the first W hits of the plain ranking are re-scored by the rows' STORED token vectors (include/hbmrag.h,
+        hr_maxsim_rerank_dev: S = sum over query tokens of the best stored token's similarity; a row without vectors scores
+        0.0) and re-sorted (stable), the best top_k returned: "score" is S, "raw_score" the hit's own.  On every collection
+        (the ranker reads row ids, not the first stage's vectors); refused like the decay ranker."""
         if isinstance(ranker, MMRRanker):
             return await self._search_mmr(query_embedding, collection_name, top_k, filters, search_params, ranker,
                                           group_by_field, group_size, strict_group_size, offset)
         if isinstance(ranker, (BoostRanker, FunctionScore)):
             return await self._search_boosted(query_embedding, collection_name, top_k, filters, search_params, ranker,
                                               group_by_field, group_size, strict_group_size, offset)
+        if isinstance(ranker, MaxSimRanker):
+            return await self._search_maxsim(query_embedding, collection_name, top_k, filters, search_params, ranker,
+                                             group_by_field, group_size, strict_group_size, offset)
         if ranker is not None:
             return await self._search_decayed(query_embedding, collection_name, top_k, filters, search_params, ranker,
                                               group_by_field, group_size, strict_group_size, offset)
@@ -1656,7 +1755,7 @@ class MilvusIndexManager:
     def _decay_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
         """(collection, W, norm code) of a search with a ranker, or the refusal — before anything is searched."""
         if not isinstance(ranker, DecayRanker):
-            raise ValueError(f"ranker must be a DecayRanker, an MMRRanker, a BoostRanker, a FunctionScore or None, got {ranker!r}")
+            raise ValueError(f"ranker must be a DecayRanker, an MMRRanker, a BoostRanker, a FunctionScore, a MaxSimRanker or None, got {ranker!r}")
         if collection_name not in self.collections:
             raise ValueError(f"Collection {collection_name} not found")
         coll = self.collections[collection_name]
@@ -1693,6 +1792,105 @@ class MilvusIndexManager:
             hit["raw_score"], hit["score"] = hit["score"], float(f)
             out.append(hit)
         return out
+
+    # ---- late interaction (MaxSim; the contract is in include/hbmrag.h, the restatement in maxsim.py) ---------------------
+    def _check_query_tokens(self, query_tokens) -> np.ndarray:
+        """fp16 [Tq, token_dim] of a query's token vectors, or ValueError: a manager without token_dim, tokens that are
+        not 2-D, of another dim, with Tq outside 1..HR_MAX_QUERY_TOKENS or not finite as fp16."""
+        if self.token_dim is None:
+            raise ValueError("late interaction needs a manager created with token_dim=...")
+        if self._synthetic_rows:
+            raise ValueError("a synthetic-payload collection keeps no token vectors")
+        from ._native import HR_MAX_QUERY_TOKENS
+        tokens = as_fp16_tokens("query_tokens", query_tokens, self.token_dim)
+        if not 1 <= tokens.shape[0] <= HR_MAX_QUERY_TOKENS:
+            raise ValueError(f"query_tokens must hold 1..{HR_MAX_QUERY_TOKENS} token vectors, got {tokens.shape[0]}")
+        return tokens
+
+    def _maxsim_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
+        """(collection, W, fp16 query tokens) of a search with a MaxSimRanker, or the refusal — before anything is searched."""
+        tokens = self._check_query_tokens(ranker.query_tokens)
+        if collection_name not in self.collections:
+            raise ValueError(f"Collection {collection_name} not found")
+        coll = self.collections[collection_name]
+        if group_by_field is not None or group_size != 1 or strict_group_size is not None:
+            raise ValueError("ranker cannot be combined with group_by_field")
+        if isinstance(offset, (bool, np.bool_)) or not isinstance(offset, (int, np.integer)) or offset != 0:
+            raise ValueError(f"ranker cannot be combined with offset, got offset={offset!r}")
+        if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
+            raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
+        window = ranker.window(top_k)
+        if window > HR_MAX_TOPK:
+            raise ValueError(f"ranker reranks the best max(top_k, candidates) = {window} rows: a deep window (> HR_MAX_TOPK = "
+                             f"{HR_MAX_TOPK}) is not built")
+        if hasattr(coll.handle, "round"):
+            raise NotImplementedError("the late-interaction rerank is not built for the torchrun form (CollectiveShardSet)")
+        return coll, window, tokens
+
+    async def _search_maxsim(self, query_embedding, collection_name, top_k, filters, search_params, ranker, group_by_field,
+                             group_size, strict_group_size, offset) -> List[Dict[str, Any]]:
+        _, window, tokens = self._maxsim_request(collection_name, top_k, ranker, group_by_field, group_size,
+                                                 strict_group_size, offset)
+        hits = await self.search(query_embedding, collection_name, window, filters, search_params)
+        if not hits:
+            return hits
+        rows = np.asarray([h["_row"] for h in hits], dtype=np.int64)
+        pos, _, final = await self._maxsim_rows_async(rows, tokens)
+        out = []
+        for p, f in zip(pos[:int(top_k)], final[:int(top_k)]):
+            hit = hits[int(p)]
+            hit["raw_score"], hit["score"] = hit["score"], float(f)
+            out.append(hit)
+        return out
+
+    def _maxsim_rows_blocking(self, payload, key=None):
+        """The numpy restatement over row numbers and the host column (sharded managers, stand-ins, the front's one-by-one
+        fallback): payload = (rows int64, fp16 query tokens) -> (positions, rows, float64 scores), whole."""
+        rows, tokens = payload
+        self._count("maxsim_host_reranks")
+        col = self._token_vector_column()
+        pos, ids, final = maxsim_rerank_csr(np.asarray(rows).tolist(), tokens, col.indptr(), col.values(), 0, len(rows))
+        return np.asarray(pos, dtype=np.int32), np.asarray(ids, dtype=np.int64), np.asarray(final, dtype=np.float64)
+
+    async def _maxsim_rows_async(self, rows: np.ndarray, tokens: np.ndarray):
+        """(positions, rows, scores) of ONE list in late-interaction order, whole.  On one GPU shard through the batching
+        front (kind "maxsim": the padded list length and the token dim are the key, the tokens and their count travel per
+        query, so concurrent requests with different token counts share one hr_maxsim_rerank_dev launch).  Everything else
+        is reranked on the host by the restatement, with the same result, counted in stats["maxsim_host_reranks"]."""
+        n, K = len(rows), HR_MAX_TOPK
+        width = next(w for w in (K // 4, K, 3 * K, n) if n <= w)      # few distinct launch shapes
+        key = ("semantic_index", width, int(self.token_dim))
+        payload = (rows, tokens)
+        front = self._coalescer(self.collections["semantic_index"]) if "semantic_index" in self.collections else None
+        if front is None or front.collective or n > 3 * K or self._device_shard(self._main) is None:
+            return await asyncio.to_thread(self._maxsim_rows_blocking, payload, key)
+        return await asyncio.wait_for(front.submit_async("maxsim", key, payload),
+                                      timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
+
+    def _maxsim_list_request(self, rows, query_tokens, top_k):
+        tokens = self._check_query_tokens(query_tokens)
+        rows = [(-1 if r is None else int(r)) for r in rows]          # a hit without a row number has no vectors: S = 0.0
+        if isinstance(top_k, (bool, np.bool_)) or not isinstance(top_k, (int, np.integer)) or top_k < 1:
+            raise ValueError(f"top_k must be an integer >= 1, got {top_k!r}")
+        return np.asarray(rows, dtype=np.int64), tokens, int(top_k)
+
+    def maxsim_rerank_lists(self, rows, query_tokens, top_k: int):
+        """The late-interaction rerank over ONE fused list (row numbers, None for a hit without one), blocking, through the
+        host restatement: -> (positions into the list, float64 scores S) of the best top_k in late-interaction order."""
+        rows, tokens, k = self._maxsim_list_request(rows, query_tokens, top_k)
+        if not len(rows):
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64)
+        pos, _, final = self._maxsim_rows_blocking((rows, tokens))
+        return pos[:k], final[:k]
+
+    async def maxsim_rerank_lists_async(self, rows, query_tokens, top_k: int):
+        """maxsim_rerank_lists for a caller on the event loop: on one GPU shard concurrent callers share one
+        hr_maxsim_rerank_dev launch (kind "maxsim" of the batching front); sharded managers use the restatement."""
+        rows, tokens, k = self._maxsim_list_request(rows, query_tokens, top_k)
+        if not len(rows):
+            return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64)
+        pos, _, final = await self._maxsim_rows_async(rows, tokens)
+        return pos[:k], final[:k]
 
     # ---- boost ranker / function score (the contract is in include/hbmrag.h, the restatement in boost.py) ------------------
     def _check_boost_functions(self, spec: FunctionScore) -> None:
@@ -1814,7 +2012,7 @@ class MilvusIndexManager:
     # ---- vector MMR (the contract is in include/hbmrag.h, the restatement in mmr.py) ----------------------------------------
     def _ranker_request(self, collection_name: str, top_k, ranker, group_by_field, group_size, strict_group_size, offset):
         """The refusals of a search with a ranker of either kind, before anything is searched."""
-        check = self._mmr_request if isinstance(ranker, MMRRanker) else \
+        check = self._maxsim_request if isinstance(ranker, MaxSimRanker) else self._mmr_request if isinstance(ranker, MMRRanker) else \
             self._boost_request if isinstance(ranker, (BoostRanker, FunctionScore)) else self._decay_request
         return check(collection_name, top_k, ranker, group_by_field, group_size, strict_group_size, offset)
 

@@ -63,6 +63,8 @@ class PipelineConfig:
     boost: Optional[Any] = None
     # RetrievalConfig.mmr_similarity: what the diversifying profiles compare, "tokens" (as the reference) or "embedding"
     mmr_similarity: str = "tokens"
+    # RetrievalConfig.late_interaction: rerank the fused list by MaxSim over the stored token vectors (a manager with token_dim)
+    late_interaction: bool = False
 
 
 @dataclass
@@ -98,7 +100,8 @@ class AdvancedRAGPipeline:
             config=RetrievalConfig(hybrid_alpha=self.config.hybrid_alpha, top_k=self.config.top_k,
                                    enable_reranking=self.config.enable_reranking, fusion=self.config.fusion,
                                    score_normalization=self.config.score_normalization, decay=self.config.decay,
-                                   mmr_similarity=self.config.mmr_similarity, boost=self.config.boost),
+                                   mmr_similarity=self.config.mmr_similarity, boost=self.config.boost,
+                                   late_interaction=self.config.late_interaction),
             learned_ranker=LearnedRanker())
         self.evaluator = RAGEvaluator()
         self.compliance = ComplianceManager(enable_audit=self.config.enable_audit_logging,

@@ -110,6 +110,11 @@ class RetrievalConfig:
     # "none" and "activation" mean identity, "minmax" rescales by the list's extremes; the order is descending.
     # `candidates` is not used here (the whole fused list is the window).
     boost: Optional[Any] = None
+    # late interaction (ColBERT-style MaxSim, maxsim.py): the WHOLE fused list is re-scored by the rows' stored token vectors
+    # against the query's token vectors (embedding_generator.encode_token_vectors([query])) — after the boost and the decay
+    # ranker, before the group pass, MMR and the cut; "fused_score" keeps the fusion's.  Takes the general path; needs an index
+    # manager created with token_dim and a generator with that hook (ValueError otherwise).
+    late_interaction: bool = False
 
     def __post_init__(self):
         if self.boost is not None:
@@ -281,7 +286,7 @@ class HybridRetriever:
                                    group_size=base.group_size,
                                    extended_filter_operators=base.extended_filter_operators,
                                    fusion=base.fusion, score_normalization=base.score_normalization, decay=base.decay, boost=base.boost,
-                                   mmr_similarity=base.mmr_similarity)
+                                   mmr_similarity=base.mmr_similarity, late_interaction=base.late_interaction)
 
         return {
             "default": base,
@@ -328,6 +333,7 @@ class HybridRetriever:
         dense_q = await self._get_semantic_embedding(query)
         sparse_q = await self._get_sparse_embedding(query)
         expr = self._build_filter_expression(filters) if filters else None
+        query_tokens = await self._get_query_tokens(query) if self.config.late_interaction else None
 
         fused = await self._retrieve_one_round(query, dense_q, sparse_q, expr) if not (use_domain_index and domain) else None
         if fused is not None:
@@ -340,8 +346,22 @@ class HybridRetriever:
         hit_lists = await asyncio.gather(*searches)
 
         self._adapt_weights(query)
-        fused = await self._fuse_results_async(hit_lists[0], hit_lists[1], hit_lists[2] if len(hit_lists) > 2 else [])
+        fused = await self._fuse_results_async(hit_lists[0], hit_lists[1], hit_lists[2] if len(hit_lists) > 2 else [],
+                                               **({"query_tokens": query_tokens} if query_tokens is not None else {}))
         return self._tag_profile(fused, profile)[:self.config.top_k]
+
+    async def _get_query_tokens(self, query: str):
+        """The query's token vectors for the late-interaction rerank: embedding_generator.encode_token_vectors([query])
+        -> (indptr, values), one row.  ValueError when the manager or the generator cannot serve it."""
+        mgr = self.index_manager
+        gen = getattr(mgr, "embedding_generator", None)
+        if getattr(mgr, "maxsim_rerank_lists_async", None) is None or getattr(mgr, "token_dim", None) is None:
+            raise ValueError("RetrievalConfig(late_interaction=True) needs an index manager created with token_dim=...")
+        if gen is None or not hasattr(gen, "encode_token_vectors"):
+            raise ValueError("RetrievalConfig(late_interaction=True) needs an embedding generator with encode_token_vectors")
+        indptr, values = await mgr._run_encoder(gen.encode_token_vectors, [query])
+        indptr = np.asarray(indptr, dtype=np.int64)
+        return mgr._check_query_tokens(np.asarray(values)[int(indptr[0]): int(indptr[1])])
 
     # ------------------------------------------------------------------ several wordings, one ranking
     MAX_WORDINGS = 8
@@ -457,6 +477,8 @@ class HybridRetriever:
         one_round = getattr(self.index_manager, "hybrid_search", None)
         if self.config.group_by_field is not None:
             return None        # the one-round path does not group: the general path serves the request
+        if self.config.late_interaction:
+            return None        # the whole fused list is reranked behind the fusion: the general path
         if one_round is None or (self.config.enable_mmr and (not getattr(self.index_manager, "mmr_on_device", False)
                                                              or self.config.mmr_similarity == "embedding")):
             return None
@@ -658,7 +680,7 @@ class HybridRetriever:
         fused_of = {doc_id: score for doc_id, score, _ in ranked}
         return [(ranked[int(p)][0], float(f), ranked[int(p)][2]) for p, f in zip(pos, final)], fused_of
 
-    async def _fuse_results_async(self, semantic_results, sparse_results, domain_results=None) -> List[Dict[str, Any]]:
+    async def _fuse_results_async(self, semantic_results, sparse_results, domain_results=None, query_tokens=None) -> List[Dict[str, Any]]:
         """_fuse_results for a caller on the event loop: with the HBM index manager the rank fusion of concurrent
         retrieve() calls shares one device launch (index_manager.fuse_rank_lists_async); same arithmetic, same result."""
         hit_lists = [semantic_results or [], sparse_results or [], domain_results or []]
@@ -680,9 +702,9 @@ class HybridRetriever:
                     logger.exception("device rank fusion failed; using host arithmetic")
         if ranked is None:
             ranked = self._rank_fusion(hit_lists, weights)
-        return await self._finish_ranked_async(hit_lists, ranked)
+        return await self._finish_ranked_async(hit_lists, ranked, **({"query_tokens": query_tokens} if query_tokens is not None else {}))
 
-    async def _finish_ranked_async(self, hit_lists, ranked) -> List[Dict[str, Any]]:
+    async def _finish_ranked_async(self, hit_lists, ranked, query_tokens=None) -> List[Dict[str, Any]]:
         """What follows a rank fusion: the boost ranker, the decay ranker, the hit dicts, the group pass and MMR (the cut is
         the caller's)."""
         boosted_of = None
@@ -700,6 +722,15 @@ class HybridRetriever:
             fused_of = fused_of if boosted_of is None else boosted_of      # (the fusion's scores, not the boosted ones)
         else:
             fused_of = boosted_of
+        if query_tokens is not None and ranked:      # late interaction: S over the stored token vectors, whole list
+            row_of: Dict[Any, Any] = {}
+            for hits in hit_lists:
+                for hit in hits:
+                    row_of.setdefault(hit["id"], hit.get("_row"))      # (None: another manager's hit, no vectors, S = 0.0)
+            rows = [row_of[doc_id] for doc_id, _, _ in ranked]
+            pos, final = await self.index_manager.maxsim_rerank_lists_async(rows, query_tokens, len(ranked))
+            ranked, before = self._decay_ranked(ranked, pos, final)
+            fused_of = before if fused_of is None else fused_of      # (the fusion's scores)
         pending: List[Any] = []      # vector MMR: the rows of the fused hits, the selection goes through the manager's front
         fused = self._assemble_fused(hit_lists, ranked, fused_of, mmr_rows=pending)
         return await self._mmr_embedding_async(fused, pending) if pending else fused

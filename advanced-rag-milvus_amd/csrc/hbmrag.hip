@@ -38,6 +38,7 @@
 #include "fuse.h"
 #include "fuse_lists.h"
 #include "group.h"
+#include "maxsim.h"
 #include "mmr.h"
 #include "query.h"
 #include "text.h"
@@ -1357,7 +1358,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 12000; }  // 1.20.0: boost ranker / function score (hr_boost_rerank_dev)
+int hr_version(void) { return 12100; }  // 1.21.0: late-interaction rerank (hr_maxsim_rerank_dev)
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2483,6 +2484,33 @@ int hr_boost_rerank_dev(const int64_t* d_ids, const void* d_scores, int score_is
                        d_out_matched, d_out_n);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "boost_rerank_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+int hr_maxsim_rerank_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_in, const void* d_qtok, const int32_t* d_qn, int tq_stride,
+                         int dim, const int64_t* d_indptr, const void* d_tok, int64_t tok_rows, int64_t first_row, int k_out,
+                         int32_t* d_out_pos, int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_n, void* stream) {
+    if (B < 0 || k_in <= 0 || k_out <= 0 || k_out > k_in || tq_stride <= 0 || tok_rows < 0 || first_row < 0)
+        return fail(nullptr, HR_EINVAL, "bad maxsim sizes");
+    if (k_in > kFuseMax) return fail(nullptr, HR_ELIMIT, "k_in exceeds 3 * HR_MAX_TOPK = %d", kFuseMax);
+    if (tq_stride > HR_MAX_QUERY_TOKENS) return fail(nullptr, HR_ELIMIT, "tq_stride exceeds HR_MAX_QUERY_TOKENS = %d", HR_MAX_QUERY_TOKENS);
+    if (dim > HR_MAX_TOKEN_DIM) return fail(nullptr, HR_ELIMIT, "token dim exceeds %d", HR_MAX_TOKEN_DIM);
+    if (dim < 8 || dim % 8 != 0) return fail(nullptr, HR_EINVAL, "token dim must be a multiple of 8, at least 8 (got %d)", dim);
+    if (B == 0) return HR_OK;
+    if (!d_ids || !d_qtok || !d_qn || !d_out_pos || !d_out_ids || !d_out_scores || !d_out_n) return fail(nullptr, HR_EINVAL, "null buffer");
+    if (tok_rows > 0 && (!d_indptr || !d_tok)) return fail(nullptr, HR_EINVAL, "tok_rows > 0 needs the token store");
+    if (((uintptr_t)d_qtok | (uintptr_t)d_tok) & 15) return fail(nullptr, HR_EINVAL, "token buffers must be 16-byte aligned");
+    const size_t lds = maxsim_lds_bytes(tq_stride, dim, k_in);
+    if (lds > 48 * 1024) {   // the attribute is per device and idempotent: set on every large launch, it costs no launch
+        hipError_t e0 = hipFuncSetAttribute((const void*)maxsim_rerank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)maxsim_lds_bytes(HR_MAX_QUERY_TOKENS, HR_MAX_TOKEN_DIM, kFuseMax));
+        if (e0 != hipSuccess) return fail(nullptr, HR_EHIP, "hipFuncSetAttribute: %s", hipGetErrorString(e0));
+    }
+    hipLaunchKernelGGL(maxsim_rerank_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, d_ids, d_n, k_in, (const chunk_t*)d_qtok, d_qn,
+                       tq_stride, dim, d_indptr, (const chunk_t*)d_tok, tok_rows, first_row, k_out, d_out_pos, d_out_ids, d_out_scores,
+                       d_out_n);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "maxsim_rerank_kernel: %s", hipGetErrorString(e));
     return HR_OK;
 }
 

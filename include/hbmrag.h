@@ -663,6 +663,38 @@ HR_API int hr_boost_rerank_dev(const int64_t* d_ids, const void* d_scores, int s
                         int32_t* d_out_pos, int64_t* d_out_ids, double* d_out_scores, int32_t* d_out_matched,
                         int32_t* d_out_n, void* stream);
 
+/* ---- late-interaction rerank (ColBERT-style MaxSim; the embedding lists with MAX_SIM of Milvus 2.6) ----------------
+ * Re-ranks B ranked lists by how well every query token is matched by the entry's best stored token.  THIS TABLE is the
+ * contract.  Operands: row r of the token store has T_r >= 0 vectors of `dim` fp16 elements (CSR: d_indptr[tok_rows + 1]
+ * non-decreasing from 0, d_tok [d_indptr[tok_rows]][dim], row r at d_indptr[r - first_row]); query q has Tq = d_qn[q]
+ * vectors (clamped into [0, tq_stride]) at d_qtok[q][0 .. Tq).  dim is a multiple of 8 in 8 .. HR_MAX_TOKEN_DIM; every
+ * element is finite.  For an entry with id i:
+ *   token similarity  s(t, u): acc = 0.0f; for k = 0 .. dim - 1: acc = fmaf(q[t][k], d[u][k], acc), both operands
+ *                     widened exactly (an fp16 x fp16 product is exact in fp32, so this is also "fp32 product, then one
+ *                     rounded fp32 add"); 256 * 65504^2 < fp32 max: no overflow, no NaN
+ *   per query token   m_t = the largest s(t, u) over u < T_r (fp32 compare); m_t = 0.0f when T_r == 0 or i lies outside
+ *                     [first_row, first_row + tok_rows)
+ *   score             S = 0.0 (fp64, plus zero); for t = 0 .. Tq - 1: S = S + (double)m_t, one rounded fp64 add each.
+ *                     S is never -0.0, whatever sign a zero m_t carries.
+ *   order             the stable descending sort of S (ties keep list order), cut to k_out
+ * A query with 0 tokens scores every entry 0.0 and so keeps list order (defined, not refused: the operand lives on the
+ * device).  CSR bounds read on the device are clamped into [0, d_indptr[tok_rows]], so a damaged CSR cannot send a load
+ * outside d_tok.  Lists and valid prefix (d_n, or with d_n == NULL the entries before the first id < 0) and the outputs
+ * (d_out_pos, d_out_ids -1 padded, d_out_scores 0.0 padded, d_out_n) are exactly as in hr_decay_rerank_dev.
+ * 1 <= k_out <= k_in <= 3 * HR_MAX_TOPK; HR_ELIMIT for a k_in beyond, for tq_stride > HR_MAX_QUERY_TOKENS and for a dim
+ * beyond HR_MAX_TOKEN_DIM; HR_EINVAL for the other orderings, a NULL required buffer (d_indptr / d_tok may be NULL iff
+ * tok_rows == 0), a dim below 8 or not a multiple of 8, d_qtok / d_tok not 16-byte aligned, tq_stride < 1, negative B /
+ * tok_rows / first_row.  A refused call launches nothing and leaves the outputs alone.  B == 0: HR_OK, nothing is
+ * launched.  Asynchronous on `stream`; allocates nothing; not tied to an hr_index.  The result is a function of the
+ * inputs alone: no atomic decides anything but the prefix length, which is a minimum. */
+#define HR_MAX_QUERY_TOKENS 64
+#define HR_MAX_TOKEN_DIM 256
+HR_API int hr_maxsim_rerank_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_in,
+                        const void* d_qtok /* fp16 [B][tq_stride][dim] */, const int32_t* d_qn /* [B] */, int tq_stride,
+                        int dim, const int64_t* d_indptr /* [tok_rows + 1] */, const void* d_tok /* fp16 [..][dim] */,
+                        int64_t tok_rows, int64_t first_row, int k_out, int32_t* d_out_pos, int64_t* d_out_ids,
+                        double* d_out_scores, int32_t* d_out_n, void* stream);
+
 /* Everything after the per-shard lists of a query batch in ONE launch (one block per query): [hr_merge_topk_dev of
  * every modality's exchanged lists] -> hr_fuse_rrf_dev (or hr_fuse_scores_dev: `fusion`) -> [hr_rerank_linear_dev]; results are bit-identical to the
  * separate calls (reference retrieval.py:421-491 fusion, :518-563 rerank, after the server-side shard merge of
