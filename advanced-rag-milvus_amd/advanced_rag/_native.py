@@ -43,6 +43,7 @@ PHASE_NAMES = ("prep", "dense_scan", "group_select", "refine", "topk",
 HR_DEBUG_FINISH_MODE, HR_DEBUG_FAIL_NEXT_BUILD, HR_DEBUG_DENSE_KERNELS, HR_DEBUG_SPARSE_RPB, HR_DEBUG_GROUP_ROWS = 1, 2, 3, 4, 5
 HR_DEBUG_NO_TRIM = 6
 HR_DEBUG_NO_RANGE_CLAMP = 7
+HR_DEBUG_MAXSIM_SCAN_BLOCKS = 8
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libhbmrag.so")
@@ -158,6 +159,8 @@ _SIGNATURES = {
     "hr_maxsim_rerank_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int,
                                         _c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int, _c.c_void_p, _c.c_void_p,
                                         _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "hr_maxsim_scan_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_int64,
+                                      _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "hr_mask_drop_groups_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_void_p, _c.c_void_p, _c.c_int, _c.c_void_p]),
     "hr_group_select_n_dev": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int, _c.c_int, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int,
                                          _c.c_int, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
@@ -827,6 +830,19 @@ def maxsim_rerank_dev(d_ids: int, d_n: int, B: int, k_in: int, d_qtok: int, d_qn
     p = lambda x: _vp(x) if x else None
     rc = L.hr_maxsim_rerank_dev(p(d_ids), p(d_n), B, k_in, p(d_qtok), p(d_qn), tq_stride, dim, p(d_indptr), p(d_tok), tok_rows,
                                 first_row, k_out, p(d_out_pos), p(d_out_ids), p(d_out_scores), p(d_out_n), p(stream))
+    if rc != 0:
+        _raise_global(L, rc)
+
+
+def maxsim_scan_dev(d_qtok: int, d_qn: int, B: int, tq_stride: int, dim: int, d_indptr: int, d_tok: int, tok_rows: int, n_rows: int,
+                    d_rowmask: int, d_scores: int, d_rows: int, stream: int = 0):
+    """hr_maxsim_scan_dev: the MaxSim score of every local row for B queries (device pointers; 0 = NULL; d_qtok = fp16
+    [B, tq_stride, dim], d_qn = int32 [B], d_rowmask packed or 0 = all rows) -> d_scores fp32 / d_rows int32 [B, n_rows],
+    the candidate arrays deep_topk_dev selects from."""
+    L = load_library()
+    p = lambda x: _vp(x) if x else None
+    rc = L.hr_maxsim_scan_dev(p(d_qtok), p(d_qn), B, tq_stride, dim, p(d_indptr), p(d_tok), tok_rows, n_rows, p(d_rowmask),
+                              p(d_scores), p(d_rows), p(stream))
     if rc != 0:
         _raise_global(L, rc)
 

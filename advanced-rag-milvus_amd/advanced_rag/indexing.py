@@ -38,7 +38,7 @@ from . import filters as _filters
 from .columns import TokenVectorColumn, FLOAT_COLUMNS, PayloadColumns, check_group_field
 from .boost import BoostRanker, FunctionScore, boost_rerank, matched_functions
 from .decay import DecayRanker, decay_rerank
-from .maxsim import MaxSimRanker, as_fp16_tokens, check_token_dim, maxsim_rerank_csr
+from .maxsim import MaxSimRanker, as_fp16_tokens, check_token_dim, maxsim_rerank_csr, maxsim_search_csr
 from .mmr import MMRRanker, vector_mmr
 from .constants import GROUP_WINDOW_FACTOR, QUERY_MAX_WINDOW, IndexingConstants
 from .embedding_cache import DeviceEmbeddingTable, EmbeddingCache, get_semantic_cache
@@ -402,10 +402,12 @@ class MilvusIndexManager:
         # multi_searches: multi_search() calls that passed their checks
         # maxsim_host_reranks: late-interaction rerankings answered by the numpy restatement instead of hr_maxsim_rerank_dev
         # (sharded managers, stand-ins without a device, the front's one-by-one fallback)
+        # maxsim_searches: maxsim_search() calls answered by hr_maxsim_scan_dev + hr_deep_topk_dev on one GPU shard;
+        # maxsim_host_searches: those answered by the restatement over the host column (sharded managers, stand-ins)
         self.stats = {"group_searches": 0, "group_rounds": 0, "group_continuations": 0, "group_fill_searches": 0,
                       "group_fill_rounds": 0, "queries": 0, "query_device": 0, "search_by_ids": 0, "deep_searches": 0,
                       "decay_host_reranks": 0, "boost_host_reranks": 0, "iterator_pages": 0, "mmr_host_selects": 0, "multi_searches": 0,
-                      "maxsim_host_reranks": 0}
+                      "maxsim_host_reranks": 0, "maxsim_searches": 0, "maxsim_host_searches": 0}
         # bumped by what renumbers or replaces the rows (compact, load_snapshot, attach_shards): a SearchIterator's cursor
         # names a row, so an iterator created under another generation refuses to go on
         self._row_space_generation = 0
@@ -1891,6 +1893,71 @@ class MilvusIndexManager:
             return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float64)
         pos, _, final = await self._maxsim_rows_async(rows, tokens)
         return pos[:k], final[:k]
+
+    async def maxsim_search(self, query_tokens, top_k: int = 20, filters: Optional[str] = None, *,
+                            offset: int = 0) -> List[Dict[str, Any]]:
+        """MaxSim as the FIRST stage (Milvus 2.6: MAX_SIM as the metric of a search over an embedding list): the whole
+        collection is ranked by the rows' stored token vectors, so a row the pooled embedding ranks 5 000th is found.
+        The hits are the rows that pass `filters` and the tombstones AND hold at least one token vector, by score
+        descending, then row ascending; "score" is the fp32 MaxSim score, (float)S of include/hbmrag.h (hr_maxsim_scan_dev);
+        the dicts are those search() on semantic_index returns for the rows.  Entries offset .. offset + top_k - 1, with
+        offset + top_k <= QUERY_MAX_WINDOW (deep_window); a shorter ranking gives a shorter list.  Two rows whose fp64 S
+        differ by less than an fp32 ulp tie and are ordered by row: maxsim_rerank_lists on the hits gives the fp64 order
+        of a window.  One GPU shard: hr_maxsim_scan_dev over the HBM mirror under the cached device mask, then
+        hr_deep_topk_dev (stats["maxsim_searches"]); every call reads the tokens of every row that passes.  Sharded
+        managers and stand-ins: the restatement (maxsim.maxsim_search_csr) over the host column and host mask
+        (stats["maxsim_host_searches"]).  ValueError before anything runs: a manager without token_dim, bad tokens (the
+        MaxSimRanker rule), the window rule, an expression the filter language refuses; NotImplementedError in the
+        torchrun form."""
+        tokens = self._check_query_tokens(query_tokens)
+        deep_window(top_k, offset)
+        if "semantic_index" not in self.collections:
+            raise ValueError("Collection semantic_index not found")
+        if hasattr(self.collections["semantic_index"].handle, "round"):
+            raise NotImplementedError("the MaxSim search is not built for the torchrun form (CollectiveShardSet)")
+        if filters:
+            _filters.lower(filters)          # whatever the filter language refuses, before a mask is built
+        try:
+            return await asyncio.wait_for(asyncio.to_thread(self._maxsim_search_blocking, tokens, int(top_k), int(offset), filters),
+                                          timeout=IndexingConstants.MILVUS_TIMEOUT_SECONDS)
+        except asyncio.TimeoutError:
+            logging.error("shard search timeout for the MaxSim search")
+            raise Exception("Search timeout for the MaxSim search")
+
+    def _maxsim_search_blocking(self, tokens: np.ndarray, top_k: int, offset: int, filters: Optional[str]) -> List[Dict[str, Any]]:
+        """ONE query's MaxSim ranking, entries offset .. offset + top_k - 1.  The score / row / scratch arrays (8 bytes per
+        row + the selection's scratch) belong to the call."""
+        shard = self._device_shard(self.collections["semantic_index"].handle)
+        if shard is None:
+            mask = self._row_mask(filters)
+            self._count("maxsim_host_searches")
+            col = self._token_vector_column()
+            return self._format_hits(*maxsim_search_csr(tokens, col.indptr(), col.values(), mask, top_k, offset))
+        import torch
+        from . import _native as nat
+        mask = self._device_row_mask(filters, "dense")
+        self._count("maxsim_searches")
+        n_rows = int(shard.num_rows)
+        if n_rows == 0:
+            return []
+        indptr, val, tok_rows = self._token_vectors_on_device().tensors()
+        dev = torch.device("cuda", int(shard.device))
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev)
+            d_q = torch.from_numpy(np.ascontiguousarray(tokens)).to(dev)
+            d_qn = torch.tensor([tokens.shape[0]], dtype=torch.int32, device=dev)
+            scores = torch.empty((1, n_rows), dtype=torch.float32, device=dev)
+            rows = torch.empty((1, n_rows), dtype=torch.int32, device=dev)
+            scratch = torch.empty(max(nat.deep_topk_scratch_bytes(n_rows, 1, top_k + offset) // 8, 1), dtype=torch.int64, device=dev)
+            out_ids = torch.empty((1, top_k), dtype=torch.int64, device=dev)
+            out_sc = torch.empty((1, top_k), dtype=torch.float32, device=dev)
+            nat.maxsim_scan_dev(d_q.data_ptr(), d_qn.data_ptr(), 1, int(tokens.shape[0]), int(self.token_dim),
+                                indptr.data_ptr() if tok_rows else 0, val.data_ptr() if tok_rows else 0, tok_rows, n_rows,
+                                mask.data_ptr() if mask is not None else 0, scores.data_ptr(), rows.data_ptr(), stream.cuda_stream)
+            nat.deep_topk_dev(scores.data_ptr(), rows.data_ptr(), n_rows, 1, top_k, offset, False, int(getattr(shard, "row_offset", 0)),
+                              out_ids.data_ptr(), out_sc.data_ptr(), scratch.data_ptr(), stream.cuda_stream)
+            ids, sc = out_ids.cpu().numpy()[0], out_sc.cpu().numpy()[0]      # the copies wait for the stream
+        return self._format_hits(ids, sc)
 
     # ---- boost ranker / function score (the contract is in include/hbmrag.h, the restatement in boost.py) ------------------
     def _check_boost_functions(self, spec: FunctionScore) -> None:

@@ -4,7 +4,10 @@ a stable descending sort.
 The contract is the table in include/hbmrag.h (hr_maxsim_rerank_dev).  This module holds the spec object a caller passes
 (`MaxSimRanker`) and the numpy restatement of the device kernel (csrc/maxsim.h): a float32 loop over k (an fp16 x fp16
 product is exact in float32, so "float32 product, then one rounded float32 add" IS the fma chain of the contract), a
-float64 sum over the query tokens, a stable sort.  Host and device agree bit for bit."""
+float64 sum over the query tokens, a stable sort.  Host and device agree bit for bit.
+
+MaxSim as a first-stage search (hr_maxsim_scan_dev + hr_deep_topk_dev; manager.maxsim_search) is restated by
+`maxsim_search_csr`: the same S, rounded once to float32, ranked by (score descending, row ascending)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -130,6 +133,25 @@ def maxsim_scores_csr(query_tokens: Any, indptr: np.ndarray, values: np.ndarray,
     for t in range(len(q)):
         S = S + m[:, t].astype(np.float64)
     return S
+
+
+def maxsim_search_csr(query_tokens: Any, indptr: np.ndarray, values: np.ndarray, mask: Optional[np.ndarray], top_k: int,
+                      offset: int = 0, first_row: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """Host restatement of the first-stage MaxSim search (hr_maxsim_scan_dev, then hr_deep_topk_dev) over a CSR token store
+    whose row 0 is global row first_row.  The hits are the rows that hold at least one token vector and pass the bool
+    `mask` over local rows (None = all; rows beyond the mask do not pass); the score of a hit is np.float32(S), S rounded
+    once; the ranking R is score descending, then row ascending.  -> (ids int64, scores float32) of R[offset : offset +
+    top_k], shorter when R is."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    has = np.diff(indptr) > 0
+    if mask is not None:
+        m = np.asarray(mask, dtype=bool).reshape(-1)[:len(has)]
+        has[:len(m)] &= m
+        has[len(m):] = False
+    rows = np.flatnonzero(has).astype(np.int64)
+    scores = maxsim_scores_csr(query_tokens, indptr, values, rows).astype(np.float32)
+    order = np.lexsort((rows, -scores))[int(offset): int(offset) + int(top_k)]   # S is finite and never -0.0: negation keeps the order
+    return rows[order] + int(first_row), scores[order]
 
 
 def maxsim_rerank_csr(ids: Sequence[int], query_tokens: Any, indptr: np.ndarray, values: np.ndarray, first_row: int,

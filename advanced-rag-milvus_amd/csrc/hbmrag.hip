@@ -756,6 +756,7 @@ enum { PHASE_SCAN = 1, PHASE_FINISH = 2, PHASE_PREP = 4, PHASE_ALL = 7 };
 // set fits LDS; otherwise the multi-launch chain, whose refine kernels spread ONE query over many compute units
 // (single-query latency path, escalated searches with hundreds of candidate groups).
 int g_finish_mode = 0;  // hr_debug_option(HR_DEBUG_FINISH_MODE): 0 = by batch size, 1 = always the chain, 2 = fused whenever it fits
+int g_maxsim_scan_blocks = 0;  // hr_debug_option(HR_DEBUG_MAXSIM_SCAN_BLOCKS): blocks per query of hr_maxsim_scan_dev (0 = by size)
 bool finish_fused_ok(int B, int n_mod, const FinishSide& f) {
     if (g_finish_mode == 1) return false;
     return ((int64_t)B * n_mod >= 64 || g_finish_mode == 2) && f.C <= kFinishMaxCand && (int64_t)f.C * f.GR <= kFinishMaxSlots &&
@@ -1358,7 +1359,7 @@ int compact_sparse(hr_index* h, hipStream_t s, const uint32_t* d_src_of, int64_t
 // =============================================================================
 extern "C" {
 
-int hr_version(void) { return 12100; }  // 1.21.0: late-interaction rerank (hr_maxsim_rerank_dev)
+int hr_version(void) { return 12200; }  // 1.22.0: MaxSim as a first-stage search (hr_maxsim_scan_dev)
 
 const char* hr_last_error(const hr_index* h) {
     if (!h) return g_last_error.c_str();
@@ -2394,6 +2395,10 @@ int hr_debug_option(hr_index* h, int key, int value) {
         case HR_DEBUG_NO_RANGE_CLAMP:
             g_no_range_clamp = value != 0;
             return HR_OK;
+        case HR_DEBUG_MAXSIM_SCAN_BLOCKS:
+            if (value < 0 || value > 65535) return fail(h, HR_EINVAL, "maxsim scan blocks must be 0..65535");
+            g_maxsim_scan_blocks = value;
+            return HR_OK;
         case HR_DEBUG_FAIL_NEXT_BUILD:
             if (!h) return fail(nullptr, HR_EINVAL, "null handle");
             h->fault_inject = value ? 1 : 0;
@@ -2511,6 +2516,37 @@ int hr_maxsim_rerank_dev(const int64_t* d_ids, const int32_t* d_n, int B, int k_
                        d_out_n);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(nullptr, HR_EHIP, "maxsim_rerank_kernel: %s", hipGetErrorString(e));
+    return HR_OK;
+}
+
+int hr_maxsim_scan_dev(const void* d_qtok, const int32_t* d_qn, int B, int tq_stride, int dim, const int64_t* d_indptr, const void* d_tok,
+                       int64_t tok_rows, int64_t n_rows, const uint8_t* d_rowmask, float* d_scores, int32_t* d_rows, void* stream) {
+    if (B < 0 || tq_stride <= 0 || tok_rows < 0 || n_rows < 0) return fail(nullptr, HR_EINVAL, "bad maxsim scan sizes");
+    if (tq_stride > HR_MAX_QUERY_TOKENS) return fail(nullptr, HR_ELIMIT, "tq_stride exceeds HR_MAX_QUERY_TOKENS = %d", HR_MAX_QUERY_TOKENS);
+    if (dim > HR_MAX_TOKEN_DIM) return fail(nullptr, HR_ELIMIT, "token dim exceeds %d", HR_MAX_TOKEN_DIM);
+    if (n_rows > 0x7fffffffll) return fail(nullptr, HR_ELIMIT, "n_rows exceeds the int32 row range");
+    if (B > 65535) return fail(nullptr, HR_ELIMIT, "batch size %d exceeds one grid (65535)", B);
+    if (dim < 8 || dim % 8 != 0) return fail(nullptr, HR_EINVAL, "token dim must be a multiple of 8, at least 8 (got %d)", dim);
+    if (B == 0 || n_rows == 0) return HR_OK;
+    if (!d_qtok || !d_qn || !d_scores || !d_rows) return fail(nullptr, HR_EINVAL, "null buffer");
+    if (tok_rows > 0 && (!d_indptr || !d_tok)) return fail(nullptr, HR_EINVAL, "tok_rows > 0 needs the token store");
+    if (((uintptr_t)d_qtok | (uintptr_t)d_tok) & 15) return fail(nullptr, HR_EINVAL, "token buffers must be 16-byte aligned");
+    // Blocks per query: about eight blocks per compute unit over the whole batch, so that one query still fills the chip;
+    // rows per wave and range: as many as keep that many blocks busy, 8 .. 64.  More ranges than blocks are walked in turn.
+    const int64_t want = g_maxsim_scan_blocks > 0 ? g_maxsim_scan_blocks : std::max(1, 2048 / B);
+    const int rpw = (int)std::min<int64_t>(kMaxSimScanLanes, std::max<int64_t>(8, (n_rows + want * kMaxSimWaves - 1) / (want * kMaxSimWaves)));
+    const int64_t n_ranges = (n_rows + (int64_t)rpw * kMaxSimWaves - 1) / ((int64_t)rpw * kMaxSimWaves);
+    const unsigned blocks = (unsigned)std::min<int64_t>(n_ranges, want);
+    const size_t lds = maxsim_scan_lds_bytes(tq_stride, dim);
+    if (lds > 48 * 1024) {   // per device and idempotent, as for the rerank
+        hipError_t e0 = hipFuncSetAttribute((const void*)maxsim_scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                            (int)maxsim_scan_lds_bytes(HR_MAX_QUERY_TOKENS, HR_MAX_TOKEN_DIM));
+        if (e0 != hipSuccess) return fail(nullptr, HR_EHIP, "hipFuncSetAttribute: %s", hipGetErrorString(e0));
+    }
+    hipLaunchKernelGGL(maxsim_scan_kernel, dim3(blocks, B), dim3(256), lds, (hipStream_t)stream, (const chunk_t*)d_qtok, d_qn, tq_stride, dim,
+                       d_indptr, (const chunk_t*)d_tok, tok_rows, n_rows, d_rowmask, rpw, d_scores, d_rows);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(nullptr, HR_EHIP, "maxsim_scan_kernel: %s", hipGetErrorString(e));
     return HR_OK;
 }
 

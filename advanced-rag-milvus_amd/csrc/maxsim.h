@@ -1,6 +1,8 @@
 // Late-interaction rerank (ColBERT-style MaxSim; Milvus 2.6 embedding lists with MAX_SIM): every entry of a ranked list is
 // re-scored as  S = sum over query tokens t of  max over the row's stored tokens u of  <q_t, d_u>  and the list is
 // re-sorted.  include/hbmrag.h holds the contract; advanced_rag/maxsim.py restates it on the host, bit for bit.
+// The first-stage search (maxsim_scan_kernel, at the end of this file) scores every row of the store with the same
+// arithmetic: the pieces both kernels need are device functions, written once.
 //
 // The similarity is DEFINED as the k-ascending fp32 fma chain.  v_mfma_f32_16x16x4_f32 is exactly that chain (one
 // rounding per product, no wider accumulation), instruction i adding k = 4i .. 4i + 3 in ascending order, so the matrix
@@ -46,6 +48,109 @@ __device__ __forceinline__ void maxsim_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- what the rerank and the scan share: one arithmetic, written once ------------------------------------------------------
+// The query's tokens into LDS: rows [0, Tq) from the operand, zeros up to the tile edge (all 256 threads).
+__device__ __forceinline__ void maxsim_load_query(unsigned char* s_q, const chunk_t* __restrict__ qtok, int q, int tq_stride,
+                                                  int Tq, int nT, int cpr, int rb, int tid) {
+    for (int c = tid; c < nT * 16 * cpr; c += 256) {
+        const int row = c / cpr, cc = c - row * cpr;
+        chunk_t v = {0u, 0u, 0u, 0u};
+        if (row < Tq) v = qtok[((int64_t)q * tq_stride + row) * cpr + cc];
+        *(chunk_t*)(s_q + (size_t)row * rb + cc * 16) = v;
+    }
+}
+
+// Where lane's chunk i of a 16-token tile goes in the wave's LDS tile.
+__device__ __forceinline__ void maxsim_tile_offsets(int (&loff)[kMaxSimChunks], int cpr, int rb, int lane) {
+#pragma unroll
+    for (int i = 0; i < kMaxSimChunks; ++i) {
+        const int c = lane + 64 * i, row = c / cpr;
+        loff[i] = row * rb + (c - row * cpr) * 16;
+    }
+}
+
+// Tokens [u, u + 16) of a row that starts at token `beg` and has T tokens: the valid ones from the store, zeros for the
+// rows the tile does not have.  Registers only: the loads are in flight while the previous tile is multiplied.
+__device__ __forceinline__ void maxsim_fetch_tile(chunk_t (&pf)[kMaxSimChunks], const chunk_t* __restrict__ tok, int64_t beg,
+                                                  int T, int u, int cpr, int lane) {
+    const chunk_t* src = tok + (beg + u) * cpr;
+    const int left = T - u, lim = (left < 16 ? left : 16) * cpr;
+#pragma unroll
+    for (int i = 0; i < kMaxSimChunks; ++i) {
+        const int x = lane + 64 * i;
+        chunk_t v = {0u, 0u, 0u, 0u};
+        if (x < lim) v = src[x];
+        pf[i] = v;
+    }
+}
+
+__device__ __forceinline__ void maxsim_store_tile(unsigned char* s_doc, const int (&loff)[kMaxSimChunks],
+                                                  const chunk_t (&pf)[kMaxSimChunks], int tile_chunks, int lane) {
+#pragma unroll
+    for (int i = 0; i < kMaxSimChunks; ++i)
+        if (lane + 64 * i < tile_chunks) *(chunk_t*)(s_doc + loff[i]) = pf[i];
+}
+
+// a[rt] = the 16 x 16 similarities of query tile rt (rt < nT) and the wave's document tile: the canonical chain.  Returned
+// by value: with the accumulators passed by reference maxsim_rerank_kernel allocates 132 registers instead of 128 and
+// loses a wave of occupancy (make asm).
+struct MaxSimTile { f32x4_t a[4]; };
+__device__ __forceinline__ MaxSimTile maxsim_tile_product(const unsigned char* s_q, const unsigned char* s_doc, int nT, int cpr,
+                                                          int rb, int g, int col) {
+    MaxSimTile tile;
+    f32x4_t (&acc)[4] = tile.a;
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    const unsigned char* dp = s_doc + col * rb;
+    const unsigned char* qp = s_q + col * rb;
+    for (int j = 0; j < cpr; ++j) {
+        const chunk_t dv = *(const chunk_t*)(dp + j * 16);
+        const float b0 = maxsim_pick<0>(dv, g), b1 = maxsim_pick<1>(dv, g);
+#pragma unroll
+        for (int rt = 0; rt < 4; ++rt) {
+            if (rt < nT) {
+                const chunk_t qv = *(const chunk_t*)(qp + (size_t)rt * 16 * rb + j * 16);
+                acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(maxsim_pick<0>(qv, g), b0, acc[rt], 0, 0, 0);   // k = 8j + g
+                acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(maxsim_pick<1>(qv, g), b1, acc[rt], 0, 0, 0);   // k = 8j + 4 + g
+            }
+        }
+    }
+    return tile;
+}
+
+// m = max(m, acc) for the columns this tile has (`have`); `first`: the row's first tile starts the maximum at -inf.
+__device__ __forceinline__ void maxsim_fold_tile(f32x4_t (&m)[4], const f32x4_t (&acc)[4], bool first, bool have) {
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float old = first ? -INFINITY : m[rt][r];
+            m[rt][r] = have ? fmaxf(old, acc[rt][r]) : old;
+        }
+}
+
+// The row's last tile is folded: the maximum over the 16 columns, m_t for t = 16 rt + 4 g + reg, into dst[t].
+__device__ __forceinline__ void maxsim_column_max(const f32x4_t (&m)[4], int nT, float* dst, int g, int col) {
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) {
+        if (rt < nT) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = m[rt][r];
+                for (int d = 1; d < 16; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
+                if (col == 0) dst[rt * 16 + g * 4 + r] = v;
+            }
+        }
+    }
+}
+
+// S = 0.0; S += (double)m_t, t ascending: one rounded fp64 add each.
+__device__ __forceinline__ double maxsim_sum_tokens(const float* m, int Tq) {
+    double S = 0.0;
+    for (int t = 0; t < Tq; ++t) S = __dadd_rn(S, (double)m[t]);
+    return S;
 }
 
 // One block (256 threads, four waves) per query.
@@ -100,13 +205,7 @@ __global__ __launch_bounds__(256) void maxsim_rerank_kernel(
     Tq = Tq < 0 ? 0 : (Tq > tq_stride ? tq_stride : Tq);
     const int nT = (Tq + 15) >> 4;
 
-    // the query's tokens: rows [0, Tq) from the operand, zeros up to the tile edge
-    for (int c = tid; c < nT * 16 * cpr; c += 256) {
-        const int row = c / cpr, cc = c - row * cpr;
-        chunk_t v = {0u, 0u, 0u, 0u};
-        if (row < Tq) v = qtok[((int64_t)q * tq_stride + row) * cpr + cc];
-        *(chunk_t*)(s_q + (size_t)row * rb + cc * 16) = v;
-    }
+    maxsim_load_query(s_q, qtok, q, tq_stride, Tq, nT, cpr, rb, tid);
     const int64_t total = tok_rows > 0 ? indptr[tok_rows] : 0;
     for (int i = tid; i < n; i += 256) {
         const int64_t id = my_ids[i];
@@ -127,36 +226,17 @@ __global__ __launch_bounds__(256) void maxsim_rerank_kernel(
 
     if (nT > 0) {   // block-uniform
         int loff[kMaxSimChunks];
-#pragma unroll
-        for (int i = 0; i < kMaxSimChunks; ++i) {
-            const int c = lane + 64 * i, row = c / cpr;
-            loff[i] = row * rb + (c - row * cpr) * 16;
-        }
+        maxsim_tile_offsets(loff, cpr, rb, lane);
         const int tile_chunks = 16 * cpr;
         chunk_t pf[kMaxSimChunks];
         auto next_entry = [&](int c) {
             while (c < n && s_T[c] == 0) c += kMaxSimWaves;
             return c;
         };
-        auto fetch = [&](int c, int u) {   // the tile's valid rows from the store, zeros for the rows it does not have
-            const chunk_t* src = tok + (s_beg[c] + u) * cpr;
-            const int left = s_T[c] - u, lim = (left < 16 ? left : 16) * cpr;
-#pragma unroll
-            for (int i = 0; i < kMaxSimChunks; ++i) {
-                const int x = lane + 64 * i;
-                chunk_t v = {0u, 0u, 0u, 0u};
-                if (x < lim) v = src[x];
-                pf[i] = v;
-            }
-        };
-        auto flush = [&](int cnt) {   // lane l sums entry l of the collected batch: S = 0.0; S += (double)m_t, t ascending
+        auto fetch = [&](int c, int u) { maxsim_fetch_tile(pf, tok, s_beg[c], s_T[c], u, cpr, lane); };
+        auto flush = [&](int cnt) {   // lane l sums entry l of the collected batch
             maxsim_wave_sync();
-            if (lane < cnt) {
-                const float* row = s_m + lane * kMaxSimMStride;
-                double S = 0.0;
-                for (int t = 0; t < Tq; ++t) S = __dadd_rn(S, (double)row[t]);
-                s_fin[s_cid[lane]] = S;
-            }
+            if (lane < cnt) s_fin[s_cid[lane]] = maxsim_sum_tokens(s_m + lane * kMaxSimMStride, Tq);
             maxsim_wave_sync();
         };
 
@@ -167,9 +247,7 @@ __global__ __launch_bounds__(256) void maxsim_rerank_kernel(
         for (int rt = 0; rt < 4; ++rt) m[rt] = f32x4_t{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
         while (ci < n) {   // wave-uniform
             const int T = s_T[ci];
-#pragma unroll
-            for (int i = 0; i < kMaxSimChunks; ++i)
-                if (lane + 64 * i < tile_chunks) *(chunk_t*)(s_doc + loff[i]) = pf[i];
+            maxsim_store_tile(s_doc, loff, pf, tile_chunks, lane);
             maxsim_wave_sync();
             int nci = ci, nu0 = u0 + 16;
             if (nu0 >= T) {
@@ -178,43 +256,10 @@ __global__ __launch_bounds__(256) void maxsim_rerank_kernel(
             }
             if (nci < n) fetch(nci, nu0);   // in flight while this tile is multiplied
 
-            f32x4_t acc[4];
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt) acc[rt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            const unsigned char* dp = s_doc + col * rb;
-            const unsigned char* qp = s_q + col * rb;
-            for (int j = 0; j < cpr; ++j) {
-                const chunk_t dv = *(const chunk_t*)(dp + j * 16);
-                const float b0 = maxsim_pick<0>(dv, g), b1 = maxsim_pick<1>(dv, g);
-#pragma unroll
-                for (int rt = 0; rt < 4; ++rt) {
-                    if (rt < nT) {
-                        const chunk_t qv = *(const chunk_t*)(qp + (size_t)rt * 16 * rb + j * 16);
-                        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(maxsim_pick<0>(qv, g), b0, acc[rt], 0, 0, 0);   // k = 8j + g
-                        acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(maxsim_pick<1>(qv, g), b1, acc[rt], 0, 0, 0);   // k = 8j + 4 + g
-                    }
-                }
-            }
-            const bool have = u0 + col < T;   // a column the last tile does not have loses every maximum
-#pragma unroll
-            for (int rt = 0; rt < 4; ++rt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float old = u0 == 0 ? -INFINITY : m[rt][r];
-                    m[rt][r] = have ? fmaxf(old, acc[rt][r]) : old;
-                }
+            const MaxSimTile tile = maxsim_tile_product(s_q, s_doc, nT, cpr, rb, g, col);
+            maxsim_fold_tile(m, tile.a, u0 == 0, u0 + col < T);   // a column the last tile does not have loses every maximum
             if (u0 + 16 >= T) {   // the row's last tile: the maximum over the 16 columns, then collect
-#pragma unroll
-                for (int rt = 0; rt < 4; ++rt) {
-                    if (rt < nT) {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float v = m[rt][r];
-                            for (int d = 1; d < 16; d <<= 1) v = fmaxf(v, __shfl_xor(v, d));
-                            if (col == 0) s_m[slot * kMaxSimMStride + rt * 16 + g * 4 + r] = v;
-                        }
-                    }
-                }
+                maxsim_column_max(m, nT, s_m + slot * kMaxSimMStride, g, col);
                 if (lane == 0) s_cid[slot] = ci;
                 if (++slot == kMaxSimBatch) {
                     flush(slot);
@@ -246,6 +291,117 @@ __global__ __launch_bounds__(256) void maxsim_rerank_kernel(
         out_scores[(int64_t)q * k_out + i] = 0.0;
     }
     if (tid == 0) out_n[q] = kept;
+}
+
+// ---- first-stage search: every row of the store instead of a list of ids (hr_maxsim_scan_dev) --------------------------------
+constexpr int kMaxSimScanLanes = 64;   // rows of one wave's piece of a range at most: a lane per row
+
+// Dynamic LDS of one scan block, in the order the kernel carves it.
+__host__ __device__ inline size_t maxsim_scan_lds_bytes(int tq_stride, int dim) {
+    const size_t rb = (size_t)maxsim_row_bytes(dim), q_rows = (size_t)((tq_stride + 15) & ~15);
+    return q_rows * rb                                                  // query tokens, rows padded to whole 16-token tiles
+           + (size_t)kMaxSimWaves * 16 * rb                             // one document tile per wave
+           + (size_t)kMaxSimWaves * kMaxSimBatch * kMaxSimMStride * 4   // collected maxima
+           + (size_t)kMaxSimWaves * kMaxSimBatch * 4;                   // the lanes (rows of the piece) they belong to
+}
+
+// Grid (blocks per query, queries), 256 threads.  Query blockIdx.y's tokens sit in LDS for the block's whole life.  The
+// rows are cut into ranges of 4 * rpw consecutive rows (rpw <= 64); block x walks ranges x, x + gridDim.x, ... and wave w
+// of it takes rows [range * 4 rpw + w * rpw, + rpw) of each: a lane per row reads the mask bit and the clamped CSR bounds,
+// writes the (0.0f, -1) cell of a row that is no hit at once, and the wave then walks the remaining rows in ascending
+// order with the rerank's loop: "the next entry" is the next set bit of the ballot.  The rows of a piece are consecutive in
+// the token store, so a wave's tiles are one forward stream; a masked-out or empty row costs its 17 bytes of mask and CSR.
+// The score is written by the lane that sums it (sixteen rows at a time), rounded once: (float)S.  No block barrier
+// after the query load; no atomic anywhere.
+__global__ __launch_bounds__(256) void maxsim_scan_kernel(
+    const chunk_t* __restrict__ qtok, const int32_t* __restrict__ qn, int tq_stride, int dim,
+    const int64_t* __restrict__ indptr, const chunk_t* __restrict__ tok, int64_t tok_rows, int64_t n_rows,
+    const uint8_t* __restrict__ rowmask, int rpw, float* __restrict__ scores, int32_t* __restrict__ rows) {
+    extern __shared__ __align__(16) unsigned char ms_lds[];
+    const int q = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, col = lane & 15;
+    const int rb = maxsim_row_bytes(dim), cpr = dim >> 3, q_rows = (tq_stride + 15) & ~15;
+    unsigned char* s_q = ms_lds;
+    unsigned char* s_doc = s_q + (size_t)q_rows * rb + (size_t)wave * 16 * rb;
+    float* s_m = (float*)(s_q + (size_t)q_rows * rb + (size_t)kMaxSimWaves * 16 * rb) + wave * kMaxSimBatch * kMaxSimMStride;
+    int* s_cid = (int*)((float*)(s_q + (size_t)q_rows * rb + (size_t)kMaxSimWaves * 16 * rb) +
+                        kMaxSimWaves * kMaxSimBatch * kMaxSimMStride) + wave * kMaxSimBatch;
+    int Tq = qn[q];
+    Tq = Tq < 0 ? 0 : (Tq > tq_stride ? tq_stride : Tq);
+    const int nT = (Tq + 15) >> 4;
+    maxsim_load_query(s_q, qtok, q, tq_stride, Tq, nT, cpr, rb, tid);
+    __syncthreads();
+
+    const int64_t total = tok_rows > 0 ? indptr[tok_rows] : 0;
+    float* my_scores = scores + (int64_t)q * n_rows;
+    int32_t* my_rows = rows + (int64_t)q * n_rows;
+    int loff[kMaxSimChunks];
+    maxsim_tile_offsets(loff, cpr, rb, lane);
+    const int tile_chunks = 16 * cpr;
+    const int64_t range_rows = (int64_t)kMaxSimWaves * rpw, n_ranges = (n_rows + range_rows - 1) / range_rows;
+    chunk_t pf[kMaxSimChunks];
+    f32x4_t m[4];
+#pragma unroll
+    for (int rt = 0; rt < 4; ++rt) m[rt] = f32x4_t{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+
+    for (int64_t range = blockIdx.x; range < n_ranges; range += gridDim.x) {
+        const int64_t base = range * range_rows + (int64_t)wave * rpw, i = base + lane;
+        const bool mine = lane < rpw && i < n_rows;
+        int64_t beg = 0;
+        int T = 0;
+        if (mine && i < tok_rows && (!rowmask || ((rowmask[i >> 3] >> (i & 7)) & 1))) {
+            int64_t b = indptr[i], e = indptr[i + 1];
+            b = b < 0 ? 0 : (b > total ? total : b);
+            e = e < b ? b : (e > total ? total : e);
+            beg = b;
+            T = e - b > (int64_t)0x40000000 ? 0x40000000 : (int)(e - b);
+        }
+        const bool hit = T > 0;
+        if (mine && !(hit && nT > 0)) {   // no hit, or a query without tokens: nothing to multiply
+            my_scores[i] = 0.f;
+            my_rows[i] = hit ? (int32_t)i : -1;
+        }
+        unsigned long long todo = nT > 0 ? __ballot(hit) : 0ull;   // wave-uniform
+        if (!todo) continue;
+        auto flush = [&](int cnt) {   // lane l sums row l of the collected batch and writes its cell
+            maxsim_wave_sync();
+            if (lane < cnt) {
+                const int64_t r = base + s_cid[lane];
+                my_scores[r] = (float)maxsim_sum_tokens(s_m + lane * kMaxSimMStride, Tq);
+                my_rows[r] = (int32_t)r;
+            }
+            maxsim_wave_sync();
+        };
+        int cur = __builtin_ctzll(todo), u0 = 0, slot = 0;
+        int cT = __shfl(T, cur);
+        maxsim_fetch_tile(pf, tok, __shfl(beg, cur), cT, 0, cpr, lane);
+        while (todo) {   // wave-uniform
+            maxsim_store_tile(s_doc, loff, pf, tile_chunks, lane);
+            maxsim_wave_sync();
+            const bool last = u0 + 16 >= cT;
+            const unsigned long long rest = last ? todo & (todo - 1) : todo;
+            const int ncur = rest ? __builtin_ctzll(rest) : cur, nu0 = last ? 0 : u0 + 16;
+            const int64_t nbeg = __shfl(beg, ncur);
+            const int nTr = __shfl(T, ncur);
+            if (rest) maxsim_fetch_tile(pf, tok, nbeg, nTr, nu0, cpr, lane);   // in flight while this tile is multiplied
+
+            const MaxSimTile tile = maxsim_tile_product(s_q, s_doc, nT, cpr, rb, g, col);
+            maxsim_fold_tile(m, tile.a, u0 == 0, u0 + col < cT);
+            if (last) {
+                maxsim_column_max(m, nT, s_m + slot * kMaxSimMStride, g, col);
+                if (lane == 0) s_cid[slot] = cur;
+                if (++slot == kMaxSimBatch) {
+                    flush(slot);
+                    slot = 0;
+                }
+            }
+            maxsim_wave_sync();   // every lane has read the tile before the next one is written
+            todo = rest;
+            cur = ncur;
+            cT = nTr;
+            u0 = nu0;
+        }
+        if (slot) flush(slot);
+    }
 }
 
 }  // namespace hbmrag

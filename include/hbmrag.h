@@ -695,6 +695,42 @@ HR_API int hr_maxsim_rerank_dev(const int64_t* d_ids, const int32_t* d_n, int B,
                         int64_t tok_rows, int64_t first_row, int k_out, int32_t* d_out_pos, int64_t* d_out_ids,
                         double* d_out_scores, int32_t* d_out_n, void* stream);
 
+/* ---- MaxSim as a first-stage search: every row of the token store is scored, not a list of ids (1.22.0) --------------
+ * Milvus 2.6 searches an embedding list with MAX_SIM as the METRIC of the request; a rerank can only reorder what another
+ * first stage found.  hr_maxsim_scan_dev writes, for B queries and the n_rows local rows of a shard, the candidate arrays
+ * hr_deep_topk_dev / hr_deep_topk_window_dev select from (row_offset = the global id of local row 0):
+ *   S of (query q, row i)   the value the table above defines, unchanged: the k-ascending fp32 fma chain per token pair,
+ *                           m_t the fp32 maximum over the row's tokens, S the fp64 sum of the m_t in ascending t from +0.0
+ *   a hit                   i < tok_rows, T_i > 0 (after the CSR bounds were clamped into [0, d_indptr[tok_rows]], as the
+ *                           rerank clamps them) and bit i of d_rowmask set (packed as every rowmask: bit i & 7 of byte
+ *                           i >> 3; NULL = every row passes): d_rows[q][i] = i, d_scores[q][i] = (float)S, S rounded ONCE
+ *                           to fp32, nearest even — the fp32 score every other search returns.  S is never -0.0, so the
+ *                           score is not; (float) is monotone, so score_a < score_b implies S_a < S_b
+ *   no hit                  d_rows[q][i] = -1, d_scores[q][i] = 0.0f: a row without vectors, beyond the token store, or
+ *                           masked out.  Such a row costs its mask bit and two CSR bounds: no token traffic and no matrix
+ *                           work, so a selective filter makes the scan proportionally cheaper
+ * Every cell of d_scores / d_rows [B][n_rows] is written by exactly one lane.  The ranking of a search is then the hits
+ * by (score descending, row ascending) — hr_deep_topk_dev's rank_key — so it is exact by construction, has no proof and
+ * no escalation, and the depth limit of the deep search (offset + k <= HR_MAX_DEEP_K).  Two rows whose S differ by less
+ * than an fp32 ulp tie and are ordered by row: the fp64 order of a window is what hr_maxsim_rerank_dev gives on the hits.
+ * Query tokens: Tq = d_qn[q] clamped into [0, tq_stride] at d_qtok[q][0 .. Tq); with Tq = 0 every row with tokens that
+ * passes the mask scores +0.0f and stays a hit (defined, not refused: the operand lives on the device).
+ * HR_ELIMIT: tq_stride > HR_MAX_QUERY_TOKENS, dim > HR_MAX_TOKEN_DIM, n_rows >= 2^31, B > 65535.  HR_EINVAL: a dim below 8
+ * or not a multiple of 8, tq_stride < 1, negative B / tok_rows / n_rows, a NULL required buffer (d_indptr / d_tok may be
+ * NULL iff tok_rows == 0; d_rowmask may always be NULL), d_qtok / d_tok not 16-byte aligned.  A refused call launches
+ * nothing and leaves the outputs alone.  B == 0 or n_rows == 0: HR_OK, nothing is launched.  tok_rows may be smaller or
+ * larger than n_rows.  Asynchronous on `stream`; allocates nothing; not tied to an hr_index.  No atomic takes part: the
+ * result is a function of the inputs alone (and not of HR_DEBUG_MAXSIM_SCAN_BLOCKS).
+ *   How: the grid is (blocks per query, B), sized so that one query still fills the chip.  A block keeps its query's
+ *   tokens in LDS and walks ranges of consecutive rows; a wave takes a run of consecutive rows of each range (one forward
+ *   stream through d_tok) with the rerank's loop, on v_mfma_f32_16x16x4_f32, which IS the canonical chain.  A document
+ *   tile is multiplied for one query only: B queries read the store B times. */
+HR_API int hr_maxsim_scan_dev(const void* d_qtok /* fp16 [B][tq_stride][dim] */, const int32_t* d_qn /* [B] */, int B,
+                              int tq_stride, int dim, const int64_t* d_indptr /* [tok_rows + 1] */,
+                              const void* d_tok /* fp16 [..][dim] */, int64_t tok_rows, int64_t n_rows,
+                              const uint8_t* d_rowmask /* packed, bit i = local row i passes; NULL = all */,
+                              float* d_scores /* [B][n_rows] */, int32_t* d_rows /* [B][n_rows] */, void* stream);
+
 /* Everything after the per-shard lists of a query batch in ONE launch (one block per query): [hr_merge_topk_dev of
  * every modality's exchanged lists] -> hr_fuse_rrf_dev (or hr_fuse_scores_dev: `fusion`) -> [hr_rerank_linear_dev]; results are bit-identical to the
  * separate calls (reference retrieval.py:421-491 fusion, :518-563 rerank, after the server-side shard merge of
@@ -1025,9 +1061,12 @@ HR_API int hr_set_scan_cus(hr_index* h, int n_cus);
  * HR_DEBUG_NO_RANGE_CLAMP (process-wide): 1 = the scans of a range search get +inf ceilings, i.e. they do not drop the
  *   rows above range_filter.  Results through the host form do not change (exactness never rests on the clamp); the
  *   device form's flags show what the clamp proves (tests, tests/probes/range_probe.py).
+ * HR_DEBUG_MAXSIM_SCAN_BLOCKS (process-wide): blocks per query of hr_maxsim_scan_dev, 1 .. 65535 (0 = by batch and store
+ *   size).  The range size follows it, so a small value makes every block walk several ranges of 256 rows on a store of
+ *   a few thousand rows (tests); the result does not depend on it.
  * The library reads no environment variables. */
 enum { HR_DEBUG_FINISH_MODE = 1, HR_DEBUG_FAIL_NEXT_BUILD = 2, HR_DEBUG_DENSE_KERNELS = 3, HR_DEBUG_SPARSE_RPB = 4,
-       HR_DEBUG_GROUP_ROWS = 5, HR_DEBUG_NO_TRIM = 6, HR_DEBUG_NO_RANGE_CLAMP = 7 };
+       HR_DEBUG_GROUP_ROWS = 5, HR_DEBUG_NO_TRIM = 6, HR_DEBUG_NO_RANGE_CLAMP = 7, HR_DEBUG_MAXSIM_SCAN_BLOCKS = 8 };
 HR_API int hr_debug_option(hr_index* h, int key, int value);
 
 /* ---- measurement hooks -------------------------------------------------------
